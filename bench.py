@@ -12,6 +12,22 @@ levels, coupled heat + Richards water transport, fp64.  With --gpus N every rank
 holds a full N145-sized shard (weak scaling: columns are independent, there is no
 collective on the step path).  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, W warm-up steps (plus the
+clock spin-up), ONE timed region of exactly K steps, the line.  `--full` adds
+everything else the line has carried: the headline region repeated 10 times (the
+line reports the median), the HBM-resident and multi-step companions, the
+one-thread multi-device leg, the sustained leg, the CPU baseline and, with N > 1,
+the strong-scaling companion and the library's own RCCL status check.  The `--no-*`
+switches thin out a `--full` run; `--repeats` overrides the region count of either.
+
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+
+writes what the timed path left after its last step -- the fields a caller of
+trm_step receives (tests/workloads.py: compared_fields) -- as DIR/<field>.npy in
+the workload's dtype, rank 0's shard.  Above DUMP_BYTES in all, every field is cut
+to the same seeded sample of columns.  The inputs are seeded: two builds run with
+the same arguments can be compared output for output.
+
 Launching N > 1: the driver's form is
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE from the environment).  A bare `python bench.py --gpus N` with
@@ -47,6 +63,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s
 PROFILE_ROUND = "r05"
 # bytes the reference's unfused passes stream per cell and step (count of arrays each kernel reads / writes)
 REFERENCE_ORDER_BYTES_PER_CELL_STEP = {"heat": 140, "richards": 300, "land": 300, "landveg": 300}
+DUMP_BYTES = 60 * 2 ** 20   # --dump-outputs: all arrays together (npy headers aside) stay below 64 MB
+DUMP_SEED = 20261015        # the column sample of a larger output
 
 WORKLOADS = {
     # name: (description, config, hydraulics, mask/columns, Nz, dtype, replicas)
@@ -248,12 +266,35 @@ def measure(dev, w, config, steps, warmup, spinup_ms, heun, sync, barrier, repea
                 kernel_us_per_step=_median(kernels) * 1e3 / K, kernel_us_per_step_min=min(kernels) * 1e3 / K)
 
 
+def dump_columns(Nh, bytes_per_column):
+    """The columns --dump-outputs keeps: all of them (None) up to DUMP_BYTES, else the DUMP_SEED sample that fits, in column order."""
+    if bytes_per_column * Nh <= DUMP_BYTES:
+        return None
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    return np.sort(rng.choice(Nh, DUMP_BYTES // bytes_per_column, replace=False))
+
+
+def dump_outputs(W, dev, w, directory):
+    """--dump-outputs: every field a caller of the timed path receives, as <directory>/<name>.npy ([rows][columns], or [columns]
+    for a per-column field) in the state's dtype, every field on the same columns (dump_columns)."""
+    names = W.compared_fields(w)
+    cols = dump_columns(w["Nh"], sum(dev.rows(n) for n in names) * w["dtype"].itemsize)
+    os.makedirs(directory, exist_ok=True)
+    for n in names:
+        a = dev.get(n)
+        np.save(os.path.join(directory, f"{n}.npy"), np.ascontiguousarray(a if cols is None else a[..., cols]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=10, help="the K-step timed region is repeated this many times (state restored in between, untimed); the line reports the median")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated timed regions, the companion legs, the CPU baseline "
+                    "(see the module docstring); off: one timed region of --steps steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the fields the timed path left after its last step as DIR/<field>.npy")
+    ap.add_argument("--repeats", type=int, default=None, help="the K-step timed region is repeated this many times (state restored in between, untimed); "
+                    "the line reports the median (default: 1, with --full 10)")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--kernel", default="fused", choices=["fused", "unfused"])
     ap.add_argument("--integrator", default="euler", choices=["euler", "heun"], help="ForwardEuler (headline) or Heun (one fused launch per step)")
@@ -261,20 +302,22 @@ def main():
     ap.add_argument("--spinup-ms", type=float, default=200.0, help="untimed device-busy time after the warm-up steps that lets the clocks settle (0: off)")
     ap.add_argument("--skip-kf", action="store_true", help="store hydraulic_conductivity only when finalizing")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-resident", action="store_true", help="skip the HBM-resident companion measurements (c3x8, c5)")
-    ap.add_argument("--no-single-process", action="store_true", help="skip the leg in which ONE host thread drives one context per device (trm_step_all)")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling companion (BASELINE config 4: N145 sharded over the ranks)")
-    ap.add_argument("--multistep", type=int, default=50, help="also time the resident-column multi-step kernel with this many steps per launch (temporal blocking; reported separately)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-hbm-resident", action="store_true", help="--full: skip the HBM-resident companion measurements (c3x8, c5)")
+    ap.add_argument("--no-single-process", action="store_true", help="--full: skip the leg in which ONE host thread drives one context per device (trm_step_all)")
+    ap.add_argument("--no-strong", action="store_true", help="--full, N > 1: skip the strong-scaling companion (BASELINE config 4: N145 sharded over the ranks)")
+    ap.add_argument("--multistep", type=int, default=50, help="--full: also time the resident-column multi-step kernel with this many steps per launch (temporal blocking; reported separately)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target wall time of the CPU baseline sample")
     ap.add_argument("--pipeline", type=int, default=None, choices=[0, 1, 2], help="TRM_OPT_PIPELINE_PARTS (default: the library's rule)")
     ap.add_argument("--derive", type=int, default=None, choices=[0, 1, 2, 3], help="TRM_OPT_DERIVE_CLOSURE_FIELDS (default: the library's rule)")
     ap.add_argument("--steps-per-launch", type=int, default=1, help="TRM_OPT_STEPS_PER_LAUNCH of the measured context: 1 (default) = one launch per step, the state streams "
                     "through memory every step -- the per-step HBM roofline; 0 = the library's own choice (what a plain run! gets)")
-    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="length of the sustained leg: back-to-back per-step launches of the measured context, reported as "
+    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="--full: length of the sustained leg: back-to-back per-step launches of the measured context, reported as "
                     "`sustained` beside the headline (0: off)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
 
     if args.cpu_baseline_worker:
         return cpu_baseline_worker(args)
@@ -314,9 +357,9 @@ def main():
     n_gpus = world
     stat_device = "cuda" if backend == "nccl" else "cpu"
     # a CPU-side group for waits that must not put a kernel on the waiting ranks' devices (an RCCL barrier spins ON the GPU): the
-    # ranks that idle while rank 0 drives every device from one host thread (single_process_leg)
+    # ranks that idle while rank 0 drives every device from one host thread (single_process_leg, --full)
     cpu_group = None
-    if world > 1 and backend == "nccl":
+    if world > 1 and backend == "nccl" and args.full:
         try:
             cpu_group = dist.new_group(backend="gloo")
         except Exception as e:   # noqa: BLE001 -- (no gloo transport on this node: the default group's barrier serves)
@@ -380,6 +423,8 @@ def main():
     heun = args.integrator == "heun"
     m = measure(dev, w, config, args.steps, args.warmup, args.spinup_ms, heun, sync, barrier, args.repeats, reduce_max)
     status = dev.status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(W, dev, w, args.dump_outputs)
     total_columns = reduce_sum(Nh)
     nan_flag = parallel.global_status(status) if world > 1 else status
     kernel_s = m["kernel_us_per_step"] * 1e-6            # median duration of one step's launches on the slowest GPU
@@ -407,7 +452,8 @@ def main():
         "data": "synthetic forcing and initial state on the reference's ERA5-land mask columns (SURVEY 8(d)); seeded",
         "config": {"workload": desc, "columns_per_gpu": Nh, "levels": Nz, "dt_s": w["dt"], "kernel": args.kernel, "integrator": args.integrator, "series": bool(args.series),
                    "steps_per_launch": args.steps_per_launch,
-                   "statistic": f"median of {m['repeats']} timed regions of {args.steps} steps each (max over ranks per region); the state is restored between regions, untimed",
+                   "statistic": (f"median of {m['repeats']} timed regions of {args.steps} steps each (max over ranks per region); the state is restored between regions, untimed"
+                                 if m["repeats"] > 1 else f"one timed region of {args.steps} steps (max over ranks)"),
                    "repeats": m["repeats"], "ms_per_step_min": m["ms_per_step_min"], "ms_per_step_max": m["ms_per_step_max"],
                    "state_restored_every": STABLE_STEPS[config] if m["chunked"] else None,
                    "warmup_executed": m["warm"], "clock_spinup_ms": args.spinup_ms,
@@ -418,7 +464,7 @@ def main():
     out["roofline"]["kernel_ms_min"] = m["kernel_us_per_step_min"] * 1e-3
     out["roofline"]["program"] = program
     hung = False
-    if world > 1:
+    if world > 1 and args.full:
         # global diagnostics through the library's own RCCL path (trm_comm_init / trm_status_global), beside torch's.  It runs
         # in a watchdog thread: should a collective of this path block, the line is still printed (with "timeout") and the
         # process leaves through os._exit with a NON-ZERO code -- a hung collective is a defect, not a pass.
@@ -433,13 +479,13 @@ def main():
         out["config"]["rccl_ranks"] = res["rccl_ranks"]
         if hung:
             out["config"]["abi_global_status_note"] = ("trm_comm_init / trm_status_global did not return within 60 s; the ranks leave with exit code 3")
-    if world > 1 and not hung and not args.no_strong and args.workload == "c3" and args.scaling == "weak":
+    if args.full and world > 1 and not hung and not args.no_strong and args.workload == "c3" and args.scaling == "weak":
         try:
             out["strong"] = strong_leg(W, parallel, args, world, rank, local_rank, configure, sync, barrier, reduce_max, reduce_sum)
         except Exception as e:   # noqa: BLE001 -- a companion leg (the same code on every rank: a failure is a failure on all of them); the headline line is still printed
             out["strong"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if not hung and not args.no_single_process and args.workload == "c3" and args.scaling == "weak" and args.kernel == "fused" and not heun:
+    if args.full and not hung and not args.no_single_process and args.workload == "c3" and args.scaling == "weak" and args.kernel == "fused" and not heun:
         # ONE host thread driving one context per device (the reference's host is one Julia process): rank 0 alone, the other
         # ranks idle at the HOST-side barrier below
         if rank == 0:
@@ -453,18 +499,18 @@ def main():
             dist.barrier(group=cpu_group)       # (gloo: the idle ranks wait on the host, their devices stay free for rank 0's contexts)
 
     single = rank == 0 and n_gpus == 1
-    if single and args.multistep > 1 and args.kernel == "fused" and not heun and not args.series and args.steps_per_launch == 1:
+    if args.full and single and args.multistep > 1 and args.kernel == "fused" and not heun and not args.series and args.steps_per_launch == 1:
         out["multistep"] = multistep_leg(W, w, desc, config, Nz, Nh, wordsize, args, sync, local_rank)
-    if single and not args.no_hbm_resident and args.workload == "c3" and args.kernel == "fused" and not heun:
+    if args.full and single and not args.no_hbm_resident and args.workload == "c3" and args.kernel == "fused" and not heun:
         out["roofline_hbm_resident"] = hbm_resident_leg(W, parallel, args, sync, local_rank)
     # The sustained leg comes LAST of the device work: three seconds of back-to-back launches leave the device in the state a long run
     # sees, in which an HBM-resident step reads ~8 % slower than after light work (profiles/r05/exp19, exp20) -- the companions above are
     # measured like the headline, from a device that has just run the warm-up and the clock spin-up.
     if not hung:
-        if args.sustained_seconds > 0:
+        if args.full and args.sustained_seconds > 0:
             out["sustained"] = sustained_leg(dev, w, config, args.sustained_seconds, heun, sync)
         dev.close()
-    if single and not args.no_cpu_baseline:
+    if args.full and single and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(out), file=line_out, flush=True)

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 for f in build/variants/*.so; do
   OUT=$GRAFT_REPO_ROOT/gpurun_out/cnt_$(basename $f .so); rm -rf $OUT; mkdir -p $OUT
   export TRM_LIBRARY=$GRAFT_REPO_ROOT/$f
-  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_ACTIVE_INST_ANY --output-format csv -d $OUT -- python bench.py --no-cpu-baseline --steps 20 --warmup 2 "$@" > /dev/null 2> $OUT/err.txt
+  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_ACTIVE_INST_ANY --output-format csv -d $OUT -- python bench.py --full --no-cpu-baseline --steps 20 --warmup 2 "$@" > /dev/null 2> $OUT/err.txt
   python - "$OUT" "$f" <<'PY'
 import csv, glob, os, sys
 out, name = sys.argv[1], sys.argv[2]

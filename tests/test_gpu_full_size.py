@@ -116,13 +116,13 @@ def test_c5_shard_fp32_properties(hydraulics, num_columns):
 
 
 def test_bench_contract_json_line():
-    """bench.py prints ONE JSON line with the driver's keys, the roofline object and the CPU baseline."""
+    """bench.py --full prints ONE JSON line with the driver's keys, the roofline object, the companion legs and the CPU baseline."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "3", "--cpu-seconds", "2", "--spinup-ms", "20"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "20", "--warmup", "3", "--cpu-seconds", "2", "--spinup-ms", "20"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -151,3 +151,52 @@ def test_bench_contract_json_line():
     assert d["config"]["steps_per_launch"] == 1 and r["kernel_ms_min"] <= r["kernel_ms"] <= d["ms_per_step"] * 1.02
     # value = whole-job columns x steps / wall time
     assert abs(d["value"] - 56951 * 20 / (d["ms_per_step"] * 1e-3 * 20)) / d["value"] < 1e-6
+
+
+def test_bench_plain_run_times_the_steps_it_is_given_and_dumps_what_they_computed(tmp_path):
+    """A plain bench.py run is ONE timed region of --steps steps and none of --full's legs.  --dump-outputs writes the fields the
+    timed path left (float64 here, under 64 MB, every field on bench.dump_columns' sample of columns): the same arrays from a second
+    run with the same arguments, and bit for bit what warm-up + timed steps give through the library directly."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 30, 3
+    lines, dumps = [], []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append([l for l in out.stdout.splitlines() if l.strip()])
+        dumps.append(d)
+    for ls in lines:
+        assert len(ls) == 1, ls
+    line = json.loads(lines[0][0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["metric"] == "column-steps/sec" and line["unit"] == "column-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == steps and line["config"]["repeats"] == 1 and line["config"]["warmup_executed"] == warmup
+    assert line["config"]["status_flags"] == 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 56951 * steps / (line["ms_per_step"] * 1e-3 * steps)) / line["value"] < 1e-6
+    for key in ("cpu_baseline", "multistep", "roofline_hbm_resident", "single_process", "sustained", "strong"):
+        assert key not in line, key
+
+    lat, lon = W.columns_from_mask("N145")
+    w = W.make_workload("richards", lat, lon, 32)
+    names = W.compared_fields(w)
+    assert sorted(p.name for p in dumps[0].iterdir()) == sorted(f"{n}.npy" for n in names)
+    assert sum(p.stat().st_size for p in dumps[0].iterdir()) < 64 * 10 ** 6
+    dev = W.setup_device(w)
+    dev.step(w["dt"], warmup, finalize=False)
+    dev.step(w["dt"], steps, finalize=False)
+    assert dev.status() == 0
+    cols = bench.dump_columns(w["Nh"], sum(dev.rows(n) for n in names) * 8)
+    assert cols is not None and cols.size > w["Nh"] // 2
+    for n in names:
+        a, b = np.load(dumps[0] / f"{n}.npy"), np.load(dumps[1] / f"{n}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True), n
+        assert np.array_equal(a, dev.get(n)[..., cols], equal_nan=True), n
+    dev.close()

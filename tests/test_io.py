@@ -1,6 +1,7 @@
 """terrarium.jl_amd/io.py: the dependency-free NetCDF-4 / HDF5 reader and the raster input source.
 The reader is checked against files the test writes itself byte by byte (tests/hdf5_writer.py, written from the HDF5
-format specification) and, where the reference tree is present, against the two land masks the reference ships."""
+format specification) and against the two land masks the reference ships (stored gzipped under tests/golden/)."""
+import gzip
 import os
 
 import numpy as np
@@ -10,7 +11,7 @@ import terrarium_jl_amd as trm
 from terrarium_jl_amd import io as tio
 from hdf5_writer import Writer
 
-REF_INPUTS = "/root/reference/inputs"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_lookup3_known_answers():
@@ -65,10 +66,11 @@ def test_reader_against_byte_by_byte_writer(tmp_path):
         tio.Hdf5File(b"not an hdf5 file at all" * 10)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INPUTS), reason="the reference tree is not present on this machine")
 @pytest.mark.parametrize("name,count,shape", [("N72", 14017, (144, 288)), ("N145", 56951, (290, 580))])
-def test_reference_masks_through_the_reader(name, count, shape):
-    path = os.path.join(REF_INPUTS, f"era5-land_land_sea_mask_{name}.nc")
+def test_reference_masks_through_the_reader(name, count, shape, tmp_path):
+    path = str(tmp_path / f"era5-land_land_sea_mask_{name}.nc")
+    with gzip.open(os.path.join(GOLDEN, f"era5-land_land_sea_mask_{name}.nc.gz"), "rb") as src, open(path, "wb") as dst:
+        dst.write(src.read())
     f = tio.Hdf5File(path)
     assert set(f.keys()) == {"time", "lat", "lon", "lsm"}
     lsm = f["lsm"].read()
