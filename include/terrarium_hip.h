@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define TRM_ABI_VERSION 19
+#define TRM_ABI_VERSION 20
 
 typedef struct trm_ctx trm_ctx;
 
@@ -235,6 +235,11 @@ enum {
     TRM_PROGRAM_DEEP = 8, TRM_PROGRAM_WIDE = 9, TRM_PROGRAM_LAND_INTERLEAVED = 10, TRM_PROGRAM_UNFUSED = 11, TRM_PROGRAM_VEGETATION = 12,
     TRM_PROGRAM_PACKED_LAND = 13
 };
+/* bits of TRM_INFO_LAST_PROGRAM beside the ones above (25-27 are per family: surface processes inline / time series in the multi-step
+ * program, the program and the generic boundaries of the deep and wide columns): how the step's time averages were accumulated
+ * (trm_average_open) -- by the step launch itself (the resident multi-step program), or by a k_accumulate launch behind it.  Neither is
+ * set while no accumulator is open. */
+enum { TRM_PROGRAM_AVERAGES_IN_LAUNCH = 268435456 /* 1 << 28 */, TRM_PROGRAM_AVERAGES_AFTER_LAUNCH = 536870912 /* 1 << 29 */ };
 enum {
     TRM_KERNEL_FUSED = 0,       /* one launch per step: lane = soil level, a column per (half-)wavefront,     */
                                 /* wavefront shuffles for the vertical stencil (Nz <= 64; two levels per lane */
@@ -524,6 +529,39 @@ int trm_stage_bc_device_ptr(trm_ctx* ctx, int var, int side, void** dev);
  * a second set of buffers owned by the context, trm_restore_state copies it back.  One slot; no host traffic. */
 int trm_save_state(trm_ctx* ctx);
 int trm_restore_state(trm_ctx* ctx);
+
+/* ---- time averages (Oceananigans' AveragedTimeInterval / WindowedTimeAverage as the reference's output writers use them) -------
+ * An accumulator lives in the context and sums one field over a window of steps; one handle per (field, window), so two writers can
+ * average the same field over different windows.
+ *   trm_average_open(ctx, field, &handle)   allocates an accumulator of `field`, zero, window length 0
+ *   trm_average_reset(ctx, handle)          starts a new window: sum and window length to zero
+ *   trm_average_read(ctx, handle, host, &window_seconds, &steps)
+ *                                           mean = sum / window_seconds, rounded once to the context precision, host layout
+ *                                           [rows][Nh] as trm_download; window_seconds and steps may be NULL.  A window of zero
+ *                                           steps is TRM_ESTALE.
+ *   trm_average_close(ctx, handle)          releases it; the handle is invalid from then on (TRM_EINVAL)
+ * Arithmetic.  Every step taken by a STEPPING entry point -- trm_step, trm_step_heun, trm_heun_correct, their _timed forms,
+ * trm_step_all / trm_step_heun_all -- adds to every open accumulator, per launch:
+ *     acc[i] <- acc[i] + P[i],   window <- window + dt (per step, in order),   P[i] = sum_k (double)dt * (double)x_k[i]
+ * where x_k is the field after step k of the launch and P starts at 0.0 and adds the launch's steps in order (a launch of one step:
+ * one term).  Products and sums are rounded separately; accumulators and partials are double for both precisions.  The value counted
+ * is the one after the step (right endpoint, weight dt): our reading of Oceananigans' WindowedTimeAverage with stride 1, from memory
+ * -- no reference-held value pins it.  "After the step" is what the step leaves in the field: the prognostic and closure fields of
+ * the new state, the water table of the new state, and the surface diagnostics (skin temperature, fluxes) as the step's own surface
+ * processes formed them -- the evaluation a finalizing call adds afterwards (compute_auxiliary!) is not counted.
+ * Component calls (trm_explicit_step, trm_update_state, trm_heun_predict, ...) do not accumulate.  trm_reset zeroes every open
+ * accumulator and keeps the handles; trm_save_state / trm_restore_state do not include accumulators.
+ * Fields: internal energy, saturation, temperature, liquid fraction, pressure head, surface excess water, water table; with the
+ * LandModel also skin temperature, ground heat flux, shortwave up, longwave up, net radiation, sensible and latent heat flux, ground
+ * evaporation, infiltration and surface runoff.  Anything else (tendencies, inputs, vegetation) is TRM_EUNSUPPORTED, as is a
+ * surface field of a SoilModel and any field of a standalone VegetationModel.
+ * Paths (TRM_INFO_LAST_PROGRAM: TRM_PROGRAM_AVERAGES_*): the resident multi-step program accumulates in its own launch; every other
+ * program is followed by one k_accumulate launch per step, and while an open accumulator needs that path (a multi-step program
+ * without the accumulation: deep columns; a field the fused form does not cover) the library steps one launch per step. */
+int trm_average_open(trm_ctx* ctx, int field, int* handle);
+int trm_average_reset(trm_ctx* ctx, int handle);
+int trm_average_read(trm_ctx* ctx, int handle, void* host, double* window_seconds, int64_t* steps);
+int trm_average_close(trm_ctx* ctx, int handle);
 
 int trm_clock(const trm_ctx* ctx, double* time, int64_t* iteration);
 int trm_set_clock(trm_ctx* ctx, double time, int64_t iteration);

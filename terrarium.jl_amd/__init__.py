@@ -34,4 +34,4 @@ from .integrator import (ForwardEuler, Heun, PrescribedSurfaceTemperature, Presc
                          checkpoint, restore, restart_fields, DeviceGroup)
 from ._capi import TerrariumHipError
 from .io import Hdf5File, RasterInputSource
-from .simulation import Simulation, Callback, IterationInterval, TimeInterval, SnapshotWriter, run_simulation
+from .simulation import Simulation, Callback, IterationInterval, TimeInterval, AveragedTimeInterval, SnapshotWriter, run_simulation

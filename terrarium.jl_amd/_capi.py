@@ -61,7 +61,11 @@ def decode_program(pid: int) -> dict:
         d.update(program=("euler", "heun", "multi")[extra & 3])
     if d["family"] in ("deep", "wide"):
         d.update(program=("euler", "heun", "multi")[extra & 3], generic_boundaries=bool(extra & 4))
+    if pid & (PROGRAM_AVERAGES_IN_LAUNCH | PROGRAM_AVERAGES_AFTER_LAUNCH):
+        d.update(averages="in_launch" if pid & PROGRAM_AVERAGES_IN_LAUNCH else "after_launch")
     return d
+# TRM_PROGRAM_AVERAGES_*: how the last step accumulated the open time averages (trm_average_open)
+PROGRAM_AVERAGES_IN_LAUNCH, PROGRAM_AVERAGES_AFTER_LAUNCH = 1 << 28, 1 << 29
 STATUS_NAN, STATUS_COMPOSITION, STATUS_HANDOFF_TIMEOUT = 1, 2, 4
 TRM_OK, TRM_EINVAL, TRM_EHIP, TRM_ENOMEM, TRM_EUNSUPPORTED, TRM_ESTALE, TRM_ECOMM = range(7)
 
@@ -77,7 +81,8 @@ EXPORTS = (
     "trm_series_append trm_series_trim_before trm_series_info trm_reset trm_download_rows trm_set_ring_grid trm_download_ring "
     "trm_scatter_ring_device trm_upload_ring trm_gather_ring_device "
     "trm_heun_predict trm_heun_stage_auxiliary trm_heun_correct trm_stage_field_device_ptr trm_stage_bc_device_ptr trm_set_forcing_device "
-    "trm_series_window trm_comm_init_all trm_step_all trm_step_heun_all trm_synchronize_all trm_reduce_global_all trm_status_global_all").split()
+    "trm_series_window trm_comm_init_all trm_step_all trm_step_heun_all trm_synchronize_all trm_reduce_global_all trm_status_global_all "
+    "trm_average_open trm_average_reset trm_average_read trm_average_close").split()
 TIME_INDEXING = dict(linear=0, clamp=1, cyclical=2, raster=3)
 
 
@@ -221,6 +226,10 @@ def lib():
     L.trm_synchronize_all.argtypes = [C.POINTER(vp), i32]
     L.trm_reduce_global_all.argtypes = [C.POINTER(vp), i32, i32, i32, vp]
     L.trm_status_global_all.argtypes = [C.POINTER(vp), i32, C.POINTER(C.c_uint32)]
+    L.trm_average_open.argtypes = [vp, i32, C.POINTER(i32)]
+    L.trm_average_reset.argtypes = [vp, i32]
+    L.trm_average_read.argtypes = [vp, i32, vp, C.POINTER(dbl), C.POINTER(i64)]
+    L.trm_average_close.argtypes = [vp, i32]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

@@ -350,6 +350,26 @@ namespace {
 
 template <class NF> int upload_impl(trm_ctx* c, int field, const NF* host);
 
+// time averages: the fused path's slot of a field (trm_average.hpp), -1 for a field it does not carry, and back
+const int kAccumField[ACC_SLOTS] = {
+    TRM_FIELD_INTERNAL_ENERGY, TRM_FIELD_SATURATION_WATER_ICE, TRM_FIELD_TEMPERATURE, TRM_FIELD_LIQUID_WATER_FRACTION, TRM_FIELD_PRESSURE_HEAD,
+    TRM_FIELD_SURFACE_EXCESS_WATER, TRM_FIELD_WATER_TABLE, TRM_FIELD_SKIN_TEMPERATURE, TRM_FIELD_GROUND_HEAT_FLUX, TRM_FIELD_SURFACE_SHORTWAVE_UP,
+    TRM_FIELD_SURFACE_LONGWAVE_UP, TRM_FIELD_SURFACE_NET_RADIATION, TRM_FIELD_SENSIBLE_HEAT_FLUX, TRM_FIELD_LATENT_HEAT_FLUX,
+    TRM_FIELD_EVAPORATION_GROUND, TRM_FIELD_INFILTRATION, TRM_FIELD_SURFACE_RUNOFF};
+int accum_slot(int field) {
+    for (int s = 0; s < ACC_SLOTS; ++s) if (kAccumField[s] == field) return s;
+    return -1;
+}
+int accum_field(int slot) { return kAccumField[slot]; }
+// the fields trm_average_open takes: the soil state and its closures, surface excess water and water table, and the LandModel's
+// surface diagnostics on a context with the surface energy balance -- never on a standalone VegetationModel
+bool averageable(const trm_ctx* c, int field) {
+    if (c->veg_mode == TRM_VEGETATION_STANDALONE || !c->state.f[field]) return false;
+    const int s = accum_slot(field);
+    if (s < 0) return false;
+    return s < ACC_TS || c->params.seb != 0;
+}
+
 // The step sequences of one precision.  The launches themselves are Unfused / Veg / ColumnLaunch / GenericLaunch / DeepLaunch /
 // LandLaunch / PackedLaunch (trm_host.hpp); the forwarders below keep their reference names in the sequences.
 template <class NF> struct Ops {
@@ -506,6 +526,7 @@ template <class NF> struct Ops {
         if (!rc) {
             rc = wide_columns(c) ? WideLaunch<NF>::run(c, PROG_HEUN, generic_bcs(c), dt, finalize) : DeepLaunch<NF>::run(c, PROG_HEUN, generic_bcs(c), dt, finalize, 1);
         }
+        if (!rc) rc = accumulate_after(c, dt);
         if (!rc) c->closure_consistent = true;
         c->tend_valid = finalize != 0;
         c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
@@ -540,8 +561,95 @@ template <class NF> struct Ops {
         int rc = update_state(c, c->state, true);
         if (!rc) rc = explicit_step(c, c->state, dt);
         if (!rc) rc = closure(c, c->state);
+        if (!rc) rc = accumulate_after(c, dt);
         if (!rc && finalize) rc = compute_auxiliary(c, c->state);
         return rc;
+    }
+    // ---- time averages (trm_average_*, trm_average.hpp) ----------------------------------------------------------------------
+    static bool averaging(const trm_ctx* c) {
+        for (const auto& a : c->averages) if (a.field >= 0) return true;
+        return false;
+    }
+    // One step's terms of every open accumulator from the fields as the step launch left them: one k_accumulate launch (per 32
+    // accumulators), the windows advanced by dt.  Nothing while none is open.
+    static int accumulate_after(trm_ctx* c, double dt) {
+        if (!averaging(c)) return TRM_OK;
+        AccumBatch b{};
+        b.w = dt;
+        for (auto& a : c->averages) {
+            if (a.field < 0) continue;
+            AccumEntry& e = b.e[b.count++];
+            e.src = c->state.f[a.field];
+            e.sum = a.d_sum;
+            e.n = (long long)field_elems(c, a.field);
+            e.pitch = is_3d(a.field) ? c->Nzp : 1;
+            e.nz = is_3d(a.field) ? c->Nz : 1;
+            e.src_double = 0;
+            a.window += dt;
+            a.steps += 1;
+            if (b.count == ACC_BATCH) {
+                if (int rc = AverageLaunch<NF>::accumulate(c, b)) return rc;
+                b.count = 0;
+            }
+        }
+        if (int rc = AverageLaunch<NF>::accumulate(c, b)) return rc;
+        c->last_program |= TRM_PROGRAM_AVERAGES_AFTER_LAUNCH;
+        return TRM_OK;
+    }
+    // The multi-step program accumulates in its own launch when it covers every open accumulator's field (the surface excess water
+    // and the water table only under Richards: the NoFlow program does not carry them) -- columns of <= 64 levels.
+    static bool averages_in_launch(const trm_ctx* c) {
+        if (c->Nz > 64 || deep_columns(c) || c->part >= 0) return false;
+        for (const auto& a : c->averages) {
+            if (a.field < 0) continue;
+            const int s = accum_slot(a.field);
+            if (s < 0 || (!richards(c) && (s == ACC_S || s == ACC_WT))) return false;
+        }
+        return true;
+    }
+    // k_column_accum: `nsteps` steps, partials added to the accumulators (one open accumulator of a field: straight into it; more:
+    // into a zeroed scratch buffer, then one k_accumulate adds the scratch to each)
+    static int multi_program_accum(trm_ctx* c, double dt, int finalize, int nsteps) {
+        AccumArgs aa{};
+        aa.dt = dt;
+        aa.mask = 0;
+        int handles[ACC_SLOTS] = {};
+        for (const auto& a : c->averages) if (a.field >= 0) handles[accum_slot(a.field)] += 1;
+        AccumBatch b{};
+        b.w = 1.0;
+        for (int sl = 0; sl < ACC_SLOTS; ++sl) {
+            if (!handles[sl]) continue;
+            aa.mask |= 1u << sl;
+            const int f = accum_field(sl);
+            if (handles[sl] == 1) {
+                for (const auto& a : c->averages) if (a.field == f) aa.dst[sl] = a.d_sum;
+                continue;
+            }
+            const size_t bytes = field_elems(c, f) * sizeof(double);
+            if (!c->d_acc_partial[sl]) TRM_HIP(c, hipMalloc(&c->d_acc_partial[sl], bytes));
+            TRM_HIP(c, hipMemsetAsync(c->d_acc_partial[sl], 0, bytes, c->stream));
+            aa.dst[sl] = c->d_acc_partial[sl];
+            for (const auto& a : c->averages) {
+                if (a.field != f) continue;
+                if (b.count == ACC_BATCH) return fail(c, TRM_EUNSUPPORTED, "more than 32 accumulators of fields that share a field");
+                AccumEntry& e = b.e[b.count++];
+                e.src = c->d_acc_partial[sl];
+                e.sum = a.d_sum;
+                e.n = (long long)field_elems(c, f);
+                e.pitch = is_3d(f) ? c->Nzp : 1;
+                e.nz = is_3d(f) ? c->Nz : 1;
+                e.src_double = 1;
+            }
+        }
+        int rc = richards(c) ? ColumnAccumLaunch<NF, true>::run(c, dt, finalize, nsteps, aa) : ColumnAccumLaunch<NF, false>::run(c, dt, finalize, nsteps, aa);
+        if (!rc) rc = AverageLaunch<NF>::accumulate(c, b);
+        if (rc) return rc;
+        for (auto& a : c->averages) {
+            if (a.field < 0) continue;
+            for (int j = 0; j < nsteps; ++j) a.window += dt;
+            a.steps += nsteps;
+        }
+        return TRM_OK;
     }
     // TRM_OPT_STEPS_PER_LAUNCH = 0: run!'s loop (model_integrator.jl:72-88) is exactly trm_step(ctx, dt, nsteps, 0), so the
     // resident-column program is what a plain call gets whenever it is legal.  Measured: 2.0-4.6 us per step
@@ -553,7 +661,7 @@ template <class NF> struct Ops {
     // (k_land_euler / k_land_pk, trm_column.hpp: one stream, two launches per step as before, each covering the soil columns
     // of one half and the 0-D surface processes of the other)
     static bool interleave_now(trm_ctx* c, int steps_left) {
-        if (c->opt_pipeline == 0 || steps_left < 2 || !c->params.seb || !richards(c) || coupled(c) || c->part_n[1] <= 0) return false;
+        if (c->opt_pipeline == 0 || steps_left < 2 || averaging(c) || !c->params.seb || !richards(c) || coupled(c) || c->part_n[1] <= 0) return false;
         if (!c->series.empty() || generic_bcs(c) || c->Nz > 64) return false;      // (inputs constant over the call; one level per lane)
         if (std::is_same<NF, float>::value && !packed_path(c)) return false;        // (fp32 off the packed kernel: not instantiated)
         // Measured (profiles/r03/exp6_ab_land_interleaved.log, bench_default.json: land_interleaved): within +-2 % at 812 500 columns
@@ -630,6 +738,7 @@ template <class NF> struct Ops {
             rc = std::is_same<NF, float>::value ? PackedLaunch::step_land(c, dt, fin) : FrontLaunch::run(c, dt, fin);
             if (!rc) c->closure_consistent = true;
         } else if (!rc) rc = wave_step(c, dt, fin);
+        if (!rc) rc = accumulate_after(c, dt);
         c->tend_valid = fin != 0;   // only the finalizing launch stores state.tendencies
         c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
         if (!rc && fin && coupled(c)) rc = surface_veg<true, false>(c, c->state, 0.0);
@@ -666,7 +775,9 @@ template <class NF> struct Ops {
         // constants, or device-resident time series the program interpolates itself -- and the branch-free boundary kinds apply.
         // (columns of 65 ... 128 levels: contexts without the surface energy balance and without series)
         const bool program_ok = program_applies(c);
-        const int spl = steps_per_launch_now(c);
+        // open time averages that the multi-step program cannot accumulate itself: one launch per step, k_accumulate behind each
+        const bool avg = averaging(c), avg_in_launch = avg && program_ok && averages_in_launch(c);
+        const int spl = (avg && !avg_in_launch) ? 1 : steps_per_launch_now(c);
         int n = 0, rc = TRM_OK;
         while (n < nsteps && !rc) {
             int m = std::min(spl, nsteps - n);
@@ -679,7 +790,11 @@ template <class NF> struct Ops {
                 if (!rc) c->closure_consistent = true;   // closure! has just run
             } else if (m > 1 || (program_ok && single_step_program(c))) {
                 rc = c->series.empty() ? update_inputs(c, c->state, c->time) : upload_series_rows(c, dt, m);
-                if (!rc) rc = deep_columns(c) ? deep_program(c, dt, fin, m) : column_program<PROG_MULTI>(c, dt, fin, m);
+                if (!rc && avg_in_launch) rc = multi_program_accum(c, dt, fin, m);
+                else if (!rc) {
+                    rc = deep_columns(c) ? deep_program(c, dt, fin, m) : column_program<PROG_MULTI>(c, dt, fin, m);
+                    if (!rc) rc = accumulate_after(c, dt);   // (m = 1 here while averaging)
+                }
                 if (!rc) c->closure_consistent = true;
                 c->tend_valid = fin != 0;
                 c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
@@ -730,6 +845,7 @@ template <class NF> struct Ops {
         const bool in_launch = !rc && surface_in_launch(c, true);      // (k_column_land<..., PROG_HEUN>: the state's surface processes in the launch)
         if (!rc && c->params.seb && !in_launch) rc = surface(c, c->state, true);
         if (!rc) rc = in_launch ? FrontLaunch::run(c, dt, finalize, true) : column_program<PROG_HEUN>(c, dt, finalize, 1);
+        if (!rc) rc = accumulate_after(c, dt);
         if (!rc) c->closure_consistent = true;
         c->tend_valid = finalize != 0;
         c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
@@ -795,6 +911,7 @@ template <class NF> struct Ops {
         rc = surface_veg_launch(c, sv, vg, b);
         if (rc) return rc;
         rc = Veg<NF>::heun_average_0d(c, vs, vg, dt);
+        if (!rc) rc = accumulate_after(c, dt);
         if (rc) return rc;
         if (finalize) rc = surface_veg<true, false>(c, c->state, 0.0);
         return rc;
@@ -805,6 +922,7 @@ template <class NF> struct Ops {
         if (!rc && c->params.seb) rc = surface(c, c->state, true);
         if (rc) return rc;
         rc = GenericLaunch<NF>::heun(c, dt, finalize);
+        if (!rc) rc = accumulate_after(c, dt);
         if (!rc) c->closure_consistent = true;
         c->tend_valid = finalize != 0;
         c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
@@ -853,6 +971,7 @@ template <class NF> struct Ops {
                 if (!rc) rc = average(c, f);
         if (!rc) rc = explicit_step(c, c->state, dt);
         if (!rc) rc = closure(c, c->state);
+        if (!rc) rc = accumulate_after(c, dt);
         if (!rc && finalize) rc = compute_auxiliary(c, c->state);
         return rc;
     }
@@ -1478,6 +1597,10 @@ int trm_destroy(trm_ctx* c) {
     }
     for (void* q : {(void*)c->d_ring_inv, (void*)c->d_ring_idx, c->d_ring})
         if (q) (void)hipFree(q);
+    for (auto& a : c->averages)
+        if (a.d_sum) (void)hipFree(a.d_sum);
+    for (double* q : c->d_acc_partial)
+        if (q) (void)hipFree(q);
 
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->args && c->args_free) c->args_free(c->args);
@@ -1829,6 +1952,12 @@ int trm_reset(trm_ctx* c) {
     TRM_HIP(c, hipMemsetAsync(c->state.kf_top, 0, (size_t)c->Nh * c->esize, c->stream));
     if (c->d_top3) TRM_HIP(c, hipMemsetAsync(c->d_top3, 0, 3 * (size_t)c->Nh * c->esize, c->stream));
     TRM_HIP(c, hipMemsetAsync(c->d_status, 0, sizeof(uint32_t), c->stream));
+    for (auto& a : c->averages) {   // open accumulators start over; their handles stay
+        if (a.field < 0) continue;
+        TRM_HIP(c, hipMemsetAsync(a.d_sum, 0, field_elems(c, a.field) * sizeof(double), c->stream));
+        a.window = 0.0;
+        a.steps = 0;
+    }
     c->time = 0.0;
     c->iteration = 0;
     c->top_valid = false;
@@ -2160,6 +2289,74 @@ int trm_restore_state(trm_ctx* c) {
     c->closure_consistent = c->saved_closure_consistent;
     c->top_valid = false;
     return finish(c, TRM_OK);
+}
+
+// ---- time averages ---------------------------------------------------------------------------------------------------------
+static trm_ctx::Average* average_of(trm_ctx* c, int h, const char* who) {
+    if (h < 0 || h >= (int)c->averages.size() || c->averages[(size_t)h].field < 0) {
+        fail(c, TRM_EINVAL, std::string(who) + ": not an open accumulator handle");
+        return nullptr;
+    }
+    return &c->averages[(size_t)h];
+}
+int trm_average_open(trm_ctx* c, int field, int* handle) {
+    TRM_ENTER_HEUN(c);
+    if (!handle || !valid_field(field)) return fail(c, TRM_EINVAL, "trm_average_open: bad argument");
+    if (!averageable(c, field))
+        return fail(c, TRM_EUNSUPPORTED, "trm_average_open: this field cannot be averaged (soil state, closures, surface excess water, water "
+                                         "table, and the LandModel's surface diagnostics can)");
+    size_t h = 0;
+    while (h < c->averages.size() && c->averages[h].field >= 0) ++h;
+    if (h == c->averages.size()) c->averages.emplace_back();
+    trm_ctx::Average& a = c->averages[h];
+    const size_t bytes = field_elems(c, field) * sizeof(double);
+    TRM_HIP(c, hipMalloc(&a.d_sum, bytes));
+    TRM_HIP(c, hipMemsetAsync(a.d_sum, 0, bytes, c->stream));
+    a.field = field;
+    a.window = 0.0;
+    a.steps = 0;
+    *handle = (int)h;
+    return finish(c, TRM_OK);
+}
+int trm_average_reset(trm_ctx* c, int handle) {
+    TRM_ENTER_HEUN(c);
+    trm_ctx::Average* a = average_of(c, handle, "trm_average_reset");
+    if (!a) return TRM_EINVAL;
+    TRM_HIP(c, hipMemsetAsync(a->d_sum, 0, field_elems(c, a->field) * sizeof(double), c->stream));
+    a->window = 0.0;
+    a->steps = 0;
+    return finish(c, TRM_OK);
+}
+int trm_average_read(trm_ctx* c, int handle, void* host, double* window_seconds, int64_t* steps) {
+    TRM_ENTER_HEUN(c);
+    trm_ctx::Average* a = average_of(c, handle, "trm_average_read");
+    if (!a) return TRM_EINVAL;
+    if (!host) return fail(c, TRM_EINVAL, "trm_average_read: host is NULL");
+    if (a->steps == 0) return fail(c, TRM_ESTALE, "trm_average_read: the window holds no step yet");
+    const size_t n = field_elems(c, a->field);
+    std::vector<double> sum(n);
+    TRM_HIP(c, hipMemcpyAsync(sum.data(), a->d_sum, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    // mean = sum / window, rounded once to the context precision; [rows][Nh] as trm_download
+    const long rows = is_3d(a->field) ? c->Nz : 1, pitch = is_3d(a->field) ? c->Nzp : 1;
+    for (long k = 0; k < rows; ++k)
+        for (long i = 0; i < c->Nh; ++i) {
+            const double m = sum[(size_t)i * pitch + k] / a->window;
+            if (c->precision == TRM_F64) ((double*)host)[(size_t)k * c->Nh + i] = m;
+            else ((float*)host)[(size_t)k * c->Nh + i] = (float)m;
+        }
+    if (window_seconds) *window_seconds = a->window;
+    if (steps) *steps = a->steps;
+    return TRM_OK;
+}
+int trm_average_close(trm_ctx* c, int handle) {
+    TRM_ENTER_HEUN(c);
+    trm_ctx::Average* a = average_of(c, handle, "trm_average_close");
+    if (!a) return TRM_EINVAL;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    TRM_HIP(c, hipFree(a->d_sum));
+    *a = trm_ctx::Average{};
+    return TRM_OK;
 }
 
 int trm_clock(const trm_ctx* c, double* time, int64_t* iteration) {

@@ -21,6 +21,7 @@
 // anything else takes k_step_wave (trm_kernels.hpp).
 #pragma once
 #include "trm_kernels.hpp"
+#include "trm_average.hpp"
 
 namespace trm {
 
@@ -272,13 +273,17 @@ template <class NF> struct ColumnArgs {
 // wave-uniform run-time branches they cost the field loads their back-to-back issue (profiles/r03/exp28: 8 x N145 +7 %).
 // FRONT (LandModel, BCSIG_LAND): ground heat flux, infiltration and the new skin temperature come from the surface workgroups of THIS
 // launch (surface_front, trm_kernels.hpp) as granules; the kernel's fourth argument is then a FrontArgs.
-template <class NF, bool RICHARDS, int HYD, int LPC, int DERIVE, int PROG, bool SEB_INLINE, bool SERIES = false, bool STAGED = false, bool SCALAR_IN = true, int BCSIG = BCSIG_RUNTIME, bool FRONT = false>
+// ACCUM (PROG_MULTI): time averages accumulated in the launch -- every step adds dt * x of the requested fields into register
+// partials that leave once per launch (trm_average.hpp); the kernel's fourth argument is then an AccumArgs.
+template <class NF, bool RICHARDS, int HYD, int LPC, int DERIVE, int PROG, bool SEB_INLINE, bool SERIES = false, bool STAGED = false, bool SCALAR_IN = true, int BCSIG = BCSIG_RUNTIME, bool FRONT = false, bool ACCUM = false>
 TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, const ColumnArgs<NF>& a, unsigned block) {
     // (kernarg layout: the arguments in order, each at its natural alignment)
     constexpr unsigned off_p = round_up_to((unsigned)sizeof(View<NF>), (unsigned)alignof(DevParams<NF>));
     constexpr unsigned off_args = round_up_to(off_p + (unsigned)sizeof(DevParams<NF>), (unsigned)alignof(ColumnArgs<NF>));
     constexpr unsigned off_front = round_up_to(off_args + (unsigned)sizeof(ColumnArgs<NF>), (unsigned)alignof(FrontArgs));
     static_assert(!FRONT || (PROG != PROG_MULTI && BCSIG == BCSIG_LAND && RICHARDS && !SEB_INLINE && sizeof(NF) == 8), "the in-launch surface processes feed the per-step fp64 LandModel programs");
+    static_assert(!ACCUM || (PROG == PROG_MULTI && !FRONT && !STAGED), "averages are accumulated in the multi-step program");
+    constexpr unsigned off_acc = round_up_to(off_args + (unsigned)sizeof(ColumnArgs<NF>), (unsigned)alignof(AccumArgs));
     const View<NF>& v = v_arg;
     const DevParams<NF>& p = p_arg;
     static_assert(!SEB_INLINE || PROG == PROG_MULTI, "the in-kernel surface energy balance belongs to the multi-step program");
@@ -544,6 +549,15 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
 
     NF over = NF(0), over_stage = NF(0);   // (top lane) overflow of the column into surface_excess_water
     Frac<NF> f_new{};                      // volumetric fractions of the new state (its closure forms them)
+    // ACCUM: partials of the 3-D slots (per lane) and of the 2-D slots (lane k of a column holds slot ACC_S + k)
+    double accU = 0.0, accSat = 0.0, accT = 0.0, accLiq = 0.0, accPsi = 0.0, acc2 = 0.0;
+    // (the top lane's value to every lane of its column, added by the lane that holds the slot)
+    auto acc_top = [&](unsigned am, double w, int slot, NF x) {
+        if (am & (1u << slot)) {
+            const NF xt = shfl_from<NF, LPC>(x, Nz - 1);
+            if (ln.k == slot - ACC_S) acc2 = acc2 + w * (double)xt;
+        }
+    };
     if (PROG == PROG_HEUN) {
         // stage 1: tendencies at the state, Euler predictor (with the state's boundary fluxes) and its closures
         t = column_tendencies<NF, RICHARDS, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, need_kc, viol, DERIVE_TL ? &f_in : nullptr);
@@ -632,6 +646,18 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
                     stg(v.Hs, ib, o.Hs); stg(v.Hl, ib, o.Hl); stg(v.evap, ib, o.evap); stg(v.infil, ib, o.infil); stg(v.runoff, ib, o.runoff);
                 }
                 sf.out.Ts = sf.out.Ts + NF(0) * dt;   // zero-tendency prognostic skin_temperature
+                if constexpr (ACCUM) {
+                    // the surface diagnostics of this step as its surface processes formed them (here, where they are live anyway)
+                    const AccumArgs& aa = kernarg_reload<AccumArgs>(off_acc);
+                    const unsigned am = aa.mask;
+                    if (am >> ACC_TS) {
+                        const double w = aa.dt;
+                        const SebOut<NF>& o = sf.out;
+                        acc_top(am, w, ACC_TS, o.Ts); acc_top(am, w, ACC_GHF, o.ghf); acc_top(am, w, ACC_SWU, o.swu); acc_top(am, w, ACC_LWU, o.lwu);
+                        acc_top(am, w, ACC_RNET, o.rnet); acc_top(am, w, ACC_HS, o.Hs); acc_top(am, w, ACC_HL, o.Hl); acc_top(am, w, ACC_EVAP, o.evap);
+                        acc_top(am, w, ACC_INFIL, o.infil); acc_top(am, w, ACC_RUNOFF, o.runoff);
+                    }
+                }
             }
             TRM_PHASE_FENCE("tendencies", c.U, c.sat, c.psi, c.T, c.liq, bc.bTb, bc.bTt, bc.flux_U, bc.flux_S, S_in, Ts_in);
             // (the cell's fractions: from the derivation at entry, from the previous step's closure inside the multi-step loop)
@@ -650,6 +676,18 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
             TRM_PHASE_FENCE("closure", n.U, n.sat, z0, over, gU, gS);
             f_new = column_closure<NF, RICHARDS, HYD>(kernarg_reload<DevParams<NF>>(off_p), L, z0, n, viol);
             gU_out = gU; gS_out = gS;
+            if constexpr (ACCUM) {
+                // the step's terms dt * x, x after the step (the surface diagnostics as this step's surface processes formed them)
+                const AccumArgs& aa = kernarg_reload<AccumArgs>(off_acc);
+                const unsigned am = aa.mask;
+                const double w = aa.dt;
+                if (am & (1u << ACC_U)) accU = accU + w * (double)n.U;
+                if (am & (1u << ACC_SAT)) accSat = accSat + w * (double)n.sat;
+                if (am & (1u << ACC_T)) accT = accT + w * (double)n.T;
+                if (am & (1u << ACC_LIQ)) accLiq = accLiq + w * (double)n.liq;
+                if (am & (1u << ACC_PSI)) accPsi = accPsi + w * (double)n.psi;
+                if (RICHARDS) { acc_top(am, w, ACC_S, S); acc_top(am, w, ACC_WT, z0); }
+            }
         }
     }
     TRM_PHASE_FENCE("outputs", n.U, n.sat, n.T, n.liq, n.psi);
@@ -745,6 +783,20 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
                                  (seb ? (1u << SMALL_TOP_T) | (1u << SMALL_TOP_SAT) | (1u << SMALL_TOP_LIQ) | (1u << SMALL_TS) : 0u);
         store_small_outputs<NF, (TRM_STEP_BLOCK / 64) * CPW>(enabled, block, Nh);
     }
+    if constexpr (ACCUM) {
+        // the partials leave once per launch: acc = acc + P (real cells; the 2-D slots from lane k = slot - ACC_S of a real column)
+        const AccumArgs& aa = kernarg_reload<AccumArgs>(off_acc);
+        const unsigned am = aa.mask;
+        if (ln.act) {
+            const size_t e = (size_t)ii * (size_t)v_arg.Nzp + (size_t)ln.k;
+            auto out3 = [&](int s, double x) { if (am & (1u << s)) { double* d = aa.dst[s]; d[e] = d[e] + x; } };
+            out3(ACC_U, accU); out3(ACC_SAT, accSat); out3(ACC_T, accT); out3(ACC_LIQ, accLiq); out3(ACC_PSI, accPsi);
+        }
+        if (i < Nh) {
+            for (int s = ACC_S; s < ACC_SLOTS; ++s)
+                if ((am & (1u << s)) && ln.k == s - ACC_S) { double* d = aa.dst[s]; d[ii] = d[ii] + acc2; }
+        }
+    }
     // (only real cells report: the clamped copies that tail lanes carry are not repaired and may be out of bounds)
     if (viol && ln.act) atomicOr(v_arg.status, viol);
 }
@@ -757,6 +809,17 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK)
 #endif
     k_column(View<NF> v_arg, DevParams<NF> p_arg, ColumnArgs<NF> a) {
     column_program<NF, RICHARDS, HYD, LPC, DERIVE, PROG, SEB_INLINE, SERIES, STAGED, SCALAR_IN, BCSIG>(v_arg, p_arg, a, xcd_block<TRM_XCD_REMAP != 0>(blockIdx.x, gridDim.x));
+}
+
+// The multi-step program with time averages accumulated in the launch (ACCUM): the kinds read at run time, nothing derived, the
+// outputs stored directly -- the configuration every PROG_MULTI launch has; the fourth argument says where the partials go.
+template <class NF, bool RICHARDS, int HYD, int LPC, bool SEB_INLINE, bool SERIES>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK)
+    __attribute__((amdgpu_waves_per_eu(HYD == HYD_BC_LINEAR ? 4 : 3, 8)))
+    k_column_accum(View<NF> v_arg, DevParams<NF> p_arg, ColumnArgs<NF> a, AccumArgs acc) {
+    (void)acc;   // (read through kernarg_reload)
+    column_program<NF, RICHARDS, HYD, LPC, DERIVE_NONE, PROG_MULTI, SEB_INLINE, SERIES, false, true, BCSIG_RUNTIME, false, true>(
+        v_arg, p_arg, a, xcd_block<TRM_XCD_REMAP != 0>(blockIdx.x, gridDim.x));
 }
 
 // ---- LandModel, ONE launch per step (TRM_OPT_SURFACE_IN_LAUNCH): the first workgroups evaluate the 0-D surface processes of 256

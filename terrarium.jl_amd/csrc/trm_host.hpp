@@ -141,6 +141,11 @@ struct trm_ctx {
     uint32_t front_epoch = 0;               // epoch of the last such launch
     int opt_front = 2;                      // 0 off, 1 whenever legal, 2 the library's rule
     int last_program = 0;                   // TRM_INFO_LAST_PROGRAM: the kernel instance the last step launch selected
+    // time averages (trm_average_*): handle = index; field -1 marks a closed slot.  d_sum is [field_elems] doubles in the field's
+    // device layout.
+    struct Average { int field = -1; double* d_sum = nullptr; double window = 0.0; int64_t steps = 0; };
+    std::vector<Average> averages;
+    double* d_acc_partial[trm::ACC_SLOTS] = {};   // the fused path's partials of a field with more than one open accumulator
     bool args_valid = false;
     void* args = nullptr;   // LaunchArgs<NF>*, owned
     void (*args_free)(void*) = nullptr;
@@ -453,6 +458,11 @@ template <class NF> struct Veg {
 };
 // the register-resident column programs k_column (trm_launch_column*.hip: one file per precision x program)
 template <class NF, bool RICH, int PROG> struct ColumnLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps); };
+// the multi-step program with time averages accumulated in the launch (trm_launch_column_accum_*.hip)
+template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps, const AccumArgs& acc); };
+// k_accumulate (trm_launch_average.hip)
+template <class NF> struct AverageLaunch { static int accumulate(trm_ctx* c, const AccumBatch& b); };
+constexpr int TRM_PROGRAM_BIT_AVERAGES_IN_LAUNCH = TRM_PROGRAM_AVERAGES_IN_LAUNCH;
 // the ForwardEuler program with the derivation of T / liq and the boundary-condition signature compiled in (BCSIG, trm_kernels.hpp):
 // one explicit instantiation per signature in the trm_launch_column_sig_*.hip files; `supported` lists them.
 template <class NF, bool RICH, int SIG> struct ColumnSigLaunch {

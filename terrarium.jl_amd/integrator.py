@@ -154,6 +154,9 @@ class DeviceState:
 
     def close(self):
         if getattr(self, "_ctx", None):
+            for h in list(self.__dict__.get("_averages", ())):
+                self._lib.trm_average_close(self._ctx, h)
+            self.__dict__.pop("_averages", None)
             self._lib.trm_destroy(self._ctx)
             self._ctx = None
 
@@ -382,6 +385,31 @@ class DeviceState:
     def explicit_step(self, dt): self._check(self._lib.trm_explicit_step(self._ctx, float(dt)), "trm_explicit_step")
     def closure(self): self._check(self._lib.trm_closure(self._ctx), "trm_closure")
     def invclosure(self): self._check(self._lib.trm_invclosure(self._ctx), "trm_invclosure")
+
+    # -- time averages (trm_average_*): sums over the steps of a window, accumulated on the device ----------------------------------
+    def open_average(self, name) -> int:
+        """An accumulator of field `name` (zero, empty window): every step from now on adds dt * (the field after the step)."""
+        h = C.c_int()
+        self._check(self._lib.trm_average_open(self._ctx, _capi.FIELD[name], C.byref(h)), "trm_average_open")
+        self.__dict__.setdefault("_averages", {})[h.value] = name
+        return h.value
+
+    def reset_average(self, handle):
+        """Starts a new window: sum and window length to zero."""
+        self._check(self._lib.trm_average_reset(self._ctx, int(handle)), "trm_average_reset")
+
+    def average(self, handle):
+        """(mean [rows][Nh] -- [Nh] for a 2-D field --, window length in seconds, steps) of the accumulator's window so far."""
+        name = self.__dict__.get("_averages", {}).get(int(handle))
+        rows = self.rows(name) if name is not None else 1
+        a = np.empty((rows, self.grid.Nh), dtype=self.dtype)
+        w, n = C.c_double(), C.c_int64()
+        self._check(self._lib.trm_average_read(self._ctx, int(handle), a.ctypes.data, C.byref(w), C.byref(n)), "trm_average_read")
+        return (a[0] if rows == 1 else a), float(w.value), int(n.value)
+
+    def close_average(self, handle):
+        self._check(self._lib.trm_average_close(self._ctx, int(handle)), "trm_average_close")
+        self.__dict__.get("_averages", {}).pop(int(handle), None)
 
     def step(self, dt, nsteps=1, finalize=True):
         self._check(self._lib.trm_step(self._ctx, float(dt), int(nsteps), int(finalize)), "trm_step")

@@ -3,9 +3,10 @@
 In the reference `ModelIntegrator` implements Oceananigans' `AbstractModel` interface (`time_step!`, `update_state!`,
 `iteration`, `time`: src/timesteppers/model_integrator.jl:39-66) so that an Oceananigans `Simulation` can drive it with
 callbacks and output writers (examples/simulations/soil_heat_global.jl:117-123, examples/extending/*.jl).  This module is
-that driver for the device-resident integrator: schedules (`IterationInterval`, `TimeInterval`), callbacks, and an output
-writer that takes snapshots of state variables -- optionally scattered to the full ring grid
-(`RingGrids.Field(field, grid)`, src/grids/column_ring_grid.jl:102-115).
+that driver for the device-resident integrator: schedules (`IterationInterval`, `TimeInterval`, `AveragedTimeInterval`),
+callbacks, and an output writer that takes snapshots of state variables -- or, on an `AveragedTimeInterval`, their time means
+accumulated on the device -- optionally scattered to the full ring grid (`RingGrids.Field(field, grid)`,
+src/grids/column_ring_grid.jl:102-115).
 
 The loop hands the library as many steps per call as fit before the next scheduled event (one `trm_step` /
 `trm_step_heun` call; with TRM_OPT_STEPS_PER_LAUNCH the columns stay in registers across them); time steps are aligned
@@ -59,6 +60,57 @@ class TimeInterval:
         return max(1, int(math.ceil((self.next_time() - time) / dt - 1e-12)))
 
 
+class AveragedTimeInterval:
+    """Time averages over windows of `window` seconds that end every `interval` seconds (Oceananigans.OutputWriters.
+    AveragedTimeInterval; docs/src/running/time_stepping.md of the reference).  Window k (k = 1, 2, ...) spans
+    [first + k * interval - window, first + k * interval]; `window` defaults to `interval` (back-to-back windows).  Both
+    window starts and window ends are event times, so that `Simulation.run` lands on both.  The mean itself is accumulated
+    on the device by the library (DeviceState.open_average): every step adds dt * (the field after the step)."""
+
+    def __init__(self, interval: float, window: Optional[float] = None):
+        self.interval = float(interval)
+        self.window = self.interval if window is None else float(window)
+        if not self.interval > 0:
+            raise ValueError("AveragedTimeInterval: interval must be > 0")
+        if not 0 < self.window <= self.interval:
+            raise ValueError("AveragedTimeInterval: the window must satisfy 0 < window <= interval")
+        self.first = 0.0
+        self.actuations = 0          # windows that have ended
+        self.collecting = False      # inside a window
+
+    def window_start(self, k):
+        return self.first + k * self.interval - self.window
+
+    def window_end(self, k):
+        return self.first + k * self.interval
+
+    def next_time(self, time=None):
+        k = self.actuations + 1
+        return self.window_end(k) if self.collecting else self.window_start(k)
+
+    def actuates(self, time, iteration):
+        return time >= self.next_time()
+
+    def steps_until_next(self, time, iteration, dt):
+        return max(1, int(math.ceil((self.next_time() - time) / dt - 1e-12)))
+
+    def due(self, time):
+        """The events at `time`, in order, as [("end", k) | ("start", k)], and the schedule moved past them (a window that ends
+        where the next one starts: its end first)."""
+        events = []
+        while True:
+            k = self.actuations + 1
+            if self.collecting and time >= self.window_end(k):
+                self.collecting = False
+                self.actuations = k
+                events.append(("end", k))
+            elif not self.collecting and time >= self.window_start(k):
+                self.collecting = True
+                events.append(("start", k))
+            else:
+                return events
+
+
 class Callback:
     """Callback(func, schedule): `func(sim)` whenever the schedule actuates (Oceananigans.Simulations.Callback)."""
 
@@ -69,12 +121,42 @@ class Callback:
 class SnapshotWriter:
     """Output writer (stand-in for Oceananigans' JLD2Writer / NetCDFWriter): on every actuation of `schedule` the named
     state variables are downloaded and kept as `[n_snapshots][rows][Nh]` (or scattered to `[rows][nlat][nlon]` when
-    `ring_grid` is given); `write()` stores them with the snapshot times in an .npz file."""
+    `ring_grid` is given); `write()` stores them with the snapshot times in an .npz file.
+    With an `AveragedTimeInterval` schedule the writer keeps one device accumulator per variable: a window start opens (or
+    resets) it, a window end records the window's mean with the end as its time and the start in `window_starts`."""
 
     def __init__(self, fields: Sequence[str], schedule, filename: Optional[str] = None, ring_grid=None, fill=np.nan):
         self.fields, self.schedule, self.filename, self.ring_grid, self.fill = list(fields), schedule, filename, ring_grid, fill
         self.times, self.iterations = [], []
         self.data: Dict[str, list] = {f: [] for f in self.fields}
+        self.window_starts = []
+        self._handles: Dict[str, int] = {}
+        self._start = None
+
+    def averaged(self, sim, events):
+        """The AveragedTimeInterval events of this moment (AveragedTimeInterval.due)."""
+        st = sim.integrator.state
+        t, it = st.clock()
+        for kind, _ in events:
+            if kind == "start":
+                for f in self.fields:
+                    field = st._alias(f)[0]
+                    if f in self._handles:
+                        st.reset_average(self._handles[f])
+                    else:
+                        self._handles[f] = st.open_average(field)
+                self._start = t
+                continue
+            self.times.append(t)
+            self.iterations.append(it)
+            self.window_starts.append(self._start)
+            for f in self.fields:
+                field, row0, rows = st._alias(f)
+                mean, _, _ = st.average(self._handles[f])
+                if field != f:      # a view of some rows of the field (ground_temperature: the top row of temperature)
+                    mean = np.asarray(mean).reshape(-1, st.grid.Nh)[row0:row0 + rows]
+                    mean = mean[0] if rows == 1 else mean
+                self.data[f].append(self.ring_grid.scatter(mean, self.fill) if self.ring_grid is not None else mean)
 
     def __call__(self, sim):
         t, it = sim.integrator.state.clock()
@@ -93,7 +175,8 @@ class SnapshotWriter:
 
     def write(self):
         if self.filename:
-            np.savez(self.filename, time=np.array(self.times), iteration=np.array(self.iterations),
+            extra = dict(window_start=np.array(self.window_starts)) if isinstance(self.schedule, AveragedTimeInterval) else {}
+            np.savez(self.filename, time=np.array(self.times), iteration=np.array(self.iterations), **extra,
                      **{f: np.stack(v) for f, v in self.data.items() if v})
 
 
@@ -130,6 +213,16 @@ class Simulation:
         advanced, so schedules that depend on the iteration alone have already fired for it and must not fire twice."""
         t, it = self.integrator.state.clock()
         for schedule, func in self._events():
+            if isinstance(schedule, AveragedTimeInterval):
+                # window starts and ends; nothing is recorded at initialisation (a window of zero length is never asked for)
+                if initial:
+                    schedule.first, schedule.actuations, schedule.collecting = t, 0, False
+                events = schedule.due(t)
+                if isinstance(func, SnapshotWriter):
+                    func.averaged(self, events)
+                elif any(kind == "end" for kind, _ in events):
+                    func(self)
+                continue
             if initial:
                 if isinstance(schedule, TimeInterval):
                     schedule.first, schedule.actuations = t, 0
