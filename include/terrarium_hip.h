@@ -233,7 +233,7 @@ enum {
     TRM_PROGRAM_NONE = 0, TRM_PROGRAM_COLUMN_EULER = 1, TRM_PROGRAM_COLUMN_HEUN = 2, TRM_PROGRAM_COLUMN_MULTI = 3,
     TRM_PROGRAM_PACKED_F32 = 4, TRM_PROGRAM_GENERIC_EULER = 5, TRM_PROGRAM_GENERIC_HEUN = 6, TRM_PROGRAM_COLUMN_LAND = 7,
     TRM_PROGRAM_DEEP = 8, TRM_PROGRAM_WIDE = 9, TRM_PROGRAM_LAND_INTERLEAVED = 10, TRM_PROGRAM_UNFUSED = 11, TRM_PROGRAM_VEGETATION = 12,
-    TRM_PROGRAM_PACKED_LAND = 13
+    TRM_PROGRAM_PACKED_LAND = 13, TRM_PROGRAM_COLUMN_TANGENT = 14
 };
 /* bits of TRM_INFO_LAST_PROGRAM beside the ones above (25-27 are per family: surface processes inline / time series in the multi-step
  * program, the program and the generic boundaries of the deep and wide columns): how the step's time averages were accumulated
@@ -562,6 +562,40 @@ int trm_average_open(trm_ctx* ctx, int field, int* handle);
 int trm_average_reset(trm_ctx* ctx, int handle);
 int trm_average_read(trm_ctx* ctx, int handle, void* host, double* window_seconds, int64_t* steps);
 int trm_average_close(trm_ctx* ctx, int handle);
+
+/* ---- forward-mode tangents of the heat-only step (the reference differentiates timestep! with Enzyme) -----------------------------
+ * Tangents with respect to the initial internal energy of a SoilModel with NoFlow, ForwardEuler, fp64, Nz <= 64, every boundary kind
+ * of the heat-only programs (NoFlux, Value / Gradient on temperature, Flux on energy) and both halo policies.  Boundary values are
+ * constants: their tangent is 0.
+ *   trm_tangent_open(ctx)                   allocates the three tangent fields below, Nz rows each, zero
+ *   trm_tangent_close(ctx)                  frees them
+ *   trm_tangent_upload / _download(ctx, which, host)
+ *                                           host layout [Nz][Nh] as trm_upload / trm_download of a 3-D field
+ *   trm_tangent_device_ptr(ctx, which, &dev, &pitch)
+ *                                           device layout as trm_field_device_ptr: element (level k, column i) at dev[i * pitch + k]
+ *   trm_tangent_closure(ctx)                dT and dliq from the stored U and dU: the tangent of trm_closure
+ *   trm_step_tangent(ctx, dt, nsteps)       nsteps ForwardEuler steps of the state and its tangent.  The state afterwards -- every
+ *                                           field, the status word, the clock -- is that of trm_step(ctx, dt, nsteps, 1), bit for bit;
+ *                                           dU, dT, dliq are the tangents of the new U, T, liq.  The stored T and liq are taken to
+ *                                           be the closure of the stored U (true after trm_initialize, trm_closure and every step).
+ * The tangent follows the branch of the closure the primal takes in every cell: dT = dU / C thawed or frozen, 0 in phase change;
+ * dliq = -dU / (-L_theta + eps) in phase change, 0 otherwise (and where L_theta = 0).
+ * TRM_INFO_LAST_PROGRAM of a trm_step_tangent is TRM_PROGRAM_COLUMN_TANGENT (bit 25: Gradient halos on temperature, where trm_step
+ * takes the generic-boundary kernel).  Up to TRM_OPT_STEPS_PER_LAUNCH steps per launch (0: as trm_step).
+ * Errors: TRM_EINVAL without a context or an open tangent; TRM_EUNSUPPORTED for fp32, Richards, the LandModel or vegetation,
+ * Nz > 64, an attached time series, an open time average, a Value or Gradient condition on saturation, liquid fraction or pressure
+ * head, or a per-cell vwc_forcing field.  Every other call that changes the state -- trm_step, trm_step_heun, the two-call Heun,
+ * trm_explicit_step, trm_initialize, trm_invclosure, trm_upload of internal energy or saturation, trm_restore_state, trm_reset --
+ * makes the tangent stale: trm_tangent_download of dT or dliq, trm_tangent_closure and trm_step_tangent return TRM_ESTALE until a
+ * new trm_tangent_upload of dU seeds it again. */
+enum { TRM_TANGENT_INTERNAL_ENERGY = 0, TRM_TANGENT_TEMPERATURE = 1, TRM_TANGENT_LIQUID_WATER_FRACTION = 2 };
+int trm_tangent_open(trm_ctx* ctx);
+int trm_tangent_close(trm_ctx* ctx);
+int trm_tangent_upload(trm_ctx* ctx, int which, const void* host);
+int trm_tangent_download(trm_ctx* ctx, int which, void* host);
+int trm_tangent_device_ptr(trm_ctx* ctx, int which, void** dev, int64_t* pitch_elems);
+int trm_tangent_closure(trm_ctx* ctx);
+int trm_step_tangent(trm_ctx* ctx, double dt, int nsteps);
 
 int trm_clock(const trm_ctx* ctx, double* time, int64_t* iteration);
 int trm_set_clock(trm_ctx* ctx, double time, int64_t iteration);

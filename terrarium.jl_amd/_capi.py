@@ -47,7 +47,7 @@ OPTION = dict(asynchronous=0, step_kernel=1, write_kf_every_step=2, vwc_forcing_
 KERNEL = dict(fused=0, unfused=1)
 # TRM_INFO_LAST_PROGRAM (include/terrarium_hip.h: TRM_PROGRAM_*; trm_host.hpp: program_id)
 PROGRAM = ("none", "column_euler", "column_heun", "column_multi", "packed_f32", "generic_euler", "generic_heun", "column_land", "deep", "wide",
-           "land_interleaved", "unfused", "vegetation", "packed_land")
+           "land_interleaved", "unfused", "vegetation", "packed_land", "column_tangent")
 DERIVE = ("none", "T_liq", "liq", "liq_psi", "all")
 
 
@@ -59,6 +59,8 @@ def decode_program(pid: int) -> dict:
         d.update(surface_inline=bool(extra & 1), series=bool(extra & 2))
     if d["family"] == "column_land":
         d.update(program=("euler", "heun", "multi")[extra & 3])
+    if d["family"] == "column_tangent":
+        d.update(generic_boundaries=bool(extra & 1))
     if d["family"] in ("deep", "wide"):
         d.update(program=("euler", "heun", "multi")[extra & 3], generic_boundaries=bool(extra & 4))
     if pid & (PROGRAM_AVERAGES_IN_LAUNCH | PROGRAM_AVERAGES_AFTER_LAUNCH):
@@ -82,7 +84,11 @@ EXPORTS = (
     "trm_scatter_ring_device trm_upload_ring trm_gather_ring_device "
     "trm_heun_predict trm_heun_stage_auxiliary trm_heun_correct trm_stage_field_device_ptr trm_stage_bc_device_ptr trm_set_forcing_device "
     "trm_series_window trm_comm_init_all trm_step_all trm_step_heun_all trm_synchronize_all trm_reduce_global_all trm_status_global_all "
-    "trm_average_open trm_average_reset trm_average_read trm_average_close").split()
+    "trm_average_open trm_average_reset trm_average_read trm_average_close "
+    "trm_tangent_open trm_tangent_close trm_tangent_upload trm_tangent_download trm_tangent_device_ptr trm_tangent_closure "
+    "trm_step_tangent").split()
+# forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
+TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
 TIME_INDEXING = dict(linear=0, clamp=1, cyclical=2, raster=3)
 
 
@@ -230,6 +236,13 @@ def lib():
     L.trm_average_reset.argtypes = [vp, i32]
     L.trm_average_read.argtypes = [vp, i32, vp, C.POINTER(dbl), C.POINTER(i64)]
     L.trm_average_close.argtypes = [vp, i32]
+    L.trm_tangent_open.argtypes = [vp]
+    L.trm_tangent_close.argtypes = [vp]
+    L.trm_tangent_upload.argtypes = [vp, i32, vp]
+    L.trm_tangent_download.argtypes = [vp, i32, vp]
+    L.trm_tangent_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
+    L.trm_tangent_closure.argtypes = [vp]
+    L.trm_step_tangent.argtypes = [vp, dbl, i32]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

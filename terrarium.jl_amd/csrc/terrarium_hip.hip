@@ -1601,6 +1601,8 @@ int trm_destroy(trm_ctx* c) {
         if (a.d_sum) (void)hipFree(a.d_sum);
     for (double* q : c->d_acc_partial)
         if (q) (void)hipFree(q);
+    for (double* q : c->d_tan)
+        if (q) (void)hipFree(q);
 
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->args && c->args_free) c->args_free(c->args);
@@ -1633,6 +1635,7 @@ int trm_upload(trm_ctx* c, int field, const void* host) {
     c->heun_pending = false;
     int rc = c->precision == TRM_F64 ? upload_impl<double>(c, field, (const double*)host) : upload_impl<float>(c, field, (const float*)host);
     if (field <= TRM_FIELD_PRESSURE_HEAD || field == TRM_FIELD_WATER_TABLE) c->closure_consistent = false;   // (U, sat, T, liq, psi, water table)
+    if (field == TRM_FIELD_INTERNAL_ENERGY || field == TRM_FIELD_SATURATION_WATER_ICE) c->tan_stale = true;
     if (!rc && field == TRM_FIELD_VWC_FORCING) {
         c->opt_vwc_field = 1;
         c->args_valid = false;
@@ -1963,6 +1966,7 @@ int trm_reset(trm_ctx* c) {
     c->top_valid = false;
     c->tend_valid = true;
     c->closure_consistent = false;
+    c->tan_stale = true;
     return finish(c, TRM_OK);
 }
 
@@ -2026,6 +2030,7 @@ static int gather_ring(trm_ctx* c, int field, const void* full, bool device, con
     if (field == TRM_FIELD_ROOT_FRACTION) return fail(c, TRM_EINVAL, std::string(who) + ": root_fraction is derived from the root distribution parameters");
     int rc = c->precision == TRM_F64 ? gather_ring_impl<double>(c, field, full, device) : gather_ring_impl<float>(c, field, full, device);
     if (field <= TRM_FIELD_PRESSURE_HEAD || field == TRM_FIELD_WATER_TABLE) c->closure_consistent = false;
+    if (field == TRM_FIELD_INTERNAL_ENERGY || field == TRM_FIELD_SATURATION_WATER_ICE) c->tan_stale = true;
     if (!rc && field == TRM_FIELD_VWC_FORCING) { c->opt_vwc_field = 1; c->args_valid = false; }
     c->top_valid = false;
     if (!rc && is_tendency(field)) c->tend_valid = true;
@@ -2044,6 +2049,7 @@ int trm_initialize(trm_ctx* c) {
     TRM_ENTER(c);
     c->top_valid = false;
     c->closure_consistent = false;   // temperature is the user's, internal_energy follows from it
+    c->tan_stale = true;
     return finish(c, DISPATCH(c, initialize(c)));
 }
 int trm_update_inputs(trm_ctx* c) {
@@ -2082,6 +2088,7 @@ int trm_explicit_step(trm_ctx* c, double dt) {
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, template veg_launch<VEG_EXPLICIT>(c, dt, 1, 0)));
     c->top_valid = false;
     c->closure_consistent = false;
+    c->tan_stale = true;
     return finish(c, DISPATCH(c, explicit_step(c, c->state, dt)));
 }
 int trm_closure(trm_ctx* c) {
@@ -2094,12 +2101,14 @@ int trm_invclosure(trm_ctx* c) {
     TRM_ENTER(c);
     c->top_valid = false;
     c->closure_consistent = false;
+    c->tan_stale = true;
     return finish(c, DISPATCH(c, invclosure(c, c->state)));
 }
 
 int trm_step(trm_ctx* c, double dt, int nsteps, int finalize) {
     TRM_ENTER(c);
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step: nsteps < 0");
+    c->tan_stale = true;
     return finish(c, DISPATCH(c, step(c, dt, nsteps, finalize)));
 }
 
@@ -2121,6 +2130,7 @@ int wait_polling(trm_ctx* c, hipEvent_t ev) {
 int trm_step_timed(trm_ctx* c, double dt, int nsteps, int finalize, float* ms) {
     TRM_ENTER(c);
     if (nsteps < 0 || !ms) return fail(c, TRM_EINVAL, "trm_step_timed: bad argument");
+    c->tan_stale = true;
     TRM_HIP(c, hipEventRecord(c->ev0, c->stream));
     int rc = DISPATCH(c, step(c, dt, nsteps, finalize));
     if (rc) return rc;
@@ -2133,6 +2143,7 @@ int trm_step_timed(trm_ctx* c, double dt, int nsteps, int finalize, float* ms) {
 int trm_step_heun(trm_ctx* c, double dt, int nsteps, int finalize) {
     TRM_ENTER(c);
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_heun: nsteps < 0");
+    c->tan_stale = true;
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, veg_step(c, dt, nsteps, finalize, true)));
     const bool generic = c->precision == TRM_F64 ? Ops<double>::generic_bcs(c) : Ops<float>::generic_bcs(c);
     // (the one-launch programs keep the stage in registers; the coupled vegetation stores part of it, the reference-order
@@ -2188,6 +2199,7 @@ int trm_heun_predict(trm_ctx* c, double dt) {
     c->top_valid = false;
     c->tend_valid = true;
     c->closure_consistent = false;     // (the state is untouched so far; the flag is set again by trm_heun_correct)
+    c->tan_stale = true;
     const int rc = DISPATCH(c, heun_predict(c, dt, true));
     if (rc) return rc;
     c->heun_pending = true;
@@ -2211,6 +2223,7 @@ int trm_heun_correct(trm_ctx* c, double dt, int finalize) {
     if (!c->heun_pending) return fail(c, TRM_EINVAL, "trm_heun_correct: call trm_heun_predict first");
     if (dt != c->heun_dt) return fail(c, TRM_EINVAL, "trm_heun_correct: dt differs from the dt of trm_heun_predict");
     c->heun_pending = false;
+    c->tan_stale = true;
     const int rc = DISPATCH(c, heun_correct(c, dt, finalize, c->heun_stage_aux));
     c->heun_stage_aux = false;
     if (rc) return rc;
@@ -2288,6 +2301,7 @@ int trm_restore_state(trm_ctx* c) {
     c->tend_valid = c->saved_tend_valid;
     c->closure_consistent = c->saved_closure_consistent;
     c->top_valid = false;
+    c->tan_stale = true;
     return finish(c, TRM_OK);
 }
 
@@ -2357,6 +2371,126 @@ int trm_average_close(trm_ctx* c, int handle) {
     TRM_HIP(c, hipFree(a->d_sum));
     *a = trm_ctx::Average{};
     return TRM_OK;
+}
+
+// ---- forward-mode tangents of the heat-only step (trm_column_tangent.hpp) ---------------------------------------------------
+namespace {
+// what the tangent program covers: the heat-only fp64 SoilModel in columns of one level per lane
+const char* tangent_unsupported(const trm_ctx* c) {
+    if (c->precision != TRM_F64) return "fp64 contexts only";
+    if (c->params.flow == TRM_FLOW_RICHARDS) return "the heat-only SoilModel (NoFlow) only";
+    if (c->params.seb || c->veg_mode != TRM_VEGETATION_OFF) return "not the LandModel or vegetation";
+    if (c->Nz > 64) return "columns of at most 64 levels";
+    return nullptr;
+}
+// ... and what a step needs besides: constant inputs, no accumulation, the temperature halos of the heat-only programs
+const char* tangent_step_unsupported(const trm_ctx* c) {
+    if (const char* why = tangent_unsupported(c)) return why;
+    if (!c->series.empty()) return "no time series may be attached";
+    for (const auto& a : c->averages)
+        if (a.field >= 0) return "no time average may be open";
+    if (c->opt_vwc_field) return "no per-cell vwc_forcing field";
+    for (int side = 0; side < 2; ++side)
+        if (c->bc_kind[TRM_BCV_LIQUID_WATER_FRACTION][side] == TRM_BC_VALUE || c->bc_kind[TRM_BCV_LIQUID_WATER_FRACTION][side] == TRM_BC_GRADIENT)
+            return "no Value or Gradient condition on the liquid water fraction";
+    return nullptr;
+}
+int tangent_args_ok(trm_ctx* c, int which, const void* ptr, const char* who) {
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no tangent is open (trm_tangent_open)");
+    if (which < 0 || which > TRM_TANGENT_LIQUID_WATER_FRACTION || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument");
+    return TRM_OK;
+}
+const char* kStaleTangent = ": the state has changed since the tangent was seeded: trm_tangent_upload a new dU first";
+}  // namespace
+
+int trm_tangent_open(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    if (const char* why = tangent_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_open: ") + why);
+    const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double);
+    for (double*& q : c->d_tan) {
+        if (!q) TRM_HIP(c, hipMalloc((void**)&q, bytes));
+        TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+    }
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    c->tan_stale = false;      // (a zero seed: zero tangents)
+    return TRM_OK;
+}
+int trm_tangent_close(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_close: no tangent is open");
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    for (double*& q : c->d_tan) {
+        TRM_HIP(c, hipFree(q));
+        q = nullptr;
+    }
+    c->tan_stale = false;
+    return TRM_OK;
+}
+int trm_tangent_upload(trm_ctx* c, int which, const void* host) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = tangent_args_ok(c, which, host, "trm_tangent_upload")) return rc;
+    const long Nh = c->Nh;
+    const size_t bytes = (size_t)c->Nz * Nh * sizeof(double);
+    if (int rc = io_buffer(c, bytes)) return rc;
+    TRM_HIP(c, hipMemcpyAsync(c->d_io, host, bytes, hipMemcpyHostToDevice, c->stream));
+    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
+    hipLaunchKernelGGL((k_transpose<double, true>), grid, dim3(256), 0, c->stream, (const double*)c->d_io, c->d_tan[which], Nh, c->Nz, c->Nzp);
+    TRM_HIP(c, hipGetLastError());
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    if (which == TRM_TANGENT_INTERNAL_ENERGY) c->tan_stale = false;
+    return TRM_OK;
+}
+int trm_tangent_download(trm_ctx* c, int which, void* host) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = tangent_args_ok(c, which, host, "trm_tangent_download")) return rc;
+    if (which != TRM_TANGENT_INTERNAL_ENERGY && c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_download") + kStaleTangent);
+    const long Nh = c->Nh;
+    const size_t bytes = (size_t)c->Nz * Nh * sizeof(double);
+    if (int rc = io_buffer(c, bytes)) return rc;
+    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
+    hipLaunchKernelGGL((k_transpose<double, false>), grid, dim3(256), 0, c->stream, (const double*)c->d_tan[which], (double*)c->d_io, Nh, c->Nz, c->Nzp);
+    TRM_HIP(c, hipGetLastError());
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_io, bytes, hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_tangent_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_elems) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = tangent_args_ok(c, which, dev, "trm_tangent_device_ptr")) return rc;
+    if (!pitch_elems) return fail(c, TRM_EINVAL, "trm_tangent_device_ptr: bad argument");
+    *dev = c->d_tan[which];
+    *pitch_elems = c->Nzp;
+    return TRM_OK;
+}
+int trm_tangent_closure(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_closure: no tangent is open (trm_tangent_open)");
+    if (const char* why = tangent_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_closure: ") + why);
+    if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_closure") + kStaleTangent);
+    return finish(c, TangentLaunch::closure(c));
+}
+int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
+    TRM_ENTER(c);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_step_tangent: no tangent is open (trm_tangent_open)");
+    if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_tangent: nsteps < 0");
+    if (const char* why = tangent_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + why);
+    if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_step_tangent") + kStaleTangent);
+    // the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to TRM_OPT_STEPS_PER_LAUNCH steps each
+    const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);
+    int n = 0;
+    while (n < nsteps) {
+        const int m = std::min(spl, nsteps - n);
+        int rc = Ops<double>::update_inputs(c, c->state, c->time);
+        if (!rc) rc = TangentLaunch::step(c, dt, m);
+        if (rc) return rc;
+        for (int j = 0; j < m; ++j) c->time += dt;   // (tick! per step, as trm_step)
+        c->iteration += m;
+        n += m;
+    }
+    c->closure_consistent = true;
+    c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
+    c->top_valid = false;
+    return finish(c, TRM_OK);
 }
 
 int trm_clock(const trm_ctx* c, double* time, int64_t* iteration) {

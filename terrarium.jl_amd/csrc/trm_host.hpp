@@ -146,6 +146,10 @@ struct trm_ctx {
     struct Average { int field = -1; double* d_sum = nullptr; double window = 0.0; int64_t steps = 0; };
     std::vector<Average> averages;
     double* d_acc_partial[trm::ACC_SLOTS] = {};   // the fused path's partials of a field with more than one open accumulator
+    // forward-mode tangents (trm_tangent_*): dU, dT, dliq in the device layout of a 3-D field ([Nh][Nzp] doubles), null while closed.
+    // `tan_stale`: another call has changed the state since the tangent was seeded (trm_tangent_upload of dU clears it).
+    double* d_tan[3] = {};
+    bool tan_stale = false;
     bool args_valid = false;
     void* args = nullptr;   // LaunchArgs<NF>*, owned
     void (*args_free)(void*) = nullptr;
@@ -460,6 +464,11 @@ template <class NF> struct Veg {
 template <class NF, bool RICH, int PROG> struct ColumnLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps); };
 // the multi-step program with time averages accumulated in the launch (trm_launch_column_accum_*.hip)
 template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps, const AccumArgs& acc); };
+// k_column_tangent / k_closure_tangent (trm_launch_column_tangent.hip, fp64 NoFlow only)
+struct TangentLaunch {
+    static int step(trm_ctx* c, double dt, int nsteps);
+    static int closure(trm_ctx* c);
+};
 // k_accumulate (trm_launch_average.hip)
 template <class NF> struct AverageLaunch { static int accumulate(trm_ctx* c, const AccumBatch& b); };
 constexpr int TRM_PROGRAM_BIT_AVERAGES_IN_LAUNCH = TRM_PROGRAM_AVERAGES_IN_LAUNCH;

@@ -411,6 +411,36 @@ class DeviceState:
         self._check(self._lib.trm_average_close(self._ctx, int(handle)), "trm_average_close")
         self.__dict__.get("_averages", {}).pop(int(handle), None)
 
+    # -- forward-mode tangents (trm_tangent_*) with respect to the initial internal energy: heat-only SoilModel, fp64 --------------
+    def open_tangent(self):
+        """Tangent fields of internal energy, temperature and liquid fraction, zero (trm_tangent_open)."""
+        self._check(self._lib.trm_tangent_open(self._ctx), "trm_tangent_open")
+        self._tangent_open = True
+
+    def close_tangent(self):
+        self._check(self._lib.trm_tangent_close(self._ctx), "trm_tangent_close")
+        self._tangent_open = False
+
+    def set_tangent(self, name, value):
+        """Seeds a tangent field ([Nz][Nh], or anything that broadcasts to it); `internal_energy` is the seed dU."""
+        a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
+        a[...] = value
+        self._check(self._lib.trm_tangent_upload(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_tangent_upload")
+
+    def tangent(self, name) -> np.ndarray:
+        """A tangent field as [Nz][Nh] (row 0 = bottom layer)."""
+        a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
+        self._check(self._lib.trm_tangent_download(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_tangent_download")
+        return a
+
+    def tangent_closure(self):
+        """dT and dliq from the stored internal energy and dU: the tangent of closure! (trm_tangent_closure)."""
+        self._check(self._lib.trm_tangent_closure(self._ctx), "trm_tangent_closure")
+
+    def step_tangent(self, dt, nsteps=1):
+        """`nsteps` ForwardEuler steps of the state and its tangent; the state ends as after step(dt, nsteps, finalize=True)."""
+        self._check(self._lib.trm_step_tangent(self._ctx, float(dt), int(nsteps)), "trm_step_tangent")
+
     def step(self, dt, nsteps=1, finalize=True):
         self._check(self._lib.trm_step(self._ctx, float(dt), int(nsteps), int(finalize)), "trm_step")
 
@@ -800,6 +830,28 @@ class ModelIntegrator:
     def _has_time_dependence(self):
         return bool(self._sf) or any(callable(v) for _, v in self.boundary_conditions.values()) or \
             any(callable(v) for v in self.inputs.values())
+
+
+def jvp(integ: ModelIntegrator, d_internal_energy, steps: int) -> dict:
+    """Forward-mode derivative of `run!(integ; steps)` with respect to the initial internal energy: the integrator is stepped `steps`
+    times with its own dt, its state carrying the tangent seeded by `d_internal_energy` ([Nz][Nh], or anything that broadcasts to
+    it).  Returns {"internal_energy", "temperature", "liquid_water_fraction"}: the tangents of those fields after the last step.
+    The heat-only SoilModel in fp64 with ForwardEuler and constant boundary conditions and inputs (trm_step_tangent)."""
+    if not isinstance(integ.timestepper, ForwardEuler):
+        raise ValueError("jvp: ForwardEuler only")
+    if integ._has_time_dependence() or integ._windowed():
+        raise ValueError("jvp: boundary conditions and inputs must be constant over the run")
+    st = integ.state
+    opened = not getattr(st, "_tangent_open", False)
+    if opened:
+        st.open_tangent()
+    try:
+        st.set_tangent("internal_energy", d_internal_energy)
+        st.step_tangent(integ.timestepper.dt, int(steps))
+        return {name: st.tangent(name) for name in _capi.TANGENT}
+    finally:
+        if opened:
+            st.close_tangent()
 
 
 def current_time(integrator: ModelIntegrator) -> float:
