@@ -9,9 +9,11 @@ path, which still holds wave-uniform branches a configuration skips (boundary ki
 finalize) -- the PMC count per wave (profiles/r04/pmc_summary_*.json) is the dynamic total to hold against it.  The marker build's
 total differs from the shipped kernel's by what the optimiser shares ACROSS phases; `--shipped other.s` prints the shipped
 kernel's totals beside it.
-    make -C terrarium.jl_amd/csrc asm F=trm_launch_column_f64_euler_rich EXTRA=-DTRM_PHASE_MARKERS OBJDIR=../../build/markers
-    python profiles/tools/isa_phases.py build/markers/trm_launch_column_f64_euler_rich.s _ZN3trm8k_columnIdLb1ELi0ELi32ELi1ELi0ELb0ELb0ELb0ELb1E \\
-        [--shipped build/obj/trm_launch_column_f64_euler_rich.s] [--json out.json]"""
+The headline instance (C3: heat + Richards, fp64, the T_TOP signature) is compiled in trm_launch_column_sig_f64_rich_a.hip:
+    make -C terrarium.jl_amd/csrc asm F=trm_launch_column_sig_f64_rich_a EXTRA=-DTRM_PHASE_MARKERS OBJDIR=../../build/markers
+    python profiles/tools/isa_phases.py build/markers/trm_launch_column_sig_f64_rich_a.s _ZN3trm8k_columnIdLb1ELi0ELi32ELi1ELi0ELb0ELb0ELb0ELb1ELi2E \\
+        [--shipped build/obj/trm_launch_column_sig_f64_rich_a.s] [--json out.json]
+tests/test_column_isa_budget.py holds that instance's common path to its budget."""
 import collections
 import json
 import re

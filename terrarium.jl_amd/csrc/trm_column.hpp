@@ -80,9 +80,10 @@ template <class NF, int CHECK = 1> TRM_DEV Frac<NF> energy_closure_wave(const De
     const NF Lth = p.L * sat * p.por;
     const NF nLth = -Lth;
     const bool thawed = U >= NF(0), frozen = U < nLth;
+    const unsigned long long m_thawed = wave_ballot(thawed), m_frozen = wave_ballot(frozen);     // (the same ballots as no_lane_divides')
     bool ok;
     if (no_lane_divides(thawed, frozen, Lth > Limits<NF>::eps())) {
-        liq = thawed ? NF(1) : NF(-0.0);
+        liq = one_or_negzero<NF>(m_thawed);        // thawed ? 1 : -0.0
         ok = (CHECK == 2 && TRM_CUT_CHECK) ? sat == sat : (TRM_CUT_CHECK ? (NF(0) <= sat && sat <= NF(1)) : ((NF(0) <= sat && sat <= NF(1)) && (NF(0) <= liq && liq <= NF(1))));
     } else {
         TRM_PHASE("rare+ phase-change divide");
@@ -93,19 +94,25 @@ template <class NF, int CHECK = 1> TRM_DEV Frac<NF> energy_closure_wave(const De
     if (CHECK != 0) viol |= ok ? 0u : 2u;
     const Frac<NF> f = fractions_unchecked(p, sat, liq);
     const NF C = heat_capacity(p, f);
-    const NF num = frozen ? (U + Lth) : U;
+    const NF num = mask_pick(~m_frozen, U, U + Lth);      // frozen ? U + Lth : U
     const NF quo = div_nr(num, C);
-    T = (frozen || thawed) ? quo : NF(0);
+    T = keep_or_zero(m_frozen | m_thawed, quo);            // (frozen || thawed) ? quo : 0
     return f;
 }
 
 // compute_auxiliary! + compute_tendencies! of the column in registers, WITHOUT the compute_z_bcs! terms.
 // `pre`: the volumetric fractions of (c.sat, c.liq) when the closure that produced the cell has just formed them (same operands,
 // same operations: same bits), else null.
-template <class NF, bool RICHARDS, int HYD, int LPC>
+// BCSIG >= 0: the temperature boundary kinds are the signature's (the launcher has matched them), not read at run time, and the
+// edge lanes' values are moved in under the masks ln.m_bot / ln.m_top (mask_pick) -- the instances with the kinds read at run time
+// keep the selects: there the saved execution masks cost the scalar registers of the 8th wave per SIMD (run-time Heun: 92 -> 102 SGPRs).
+template <class NF, bool RICHARDS, int HYD, int LPC, int BCSIG = BCSIG_RUNTIME>
 TRM_DEV Tendency<NF> column_tendencies(const View<NF>& v, const DevParams<NF>& p, const LevelGeom<NF>& L, const LaneInfo& ln,
                                        const Cell<NF>& c, NF bTb, NF bTt, bool need_kc, uint32_t& viol, const Frac<NF>* pre = nullptr) {
     const bool is_bot = ln.is_bot, is_top = ln.is_top;
+    const unsigned long long m_bot = ln.m_bot, m_top = ln.m_top;
+    auto at_bot = [&](NF e, NF x) { return BCSIG >= 0 ? mask_pick(m_bot, e, x) : (is_bot ? e : x); };
+    auto at_top = [&](NF e, NF x) { return BCSIG >= 0 ? mask_pick(m_top, e, x) : (is_top ? e : x); };
     // (composition bounds of an incoming state were flagged by the launch / program step that produced it)
     const Frac<NF> f = (pre && TRM_CUT_FRAC) ? *pre : fractions_unchecked(p, c.sat, c.liq);
     const NF kap = conductivity(p, f);
@@ -117,21 +124,22 @@ TRM_DEV Tendency<NF> column_tendencies(const View<NF>& v, const DevParams<NF>& p
     NF T_ext_b = c.T, T_ext_t = c.T;
     // (div_const_nsz: a zero gradient's sign reaches T_ext only when T itself is a zero, then the face flux q_T as a signed zero,
     // and `0 + (-(dq * rdz))` below gives +0 whatever its sign -- or a non-zero neighbour flux absorbs it)
-    if (v.bc.kind[2][0] == 1) T_ext_b = c.T + div_const_nsz(c.T - bTb, v.g.hdzf_bot, v.g.rhdzf_bot) * (-v.g.dzf_bot);
-    if (v.bc.kind[2][1] == 1) T_ext_t = c.T + div_const_nsz(bTt - c.T, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top;
-    const NF T_m = is_bot ? T_ext_b : T_sh;
+    const bool vTb = BCSIG >= 0 ? (BCSIG & BCSIG_T_BOT) != 0 : v.bc.kind[2][0] == 1, vTt = BCSIG >= 0 ? (BCSIG & BCSIG_T_TOP) != 0 : v.bc.kind[2][1] == 1;
+    if (vTb) T_ext_b = c.T + div_const_nsz(c.T - bTb, v.g.hdzf_bot, v.g.rhdzf_bot) * (-v.g.dzf_bot);
+    if (vTt) T_ext_t = c.T + div_const_nsz(bTt - c.T, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top;
+    const NF T_m = at_bot(T_ext_b, T_sh);
     const NF T_h = T_ext_t;
     // liquid fraction / saturation / pressure head carry the default condition (halo = edge cell): the halo cell's
     // conductivity is the edge cell's, bit for bit -- except under NoFlow with the reference's never-filled saturation
     // halo (SURVEY C-1), where the halo cell is dry
     NF kap_halo = kap;
     if (!RICHARDS && p.halo_policy != 1) kap_halo = conductivity(p, fractions(p, NF(0), c.liq, viol));
-    const NF kap_m = is_bot ? kap_halo : kap_sh;
+    const NF kap_m = at_bot(kap_halo, kap_sh);
     const NF kap_h = kap_halo;
     // heat: every lane forms its lower face, the top lane also the boundary face (soil_energy.jl:112-149)
     const NF qT_lo = -(NF(0.5) * (kap + kap_m)) * ((c.T - T_m) * L.rdzf_lo);
     const NF qT_sh = shfl_dn1<NF, LPC>(qT_lo);
-    const NF qT_hi = is_top ? -(NF(0.5) * (kap_h + kap)) * ((T_h - c.T) * L.rdzf_hi) : qT_sh;
+    const NF qT_hi = at_top(-(NF(0.5) * (kap_h + kap)) * ((T_h - c.T) * L.rdzf_hi), qT_sh);
     Tendency<NF> t;
     t.gU = NF(0) + (-((qT_hi - qT_lo) * L.rdzc));
     t.gS = NF(0);
@@ -140,7 +148,7 @@ TRM_DEV Tendency<NF> column_tendencies(const View<NF>& v, const DevParams<NF>& p
     if (need_kc) {   // face conductivities (soil_hydrology.jl:145-163)
         const NF Kc_m = shfl_up1<NF, LPC>(Kc);
         const NF Kmin = jl_min(Kc, Kc_m);
-        t.Kf_lo = (is_bot || is_top) ? Kc : Kmin;
+        t.Kf_lo = BCSIG >= 0 ? mask_pick(m_bot | m_top, Kc, Kmin) : ((is_bot || is_top) ? Kc : Kmin);
     }
     if (RICHARDS) {  // Darcy fluxes (soil_hydrology_rre.jl:95-131)
         const NF Kf_lo = t.Kf_lo;
@@ -149,8 +157,8 @@ TRM_DEV Tendency<NF> column_tendencies(const View<NF>& v, const DevParams<NF>& p
         // default condition the bottom lane's gradient is (psi - psi) * rdz = +0 or NaN, never negative: its value is never
         // taken, and the select that put the 0 there is gone (the lane receives its neighbour column's top face instead).
         const NF Kf_m = Kf_up;
-        const NF Kf_p = is_top ? Kc : Kf_dn;      // face Nz repeats the top cell's value
-        const NF psi_m = is_bot ? c.psi : psi_sh;
+        const NF Kf_p = at_top(Kc, Kf_dn);      // face Nz repeats the top cell's value
+        const NF psi_m = at_bot(c.psi, psi_sh);
         const NF g_lo = (c.psi - psi_m) * L.rdzf_lo;
         const NF Ks_lo = upwind_conductivity(g_lo, Kf_m, Kf_lo, Kf_p);
         const NF qW_lo = -Ks_lo * g_lo;
@@ -159,7 +167,7 @@ TRM_DEV Tendency<NF> column_tendencies(const View<NF>& v, const DevParams<NF>& p
         // (NaN for a non-finite psi), never negative: K* = min(K, K_halo_face = 0)
         const NF zero_or_nan = c.psi - c.psi;
         const NF qW_t = -jl_min(Kc, NF(0)) * zero_or_nan;
-        const NF qW_hi = is_top ? qW_t : qW_sh;
+        const NF qW_hi = at_top(qW_t, qW_sh);
         const NF dtheta = -((qW_hi - qW_lo) * L.rdzc) + NF(0) + p.vwc_forcing;
         t.gS = NF(0) + div_const_nsz(dtheta, p.por, p.rpor);       // (`0 + q`: +0 for a zero quotient of either sign)
     }
@@ -294,9 +302,11 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     ln.lane = threadIdx.x & 63;
 #if TRM_CUT_MASKS
     // (the wave index and everything that follows from it alone lives on the scalar unit)
-    const int wave = __builtin_amdgcn_readfirstlane((int)((block * (unsigned)TRM_STEP_BLOCK + threadIdx.x) >> 6));
-    ln.k = ln.lane % LPC;
-    const int sub = ln.lane / LPC;
+    // (the wave's index from its first lane's thread index: one v_readfirstlane, the rest on the scalar unit;
+    //  level and column of the lane as unsigned shifts and masks of the lane index)
+    const int wave = (int)(block * (unsigned)(TRM_STEP_BLOCK / 64) + ((unsigned)__builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6));
+    ln.k = (int)((unsigned)ln.lane % (unsigned)LPC);
+    const int sub = (int)((unsigned)ln.lane / (unsigned)LPC);
     const int Nz = v.Nz, Nh = (int)v.Nh;
     // which lanes hold the bottom / top cell, a real cell, the wave's second column: wave-uniform masks, no lane-wise compare
     const bool upper = CPW == 2 && lane_in(0xffffffff00000000ull);
@@ -380,20 +390,18 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     };
     // The select between the wave's two columns, both values wave-uniform: `upper ? x1 : x0` is two v_mov (scalar -> vector, the
     // select takes one scalar operand: its mask) and a v_cndmask per 32-bit half.  Writing x0 to every lane and then x1 to the upper
-    // half-wave under an execution mask is two v_mov per half (TRM_PICK_EXEC 0: the select, A/B).
+    // half-wave under an execution mask is one v_mov_b64 from the scalar pair each (TRM_PICK_EXEC 0: the select, A/B).
     auto pick_column = [&](NF x0, NF x1) -> NF {
 #if TRM_PICK_EXEC
         if (__builtin_constant_p(x0 == x1) && x0 == x1) return x0;      // (a condition that is not set: both halves the same constant)
         if constexpr (sizeof(NF) == 8) {
-            const unsigned long long b0 = __builtin_bit_cast(unsigned long long, x0), b1 = __builtin_bit_cast(unsigned long long, x1);
-            unsigned lo = (unsigned)b0, hi = (unsigned)(b0 >> 32);
-            const unsigned lo1 = (unsigned)b1, hi1 = (unsigned)(b1 >> 32);
+            NF r;
             unsigned long long save;
-            asm("s_mov_b64 %[save], exec\n\ts_and_b64 exec, %[save], %[m]\n\tv_mov_b32 %[lo], %[slo]\n\tv_mov_b32 %[hi], %[shi]\n\ts_mov_b64 exec, %[save]"
-                         : [lo] "+v"(lo), [hi] "+v"(hi), [save] "=&s"(save)
-                         : [slo] "s"(lo1), [shi] "s"(hi1), [m] "s"(0xffffffff00000000ull)
+            asm("v_mov_b64 %[r], %[s0]\n\ts_mov_b64 %[save], exec\n\ts_and_b64 exec, %[save], %[m]\n\tv_mov_b64 %[r], %[s1]\n\ts_mov_b64 exec, %[save]"
+                         : [r] "=&v"(r), [save] "=&s"(save)
+                         : [s0] "s"(x0), [s1] "s"(x1), [m] "s"(0xffffffff00000000ull)
                          : "scc");
-            return __builtin_bit_cast(NF, ((unsigned long long)hi << 32) | lo);
+            return r;
         } else
 #endif
         return upper ? x1 : x0;
@@ -491,9 +499,10 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
 #endif
         bc.flux_U = fU;
         bc.flux_S = fS;
-        // (the multi-step program may receive its terms later: from a series, from the inline surface energy balance)
-        bc.has_U = !TRM_CUT_FLUX || PROG == PROG_MULTI || bU || tU;
-        bc.has_S = !TRM_CUT_FLUX || PROG == PROG_MULTI || bS || tS;
+        // (the multi-step program may receive its terms later: from a series, from the inline surface energy balance; with the kinds
+        // a compile-time signature, a side without a flux condition is known to receive +0 and is left alone)
+        bc.has_U = (!TRM_CUT_FLUX && !SIG) || PROG == PROG_MULTI || bU || tU;
+        bc.has_S = (!TRM_CUT_FLUX && !SIG) || PROG == PROG_MULTI || bS || tS;
     }
     NF S = NF(0);
     SurfaceRegs<NF> sf;
@@ -560,7 +569,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     };
     if (PROG == PROG_HEUN) {
         // stage 1: tendencies at the state, Euler predictor (with the state's boundary fluxes) and its closures
-        t = column_tendencies<NF, RICHARDS, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, need_kc, viol, DERIVE_TL ? &f_in : nullptr);
+        t = column_tendencies<NF, RICHARDS, HYD, LPC, BCSIG>(v, p, L, ln, c, bc.bTb, bc.bTt, need_kc, viol, DERIVE_TL ? &f_in : nullptr);
         const NF G1U = t.gU, G1S = t.gS;
         NF gU = G1U, gS = G1S, z0s;
         Cell<NF> s;
@@ -576,7 +585,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
         // stage 2: tendencies at the stage, its temperature boundary values taken at t + dt (heun.jl:52-59)
         const NF bTb2 = in_Tb2, bTt2 = in_Tt2;
         uint32_t viol_stage = 0;
-        const Tendency<NF> t2 = column_tendencies<NF, RICHARDS, HYD, LPC>(kernarg_reload<View<NF>>(0), kernarg_reload<DevParams<NF>>(off_p), L, ln, s, bTb2, bTt2, RICHARDS, viol_stage, &f_stage);
+        const Tendency<NF> t2 = column_tendencies<NF, RICHARDS, HYD, LPC, BCSIG>(kernarg_reload<View<NF>>(0), kernarg_reload<DevParams<NF>>(off_p), L, ln, s, bTb2, bTt2, RICHARDS, viol_stage, &f_stage);
         viol |= viol_stage;
         // average_tendencies! (heun.jl:27-35), then the step of the STATE with its own boundary fluxes
         gU = (G1U + t2.gU) / NF(2);
@@ -662,7 +671,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
             TRM_PHASE_FENCE("tendencies", c.U, c.sat, c.psi, c.T, c.liq, bc.bTb, bc.bTt, bc.flux_U, bc.flux_S, S_in, Ts_in);
             // (the cell's fractions: from the derivation at entry, from the previous step's closure inside the multi-step loop)
             const Frac<NF>* pre = (PROG == PROG_MULTI && step > 0) ? &f_new : (DERIVE_TL ? &f_in : nullptr);
-            t = column_tendencies<NF, RICHARDS, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, need_kc, viol, pre);
+            t = column_tendencies<NF, RICHARDS, HYD, LPC, BCSIG>(v, p, L, ln, c, bc.bTb, bc.bTt, need_kc, viol, pre);
             NF gU = t.gU, gS = t.gS;
             TRM_PHASE_FENCE("advance", gU, gS, t.Kf_lo, t.Kc);
             front_wait();
@@ -699,7 +708,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
         const NF Kc_new = conductivity_hydraulic<NF, HYD, false>(p, n.liq, f_new);     // (the closure has checked this composition)
         const NF Kc_new_m = shfl_up1<NF, LPC>(Kc_new);
         const NF Kmin_new = jl_min(Kc_new, Kc_new_m);
-        Kf_out = (ln.is_bot || ln.is_top) ? Kc_new : Kmin_new;
+        Kf_out = mask_pick(ln.m_bot | ln.m_top, Kc_new, Kmin_new);
         Kf_out_top = Kc_new;
     }
     // surface_excess_water and the skin temperature after the step, formed BEFORE the first store is issued: every loaded value
@@ -709,7 +718,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
         if (RICHARDS) {
             // tendency min(0, S) once per column (SURVEY C-3), Euler / Heun update, overflow
             S = S_in;
-            GS_out = NF(0) + jl_min(NF(0), S);
+            GS_out = NF(0) + jl_min_zero(S);
             if (PROG == PROG_HEUN) {
                 S_stage_out = (S + GS_out * dt) + over_stage;
                 GS_out = (GS_out + (NF(0) + jl_min(NF(0), S_stage_out))) / NF(2);
@@ -717,28 +726,36 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
             S = (S + GS_out * dt) + over;
         }
         if (seb) Ts_new = Ts_in + NF(0) * dt;   // zero-tendency prognostic skin_temperature
-        asm volatile("" : "+v"(S), "+v"(GS_out), "+v"(Ts_new), "+v"(S_stage_out));
+        // (a value that is the constant 0 in this instance is left out: pinned, it costs a vector move per half)
+        if (RICHARDS) asm volatile("" : "+v"(S), "+v"(GS_out));
+        if (!SIG || seb) asm volatile("" : "+v"(Ts_new));
+        if (RICHARDS && PROG == PROG_HEUN) asm volatile("" : "+v"(S_stage_out));
     }
     // ---- the column goes out: 6 coalesced stores ---------------------------------------------------------------------------
-    TRM_PHASE_FENCE("stores", Kf_out, Kf_out_top, S, GS_out, Ts_new);
+    TRM_PHASE_FENCE("stores", Kf_out, Kf_out_top, S, GS_out);
     if (ln.act) {
         const View<NF>& v = kernarg_reload<View<NF>>(0);
         // every base pointer the store phase may need in ONE batch of scalar loads: fetched where they are used -- inside the
         // finalize / write_kf / top-lane branches -- each is a scalar load and a wait of its own in front of its store
         NF* const pGU = v.G_U; NF* const pGS3 = v.G_sat; NF* const pKf = v.Kf; NF* const pKft = v.Kf_top; NF* const pS = v.S; NF* const pwt = v.wt;
         asm volatile("" : : "s"(pGU), "s"(pGS3), "s"(pKf), "s"(pKft), "s"(pS), "s"(pwt));
-        // (block_local in EVERY block that stores: an offset defined in another block has been widened to 64 bits there)
-        const unsigned cb = block_local(cb0), ib = block_local(ib0);
+        // (block_local in EVERY block that stores: an offset defined in another block has been widened to 64 bits there.  One
+        //  variable per offset, re-materialised in place: a fresh `block_local(cb0)` per block keeps cb0 alive beside it -- a
+        //  vector move per block)
+        unsigned cb = block_local(cb0);
         stg(v.U, cb, n.U);
         stg(v.T, cb, n.T);
         stg(v.liq, cb, n.liq);
         if (RICHARDS) { stg(v.sat, cb, n.sat); stg(v.psi, cb, n.psi); }
-        if (finalize) {   // state.tendencies as the reference leaves them after its last step
-            stg(pGU, block_local(cb0), gU_out);
-            if (RICHARDS) stg(pGS3, block_local(cb0), gS_out);
+        // (the flags are tested afresh in every block: a wave-uniform bool carried into the divergent top-lane block becomes a
+        //  lane mask there, formed by a v_cndmask and a v_cmp)
+        if (uniform_flag(finalize)) {   // state.tendencies as the reference leaves them after its last step
+            cb = block_local(cb);
+            stg(pGU, cb, gU_out);
+            if (RICHARDS) stg(pGS3, cb, gS_out);
         }
-        if (write_kf) stg(pKf, block_local(cb0), Kf_out);
-        if (ln.is_top && RICHARDS && PROG == PROG_HEUN && a.stage_S) stg(a.stage_S, ib, S_stage_out);
+        if (uniform_flag(write_kf)) { cb = block_local(cb); stg(pKf, cb, Kf_out); }
+        if (ln.is_top && RICHARDS && PROG == PROG_HEUN && a.stage_S) stg(a.stage_S, block_local(ib0), S_stage_out);
         if (ln.is_top && STAGED) {
             // The per-column outputs (up to eight 8-byte values: top face of K, surface excess water, water table, its tendency,
             // the top cell for the next surface energy balance, the skin temperature) go to the workgroup's staging table: one
@@ -760,12 +777,13 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
                 st[SMALL_TS * cpb + cib] = SEB_INLINE ? sf.out.Ts : Ts_new;
             }
         } else if (ln.is_top) {
-            if (write_kf) stg(pKft, block_local(ib0), Kf_out_top);
+            unsigned ib = ib0;
+            if (uniform_flag(write_kf)) { ib = block_local(ib); stg(pKft, ib, Kf_out_top); }
             if (RICHARDS) {
-                const unsigned ib = block_local(ib0);
+                ib = block_local(ib);
                 stg(pS, ib, S);
                 stg(pwt, ib, z0);
-                if (finalize) stg(v.G_S, block_local(ib0), GS_out);
+                if (uniform_flag(finalize)) { ib = block_local(ib); stg(v.G_S, ib, GS_out); }
             }
             if (seb) {   // the next surface energy balance reads these
                 const unsigned ib = block_local(ib0);

@@ -19,7 +19,11 @@
 #ifdef TRM_PHASE_MARKERS
 #define TRM_PHASE(name) asm volatile("; TRM_PHASE " name)
 namespace trm {
-template <class T> __device__ __forceinline__ void phase_opaque(T& x) { asm volatile("" : "+v"(x)); }
+// (a compile-time constant is left as it is: pinned in a register it costs vector moves the shipped kernel does not have, and no
+//  arithmetic can cross the boundary through it)
+template <class T> __device__ __forceinline__ void phase_opaque(T& x) {
+    if (!__builtin_constant_p(x)) asm volatile("" : "+v"(x));
+}
 template <class... T> __device__ __forceinline__ void phase_fence_values(T&... x) { (phase_opaque(x), ...); }
 }
 // (the comment FIRST: volatile asms keep their order, so everything that depends on a fenced value follows the comment line)
@@ -80,6 +84,61 @@ template <class NF> TRM_HD bool is_nan(NF x) { return x != x; }
 // the wave's predicate mask straight from the compare (s_and with exec); HIP's __ballot takes the predicate through a vector
 // register (v_cndmask 0/1 + v_cmp_ne)
 __device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// Lane selects of fp64 values as moves under an execution mask.  A select is a v_cndmask per 32-bit half; a v_mov_b64 moves
+// both halves, so where one operand of the select is dead after it, moving the other one into it under the mask takes one vector
+// instruction (and three scalar ones) instead of two -- same bits in every lane.  The float forms are the plain selects.
+#ifndef TRM_MASK_PICK       // the fp64 lane selects below as moves under an execution mask (0: the plain selects, A/B)
+#define TRM_MASK_PICK 1
+#endif
+// `lane_in(mask) ? edge : x` for a wave-uniform mask (the edge lanes of a column: a DPP shift and this, not a shift and a select)
+__device__ __forceinline__ double mask_pick(unsigned long long mask, double edge, double x) {
+    if (!TRM_MASK_PICK) return __builtin_amdgcn_inverse_ballot_w64(mask) ? edge : x;
+    unsigned long long save;
+    asm("s_mov_b64 %[save], exec\n\ts_and_b64 exec, %[save], %[m]\n\tv_mov_b64 %[x], %[e]\n\ts_mov_b64 exec, %[save]"
+        : [x] "+v"(x), [save] "=&s"(save)
+        : [e] "v"(edge), [m] "s"(mask)
+        : "scc");
+    return x;
+}
+__device__ __forceinline__ float mask_pick(unsigned long long mask, float edge, float x) { return __builtin_amdgcn_inverse_ballot_w64(mask) ? edge : x; }
+// the same with a wave-uniform edge value, moved from its scalar registers
+__device__ __forceinline__ double mask_pick_uniform(unsigned long long mask, double edge, double x) {
+    if (!TRM_MASK_PICK) return __builtin_amdgcn_inverse_ballot_w64(mask) ? edge : x;
+    unsigned long long save;
+    asm("s_mov_b64 %[save], exec\n\ts_and_b64 exec, %[save], %[m]\n\tv_mov_b64 %[x], %[e]\n\ts_mov_b64 exec, %[save]"
+        : [x] "+v"(x), [save] "=&s"(save)
+        : [e] "s"(edge), [m] "s"(mask)
+        : "scc");
+    return x;
+}
+__device__ __forceinline__ float mask_pick_uniform(unsigned long long mask, float edge, float x) { return mask_pick(mask, edge, x); }
+// (the masks below are ballots: take them in the block that forms the predicate -- the ballot of a predicate formed in another
+//  block goes through a vector register, a v_cndmask 0/1 and a v_cmp)
+// `lane_in(keep) ? x : +0.0`
+__device__ __forceinline__ double keep_or_zero(unsigned long long keep, double x) {
+    if (!TRM_MASK_PICK) return __builtin_amdgcn_inverse_ballot_w64(keep) ? x : 0.0;
+    unsigned long long save;
+    asm("s_mov_b64 %[save], exec\n\ts_andn2_b64 exec, %[save], %[m]\n\tv_mov_b64 %[x], 0\n\ts_mov_b64 exec, %[save]"
+        : [x] "+v"(x), [save] "=&s"(save)
+        : [m] "s"(keep)
+        : "scc");
+    return x;
+}
+__device__ __forceinline__ float keep_or_zero(unsigned long long keep, float x) { return __builtin_amdgcn_inverse_ballot_w64(keep) ? x : 0.0f; }
+// `lane_in(one) ? 1.0 : -0.0`: 1.0 in every lane (its low half is 0, as -0.0's), then the sign bit alone as the high half elsewhere
+template <class NF> __device__ __forceinline__ NF one_or_negzero(unsigned long long one_lanes) {
+    if constexpr (sizeof(NF) == 4 || !TRM_MASK_PICK) return __builtin_amdgcn_inverse_ballot_w64(one_lanes) ? NF(1) : NF(-0.0);
+    double one = 1.0;
+    asm("" : "+v"(one));      // (one v_mov_b64 of the inline constant, not two moves of its halves)
+    const unsigned long long bits = __builtin_bit_cast(unsigned long long, one);
+    unsigned lo = (unsigned)bits, hi = (unsigned)(bits >> 32);
+    unsigned long long save;
+    asm("s_mov_b64 %[save], exec\n\ts_andn2_b64 exec, %[save], %[m]\n\tv_bfrev_b32 %[hi], 1\n\ts_mov_b64 exec, %[save]"
+        : [hi] "+v"(hi), [save] "=&s"(save)
+        : [m] "s"(one_lanes)
+        : "scc");
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
 // Workgroups are dealt to the 8 XCDs round-robin (workgroup b runs on XCD b mod 8).  xcd_block<true> makes every XCD work on
 // ONE contiguous eighth of the columns instead of every eighth workgroup-sized chunk.  Measured twice, same build, two boxes
 // (profiles/r03/exp16_xcd_remap.log, exp16b_xcd_remap_pk.log): the packed fp32 step at C5 454.2 -> 437.4 us on one box and
@@ -116,6 +175,14 @@ TRM_DEV double jl_min(double x, double y) {
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
     return r;
 }
+// min(x, +0) of a value the optimiser cannot prove canonical (one that arrives by load or from an asm): the builtin quiets it first
+// (v_max x, x); the instruction alone differs from that only for a signalling NaN, which no arithmetic produces (as for jl_min)
+TRM_DEV double jl_min_zero(double x) {
+    double r;
+    asm("v_min_f64 %0, %1, 0" : "=v"(r) : "v"(x));
+    return r;
+}
+TRM_DEV float jl_min_zero(float x) { return __builtin_fminf(x, 0.0f); }
 TRM_DEV double jl_max(double x, double y) {
     if (__builtin_constant_p(x) || __builtin_constant_p(y)) return __builtin_fmax(x, y);
     double r;
@@ -221,7 +288,7 @@ template <> struct Limits<float> {
 // sign of a zero, and a NaN gradient gives q = NaN either way.  The select form is therefore
 // value-identical downstream (verified bit for bit against the oracle, which keeps the product form).
 template <class NF> TRM_DEV NF upwind_conductivity(NF g, NF Kdn, NF Kmid, NF Kup) {
-    const NF other = (g < NF(0)) ? Kdn : Kup;   // min is symmetric bit for bit: select the operand, then one min
+    const NF other = mask_pick(wave_ballot(g < NF(0)), Kdn, Kup);   // (g < 0) ? Kdn : Kup -- min is symmetric bit for bit: select the operand, then one min
     return jl_min(Kmid, other);
 }
 
@@ -548,7 +615,7 @@ template <class NF> TRM_DEV void energy_invclosure(const DevParams<NF>& p, NF T,
 template <class NF, bool M5 = false, bool NSZ = false> TRM_DEV NF swrc_psi_bc(const DevParams<NF>& p, NF theta) {
     NF r = NSZ ? div_const_nsz(theta - p.theta_res, p.theta_span, p.rtheta_span) : div_const(theta - p.theta_res, p.theta_span, p.rtheta_span);
     NF v = -p.bc_psi_s * (M5 ? pow_int_m5(r) : jl_pow(r, p.bc_neg_inv_lambda));
-    return (theta < p.por) ? v : -p.bc_psi_s;
+    return mask_pick_uniform(~wave_ballot(theta < p.por), -p.bc_psi_s, v);     // (theta < por) ? v : -psi_s
 }
 template <class NF, bool N2 = false, bool NSZ = false> TRM_DEV NF swrc_psi_vg(const DevParams<NF>& p, NF theta) {
     if (theta < p.por) {

@@ -520,6 +520,11 @@ TRM_DEV unsigned block_local(unsigned byte_off) {
     asm volatile("" : "+v"(byte_off));
     return byte_off;
 }
+// A wave-uniform integer flag tested where it is used: the compare is formed on the scalar unit in the block that branches on it
+TRM_DEV bool uniform_flag(int x) {
+    asm volatile("" : "+s"(x));
+    return x != 0;
+}
 
 template <class NF> struct LevelGeom {
     NF zC, psiz, zFlo, dzc, rdzc, rdzf_lo, rdzf_hi, zF_top, dzc_top;
@@ -570,21 +575,25 @@ TRM_DEV NF repair_saturation(const View<NF>& v, NF& snew, int k, int Nz, unsigne
     const unsigned long long any_bad = any_over | (wave_ballot(snew < NF(0)) & m_act & ~m_bot);
     // every cell but the bottom one receives `+ carry` / `+ deficit`; with nothing to move that is `+ 0`
     // (idempotent, and absorbed by a later non-zero addend), so apply it once up front
-    snew = is_bot ? snew : snew + NF(0);
+    snew = mask_pick(m_bot, snew, snew + NF(0));
     if (any_bad != 0ull) {
         TRM_PHASE("rare+ repair");
         // thickness of the cells above / below, from the neighbouring lanes' level records (wave-uniform branch: every lane
         // executes the shifts; the edge lanes, which would receive the next column's value, keep their own as
         // neighbour_dz() does -- no loads in this rare path, so nothing of it is ever pending in the common one)
+        // (the thicknesses made opaque here, and used in this branch only in that form: the optimiser hoisted the four shifts --
+        //  eight DPP moves -- out of the branch into the common path)
+        NF dzc = L.dzc, rdzc = L.rdzc;
+        asm volatile("" : "+v"(dzc), "+v"(rdzc));
         NeighbourDz<NF> nb;
         {
-            const NF dz_up = shfl_dn1<NF, LPC>(L.dzc), rdz_up = shfl_dn1<NF, LPC>(L.rdzc);
-            const NF dz_dn = shfl_up1<NF, LPC>(L.dzc), rdz_dn = shfl_up1<NF, LPC>(L.rdzc);
+            const NF dz_up = shfl_dn1<NF, LPC>(dzc), rdz_up = shfl_dn1<NF, LPC>(rdzc);
+            const NF dz_dn = shfl_up1<NF, LPC>(dzc), rdz_dn = shfl_up1<NF, LPC>(rdzc);
             const bool edge_up = k >= Nz - 1;
-            nb.dzc_up = edge_up ? L.dzc : dz_up;
-            nb.rdzc_up = edge_up ? L.rdzc : rdz_up;
-            nb.dzc_dn = is_bot ? L.dzc : dz_dn;
-            nb.rdzc_dn = is_bot ? L.rdzc : rdz_dn;
+            nb.dzc_up = edge_up ? dzc : dz_up;
+            nb.rdzc_up = edge_up ? rdzc : rdz_up;
+            nb.dzc_dn = is_bot ? dzc : dz_dn;
+            nb.rdzc_dn = is_bot ? rdzc : rdz_dn;
         }
         // Lane-serial passes, restricted to the levels that can change: the upward pass starts at the lowest
         // oversaturated level and stops once the carry is zero with no oversaturated level left above;
@@ -598,7 +607,7 @@ TRM_DEV NF repair_saturation(const View<NF>& v, NF& snew, int k, int Nz, unsigne
                     snew = snew + carry;
                     NF e = jl_max(snew - NF(1), NF(0));
                     snew = snew - e;
-                    cout = div_const(e * L.dzc, nb.dzc_up, nb.rdzc_up);
+                    cout = div_const(e * dzc, nb.dzc_up, nb.rdzc_up);
                 }
                 carry = shfl_from<NF, LPC>(cout, q);
                 if ((lv >> (q + 1)) == 0ull && wave_ballot(!(carry == NF(0))) == 0ull) break;
@@ -615,7 +624,7 @@ TRM_DEV NF repair_saturation(const View<NF>& v, NF& snew, int k, int Nz, unsigne
                     snew = snew - pend;
                     NF d = jl_max(-snew, NF(0));
                     snew = snew + d;
-                    pout = div_const(d * L.dzc, nb.dzc_dn, nb.rdzc_dn);
+                    pout = div_const(d * dzc, nb.dzc_dn, nb.rdzc_dn);
                 }
                 pend = shfl_from<NF, LPC>(pout, q);
                 if ((lv & ((1ull << q) - 1ull)) == 0ull && wave_ballot(!(pend == NF(0))) == 0ull) break;
