@@ -370,7 +370,7 @@ bool averageable(const trm_ctx* c, int field) {
     return s < ACC_TS || c->params.seb != 0;
 }
 
-// The step sequences of one precision.  The launches themselves are Unfused / Veg / ColumnLaunch / GenericLaunch / DeepLaunch /
+// The step sequences of one precision.  The launches themselves are Unfused / Veg / ColumnLaunch / GenericLaunch / LevelsLaunch /
 // LandLaunch / PackedLaunch (trm_host.hpp); the forwarders below keep their reference names in the sequences.
 template <class NF> struct Ops {
     using P = Policy<NF>;
@@ -380,8 +380,7 @@ template <class NF> struct Ops {
     static int hyd(const trm_ctx* c) { return P::hyd(c); }
     static bool generic_bcs(const trm_ctx* c) { return P::generic_bcs(c); }
     static bool packed_path(trm_ctx* c) { return P::packed_path(c); }
-    static bool deep_columns(const trm_ctx* c) { return P::deep_columns(c); }
-    static bool wide_columns(const trm_ctx* c) { return P::wide_columns(c); }
+    static int levels_per_lane(const trm_ctx* c) { return P::levels_per_lane(c); }
     static int series_slot(const trm_ctx* c, const trm_ctx::Series& sr) { return P::series_slot(c, sr); }
     static bool series_fit_program(const trm_ctx* c) { return P::series_fit_program(c); }
     static VegDev<NF> veg_dev(const trm_ctx* c) { return P::veg_dev(c); }
@@ -516,16 +515,12 @@ template <class NF> struct Ops {
     template <int PROG> static int column_program(trm_ctx* c, double dt, int finalize, int nsteps) {
         return richards(c) ? ColumnLaunch<NF, true, PROG>::run(c, dt, finalize, nsteps) : ColumnLaunch<NF, false, PROG>::run(c, dt, finalize, nsteps);
     }
-    // the resident multi-step program on deep columns (no surface energy balance, no series: see step())
-    static int deep_program(trm_ctx* c, double dt, int finalize, int nsteps) { return DeepLaunch<NF>::run(c, PROG_MULTI, false, dt, finalize, nsteps); }
-    // Heun of deep columns: the sequence of heun_step_fused with k_column_deep<PROG_HEUN> as the column program
+    // Heun of deep columns: the sequence of heun_step_fused with k_column_deep / k_column_wide<PROG_HEUN> as the column program
     static int heun_step_deep(trm_ctx* c, double dt, int finalize) {
         int rc = update_inputs(c, c->state, c->time);
         if (!rc) rc = update_inputs(c, c->stage, c->time + dt);   // boundary value series at the stage's clock (heun.jl:52)
         if (!rc && c->params.seb) rc = surface(c, c->state, true);
-        if (!rc) {
-            rc = wide_columns(c) ? WideLaunch<NF>::run(c, PROG_HEUN, generic_bcs(c), dt, finalize) : DeepLaunch<NF>::run(c, PROG_HEUN, generic_bcs(c), dt, finalize, 1);
-        }
+        if (!rc) rc = levels_launch<NF>(c, PROG_HEUN, generic_bcs(c), dt, finalize);
         if (!rc) rc = accumulate_after(c, dt);
         if (!rc) c->closure_consistent = true;
         c->tend_valid = finalize != 0;
@@ -536,17 +531,9 @@ template <class NF> struct Ops {
     // one fused ForwardEuler step (the state's surface processes have run)
     static int wave_step(trm_ctx* c, double dt, int finalize) {
         int rc = TRM_OK;
-        if (wide_columns(c)) {
-            rc = WideLaunch<NF>::run(c, PROG_EULER, generic_bcs(c), dt, finalize);
-            if (!rc) c->closure_consistent = true;
-            return rc;
-        }
-        if (deep_columns(c)) {
-            rc = DeepLaunch<NF>::run(c, PROG_EULER, generic_bcs(c), dt, finalize, 1);
-            if (!rc) c->closure_consistent = true;
-            return rc;
-        }
-        if (packed_path(c)) {
+        if (levels_per_lane(c) > 1) {
+            rc = levels_launch<NF>(c, PROG_EULER, generic_bcs(c), dt, finalize);
+        } else if (packed_path(c)) {
             rc = PackedLaunch::step(c, dt, finalize);
         } else if (generic_bcs(c)) {
             rc = GenericLaunch<NF>::step(c, dt, finalize);
@@ -599,7 +586,7 @@ template <class NF> struct Ops {
     // The multi-step program accumulates in its own launch when it covers every open accumulator's field (the surface excess water
     // and the water table only under Richards: the NoFlow program does not carry them) -- columns of <= 64 levels.
     static bool averages_in_launch(const trm_ctx* c) {
-        if (c->Nz > 64 || deep_columns(c) || c->part >= 0) return false;
+        if (c->Nz > 64 || c->part >= 0) return false;
         for (const auto& a : c->averages) {
             if (a.field < 0) continue;
             const int s = accum_slot(a.field);
@@ -757,20 +744,18 @@ template <class NF> struct Ops {
     }
     // how many steps ONE launch of trm_step covers for this context: 1 unless the resident multi-step program applies
     static bool program_applies(const trm_ctx* c) {
-        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && (c->Nz <= 64 || deep_columns(c) || wide_columns(c));
+        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && levels_per_lane(c) > 0;
         return fused && !generic_bcs(c) && !coupled(c) && c->veg_mode != TRM_VEGETATION_STANDALONE &&
-               ((c->Nz <= 64 && series_fit_program(c)) || (deep_columns(c) && !c->params.seb && c->series.empty()));
+               ((c->Nz <= 64 && series_fit_program(c)) || (levels_per_lane(c) == 2 && !c->params.seb && c->series.empty()));
     }
     static int steps_per_launch_now(trm_ctx* c) {
         return !program_applies(c) ? 1 : (c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : auto_steps_per_launch(c));
     }
     static int step(trm_ctx* c, double dt, int nsteps, int finalize) {
         if (c->veg_mode == TRM_VEGETATION_STANDALONE) return veg_step(c, dt, nsteps, finalize, false);
-        // the fused kernels map one soil level (two for 65 ... 128 levels, branch-free boundary kinds) to one lane; anything
-        // deeper takes the reference-order kernels
         // the fused kernels map one soil level to one lane (two for 65 ... 128 levels, four for 129 ... 256); anything deeper takes the
         // reference-order kernels.
-        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && (c->Nz <= 64 || deep_columns(c) || wide_columns(c));
+        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && levels_per_lane(c) > 0;
         // Resident-column multi-step program: legal when nothing the host evaluates changes between the steps of a launch --
         // constants, or device-resident time series the program interpolates itself -- and the branch-free boundary kinds apply.
         // (columns of 65 ... 128 levels: contexts without the surface energy balance and without series)
@@ -792,7 +777,7 @@ template <class NF> struct Ops {
                 rc = c->series.empty() ? update_inputs(c, c->state, c->time) : upload_series_rows(c, dt, m);
                 if (!rc && avg_in_launch) rc = multi_program_accum(c, dt, fin, m);
                 else if (!rc) {
-                    rc = deep_columns(c) ? deep_program(c, dt, fin, m) : column_program<PROG_MULTI>(c, dt, fin, m);
+                    rc = levels_per_lane(c) > 1 ? levels_launch<NF>(c, PROG_MULTI, false, dt, fin, m) : column_program<PROG_MULTI>(c, dt, fin, m);
                     if (!rc) rc = accumulate_after(c, dt);   // (m = 1 here while averaging)
                 }
                 if (!rc) c->closure_consistent = true;
@@ -895,8 +880,7 @@ template <class NF> struct Ops {
         a.store_paw = c->opt_write_kf != 0;
         a.st_w_can = vg.w_can; a.st_C_veg = vg.C_veg; a.st_nu = vg.nu; a.st_An = vg.An; a.st_Ts = sv.Ts;
         rc = surface_veg_launch(c, v0, vs, a);
-        if (!rc) rc = wide_columns(c) ? WideLaunch<NF>::run(c, PROG_HEUN, false, dt, finalize)
-                              : (deep_columns(c) ? DeepLaunch<NF>::run(c, PROG_HEUN, false, dt, finalize, 1) : column_program<PROG_HEUN>(c, dt, finalize, 1));
+        if (!rc) rc = levels_per_lane(c) > 1 ? levels_launch<NF>(c, PROG_HEUN, false, dt, finalize) : column_program<PROG_HEUN>(c, dt, finalize, 1);
         if (rc) return rc;
         c->closure_consistent = true;
         c->tend_valid = finalize != 0;
@@ -978,9 +962,9 @@ template <class NF> struct Ops {
     static int heun_step(trm_ctx* c, double dt, int finalize) {
         if (int rr = refresh_user_stage_buffers(c)) return rr;
         if (c->opt_kernel == TRM_KERNEL_FUSED && c->Nz <= 64 && generic_bcs(c) && !coupled(c)) return heun_step_generic_fused(c, dt, finalize);
-        if (c->opt_kernel == TRM_KERNEL_FUSED && (c->Nz <= 64 || deep_columns(c) || wide_columns(c)) && !generic_bcs(c) && coupled(c)) return heun_step_coupled_fused(c, dt, finalize);
+        if (c->opt_kernel == TRM_KERNEL_FUSED && levels_per_lane(c) > 0 && !generic_bcs(c) && coupled(c)) return heun_step_coupled_fused(c, dt, finalize);
         if (c->opt_kernel == TRM_KERNEL_FUSED && c->Nz <= 64 && !generic_bcs(c) && !coupled(c)) return heun_step_fused(c, dt, finalize);
-        if (c->opt_kernel == TRM_KERNEL_FUSED && (deep_columns(c) || wide_columns(c)) && !coupled(c)) return heun_step_deep(c, dt, finalize);      // (every boundary kind)
+        if (c->opt_kernel == TRM_KERNEL_FUSED && levels_per_lane(c) > 1 && !coupled(c)) return heun_step_deep(c, dt, finalize);      // (every boundary kind)
         c->top_valid = false;
         c->tend_valid = true;
         c->closure_consistent = true;   // (ends with closure!)

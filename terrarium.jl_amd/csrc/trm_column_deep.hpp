@@ -135,9 +135,6 @@ TRM_DEV NF repair_saturation_deep(Two<NF>& s, const DeepLane& ln, int Nz, const 
     return (e_a + e_b) * dzc_top;      // (one of the two is the top cell's excess, the other +0)
 }
 
-#ifndef TRM_DEEP_WAVES
-#define TRM_DEEP_WAVES 1
-#endif
 // word w of the level record at byte offset `rec` of the level table (see level_geom)
 template <class NF> TRM_DEV NF level_word(const View<NF>& v, unsigned rec, int w) {
     return *reinterpret_cast<const NF*>(reinterpret_cast<const char*>(v.lvl) + rec + (unsigned)w * (unsigned)sizeof(NF));
@@ -149,7 +146,7 @@ template <class NF> TRM_DEV NF level_word(const View<NF>& v, unsigned rec, int w
 // `vs_arg`: the Heun stage's view -- its boundary kinds and values (series evaluated at t + dt, arrays the caller of the two-call
 // Heun wrote) are what the stage's tendencies see with GENERIC (k_heun_generic, trm_column.hpp); unused otherwise.
 template <class NF, bool RICHARDS, int HYD, bool DERIVE = false, int PROG = PROG_EULER, bool GENERIC = false>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(TRM_DEEP_WAVES, 8)))
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 8)))
     k_column_deep(View<NF> v_arg, DevParams<NF> p_arg, ColumnArgs<NF> a, View<NF> vs_arg) {
     static_assert(!GENERIC || PROG != PROG_MULTI, "generic boundary kinds on deep columns: one step per launch");
     // PROG_MULTI: a.nsteps ForwardEuler steps on the resident column (contexts without the surface energy balance and without
@@ -181,15 +178,11 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) __attribute__((amdgpu_waves_pe
     const int ka_ld = ln.ka <= last_pair ? ln.ka : last_pair;
     const unsigned ib0 = (unsigned)ii * (unsigned)sizeof(NF);
     const unsigned cb0 = ((unsigned)ii * (unsigned)v.Nzp + (unsigned)ka_ld) * (unsigned)sizeof(NF);
-#if TRM_DEEP_SCALAR_INPUTS
     // One column per wave: the per-column inputs (boundary values, ground heat flux, infiltration, the 0-D fields) are wave-uniform and
     // come through the SCALAR memory path -- no vector registers, no vector load in the middle of the wave's life, no wait for vector
     // memory where conditional loads meet (k_column: col_req; profiles/r04/exp18)
     const unsigned ib_u = (unsigned)__builtin_amdgcn_readfirstlane((int)ib0);
     auto col_ld = [&](const NF* ptr, unsigned) -> NF { return sld_off<NF>(ptr, ib_u); };
-#else
-    auto col_ld = [&](const NF* ptr, unsigned off) -> NF { return ldg(ptr, off); };
-#endif
     const NF dt = a.dt;
     const int finalize = a.finalize, write_kf = a.write_kf;
     const bool need_kc = RICHARDS || write_kf;

@@ -177,12 +177,8 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) __attribute__((amdgpu_waves_pe
     const int k_ld = ln.k0 <= last_group ? ln.k0 : last_group;
     const unsigned ib0 = (unsigned)ii * (unsigned)sizeof(NF);
     // (one column per wave: the per-column inputs through the scalar memory path, as in k_column_deep -- profiles/r04/exp18)
-#if TRM_DEEP_SCALAR_INPUTS
     const unsigned ib_u = (unsigned)__builtin_amdgcn_readfirstlane((int)ib0);
     auto col_ld = [&](const NF* ptr, unsigned) -> NF { return sld_off<NF>(ptr, ib_u); };
-#else
-    auto col_ld = [&](const NF* ptr, unsigned off) -> NF { return ldg(ptr, off); };
-#endif
     const unsigned cb0 = ((unsigned)ii * (unsigned)v.Nzp + (unsigned)k_ld) * (unsigned)sizeof(NF);
     const NF dt = a.dt;
     const int finalize = a.finalize, write_kf = a.write_kf;

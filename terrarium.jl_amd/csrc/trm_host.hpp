@@ -330,10 +330,10 @@ template <class NF> struct Policy {
         if (hyd(c) == HYD_VG_N2) return true;
         return hyd(c) == HYD_BC_LINEAR;
     }
-    // columns of 65 ... 128 levels: two levels per lane, one column per wavefront (trm_column_deep.hpp)
-    static bool deep_columns(const trm_ctx* c) { return c->Nz > 64 && c->Nz <= 128; }
-    // columns of 129 ... 256 levels: four levels per lane (trm_column_wide.hpp)
-    static bool wide_columns(const trm_ctx* c) { return c->Nz > 128 && c->Nz <= 256; }
+    // soil levels per lane of the fused column kernels: one (k_column, <= 64 levels), two (k_column_deep, 65 ... 128) or four
+    // (k_column_wide, 129 ... 256: trm_column_deep.hpp / trm_column_wide.hpp), one column per wavefront from two on; 0: deeper, no
+    // fused kernel
+    static int levels_per_lane(const trm_ctx* c) { return c->Nz <= 64 ? 1 : c->Nz <= 128 ? 2 : c->Nz <= 256 ? 4 : 0; }
     // slot of the multi-step program a series feeds, or -1 when the program cannot take it (the step then runs per launch)
     static int series_slot(const trm_ctx* c, const trm_ctx::Series& sr) {
         if (sr.is_bc) {
@@ -510,10 +510,13 @@ template <class NF> struct GenericLaunch {
     static int step(trm_ctx* c, double dt, int finalize);
     static int heun(trm_ctx* c, double dt, int finalize);
 };
-// columns of 65 ... 128 levels: k_column_deep (trm_launch_deep_f64.hip / _f32.hip)
-template <class NF> struct DeepLaunch { static int run(trm_ctx* c, int prog, bool generic, double dt, int finalize, int nsteps); };
-// columns of 129 ... 256 levels, four levels per lane: k_column_wide (trm_launch_wide_f64.hip / _f32.hip)
-template <class NF> struct WideLaunch { static int run(trm_ctx* c, int prog, bool generic, double dt, int finalize); };
+// columns of 65 ... 256 levels, M levels per lane: k_column_deep (M = 2: trm_launch_deep_f64.hip / _f32.hip) and k_column_wide
+// (M = 4: trm_launch_wide_f64.hip / _f32.hip)
+template <class NF, int M> struct LevelsLaunch { static int run(trm_ctx* c, int prog, bool generic, double dt, int finalize, int nsteps); };
+// the launch of the context's M (Policy::levels_per_lane: 2 or 4)
+template <class NF> inline int levels_launch(trm_ctx* c, int prog, bool generic, double dt, int finalize, int nsteps = 1) {
+    return Policy<NF>::levels_per_lane(c) == 4 ? LevelsLaunch<NF, 4>::run(c, prog, generic, dt, finalize, nsteps) : LevelsLaunch<NF, 2>::run(c, prog, generic, dt, finalize, nsteps);
+}
 // interleaved LandModel launches: k_land_euler (fp64, trm_launch_land.hip) / k_land_pk (fp32, trm_launch_packed.hip)
 template <class NF> struct LandLaunch { static int run(trm_ctx* c, int qcol, int qsurf, double dt, int finalize, bool top_arrays); };
 template <> int LandLaunch<double>::run(trm_ctx* c, int qcol, int qsurf, double dt, int finalize, bool top_arrays);

@@ -1,5 +1,5 @@
-// trm_launch_deep_f32.hip -- k_column_deep instantiations, float (see trm_launch_deep.inl)
-#include "trm_launch_deep.inl"
+// trm_launch_deep_f32.hip -- k_column_deep instantiations, float (see trm_launch_levels.inl)
+#include "trm_launch_levels.inl"
 namespace trmh {
-template struct DeepLaunch<float>;
+template struct LevelsLaunch<float, 2>;
 }  // namespace trmh

@@ -1,5 +1,5 @@
-// trm_launch_deep_f64.hip -- k_column_deep instantiations, double (see trm_launch_deep.inl)
-#include "trm_launch_deep.inl"
+// trm_launch_deep_f64.hip -- k_column_deep instantiations, double (see trm_launch_levels.inl)
+#include "trm_launch_levels.inl"
 namespace trmh {
-template struct DeepLaunch<double>;
+template struct LevelsLaunch<double, 2>;
 }  // namespace trmh

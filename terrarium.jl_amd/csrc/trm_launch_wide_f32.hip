@@ -1,5 +1,5 @@
-// trm_launch_wide_f32.hip -- k_column_wide instantiations, float (see trm_launch_wide.inl)
-#include "trm_launch_wide.inl"
+// trm_launch_wide_f32.hip -- k_column_wide instantiations, float (see trm_launch_levels.inl)
+#include "trm_launch_levels.inl"
 namespace trmh {
-template struct WideLaunch<float>;
+template struct LevelsLaunch<float, 4>;
 }  // namespace trmh

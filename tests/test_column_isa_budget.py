@@ -30,11 +30,17 @@ def _hipcc():
 pytestmark = pytest.mark.skipif(_hipcc() is None or shutil.which("make") is None, reason="hipcc / make not available")
 
 
-def _asm(tmp_path, name, extra):
+def _asm(tmp_path, name, extra, source=SOURCE):
     out = tmp_path / name
-    subprocess.run(["make", "-s", "-C", CSRC, "asm", f"F={SOURCE}", f"OBJDIR={out}", f"EXTRA={extra}", f"HIPCC={_hipcc()}"],
+    subprocess.run(["make", "-s", "-C", CSRC, "asm", f"F={source}", f"OBJDIR={out}", f"EXTRA={extra}", f"HIPCC={_hipcc()}"],
                    check=True, capture_output=True, text=True)
-    return str(out / f"{SOURCE}.s")
+    return str(out / f"{source}.s")
+
+
+def _resources(txt, symbol):
+    m = re.search(r"^" + symbol + r"\w*:.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+).*?; Occupancy: (\d+)", txt, re.S | re.M)
+    assert m, f"kernel {symbol} or its resource summary not found"
+    return tuple(int(x) for x in m.groups())
 
 
 def test_c3_common_path_valu_budget(tmp_path):
@@ -52,9 +58,23 @@ def test_c3_common_path_valu_budget(tmp_path):
 
 def test_c3_registers_and_scratch(tmp_path):
     txt = open(_asm(tmp_path, "shipped", "")).read()
-    m = re.search(r"^" + SYMBOL + r"\w*:.*?; NumVgprs: (\d+).*?; ScratchSize: (\d+).*?; Occupancy: (\d+)", txt, re.S | re.M)
-    assert m, "kernel or its resource summary not found"
-    vgprs, scratch, occupancy = (int(x) for x in m.groups())
+    vgprs, scratch, occupancy = _resources(txt, SYMBOL)
     assert scratch == 0
     assert vgprs <= VGPR_BUDGET
     assert occupancy == 8
+
+
+# Columns of 65 ... 128 levels (k_column_deep, two levels per lane, fp64 heat + Richards, reference-default hydraulics, T / liq
+# derived): no scratch, and the waves per SIMD of the shipped instances (78 VGPRs / 6 waves for Euler, 100 / 4 for the multi-step
+# program; EXPERIMENTS 4.7)
+DEEP_SOURCE = "trm_launch_deep_f64"
+DEEP_CASES = [("_ZN3trm13k_column_deepIdLb1ELi0ELb1ELi0ELb0E", 6),      # <double, RICHARDS, HYD_BC_LINEAR, DERIVE, PROG_EULER, no GENERIC>
+              ("_ZN3trm13k_column_deepIdLb1ELi0ELb1ELi2ELb0E", 4)]      # <double, RICHARDS, HYD_BC_LINEAR, DERIVE, PROG_MULTI, no GENERIC>
+
+
+def test_deep_column_registers_and_scratch(tmp_path):
+    txt = open(_asm(tmp_path, "deep", "", DEEP_SOURCE)).read()
+    for symbol, min_occupancy in DEEP_CASES:
+        vgprs, scratch, occupancy = _resources(txt, symbol)
+        assert scratch == 0, symbol
+        assert occupancy >= min_occupancy, (symbol, vgprs, occupancy)
