@@ -249,7 +249,8 @@ template <class NF> StageView<NF> make_stage_view(const trm_ctx* c) {
 }  // namespace
 
 namespace trmh {
-int front_epoch_next(trm_ctx* c) {
+int front_args(trm_ctx* c, const char* kernel, FrontArgs& fa) {
+    if (!c->d_top3 || !c->top_valid) return fail(c, TRM_EINVAL, std::string(kernel) + ": the surface workgroups read the top-cell arrays, which are not current");
     const size_t bytes = (size_t)c->Nh * FRONT_GRANULES * sizeof(unsigned long long);
     if (!c->d_gran) {
         TRM_HIP(c, hipMalloc((void**)&c->d_gran, bytes));
@@ -260,6 +261,11 @@ int front_epoch_next(trm_ctx* c) {
         TRM_HIP(c, hipMemsetAsync(c->d_gran, 0, bytes, c->stream));
         c->front_epoch = 1;
     }
+    fa = FrontArgs{};
+    fa.gran = c->d_gran;
+    fa.epoch = c->front_epoch;
+    fa.tag_bias = c->debug_handoff_tag_bias;
+    fa.chain_blocks = (int)((c->Nh + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK);
     return TRM_OK;
 }
 template <class NF> const LaunchArgs<NF>& launch_args(trm_ctx* c) {
@@ -370,42 +376,26 @@ bool averageable(const trm_ctx* c, int field) {
     return s < ACC_TS || c->params.seb != 0;
 }
 
+// tick! per step: the same sequence of sums as per-step calls (restarts compare the clock bit for bit)
+void tick(trm_ctx* c, double dt, int nsteps) {
+    for (int j = 0; j < nsteps; ++j) c->time += dt;
+    c->iteration += nsteps;
+}
+
+// Heun's path (Ops::heun_path).  One launch with both stages on the column in registers (Ops::fused_launch<PROG_HEUN>), by
+// k_column / k_column_land / k_heun_generic (HEUN_ONE_LAUNCH) or the levels kernels (HEUN_LEVELS: 65 ... 256 levels; the stage's
+// fields are allocated for them as for the reference-order kernels that ran there before them).  The stage's surface energy
+// balance is not evaluated: its fluxes would only enter through compute_z_bcs!, which the reference runs for the state alone
+// (heun.jl:54-69).  HEUN_COUPLED: the four launches of the vegetation-coupled LandModel, which store part of the stage.
+// HEUN_REFERENCE: the reference-order kernels on a second copy of the state.
+enum HeunPath { HEUN_ONE_LAUNCH, HEUN_LEVELS, HEUN_COUPLED, HEUN_REFERENCE };
+
 // The step sequences of one precision.  The launches themselves are Unfused / Veg / ColumnLaunch / GenericLaunch / LevelsLaunch /
-// LandLaunch / PackedLaunch (trm_host.hpp); the forwarders below keep their reference names in the sequences.
-template <class NF> struct Ops {
+// LandLaunch / PackedLaunch (trm_host.hpp); the C ABI reaches the policies and the Unfused / Veg launches through Ops too.
+template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     using P = Policy<NF>;
     using U = Unfused<NF>;
-    static bool richards(const trm_ctx* c) { return P::richards(c); }
-    static bool coupled(const trm_ctx* c) { return P::coupled(c); }
-    static int hyd(const trm_ctx* c) { return P::hyd(c); }
-    static bool generic_bcs(const trm_ctx* c) { return P::generic_bcs(c); }
-    static bool packed_path(trm_ctx* c) { return P::packed_path(c); }
-    static int levels_per_lane(const trm_ctx* c) { return P::levels_per_lane(c); }
-    static int series_slot(const trm_ctx* c, const trm_ctx::Series& sr) { return P::series_slot(c, sr); }
-    static bool series_fit_program(const trm_ctx* c) { return P::series_fit_program(c); }
-    static VegDev<NF> veg_dev(const trm_ctx* c) { return P::veg_dev(c); }
-    static VegView<NF> veg_view(const trm_ctx* c) { return P::veg_view(c); }
-    static VegView<NF> veg_view(const trm_ctx* c, const FieldSet& s) { return P::veg_view(c, s); }
-    static int await_levels(trm_ctx* c, trm_ctx::Series& sr, int last_level) { return U::await_levels(c, sr, last_level); }
-    static int update_inputs(trm_ctx* c, const FieldSet& s, double time) { return U::update_inputs(c, s, time); }
-    static int hydraulics(trm_ctx* c, const FieldSet& s) { return U::hydraulics(c, s); }
-    static int surface(trm_ctx* c, const FieldSet& s, bool from_state = false) { return U::surface(c, s, from_state); }
-    static int compute_auxiliary(trm_ctx* c, const FieldSet& s) { return U::compute_auxiliary(c, s); }
-    static int compute_tendencies(trm_ctx* c, const FieldSet& s) { return U::compute_tendencies(c, s); }
-    static int reset_tendencies(trm_ctx* c, const FieldSet& s) { return U::reset_tendencies(c, s); }
-    static int update_state(trm_ctx* c, const FieldSet& s, bool tendencies) { return U::update_state(c, s, tendencies); }
-    static int explicit_step(trm_ctx* c, const FieldSet& s, double dt) { return U::explicit_step(c, s, dt); }
-    static int closure(trm_ctx* c, const FieldSet& s) { return U::closure(c, s); }
-    static int invclosure(trm_ctx* c, const FieldSet& s) { return U::invclosure(c, s); }
-    static int initialize(trm_ctx* c) { return U::initialize(c); }
-    static int average(trm_ctx* c, int field) { return U::average(c, field); }
-    template <bool FROM_STATE, bool ADVANCE> static int surface_veg(trm_ctx* c, const FieldSet& s, double dt, bool store_paw = true) {
-        return Veg<NF>::surface_veg(c, s, FROM_STATE, ADVANCE, dt, store_paw);
-    }
-    static int surface_veg_launch(trm_ctx* c, const View<NF>& v, const VegView<NF>& vv, const SurfaceVegArgs<NF>& a) { return Veg<NF>::surface_veg_launch(c, v, vv, a); }
-    template <int MODE> static int veg_launch(trm_ctx* c, double dt, int nsteps, int finalize) { return Veg<NF>::vegetation(c, c->state, MODE, dt, nsteps, finalize); }
-    static int plant_available_water(trm_ctx* c) { return Veg<NF>::plant_available_water(c, c->state, true); }
-    static int plant_available_water(trm_ctx* c, const FieldSet& s, bool store_paw) { return Veg<NF>::plant_available_water(c, s, store_paw); }
+    using V = Veg<NF>;
 
     // nsteps steps of the standalone VegetationModel; time series inputs are evaluated by the host between launches
     static int veg_step(trm_ctx* c, double dt, int nsteps, int finalize, bool heun) {
@@ -414,18 +404,17 @@ template <class NF> struct Ops {
         while (n < nsteps) {
             const int m = c->series.empty() ? nsteps - n : 1;
             const int fin = (finalize && n + m == nsteps) ? 1 : 0;
-            int rc = update_inputs(c, c->state, c->time);
-            if (!rc) rc = heun ? veg_launch<VEG_HEUN>(c, dt, m, fin) : veg_launch<VEG_EULER>(c, dt, m, fin);
+            int rc = U::update_inputs(c, c->state, c->time);
+            if (!rc) rc = V::vegetation(c, c->state, heun ? VEG_HEUN : VEG_EULER, dt, m, fin);
             if (rc) return rc;
-            for (int j = 0; j < m; ++j) c->time += dt;
-            c->iteration += m;
+            tick(c, dt, m);
             n += m;
         }
         return TRM_OK;
     }
     // static root fractions: density at the cell centres x thickness, normalised over the column (root_distribution.jl:45-63)
     static int upload_root_fraction(trm_ctx* c) {
-        const VegDev<NF> p = veg_dev(c);
+        const VegDev<NF> p = P::veg_dev(c);
         std::vector<NF> R((size_t)c->Nz);
         NF total = NF(0);
         for (int k = 0; k < c->Nz; ++k) {
@@ -466,7 +455,7 @@ template <class NF> struct Ops {
         std::memset(&tb, 0, sizeof(tb));
         for (int j = 0; j < ns; ++j) {
             auto& sr = c->series[j];
-            const int slot = series_slot(c, sr);
+            const int slot = P::series_slot(c, sr);
             tb.base[slot] = (const NF*)sr.d_values;
             tb.row_of[slot] = j;
             tb.raster[slot] = sr.indexing == TRM_TIME_RASTER ? 1 : 0;
@@ -487,7 +476,7 @@ template <class NF> struct Ops {
                 int n1, n2;
                 double f, g;
                 series_time_indices(sr.times, sr.indexing, t, n1, n2, f, g);
-                if (int rw = await_levels(c, sr, std::max(n1, n2))) return rw;
+                if (int rw = U::await_levels(c, sr, std::max(n1, n2))) return rw;
                 rows[(size_t)s * ns + j] = SeriesRow{(long long)(sr.slot(n1) * (size_t)c->Nh), (long long)(sr.slot(n2) * (size_t)c->Nh), f, g};
                 t += dt;
             }
@@ -512,44 +501,13 @@ template <class NF> struct Ops {
     // pointer to T / sat / liq has been handed out.  Every "the next surface evaluation may read the arrays" decision goes
     // through here -- a launch with TOP_ARRAYS on a context without them would read through a null pointer.
     static bool tops_current(const trm_ctx* c) { return c->d_top3 != nullptr && !c->top_escaped; }
-    template <int PROG> static int column_program(trm_ctx* c, double dt, int finalize, int nsteps) {
-        return richards(c) ? ColumnLaunch<NF, true, PROG>::run(c, dt, finalize, nsteps) : ColumnLaunch<NF, false, PROG>::run(c, dt, finalize, nsteps);
-    }
-    // Heun of deep columns: the sequence of heun_step_fused with k_column_deep / k_column_wide<PROG_HEUN> as the column program
-    static int heun_step_deep(trm_ctx* c, double dt, int finalize) {
-        int rc = update_inputs(c, c->state, c->time);
-        if (!rc) rc = update_inputs(c, c->stage, c->time + dt);   // boundary value series at the stage's clock (heun.jl:52)
-        if (!rc && c->params.seb) rc = surface(c, c->state, true);
-        if (!rc) rc = levels_launch<NF>(c, PROG_HEUN, generic_bcs(c), dt, finalize);
-        if (!rc) rc = accumulate_after(c, dt);
-        if (!rc) c->closure_consistent = true;
-        c->tend_valid = finalize != 0;
-        c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
-        if (!rc && finalize && c->params.seb) rc = surface(c, c->state, true);
-        return rc;
-    }
-    // one fused ForwardEuler step (the state's surface processes have run)
-    static int wave_step(trm_ctx* c, double dt, int finalize) {
-        int rc = TRM_OK;
-        if (levels_per_lane(c) > 1) {
-            rc = levels_launch<NF>(c, PROG_EULER, generic_bcs(c), dt, finalize);
-        } else if (packed_path(c)) {
-            rc = PackedLaunch::step(c, dt, finalize);
-        } else if (generic_bcs(c)) {
-            rc = GenericLaunch<NF>::step(c, dt, finalize);
-        } else {
-            rc = column_program<PROG_EULER>(c, dt, finalize, 1);
-        }
-        if (!rc) c->closure_consistent = true;
-        return rc;
-    }
     static int unfused_step(trm_ctx* c, double dt, int finalize) {
         c->last_program = TRM_PROGRAM_UNFUSED;
-        int rc = update_state(c, c->state, true);
-        if (!rc) rc = explicit_step(c, c->state, dt);
-        if (!rc) rc = closure(c, c->state);
+        int rc = U::update_state(c, c->state, true);
+        if (!rc) rc = U::explicit_step(c, c->state, dt);
+        if (!rc) rc = U::closure(c, c->state);
         if (!rc) rc = accumulate_after(c, dt);
-        if (!rc && finalize) rc = compute_auxiliary(c, c->state);
+        if (!rc && finalize) rc = U::compute_auxiliary(c, c->state);
         return rc;
     }
     // ---- time averages (trm_average_*, trm_average.hpp) ----------------------------------------------------------------------
@@ -590,7 +548,7 @@ template <class NF> struct Ops {
         for (const auto& a : c->averages) {
             if (a.field < 0) continue;
             const int s = accum_slot(a.field);
-            if (s < 0 || (!richards(c) && (s == ACC_S || s == ACC_WT))) return false;
+            if (s < 0 || (!P::richards(c) && (s == ACC_S || s == ACC_WT))) return false;
         }
         return true;
     }
@@ -628,7 +586,7 @@ template <class NF> struct Ops {
                 e.src_double = 1;
             }
         }
-        int rc = richards(c) ? ColumnAccumLaunch<NF, true>::run(c, dt, finalize, nsteps, aa) : ColumnAccumLaunch<NF, false>::run(c, dt, finalize, nsteps, aa);
+        int rc = P::richards(c) ? ColumnAccumLaunch<NF, true>::run(c, dt, finalize, nsteps, aa) : ColumnAccumLaunch<NF, false>::run(c, dt, finalize, nsteps, aa);
         if (!rc) rc = AverageLaunch<NF>::accumulate(c, b);
         if (rc) return rc;
         for (auto& a : c->averages) {
@@ -644,22 +602,69 @@ template <class NF> struct Ops {
     // the packed kernel as well: C5 371 against 447-451 us, C5-VG 479 against 489, a 12 696-column fp32 shard 7.3 against 13.3
     // (r3: the rule used to keep the packed kernel there).
     static int auto_steps_per_launch(trm_ctx*) { return 50; }
+    // ---- the fused step of the state: one sequence for every program -------------------------------------------------------
+    // update_inputs! of the state; Heun: of the stage as well, at its clock t + dt (heun.jl:52); the multi-step program with time
+    // series: the rows it interpolates itself instead
+    template <int PROG> static int fused_prologue(trm_ctx* c, double dt, int nsteps) {
+        if (PROG == PROG_MULTI && !c->series.empty()) return upload_series_rows(c, dt, nsteps);
+        int rc = U::update_inputs(c, c->state, c->time);
+        if (!rc && PROG == PROG_HEUN) rc = U::update_inputs(c, c->stage, c->time + dt);
+        return rc;
+    }
+    // The launch of a fused step, by program.  ForwardEuler: the surface processes in the launch
+    // (k_column_land / k_step_pk_land), 65 ... 256 levels (k_column_deep / k_column_wide), the packed fp32 step (k_step_pk), the generic
+    // boundary kinds (k_step_wave) or k_column.  Heun: in the launch, levels, generic (k_heun_generic) or k_column.  The multi-step
+    // program: the time averages accumulated in the launch (k_column_accum), levels or k_column.
+    template <int PROG> static int step_launch(trm_ctx* c, bool in_launch, bool accum, double dt, int fin, int nsteps) {
+        if (in_launch) return std::is_same<NF, float>::value ? PackedLaunch::step_land(c, dt, fin) : FrontLaunch::run(c, dt, fin, PROG == PROG_HEUN);
+        if (accum) return multi_program_accum(c, dt, fin, nsteps);
+        if (P::levels_per_lane(c) > 1) return levels_launch<NF>(c, PROG, P::generic_bcs(c), dt, fin, nsteps);
+        if (PROG == PROG_EULER && P::packed_path(c)) return PackedLaunch::step(c, dt, fin);
+        if (PROG != PROG_MULTI && P::generic_bcs(c)) return PROG == PROG_HEUN ? GenericLaunch<NF>::heun(c, dt, fin) : GenericLaunch<NF>::step(c, dt, fin);
+        return P::richards(c) ? ColumnLaunch<NF, true, PROG>::run(c, dt, fin, nsteps) : ColumnLaunch<NF, false, PROG>::run(c, dt, fin, nsteps);
+    }
+    // What a fused launch leaves (rc: the launch's): the stored T / liq are the closure of the state once it has succeeded; the open
+    // time averages take the step's terms (`accumulate`: the launch has not added them itself); only the finalizing launch stores
+    // state.tendencies; the top-cell arrays describe the state after a successful LandModel launch.  Then, finalizing, the state's
+    // surface processes once more (+ the 0-D auxiliaries of the coupled vegetation).
+    static int fused_epilogue(trm_ctx* c, int rc, double dt, int fin, bool accumulate = true) {
+        if (!rc) c->closure_consistent = true;
+        if (!rc && accumulate) rc = accumulate_after(c, dt);
+        c->tend_valid = fin != 0;
+        c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
+        if (rc || !fin) return rc;
+        if (P::coupled(c)) return V::surface_veg(c, c->state, true, false, 0.0);
+        return c->params.seb ? U::surface(c, c->state, true) : TRM_OK;
+    }
+    // One fused launch of the columns the launch helpers currently address: one ForwardEuler or Heun step, or `nsteps` steps of the
+    // multi-step program (PROG_MULTI; it carries the surface processes and the series itself).  The 0-D surface processes run as
+    // their own small launch in front of the column kernel (LandModel; + the 0-D prognostics' step of the coupled vegetation) unless
+    // the launch carries them (surface_in_launch).  (The per-cell plant_available_water field is materialised with the other per-cell
+    // auxiliaries: by the finalizing launch, or every step under TRM_OPT_WRITE_KF_EVERY_STEP.)
+    template <int PROG> static int fused_launch(trm_ctx* c, double dt, int fin, int nsteps = 1) {
+        int rc = fused_prologue<PROG>(c, dt, nsteps);
+        const bool in_launch = !rc && PROG != PROG_MULTI && surface_in_launch(c, PROG == PROG_HEUN);
+        if (!rc && PROG != PROG_MULTI && P::coupled(c)) rc = V::surface_veg(c, c->state, true, true, dt, c->opt_write_kf != 0);
+        else if (!rc && PROG != PROG_MULTI && c->params.seb && !in_launch) rc = U::surface(c, c->state, true);
+        const bool accum = PROG == PROG_MULTI && averaging(c) && averages_in_launch(c);
+        if (!rc) rc = step_launch<PROG>(c, in_launch, accum, dt, fin, nsteps);
+        return fused_epilogue(c, rc, dt, fin, !accum);
+    }
     // ---- LandModel, per-step path: the surface processes of one half of the columns UNDER the column program of the other ----
     // (k_land_euler / k_land_pk, trm_column.hpp: one stream, two launches per step as before, each covering the soil columns
     // of one half and the 0-D surface processes of the other)
     static bool interleave_now(trm_ctx* c, int steps_left) {
-        if (c->opt_pipeline == 0 || steps_left < 2 || averaging(c) || !c->params.seb || !richards(c) || coupled(c) || c->part_n[1] <= 0) return false;
-        if (!c->series.empty() || generic_bcs(c) || c->Nz > 64) return false;      // (inputs constant over the call; one level per lane)
-        if (std::is_same<NF, float>::value && !packed_path(c)) return false;        // (fp32 off the packed kernel: not instantiated)
+        if (c->opt_pipeline == 0 || steps_left < 2 || averaging(c) || !c->params.seb || !P::richards(c) || P::coupled(c) || c->part_n[1] <= 0) return false;
+        if (!c->series.empty() || P::generic_bcs(c) || c->Nz > 64) return false;      // (inputs constant over the call; one level per lane)
+        if (std::is_same<NF, float>::value && !P::packed_path(c)) return false;        // (fp32 off the packed kernel: not instantiated)
         // Measured (profiles/r03/exp6_ab_land_interleaved.log, bench_default.json: land_interleaved): within +-2 % at 812 500 columns
         // (492 vs 497, 503 vs 511 us on one box; 523 vs 512 on another), +10 % at N145 and on its shards -- every launch carries ~4 us
         // of fixed cost, and two half-size column launches pay it twice where the k_surface launch they absorb was little more than
         // that fixed cost itself.  Not a win anywhere it was measured: AUTO (2) leaves it off; 1 forces it.
         return c->opt_pipeline == 1;
     }
-    // columns of part `qcol` step; the surface processes of part `qsurf` run beside them for ITS next column step
-    static int land_launch(trm_ctx* c, int qcol, int qsurf, double dt, int finalize, bool top_arrays) { return LandLaunch<NF>::run(c, qcol, qsurf, dt, finalize, top_arrays); }
-    // `nsteps` >= 2 ForwardEuler steps of a bare-ground LandModel with constant inputs:
+    // `nsteps` >= 2 ForwardEuler steps of a bare-ground LandModel with constant inputs; columns of part `qcol` step, the surface
+    // processes of part `qsurf` run beside them for ITS next column step:
     //     surf(A, 0) | col(A, 0) + surf(B, 0) | col(B, 0) + surf(A, 1) | ... | col(A, N-1) + surf(B, N-1) | col(B, N-1)
     static int land_steps_interleaved(trm_ctx* c, double dt, int nsteps, int finalize) {
         const bool top0 = c->top_valid, cc0 = c->closure_consistent;
@@ -667,45 +672,36 @@ template <class NF> struct Ops {
         {   // the state's surface processes for half A
             PartScope scope(c, 0);
             c->top_valid = top0;
-            rc = surface(c, c->state, true);
+            rc = U::surface(c, c->state, true);
         }
         for (int n = 0; n < nsteps && !rc; ++n) {
             const int fin = (finalize && n == nsteps - 1) ? 1 : 0;
             const bool tops = (n == 0) ? top0 : tops_current(c);     // what a surface evaluation of an UNSTEPPED / stepped half reads
             c->closure_consistent = (n == 0) ? cc0 : true;
-            rc = land_launch(c, 0, 1, dt, fin, tops);
+            rc = LandLaunch<NF>::run(c, 0, 1, dt, fin, tops);
             if (rc) break;
             if (n < nsteps - 1) {
-                rc = land_launch(c, 1, 0, dt, 0, tops_current(c));   // (half A has just been stepped: its top arrays are current)
+                rc = LandLaunch<NF>::run(c, 1, 0, dt, 0, tops_current(c));   // (half A has just been stepped: its top arrays are current)
             } else {
                 PartScope scope(c, 1);
-                rc = wave_step(c, dt, fin);
+                rc = step_launch<PROG_EULER>(c, false, false, dt, fin, 1);
             }
-            c->time += dt;
-            c->iteration += 1;
+            tick(c, dt, 1);
         }
-        c->closure_consistent = !rc;
-        c->tend_valid = finalize != 0;
-        c->top_valid = !rc && tops_current(c);
-        if (!rc && finalize) rc = surface(c, c->state, true);
-        return rc;
+        return fused_epilogue(c, rc, dt, finalize);
     }
-    // One fused ForwardEuler step of the columns the launch helpers currently address: update_inputs!, the 0-D surface
-    // processes as their own small launch in front of the column kernel (LandModel), and once more after it when finalizing.
-    // (+ the 0-D prognostics' step of the coupled vegetation; the per-cell plant_available_water field is materialised with the
-    // other per-cell auxiliaries: by the finalizing launch, or every step under TRM_OPT_WRITE_KF_EVERY_STEP)
     // TRM_OPT_SURFACE_IN_LAUNCH: a per-step launch of this context can carry its own surface processes (k_column_land) -- a
     // bare-ground LandModel in fp64 on the branch-free program with the LandModel's boundary wiring, one level per lane, every
     // column in one launch, the top-cell arrays current (the surface workgroups read them).
     static bool surface_in_launch(trm_ctx* c, bool heun = false) {
         if (c->opt_front == 0 || (heun && std::is_same<NF, float>::value)) return false;
-        if (!c->params.seb || !richards(c) || coupled(c) || c->Nz > 64 || generic_bcs(c) || c->part >= 0) return false;
+        if (!c->params.seb || !P::richards(c) || P::coupled(c) || c->Nz > 64 || P::generic_bcs(c) || c->part >= 0) return false;
         if (c->opt_kernel != TRM_KERNEL_FUSED || !c->opt_bc_signature || bc_signature_of(c) != BCSIG_LAND) return false;
-        if (hyd(c) != HYD_BC_LINEAR && hyd(c) != HYD_VG_N2) return false;
+        if (P::hyd(c) != HYD_BC_LINEAR && P::hyd(c) != HYD_VG_N2) return false;
         if (!c->top_valid || !tops_current(c)) return false;
         const int d = heun ? DERIVE_NONE : P::template derive_now<true>(c);      // (the Heun program reads T / liq as stored)
-        if (std::is_same<NF, float>::value ? !(packed_path(c) && (d == DERIVE_NONE || d == DERIVE_LIQ))         // k_step_pk_land
-                                           : !(d == DERIVE_NONE || d == DERIVE_T_LIQ)) return false;          // k_column_land
+        if (std::is_same<NF, float>::value ? !(P::packed_path(c) && (d == DERIVE_NONE || d == DERIVE_LIQ))         // k_step_pk_land
+                                           : !(d == DERIVE_NONE || d == DERIVE_T_LIQ)) return false;             // k_column_land
         if (c->opt_front == 1) return true;
         // The library's rule (2).  What the single launch saves is the FIXED cost of the second launch (~3-4 us); the surface chain
         // itself is still evaluated, and the column waves of the first generation wait for it.  Measured, same box, pair -> one launch
@@ -714,23 +710,6 @@ template <class NF> struct Ops {
         // (56 951) 30.3 -> 29.6 ... 30.0; fp32 12 696 columns 15.2 -> 10.6, 50 782 29.5 -> 31.2, 203 125 108.6 -> 106.6, C5
         // (812 500) 425.4 -> 426.7, C5-VG 437.1 -> 451.0: a clear win where the step is launch-bound, nothing beyond.
         return c->Nh <= (std::is_same<NF, float>::value ? 32768 : 65536);
-    }
-    static int fused_step(trm_ctx* c, double dt, int fin) {
-        int rc = update_inputs(c, c->state, c->time);
-        if (rc) return rc;
-        const bool in_launch = surface_in_launch(c);
-        if (coupled(c)) rc = surface_veg<true, true>(c, c->state, dt, c->opt_write_kf != 0);
-        else if (c->params.seb && !in_launch) rc = surface(c, c->state, true);
-        if (!rc && in_launch) {
-            rc = std::is_same<NF, float>::value ? PackedLaunch::step_land(c, dt, fin) : FrontLaunch::run(c, dt, fin);
-            if (!rc) c->closure_consistent = true;
-        } else if (!rc) rc = wave_step(c, dt, fin);
-        if (!rc) rc = accumulate_after(c, dt);
-        c->tend_valid = fin != 0;   // only the finalizing launch stores state.tendencies
-        c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
-        if (!rc && fin && coupled(c)) rc = surface_veg<true, false>(c, c->state, 0.0);
-        else if (!rc && fin && c->params.seb) rc = surface(c, c->state, true);
-        return rc;
     }
     // TRM_OPT_SINGLE_STEP_PROGRAM: a bare-ground LandModel stepped ONE step per call (its inputs change every step: a coupled
     // atmosphere) takes the resident column program with the surface processes inline -- one launch instead of the
@@ -744,9 +723,9 @@ template <class NF> struct Ops {
     }
     // how many steps ONE launch of trm_step covers for this context: 1 unless the resident multi-step program applies
     static bool program_applies(const trm_ctx* c) {
-        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && levels_per_lane(c) > 0;
-        return fused && !generic_bcs(c) && !coupled(c) && c->veg_mode != TRM_VEGETATION_STANDALONE &&
-               ((c->Nz <= 64 && series_fit_program(c)) || (levels_per_lane(c) == 2 && !c->params.seb && c->series.empty()));
+        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && P::levels_per_lane(c) > 0;
+        return fused && !P::generic_bcs(c) && !P::coupled(c) && c->veg_mode != TRM_VEGETATION_STANDALONE &&
+               ((c->Nz <= 64 && P::series_fit_program(c)) || (P::levels_per_lane(c) == 2 && !c->params.seb && c->series.empty()));
     }
     static int steps_per_launch_now(trm_ctx* c) {
         return !program_applies(c) ? 1 : (c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : auto_steps_per_launch(c));
@@ -755,7 +734,7 @@ template <class NF> struct Ops {
         if (c->veg_mode == TRM_VEGETATION_STANDALONE) return veg_step(c, dt, nsteps, finalize, false);
         // the fused kernels map one soil level to one lane (two for 65 ... 128 levels, four for 129 ... 256); anything deeper takes the
         // reference-order kernels.
-        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && levels_per_lane(c) > 0;
+        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && P::levels_per_lane(c) > 0;
         // Resident-column multi-step program: legal when nothing the host evaluates changes between the steps of a launch --
         // constants, or device-resident time series the program interpolates itself -- and the branch-free boundary kinds apply.
         // (columns of 65 ... 128 levels: contexts without the surface energy balance and without series)
@@ -768,22 +747,13 @@ template <class NF> struct Ops {
             int m = std::min(spl, nsteps - n);
             const int fin = (finalize && n + m == nsteps) ? 1 : 0;
             if (!fused) {
-                rc = update_inputs(c, c->state, c->time);
+                rc = U::update_inputs(c, c->state, c->time);
                 c->top_valid = false;
                 c->tend_valid = true;
                 if (!rc) rc = unfused_step(c, dt, fin);
                 if (!rc) c->closure_consistent = true;   // closure! has just run
             } else if (m > 1 || (program_ok && single_step_program(c))) {
-                rc = c->series.empty() ? update_inputs(c, c->state, c->time) : upload_series_rows(c, dt, m);
-                if (!rc && avg_in_launch) rc = multi_program_accum(c, dt, fin, m);
-                else if (!rc) {
-                    rc = levels_per_lane(c) > 1 ? levels_launch<NF>(c, PROG_MULTI, false, dt, fin, m) : column_program<PROG_MULTI>(c, dt, fin, m);
-                    if (!rc) rc = accumulate_after(c, dt);   // (m = 1 here while averaging)
-                }
-                if (!rc) c->closure_consistent = true;
-                c->tend_valid = fin != 0;
-                c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
-                if (!rc && fin && c->params.seb) rc = surface(c, c->state, true);
+                rc = fused_launch<PROG_MULTI>(c, dt, fin, m);
             } else if (interleave_now(c, nsteps - n)) {
                 // every remaining step of the call in one go (the clock is ticked inside)
                 m = nsteps - n;
@@ -791,11 +761,10 @@ template <class NF> struct Ops {
                 n += m;
                 continue;
             } else {
-                rc = fused_step(c, dt, fin);
+                rc = fused_launch<PROG_EULER>(c, dt, fin);
             }
             if (rc) break;
-            for (int j = 0; j < m; ++j) c->time += dt;   // tick! per step: the same sequence of sums as per-step calls
-            c->iteration += m;
+            tick(c, dt, m);
             n += m;
         }
         return rc;
@@ -821,22 +790,6 @@ template <class NF> struct Ops {
             TRM_HIP(c, hipMemcpyAsync(c->stage.kf_top, c->state.kf_top, (size_t)c->Nh * sizeof(NF), hipMemcpyDeviceToDevice, c->stream));
         return TRM_OK;
     }
-    // Heun in ONE launch (TRM_KERNEL_FUSED, Nz <= 64, branch-free boundary kinds): both stages on the column in registers
-    // (k_column<PROG_HEUN>), the stage never touches memory.  The stage's surface energy balance is not evaluated: its
-    // fluxes would only enter through compute_z_bcs!, which the reference runs for the state alone (heun.jl:54-69).
-    static int heun_step_fused(trm_ctx* c, double dt, int finalize) {
-        int rc = update_inputs(c, c->state, c->time);
-        if (!rc) rc = update_inputs(c, c->stage, c->time + dt);   // boundary value series at the stage's clock (heun.jl:52)
-        const bool in_launch = !rc && surface_in_launch(c, true);      // (k_column_land<..., PROG_HEUN>: the state's surface processes in the launch)
-        if (!rc && c->params.seb && !in_launch) rc = surface(c, c->state, true);
-        if (!rc) rc = in_launch ? FrontLaunch::run(c, dt, finalize, true) : column_program<PROG_HEUN>(c, dt, finalize, 1);
-        if (!rc) rc = accumulate_after(c, dt);
-        if (!rc) c->closure_consistent = true;
-        c->tend_valid = finalize != 0;
-        c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
-        if (!rc && finalize && c->params.seb) rc = surface(c, c->state, true);
-        return rc;
-    }
     // Heun of the vegetation-coupled LandModel in four launches (heun.jl:37-71 with land_model.jl:79-97).  The soil column's
     // two stages stay in registers (k_column<PROG_HEUN>); what the 0-D processes need AT the stage -- the stage's saturation,
     // liquid fraction, temperature, surface excess water -- is the only part of it that is stored.  The final soil state does not
@@ -846,11 +799,10 @@ template <class NF> struct Ops {
     //   3. k_surface_veg(stage): auxiliaries and 0-D tendencies at the stage (inputs evaluated at t + dt)
     //   4. k_heun_average_0d: averaged tendencies, explicit step of canopy water, vegetation carbon, area fraction
     static int heun_step_coupled_fused(trm_ctx* c, double dt, int finalize) {
-        int rc = update_inputs(c, c->state, c->time);
-        if (!rc) rc = update_inputs(c, c->stage, c->time + dt);
-        if (rc) return rc;
-        const VegView<NF> vs = veg_view(c, c->state);
-        VegView<NF> vg = veg_view(c, c->stage);
+        int rc = fused_prologue<PROG_HEUN>(c, dt, 1);
+        if (rc) return fused_epilogue(c, rc, dt, finalize);
+        const VegView<NF> vs = P::veg_view(c, c->state);
+        VegView<NF> vg = P::veg_view(c, c->stage);
         View<NF> sv = cached_view<NF>(c, c->stage);
         // inputs of the stage: its own arrays where a time series feeds them (evaluated at t + dt above), else the state's
         auto fed = [&](int field) {
@@ -873,45 +825,26 @@ template <class NF> struct Ops {
         if (!fed(TRM_FIELD_STEM_AREA_INDEX)) vg.SAI = vs.SAI;
         SurfaceVegArgs<NF> a{};
         a.dt = (NF)dt;
-        a.richards = richards(c) ? 1 : 0;
+        a.richards = P::richards(c) ? 1 : 0;
         a.from_state = 1;
         a.top_arrays = (c->top_valid && tops_current(c)) ? 1 : 0;
         a.advance = 3;
         a.store_paw = c->opt_write_kf != 0;
         a.st_w_can = vg.w_can; a.st_C_veg = vg.C_veg; a.st_nu = vg.nu; a.st_An = vg.An; a.st_Ts = sv.Ts;
-        rc = surface_veg_launch(c, v0, vs, a);
-        if (!rc) rc = levels_per_lane(c) > 1 ? levels_launch<NF>(c, PROG_HEUN, false, dt, finalize) : column_program<PROG_HEUN>(c, dt, finalize, 1);
-        if (rc) return rc;
-        c->closure_consistent = true;
-        c->tend_valid = finalize != 0;
-        c->top_valid = tops_current(c);
-        SurfaceVegArgs<NF> b{};
-        b.dt = (NF)dt;
-        b.richards = a.richards;
-        b.from_state = 1;
-        b.top_arrays = 0;
-        b.advance = 2;
-        b.store_paw = 0;
-        rc = surface_veg_launch(c, sv, vg, b);
-        if (rc) return rc;
-        rc = Veg<NF>::heun_average_0d(c, vs, vg, dt);
-        if (!rc) rc = accumulate_after(c, dt);
-        if (rc) return rc;
-        if (finalize) rc = surface_veg<true, false>(c, c->state, 0.0);
-        return rc;
-    }
-    static int heun_step_generic_fused(trm_ctx* c, double dt, int finalize) {
-        int rc = update_inputs(c, c->state, c->time);
-        if (!rc) rc = update_inputs(c, c->stage, c->time + dt);   // boundary value series at the stage's clock (heun.jl:52)
-        if (!rc && c->params.seb) rc = surface(c, c->state, true);
-        if (rc) return rc;
-        rc = GenericLaunch<NF>::heun(c, dt, finalize);
-        if (!rc) rc = accumulate_after(c, dt);
-        if (!rc) c->closure_consistent = true;
-        c->tend_valid = finalize != 0;
-        c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
-        if (!rc && finalize && c->params.seb) rc = surface(c, c->state, true);
-        return rc;
+        rc = V::surface_veg_launch(c, v0, vs, a);
+        if (!rc) rc = step_launch<PROG_HEUN>(c, false, false, dt, finalize, 1);
+        if (!rc) {
+            SurfaceVegArgs<NF> b{};
+            b.dt = (NF)dt;
+            b.richards = a.richards;
+            b.from_state = 1;
+            b.top_arrays = 0;
+            b.advance = 2;
+            b.store_paw = 0;
+            rc = V::surface_veg_launch(c, sv, vg, b);
+        }
+        if (!rc) rc = V::heun_average_0d(c, vs, vg, dt);
+        return fused_epilogue(c, rc, dt, finalize);
     }
     // Stage buffers the caller of the two-call Heun has been handed (trm_stage_bc_device_ptr, the stage's vwc_forcing) hold
     // what it wrote for ITS last stage.  Whenever the library forms a stage on its own they are the state's values again: the
@@ -927,44 +860,49 @@ template <class NF> struct Ops {
     }
     // heun.jl:41-52: the first half of timestep!(integrator, ::Heun) on the reference-order kernels
     static int heun_predict(trm_ctx* c, double dt, bool copy_everything = false) {
-        int rc = update_inputs(c, c->state, c->time);
-        if (!rc) rc = update_state(c, c->state, true);
+        int rc = U::update_inputs(c, c->state, c->time);
+        if (!rc) rc = U::update_state(c, c->state, true);
         if (!rc) rc = copy_state_to_stage(c, copy_everything);
         if (!rc) rc = refresh_user_stage_buffers(c);
-        if (!rc) rc = update_inputs(c, c->stage, c->time);   // the stage's clock is still t for its predictor step (heun.jl:47-50)
-        if (!rc) rc = explicit_step(c, c->stage, dt);
-        if (!rc) rc = closure(c, c->stage);
-        if (!rc) rc = update_inputs(c, c->stage, c->time + dt);   // the stage's clock has ticked (heun.jl:52)
+        if (!rc) rc = U::update_inputs(c, c->stage, c->time);   // the stage's clock is still t for its predictor step (heun.jl:47-50)
+        if (!rc) rc = U::explicit_step(c, c->stage, dt);
+        if (!rc) rc = U::closure(c, c->stage);
+        if (!rc) rc = U::update_inputs(c, c->stage, c->time + dt);   // the stage's clock has ticked (heun.jl:52)
         return rc;
     }
     // heun.jl:54-71: the second half
     // update_state!(stage) up to and including compute_auxiliary!(stage) (heun.jl:54, state_variables.jl:72-80): what a forcing
     // function evaluated inside compute_tendencies!(stage) finds in `fields`
     static int heun_stage_auxiliary(trm_ctx* c) {
-        int rc = reset_tendencies(c, c->stage);
-        if (!rc) rc = compute_auxiliary(c, c->stage);
+        int rc = U::reset_tendencies(c, c->stage);
+        if (!rc) rc = U::compute_auxiliary(c, c->stage);
         return rc;
     }
     static int heun_correct(trm_ctx* c, double dt, int finalize, bool stage_auxiliary_done = false) {
-        int rc = stage_auxiliary_done ? compute_tendencies(c, c->stage) : update_state(c, c->stage, true);
-        if (!rc) rc = average(c, TRM_FIELD_TEND_INTERNAL_ENERGY);
-        if (!rc && richards(c)) rc = average(c, TRM_FIELD_TEND_SATURATION_WATER_ICE);
-        if (!rc && richards(c)) rc = average(c, TRM_FIELD_TEND_SURFACE_EXCESS_WATER);
-        if (coupled(c))
+        int rc = stage_auxiliary_done ? U::compute_tendencies(c, c->stage) : U::update_state(c, c->stage, true);
+        if (!rc) rc = U::average(c, TRM_FIELD_TEND_INTERNAL_ENERGY);
+        if (!rc && P::richards(c)) rc = U::average(c, TRM_FIELD_TEND_SATURATION_WATER_ICE);
+        if (!rc && P::richards(c)) rc = U::average(c, TRM_FIELD_TEND_SURFACE_EXCESS_WATER);
+        if (P::coupled(c))
             for (int f : {TRM_FIELD_TEND_CANOPY_WATER, TRM_FIELD_TEND_CARBON_VEGETATION, TRM_FIELD_TEND_VEGETATION_AREA_FRACTION})
-                if (!rc) rc = average(c, f);
-        if (!rc) rc = explicit_step(c, c->state, dt);
-        if (!rc) rc = closure(c, c->state);
+                if (!rc) rc = U::average(c, f);
+        if (!rc) rc = U::explicit_step(c, c->state, dt);
+        if (!rc) rc = U::closure(c, c->state);
         if (!rc) rc = accumulate_after(c, dt);
-        if (!rc && finalize) rc = compute_auxiliary(c, c->state);
+        if (!rc && finalize) rc = U::compute_auxiliary(c, c->state);
         return rc;
+    }
+    // the path of one Heun step (HeunPath); trm_step_heun allocates the stage's fields for every path but HEUN_ONE_LAUNCH
+    static int heun_path(const trm_ctx* c) {
+        if (c->opt_kernel != TRM_KERNEL_FUSED || P::levels_per_lane(c) == 0) return HEUN_REFERENCE;
+        if (P::coupled(c)) return P::generic_bcs(c) ? HEUN_REFERENCE : HEUN_COUPLED;
+        return P::levels_per_lane(c) > 1 ? HEUN_LEVELS : HEUN_ONE_LAUNCH;
     }
     static int heun_step(trm_ctx* c, double dt, int finalize) {
         if (int rr = refresh_user_stage_buffers(c)) return rr;
-        if (c->opt_kernel == TRM_KERNEL_FUSED && c->Nz <= 64 && generic_bcs(c) && !coupled(c)) return heun_step_generic_fused(c, dt, finalize);
-        if (c->opt_kernel == TRM_KERNEL_FUSED && levels_per_lane(c) > 0 && !generic_bcs(c) && coupled(c)) return heun_step_coupled_fused(c, dt, finalize);
-        if (c->opt_kernel == TRM_KERNEL_FUSED && c->Nz <= 64 && !generic_bcs(c) && !coupled(c)) return heun_step_fused(c, dt, finalize);
-        if (c->opt_kernel == TRM_KERNEL_FUSED && levels_per_lane(c) > 1 && !coupled(c)) return heun_step_deep(c, dt, finalize);      // (every boundary kind)
+        const int path = heun_path(c);
+        if (path == HEUN_ONE_LAUNCH || path == HEUN_LEVELS) return fused_launch<PROG_HEUN>(c, dt, finalize);
+        if (path == HEUN_COUPLED) return heun_step_coupled_fused(c, dt, finalize);
         c->top_valid = false;
         c->tend_valid = true;
         c->closure_consistent = true;   // (ends with closure!)
@@ -2045,7 +1983,7 @@ int trm_update_state(trm_ctx* c, int compute_tendencies) {
     c->tend_valid = true;
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) {
         int rc = DISPATCH(c, update_inputs(c, c->state, c->time));
-        if (!rc) rc = compute_tendencies ? DISPATCH(c, template veg_launch<VEG_UPDATE>(c, 0.0, 1, 0)) : DISPATCH(c, template veg_launch<VEG_AUX>(c, 0.0, 1, 0));
+        if (!rc) rc = compute_tendencies ? DISPATCH(c, vegetation(c, c->state, VEG_UPDATE, 0.0, 1, 0)) : DISPATCH(c, vegetation(c, c->state, VEG_AUX, 0.0, 1, 0));
         return finish(c, rc);
     }
     int rc = DISPATCH(c, update_inputs(c, c->state, c->time));
@@ -2054,12 +1992,12 @@ int trm_update_state(trm_ctx* c, int compute_tendencies) {
 }
 int trm_compute_auxiliary(trm_ctx* c) {
     TRM_ENTER(c);
-    if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, template veg_launch<VEG_AUX>(c, 0.0, 1, 0)));
+    if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, vegetation(c, c->state, VEG_AUX, 0.0, 1, 0)));
     return finish(c, DISPATCH(c, compute_auxiliary(c, c->state)));
 }
 int trm_compute_tendencies(trm_ctx* c) {
     TRM_ENTER(c);
-    if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, template veg_launch<VEG_TEND>(c, 0.0, 1, 0)));
+    if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, vegetation(c, c->state, VEG_TEND, 0.0, 1, 0)));
     return finish(c, DISPATCH(c, compute_tendencies(c, c->state)));
 }
 int trm_reset_tendencies(trm_ctx* c) {
@@ -2069,7 +2007,7 @@ int trm_reset_tendencies(trm_ctx* c) {
 }
 int trm_explicit_step(trm_ctx* c, double dt) {
     TRM_ENTER(c);
-    if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, template veg_launch<VEG_EXPLICIT>(c, dt, 1, 0)));
+    if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, vegetation(c, c->state, VEG_EXPLICIT, dt, 1, 0)));
     c->top_valid = false;
     c->closure_consistent = false;
     c->tan_stale = true;
@@ -2124,28 +2062,30 @@ int trm_step_timed(trm_ctx* c, double dt, int nsteps, int finalize, float* ms) {
     return TRM_OK;
 }
 
+namespace {
+// the stage's fields: a second copy of the state (fields enabled since the last call included)
+int ensure_stage(trm_ctx* c) {
+    int rc = alloc_fields(c, c->stage);
+    if (rc) return rc;
+    if (!c->has_stage) c->args_valid = false;
+    c->has_stage = true;
+    return TRM_OK;
+}
+}  // namespace
+
 int trm_step_heun(trm_ctx* c, double dt, int nsteps, int finalize) {
     TRM_ENTER(c);
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_heun: nsteps < 0");
     c->tan_stale = true;
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, veg_step(c, dt, nsteps, finalize, true)));
-    const bool generic = c->precision == TRM_F64 ? Ops<double>::generic_bcs(c) : Ops<float>::generic_bcs(c);
-    // (the one-launch programs keep the stage in registers; the coupled vegetation stores part of it, the reference-order
-    // kernels all of it -- with the generic boundary kinds AND the coupled vegetation they are what runs)
-    const bool fused_heun = c->opt_kernel == TRM_KERNEL_FUSED && c->Nz <= 64 && c->veg_mode != TRM_VEGETATION_COUPLED;
-    (void)generic;
-    if (!fused_heun) {   // the reference-order kernels work on a second copy of the state (fields enabled since the last call included)
-        int rc = alloc_fields(c, c->stage);
-        if (rc) return rc;
-        if (!c->has_stage) c->args_valid = false;
-        c->has_stage = true;
-    }
+    // (HeunPath: the stage's fields exist for every path but the one launch of <= 64 levels, which keeps the stage in registers)
+    if (DISPATCH(c, heun_path(c)) != HEUN_ONE_LAUNCH)
+        if (int rc = ensure_stage(c)) return rc;
     for (int n = 0; n < nsteps; ++n) {
         int fin = (finalize && n == nsteps - 1) ? 1 : 0;
         int rc = DISPATCH(c, heun_step(c, dt, fin));
         if (rc) return rc;
-        c->time += dt;
-        c->iteration += 1;
+        tick(c, dt, 1);
     }
     return finish(c, TRM_OK);
 }
@@ -2166,16 +2106,6 @@ int trm_step_heun_timed(trm_ctx* c, double dt, int nsteps, int finalize, float* 
 }
 
 // ---- Heun in two calls: the caller evaluates state-dependent forcings / boundary values at the stage in between ------------
-namespace {
-int ensure_stage(trm_ctx* c) {
-    int rc = alloc_fields(c, c->stage);
-    if (rc) return rc;
-    if (!c->has_stage) c->args_valid = false;
-    c->has_stage = true;
-    return TRM_OK;
-}
-}  // namespace
-
 int trm_heun_predict(trm_ctx* c, double dt) {
     TRM_ENTER_HEUN(c);
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) return fail(c, TRM_EUNSUPPORTED, "trm_heun_predict: the standalone VegetationModel has no state-dependent callbacks; use trm_step_heun");
@@ -2214,8 +2144,7 @@ int trm_heun_correct(trm_ctx* c, double dt, int finalize) {
     c->top_valid = false;
     c->tend_valid = true;
     c->closure_consistent = true;      // (ends with closure!)
-    c->time += dt;
-    c->iteration += 1;
+    tick(c, dt, 1);
     return finish(c, TRM_OK);
 }
 
@@ -2467,8 +2396,7 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
         int rc = Ops<double>::update_inputs(c, c->state, c->time);
         if (!rc) rc = TangentLaunch::step(c, dt, m);
         if (rc) return rc;
-        for (int j = 0; j < m; ++j) c->time += dt;   // (tick! per step, as trm_step)
-        c->iteration += m;
+        tick(c, dt, m);
         n += m;
     }
     c->closure_consistent = true;
@@ -2546,7 +2474,7 @@ int trm_set_vegetation(trm_ctx* c, const trm_vegetation_params* p, int mode) {
 int trm_compute_plant_available_water(trm_ctx* c) {
     TRM_ENTER(c);
     if (c->veg_mode == TRM_VEGETATION_OFF) return fail(c, TRM_EINVAL, "trm_compute_plant_available_water: call trm_set_vegetation first");
-    return finish(c, DISPATCH(c, plant_available_water(c)));
+    return finish(c, DISPATCH(c, plant_available_water(c, c->state, true)));
 }
 
 // ---- multi-device diagnostics --------------------------------------------------------

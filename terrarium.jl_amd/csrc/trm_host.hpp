@@ -433,6 +433,31 @@ inline int program_id(int family, int hyd, int lpc, int derive, int staged, int 
         case HYD_VG_N2: { constexpr int H = HYD_VG_N2; CALL; } break;         \
         default: { constexpr int H = HYD_GENERIC; CALL; } break;             \
     }
+// whether a step launch stores the hydraulic conductivity: the finalizing one, or every one under TRM_OPT_WRITE_KF_EVERY_STEP
+inline int write_kf(const trm_ctx* c, int finalize) { return (c->opt_write_kf || finalize) ? 1 : 0; }
+// The arguments of a column program launch: `nsteps` steps of program `prog` (PROG_*), the stage's temperature boundary values
+// (Heun: evaluated at t + dt), the multi-step program's series table, and for the Heun of the vegetation-coupled LandModel the
+// stage's soil state, which the 0-D processes evaluated at the stage read (null otherwise)
+template <class NF> ColumnArgs<NF> column_args(trm_ctx* c, double dt, int finalize, int nsteps, int prog) {
+    const LaunchArgs<NF>& la = launch_args<NF>(c);
+    ColumnArgs<NF> a{};
+    a.dt = (NF)dt;
+    a.finalize = finalize;
+    a.write_kf = write_kf(c, finalize);
+    a.nsteps = nsteps;
+    a.bcT_bot_stage = la.w.bcT_bot;
+    a.bcT_top_stage = la.w.bcT_top;
+    a.series = (const SeriesTable<NF>*)c->d_series_table;
+    a.series_rows = (const SeriesRow*)c->d_series_rows;
+    a.nseries = (int)c->series.size();
+    if (prog == PROG_HEUN && Policy<NF>::coupled(c)) {
+        a.stage_sat = (NF*)c->stage.f[TRM_FIELD_SATURATION_WATER_ICE];
+        a.stage_liq = (NF*)c->stage.f[TRM_FIELD_LIQUID_WATER_FRACTION];
+        a.stage_T = (NF*)c->stage.f[TRM_FIELD_TEMPERATURE];
+        a.stage_S = (NF*)c->stage.f[TRM_FIELD_SURFACE_EXCESS_WATER];
+    }
+    return a;
+}
 
 // ---- the launchers: declared here, defined and explicitly instantiated in the trm_launch_*.hip files ------------------------
 // reference-order kernels, the 0-D surface kernel, update_inputs! of the time series (trm_launch_unfused.hip)
@@ -526,8 +551,10 @@ struct PackedLaunch {
     static int step(trm_ctx* c, double dt, int finalize);
     static int step_land(trm_ctx* c, double dt, int finalize);      // k_step_pk_land: the surface processes in the launch
 };
-// the granule buffer and the epoch of the next launch that carries its own surface processes (k_column_land, k_step_pk_land)
-int front_epoch_next(trm_ctx* c);
+// The hand-off of a launch that carries its own surface processes (k_column_land, k_step_pk_land; defined in terrarium_hip.hip):
+// refused unless the top-cell arrays are current (the surface workgroups read them), then the granule buffer, the launch's epoch
+// and the number of surface workgroups in front of the column workgroups.  `kernel` names the launch in the refusal.
+int front_args(trm_ctx* c, const char* kernel, FrontArgs& fa);
 // the LandModel's per-step launch with the surface processes in its first workgroups: k_column_land (fp64; trm_launch_column_land_*.hip)
 struct FrontLaunch {
     static int run(trm_ctx* c, double dt, int finalize, bool heun = false);

@@ -6,26 +6,9 @@ namespace trmh {
 
 template <class NF, bool RICH, int H, int LPC, int PROG> static int launch_column(trm_ctx* c, double dt, int finalize, int nsteps) {
     using P = Policy<NF>;
-    const LaunchArgs<NF>& la = launch_args<NF>(c);
     const View<NF>& v = state_view<NF>(c);
-    const DevParams<NF>& p = la.p;
-    ColumnArgs<NF> a;
-    a.dt = (NF)dt;
-    a.finalize = finalize;
-    a.write_kf = (c->opt_write_kf || finalize) ? 1 : 0;
-    a.nsteps = nsteps;
-    a.bcT_bot_stage = la.w.bcT_bot;
-    a.bcT_top_stage = la.w.bcT_top;
-    a.series = (const SeriesTable<NF>*)c->d_series_table;
-    a.series_rows = (const SeriesRow*)c->d_series_rows;
-    a.nseries = (int)c->series.size();
-    a.stage_sat = a.stage_liq = a.stage_T = a.stage_S = nullptr;
-    if (PROG == PROG_HEUN && P::coupled(c)) {   // the stage's soil state is needed by the 0-D processes evaluated at the stage
-        a.stage_sat = (NF*)c->stage.f[TRM_FIELD_SATURATION_WATER_ICE];
-        a.stage_liq = (NF*)c->stage.f[TRM_FIELD_LIQUID_WATER_FRACTION];
-        a.stage_T = (NF*)c->stage.f[TRM_FIELD_TEMPERATURE];
-        a.stage_S = (NF*)c->stage.f[TRM_FIELD_SURFACE_EXCESS_WATER];
-    }
+    const DevParams<NF>& p = launch_args<NF>(c).p;
+    const ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, nsteps, PROG);
     const dim3 grid = column_grid(c, LPC), block(TRM_STEP_BLOCK);
     const int derive = P::template derive_now<RICH>(c);     // (for this kernel: DERIVE_NONE or DERIVE_T_LIQ)
     if (derive != DERIVE_NONE && derive != DERIVE_T_LIQ) return fail(c, TRM_EINVAL, "k_column: no instance for this derivation mode");

@@ -6,20 +6,9 @@
 namespace trmh {
 
 template <class NF, bool RICH, int H, int LPC> static int launch_column_accum(trm_ctx* c, double dt, int finalize, int nsteps, const AccumArgs& acc) {
-    const LaunchArgs<NF>& la = launch_args<NF>(c);
     const View<NF>& v = state_view<NF>(c);
-    const DevParams<NF>& p = la.p;
-    ColumnArgs<NF> a;
-    a.dt = (NF)dt;
-    a.finalize = finalize;
-    a.write_kf = (c->opt_write_kf || finalize) ? 1 : 0;
-    a.nsteps = nsteps;
-    a.bcT_bot_stage = la.w.bcT_bot;
-    a.bcT_top_stage = la.w.bcT_top;
-    a.series = (const SeriesTable<NF>*)c->d_series_table;
-    a.series_rows = (const SeriesRow*)c->d_series_rows;
-    a.nseries = (int)c->series.size();
-    a.stage_sat = a.stage_liq = a.stage_T = a.stage_S = nullptr;
+    const DevParams<NF>& p = launch_args<NF>(c).p;
+    const ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, nsteps, PROG_MULTI);
     const dim3 grid = column_grid(c, LPC), block(TRM_STEP_BLOCK);
     const bool series = !c->series.empty();
     // (the same instance choice as the PROG_MULTI launch of trm_launch_column.inl, and the same TRM_INFO_LAST_PROGRAM + the bit of

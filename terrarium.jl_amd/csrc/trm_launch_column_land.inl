@@ -10,20 +10,9 @@ template <int H, int LPC> static int launch_column_land(trm_ctx* c, double dt, i
     using P = Policy<NF>;
     const LaunchArgs<NF>& la = launch_args<NF>(c);
     const View<NF>& v = la.state;
-    if (!v.top_T || !c->top_valid) return fail(c, TRM_EINVAL, "k_column_land: the surface workgroups read the top-cell arrays, which are not current");
-    if (int rc = front_epoch_next(c)) return rc;
-    ColumnArgs<NF> a{};
-    a.dt = (NF)dt;
-    a.finalize = finalize;
-    a.write_kf = (c->opt_write_kf || finalize) ? 1 : 0;
-    a.nsteps = 1;
-    a.bcT_bot_stage = la.w.bcT_bot;
-    a.bcT_top_stage = la.w.bcT_top;
-    FrontArgs fa{};
-    fa.gran = c->d_gran;
-    fa.epoch = c->front_epoch;
-    fa.tag_bias = c->debug_handoff_tag_bias;
-    fa.chain_blocks = (int)((c->Nh + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK);
+    FrontArgs fa;
+    if (int rc = front_args(c, "k_column_land", fa)) return rc;
+    const ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, 1, heun ? PROG_HEUN : PROG_EULER);
     dim3 grid = column_grid(c, LPC);
     grid.x += (unsigned)fa.chain_blocks;
     const dim3 block(TRM_STEP_BLOCK);

@@ -17,11 +17,7 @@ TangentArgs tangent_args(const trm_ctx* c) {
 
 template <int H, int LPC> int launch_tangent(trm_ctx* c, double dt, int nsteps) {
     const LaunchArgs<double>& la = launch_args<double>(c);
-    ColumnArgs<double> a{};
-    a.dt = dt;
-    a.finalize = 1;
-    a.write_kf = 1;
-    a.nsteps = nsteps;
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
     const TangentArgs ta = tangent_args(c);
     hipLaunchKernelGGL((k_column_tangent<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, ta);
     TRM_HIP(c, hipGetLastError());

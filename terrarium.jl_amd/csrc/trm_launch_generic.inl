@@ -9,8 +9,7 @@ template <class NF, bool RICH, int H, int LPC> static int launch_wave(trm_ctx* c
     const LaunchArgs<NF>& la = launch_args<NF>(c);
     const View<NF>& v = state_view<NF>(c);
     const DevParams<NF>& p = la.p;
-    const int wkf = (c->opt_write_kf || finalize) ? 1 : 0;
-    hipLaunchKernelGGL((k_step_wave<NF, RICH, H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, v, p, (NF)dt, finalize, wkf);
+    hipLaunchKernelGGL((k_step_wave<NF, RICH, H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, v, p, (NF)dt, finalize, write_kf(c, finalize));
     TRM_HIP(c, hipGetLastError());
     c->last_program = program_id(TRM_PROGRAM_GENERIC_EULER, H, LPC, DERIVE_NONE, 0, 0, -1);
     return TRM_OK;
@@ -26,11 +25,7 @@ template <class NF> int GenericLaunch<NF>::step(trm_ctx* c, double dt, int final
 // Heun with the generic boundary kinds: k_heun_generic, one launch per step like k_column<PROG_HEUN>
 template <class NF, bool RICH, int H, int LPC> static int launch_heun_generic(trm_ctx* c, double dt, int finalize) {
     const LaunchArgs<NF>& la = launch_args<NF>(c);
-    ColumnArgs<NF> a{};
-    a.dt = (NF)dt;
-    a.finalize = finalize;
-    a.write_kf = (c->opt_write_kf || finalize) ? 1 : 0;
-    a.nsteps = 1;
+    const ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, 1, PROG_HEUN);
     hipLaunchKernelGGL((k_heun_generic<NF, RICH, H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, la.stage, a);
     TRM_HIP(c, hipGetLastError());
     c->last_program = program_id(TRM_PROGRAM_GENERIC_HEUN, H, LPC, DERIVE_NONE, 0, 0, -1);

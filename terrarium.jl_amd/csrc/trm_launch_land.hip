@@ -10,16 +10,9 @@ template <int H, int LPC> static int launch_land(trm_ctx* c, int qcol, int qsurf
     const LaunchArgs<NF>& la = launch_args<NF>(c);
     const View<NF>&vc = la.part[qcol], &vs = la.part[qsurf];
     if (top_arrays && !vs.top_T) return fail(c, TRM_EINVAL, "LandModel launch: the top-cell arrays were requested on a context that has none");
-    const int wkf = (c->opt_write_kf || finalize) ? 1 : 0;
     const unsigned sblocks = (unsigned)((c->part_n[qsurf] + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK);
     const dim3 block(TRM_STEP_BLOCK);
-    ColumnArgs<NF> a{};
-    a.dt = (NF)dt;
-    a.finalize = finalize;
-    a.write_kf = wkf;
-    a.nsteps = 1;
-    a.bcT_bot_stage = la.w.bcT_bot;
-    a.bcT_top_stage = la.w.bcT_top;
+    const ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, 1, PROG_EULER);
     const long waves = (c->part_n[qcol] + (64 / LPC) - 1) / (64 / LPC);
     const dim3 grid(sblocks + (unsigned)((waves * 64 + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK));
     const bool derive = Policy<NF>::derive_now<RICH>(c) == DERIVE_T_LIQ;

@@ -9,19 +9,7 @@ namespace trmh {
 
 template <class NF, int M, bool RICH, int H, int PROG, bool GENERIC> static int launch_levels(trm_ctx* c, double dt, int finalize, int nsteps) {
     const LaunchArgs<NF>& la = launch_args<NF>(c);
-    ColumnArgs<NF> a{};
-    a.dt = (NF)dt;
-    a.finalize = finalize;
-    a.write_kf = (c->opt_write_kf || finalize) ? 1 : 0;
-    a.nsteps = nsteps;
-    a.bcT_bot_stage = la.w.bcT_bot;      // Heun: the stage's temperature boundary values (evaluated at t + dt)
-    a.bcT_top_stage = la.w.bcT_top;
-    if (PROG == PROG_HEUN && Policy<NF>::coupled(c)) {   // the stage's soil state is needed by the 0-D processes evaluated at the stage
-        a.stage_sat = (NF*)c->stage.f[TRM_FIELD_SATURATION_WATER_ICE];
-        a.stage_liq = (NF*)c->stage.f[TRM_FIELD_LIQUID_WATER_FRACTION];
-        a.stage_T = (NF*)c->stage.f[TRM_FIELD_TEMPERATURE];
-        a.stage_S = (NF*)c->stage.f[TRM_FIELD_SURFACE_EXCESS_WATER];
-    }
+    const ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, nsteps, PROG);
     const dim3 grid((unsigned)((ncols(c) + (TRM_STEP_BLOCK / 64) - 1) / (TRM_STEP_BLOCK / 64))), block(TRM_STEP_BLOCK);
     // T / liq derived in registers: two levels per lane, branch-free kinds (no generic instance of its own)
     const bool derive = M == 2 && !GENERIC && Policy<NF>::template derive_now<RICH>(c) == DERIVE_T_LIQ;

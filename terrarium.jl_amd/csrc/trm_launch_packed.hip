@@ -9,7 +9,7 @@ template <bool RICH, int LPC> static int launch_packed(trm_ctx* c, double dt, in
     using NF = float;
     using P = Policy<float>;
     const LaunchArgs<NF>& la = launch_args<NF>(c);
-    const int wkf = (c->opt_write_kf || finalize) ? 1 : 0;
+    const int wkf = write_kf(c, finalize);
     const long pairs = (ncols(c) + 1) / 2;
     const View<NF>& sv = state_view<NF>(c);
     const long waves = (pairs + (64 / LPC) - 1) / (64 / LPC);
@@ -43,14 +43,9 @@ template <int LPC> static int launch_packed_land(trm_ctx* c, double dt, int fina
     using P = Policy<float>;
     const LaunchArgs<float>& la = launch_args<float>(c);
     const View<float>& sv = la.state;
-    if (!sv.top_T || !c->top_valid) return fail(c, TRM_EINVAL, "k_step_pk_land: the surface workgroups read the top-cell arrays, which are not current");
-    if (int rc = front_epoch_next(c)) return rc;
-    FrontArgs fa{};
-    fa.gran = c->d_gran;
-    fa.epoch = c->front_epoch;
-    fa.tag_bias = c->debug_handoff_tag_bias;
-    fa.chain_blocks = (int)((c->Nh + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK);
-    const int wkf = (c->opt_write_kf || finalize) ? 1 : 0;
+    FrontArgs fa;
+    if (int rc = front_args(c, "k_step_pk_land", fa)) return rc;
+    const int wkf = write_kf(c, finalize);
     const long pairs = (c->Nh + 1) / 2;
     const long waves = (pairs + (64 / LPC) - 1) / (64 / LPC);
     const dim3 pg((unsigned)fa.chain_blocks + (unsigned)((waves * 64 + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK)), blk(TRM_STEP_BLOCK);
@@ -81,7 +76,7 @@ template <int H, int LPC> static int launch_land_pk(trm_ctx* c, int qcol, int qs
     const LaunchArgs<float>& la = launch_args<float>(c);
     const View<float>&vc = la.part[qcol], &vs = la.part[qsurf];
     if (top_arrays && !vs.top_T) return fail(c, TRM_EINVAL, "LandModel launch: the top-cell arrays were requested on a context that has none");
-    const int wkf = (c->opt_write_kf || finalize) ? 1 : 0;
+    const int wkf = write_kf(c, finalize);
     const unsigned sblocks = (unsigned)((c->part_n[qsurf] + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK);
     const dim3 block(TRM_STEP_BLOCK);
     const long pairs = (c->part_n[qcol] + 1) / 2;
