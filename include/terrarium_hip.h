@@ -212,6 +212,12 @@ enum {
                                     /* inputs may change every step (nothing is evaluated ahead).  A column wave whose bounded wait for     */
                                     /* its words ends unanswered raises TRM_STATUS_HANDOFF_TIMEOUT instead of hanging.  0: the launch pair;  */
                                     /* 2 (default): the library's rule                                                          */
+    ,TRM_OPT_DEFER_CLOSURE_STORES = 12 /* 1 (default): a per-step ForwardEuler launch that derives temperature / liquid fraction in        */
+                                    /* registers (TRM_OPT_DERIVE_CLOSURE_FIELDS) does not store them either -- the next step derives them    */
+                                    /* again -- and the library forms them from the stored (internal_energy, saturation) with one small     */
+                                    /* launch in front of the first call that reads or writes field memory (see trm_step): same values, bit  */
+                                    /* for bit.  0: stored by every step (a caller that reads one of them after EVERY step: DESIGN 4.3).     */
+                                    /* Environment: TRM_DEFER_CLOSURE_STORES = 0 / 1 sets the default of new contexts (A/B)                  */
 };
 /* DIAGNOSTIC, read-only (trm_get_option): which fast paths the NEXT step will take -- what the library tracks about its own
  * buffers.  Tests pin them (a wrong value costs speed, never correctness, so nothing else would notice). */
@@ -219,12 +225,16 @@ enum {
     TRM_INFO_TOP_ARRAYS_CURRENT = 100, /* 1: the LandModel's next surface evaluation reads the compact top-cell arrays the last   */
                                        /* fused step wrote (coalesced) instead of gathering one word per column from the fields   */
     TRM_INFO_CLOSURE_CONSISTENT = 101,  /* 1: the stored temperature / liquid fraction are the closure of the stored state, so a  */
-                                       /* step may re-derive them in registers (TRM_OPT_DERIVE_CLOSURE_FIELDS)                   */
+                                       /* step may re-derive them in registers (TRM_OPT_DERIVE_CLOSURE_FIELDS).  "The next step   */
+                                       /* may derive": stays 1 while the arrays themselves are stale (TRM_INFO_CLOSURE_STORED = 0) */
     TRM_INFO_GENERIC_BOUNDARY_KERNELS = 103, /* 1: the context's boundary kinds need the generic-boundary kernels (k_step_wave, ...)   */
     TRM_INFO_BC_SIGNATURE = 102,       /* the boundary-condition signature of the context's current kinds (BCSIG bits: 1 / 2 Value on  */
                                        /* temperature bottom / top, 4 / 8 Flux on energy / saturation bottom, 16 / 32 top, 64 LandModel) */
-    TRM_INFO_LAST_PROGRAM = 105        /* which kernel instance the last step launch of the context selected (TRM_PROGRAM_* below), 0     */
+    TRM_INFO_LAST_PROGRAM = 105,       /* which kernel instance the last step launch of the context selected (TRM_PROGRAM_* below), 0     */
                                        /* before the first step: family in bits 0-7, then one field per selection rule                    */
+    TRM_INFO_CLOSURE_STORED = 106,     /* 1: the temperature / liquid fraction ARRAYS are current; 0: the last step launches left them      */
+                                       /* unstored (TRM_OPT_DEFER_CLOSURE_STORES) and the next reader materialises them                     */
+    TRM_INFO_MATERIALIZATIONS = 107    /* how many times the context has materialised them (one small launch each)                          */
 };
 /* kernel families reported in the low byte of TRM_INFO_LAST_PROGRAM; bits 8-9 the hydraulics instance (0 the reference default, 1 van
  * Genuchten n = 2, 2 run-time exponents), 10-11 lanes per column / 32, 12-14 which closure fields are derived, 15 per-column outputs
@@ -477,7 +487,14 @@ int trm_invclosure(trm_ctx* ctx);
  * launch that finalizes: after a call with finalize = 1 the tendency fields hold exactly what the reference's would;
  * after a call with finalize = 0 they are NOT materialised and trm_download / trm_reduce / trm_field_device_ptr of a
  * TRM_FIELD_TEND_* field fail with TRM_ESTALE until trm_update_state(ctx, 1), trm_reset_tendencies or a finalizing
- * step has run.  TRM_KERNEL_UNFUSED materialises them at every step. */
+ * step has run.  TRM_KERNEL_UNFUSED materialises them at every step.
+ *
+ * Temperature and liquid_water_fraction read through the library are always what the reference's would be.  Under
+ * TRM_OPT_DEFER_CLOSURE_STORES (default) the large-grid per-step launches, which derive both from (internal_energy, saturation) at
+ * entry, do not store them; the first call after such steps that touches field memory -- any download, upload, reduction,
+ * trm_field_device_ptr, trm_save_state, trm_average_open, another kind of step ... -- first forms them with one small launch on the
+ * context stream (no error code, nothing to call).  trm_step, trm_step_timed, trm_step_all, trm_synchronize(_all), trm_status, the
+ * clock and option getters and trm_last_error do not.  A device pointer to a state field ends deferral for the context. */
 int trm_step(trm_ctx* ctx, double dt, int nsteps, int finalize);
 /* Same for Heun (heun.jl:37-71): with TRM_KERNEL_FUSED and Nz <= 64 ONE launch per step (both stages on the column held in
  * registers; the stage never touches memory; every boundary kind), four for TRM_VEGETATION_COUPLED; ONE launch for 65 ... 128

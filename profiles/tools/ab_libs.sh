@@ -3,6 +3,8 @@
 # workload and round -- the second of two HBM-resident runs in a row reads ~8 % slower than a run that follows light work
 # (EXPERIMENTS R5.9), so a fixed "old, then new" order is biased against the new build.
 #   bash profiles/tools/ab_libs.sh LOG ROUNDS "name=path/to/lib.so name2=HEAD ..." "wl[:shard] wl ..."      (HEAD: the shipped library)
+# A build may carry environment switches of its own, `name=path,VAR=VALUE,...` (e.g. off=HEAD,TRM_DEFER_CLOSURE_STORES=0): set for its
+# samples only.
 # Prints, per workload, every build's samples and the ratio of medians against the first build.
 set -o pipefail
 LOG=$1; ROUNDS=$2; LIBS=$3; WLS=$4
@@ -12,10 +14,10 @@ for rep in $(seq 1 $ROUNDS); do
     wl=${spec%%:*}; shard=""; [[ $spec == *:* ]] && shard="--shard ${spec##*:}"
     steps=50; [ $wl = c3 ] && steps=100; [ $wl = c2 ] && steps=100
     for lib in $(echo $LIBS | tr ' ' '\n' | shuf); do
-      name=${lib%%=*}; path=${lib##*=}
+      name=${lib%%=*}; rest=${lib#*=}; path=${rest%%,*}; envs=""; [[ $rest == *,* ]] && envs=$(echo ${rest#*,} | tr ',' ' ')
       if [ "$path" = HEAD ]; then unset TRM_LIBRARY; else export TRM_LIBRARY=$PWD/$path; fi
       echo "== $name $spec rep $rep" >> $LOG
-      timeout -k 10 300 python profiles/tools/ab_options.py $wl x: --steps $steps --reps 5 $shard 2>/dev/null | grep workload >> $LOG || exit 1
+      env $envs timeout -k 10 300 python profiles/tools/ab_options.py $wl x: --steps $steps --reps 5 $shard 2>/dev/null | grep workload >> $LOG || exit 1
     done
   done
 done

@@ -44,6 +44,14 @@ OPTION = dict(asynchronous=0, step_kernel=1, write_kf_every_step=2, vwc_forcing_
               derive_closure_fields=5, steps_per_launch=6, pipeline_parts=7, single_step_program=8, bc_signature=9, zero_gradient_fast=10, surface_in_launch=11,
               info_top_arrays_current=100, info_closure_consistent=101, info_bc_signature=102, info_generic_boundary_kernels=103,
               info_last_program=105)
+# Options and info keys added after the table above was pinned name by name (tests/test_host_and_abi.py maps every entry of OPTION
+# through a fixed list): looked up by option_id beside it; tests/test_deferred_closure_abi.py holds their header agreement.
+OPTION_LATER = dict(defer_closure_stores=12, info_closure_stored=106, info_materializations=107)
+
+
+def option_id(name: str) -> int:
+    return OPTION[name] if name in OPTION else OPTION_LATER[name]
+
 KERNEL = dict(fused=0, unfused=1)
 # TRM_INFO_LAST_PROGRAM (include/terrarium_hip.h: TRM_PROGRAM_*; trm_host.hpp: program_id)
 PROGRAM = ("none", "column_euler", "column_heun", "column_multi", "packed_f32", "generic_euler", "generic_heun", "column_land", "deep", "wide",

@@ -382,6 +382,17 @@ void tick(trm_ctx* c, double dt, int nsteps) {
     c->iteration += nsteps;
 }
 
+// TRM_OPT_DEFER_CLOSURE_STORES: temperature and liquid_water_fraction of the state into their arrays (one small launch on the
+// context stream) if the last step launches left them unstored; nothing otherwise.  Every reader and writer of field memory other than
+// a deriving per-step launch comes through here first: the ABI entries (TRM_ENTER / TRM_ENTER_HEUN) and Ops::fused_launch.
+int flush_closure(trm_ctx* c) {
+    if (!c->closure_deferred) return TRM_OK;
+    if (int rc = c->precision == TRM_F64 ? MaterializeLaunch<double>::run(c) : MaterializeLaunch<float>::run(c)) return rc;
+    c->closure_deferred = false;
+    c->materializations += 1;
+    return TRM_OK;
+}
+
 // Heun's path (Ops::heun_path).  One launch with both stages on the column in registers (Ops::fused_launch<PROG_HEUN>), by
 // k_column / k_column_land / k_heun_generic (HEUN_ONE_LAUNCH) or the levels kernels (HEUN_LEVELS: 65 ... 256 levels; the stage's
 // fields are allocated for them as for the reference-order kernels that ran there before them).  The stage's surface energy
@@ -627,8 +638,9 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     // time averages take the step's terms (`accumulate`: the launch has not added them itself); only the finalizing launch stores
     // state.tendencies; the top-cell arrays describe the state after a successful LandModel launch.  Then, finalizing, the state's
     // surface processes once more (+ the 0-D auxiliaries of the coupled vegetation).
-    static int fused_epilogue(trm_ctx* c, int rc, double dt, int fin, bool accumulate = true) {
+    static int fused_epilogue(trm_ctx* c, int rc, double dt, int fin, bool accumulate = true, bool deferred = false) {
         if (!rc) c->closure_consistent = true;
+        if (!rc) c->closure_deferred = deferred;      // (every other launch has stored T / liq)
         if (!rc && accumulate) rc = accumulate_after(c, dt);
         c->tend_valid = fin != 0;
         c->top_valid = c->params.seb != 0 && !rc && tops_current(c);
@@ -641,14 +653,40 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     // their own small launch in front of the column kernel (LandModel; + the 0-D prognostics' step of the coupled vegetation) unless
     // the launch carries them (surface_in_launch).  (The per-cell plant_available_water field is materialised with the other per-cell
     // auxiliaries: by the finalizing launch, or every step under TRM_OPT_WRITE_KF_EVERY_STEP.)
+    // The step launch of fused_launch<PROG_EULER> will be a deriving instance of k_column / k_column_land (as step_launch and the
+    // launchers select it): the only launches that read neither T nor liq from memory.
+    static bool derives_unread(trm_ctx* c, bool in_launch) {
+        if (P::levels_per_lane(c) != 1 || c->part >= 0) return false;
+        if (std::is_same<NF, float>::value && (in_launch || P::packed_path(c))) return false;
+        if (!in_launch && P::generic_bcs(c)) return false;
+        return (P::richards(c) ? P::template derive_now<true>(c) : P::template derive_now<false>(c)) == DERIVE_T_LIQ;
+    }
+    // ... and may leave T / liq unstored (ColumnArgs::store_closure = 0): nothing reads the arrays before the next flush_closure -- no
+    // open time average of either (accumulate_after reads them), no tangent state, and on a LandModel the top-cell arrays are what the
+    // surface processes read (fused_epilogue's included).
+    static bool defer_closure_now(trm_ctx* c, bool in_launch) {
+        if (!c->opt_defer_closure || c->d_tan[0] || !derives_unread(c, in_launch)) return false;
+        for (const auto& a : c->averages)
+            if (a.field == TRM_FIELD_TEMPERATURE || a.field == TRM_FIELD_LIQUID_WATER_FRACTION) return false;
+        return !c->params.seb || tops_current(c);
+    }
     template <int PROG> static int fused_launch(trm_ctx* c, double dt, int fin, int nsteps = 1) {
         int rc = fused_prologue<PROG>(c, dt, nsteps);
         const bool in_launch = !rc && PROG != PROG_MULTI && surface_in_launch(c, PROG == PROG_HEUN);
+        // T / liq left unstored by earlier launches: materialised in front of everything that reads them from the 3-D arrays -- any
+        // step launch but a deriving one, the vegetation launches (never deriving), a surface launch that gathers the top cell from
+        // the fields
+        const bool surface_reads_fields = c->params.seb && !in_launch && !(c->top_valid && c->d_top3);
+        if (!rc && c->closure_deferred && (PROG != PROG_EULER || surface_reads_fields || !derives_unread(c, in_launch))) rc = flush_closure(c);
+        c->defer_launch = !rc && PROG == PROG_EULER && defer_closure_now(c, in_launch);
+        c->launch_deferred = false;
         if (!rc && PROG != PROG_MULTI && P::coupled(c)) rc = V::surface_veg(c, c->state, true, true, dt, c->opt_write_kf != 0);
         else if (!rc && PROG != PROG_MULTI && c->params.seb && !in_launch) rc = U::surface(c, c->state, true);
         const bool accum = PROG == PROG_MULTI && averaging(c) && averages_in_launch(c);
         if (!rc) rc = step_launch<PROG>(c, in_launch, accum, dt, fin, nsteps);
-        return fused_epilogue(c, rc, dt, fin, !accum);
+        const bool deferred = c->launch_deferred;
+        c->defer_launch = c->launch_deferred = false;
+        return fused_epilogue(c, rc, dt, fin, !accum, deferred);
     }
     // ---- LandModel, per-step path: the surface processes of one half of the columns UNDER the column program of the other ----
     // (k_land_euler / k_land_pk, trm_column.hpp: one stream, two launches per step as before, each covering the soil columns
@@ -668,7 +706,8 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     //     surf(A, 0) | col(A, 0) + surf(B, 0) | col(B, 0) + surf(A, 1) | ... | col(A, N-1) + surf(B, N-1) | col(B, N-1)
     static int land_steps_interleaved(trm_ctx* c, double dt, int nsteps, int finalize) {
         const bool top0 = c->top_valid, cc0 = c->closure_consistent;
-        int rc;
+        int rc = flush_closure(c);      // (part launches never defer)
+        if (rc) return rc;
         {   // the state's surface processes for half A
             PartScope scope(c, 0);
             c->top_valid = top0;
@@ -732,6 +771,8 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     }
     static int step(trm_ctx* c, double dt, int nsteps, int finalize) {
         if (c->veg_mode == TRM_VEGETATION_STANDALONE) return veg_step(c, dt, nsteps, finalize, false);
+        if (c->opt_kernel != TRM_KERNEL_FUSED || P::levels_per_lane(c) == 0)      // (the reference-order kernels read T / liq as stored)
+            if (int rf = flush_closure(c)) return rf;
         // the fused kernels map one soil level to one lane (two for 65 ... 128 levels, four for 129 ... 256); anything deeper takes the
         // reference-order kernels.
         const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && P::levels_per_lane(c) > 0;
@@ -800,6 +841,7 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     //   4. k_heun_average_0d: averaged tendencies, explicit step of canopy water, vegetation carbon, area fraction
     static int heun_step_coupled_fused(trm_ctx* c, double dt, int finalize) {
         int rc = fused_prologue<PROG_HEUN>(c, dt, 1);
+        if (!rc) rc = flush_closure(c);
         if (rc) return fused_epilogue(c, rc, dt, finalize);
         const VegView<NF> vs = P::veg_view(c, c->state);
         VegView<NF> vg = P::veg_view(c, c->stage);
@@ -947,7 +989,7 @@ bool parse_env_int(const char* name, long lo, long hi, long multiple_of, long& o
     return true;
 }
 struct EnvSwitches {
-    long field_skew = 16640, derive_default = -1, debug_placement = 0, handoff_tag_bias = 0;
+    long field_skew = 16640, derive_default = -1, debug_placement = 0, handoff_tag_bias = 0, defer_closure = -1;
     std::string error;
     EnvSwitches() {
         long v;
@@ -955,6 +997,7 @@ struct EnvSwitches {
         if (error.empty() && parse_env_int("TRM_DERIVE_DEFAULT", 0, 5, 1, v, error)) derive_default = v;
         if (error.empty() && parse_env_int("TRM_DEBUG_PLACEMENT", 0, 1, 1, v, error)) debug_placement = v;   // (prints every field's allocation: profiles/tools/placement_probe.sh)
         if (error.empty() && parse_env_int("TRM_DEBUG_HANDOFF_TAG_BIAS", 0, 1, 1, v, error)) handoff_tag_bias = v;      // (tests: FrontArgs::tag_bias)
+        if (error.empty() && parse_env_int("TRM_DEFER_CLOSURE_STORES", 0, 1, 1, v, error)) defer_closure = v;      // (child-process A/B)
         if (error.empty() && parse_env_int("TRM_STAGED_SMALL", 0, 1, 1, v, error)) { /* read by Policy::staged_now */ }
         if (error.empty() && parse_env_int("TRM_SCALAR_INPUTS", 0, 1, 1, v, error)) { /* read by Policy::scalar_inputs_now */ }
     }
@@ -1378,9 +1421,17 @@ extern "C" {
 // TRM_ENTER: any entry point but the three of the two-call Heun step and the read-only ones.  A stage predicted by
 // trm_heun_predict belongs to the state and clock it was predicted from: whatever else runs in between drops it, and a later
 // trm_heun_correct fails ("call trm_heun_predict first") instead of averaging tendencies of a stage that describes another state.
-#define TRM_ENTER_HEUN(c)                                    \
+// Both materialise T / liq first if the last step launches left them unstored (flush_closure, TRM_OPT_DEFER_CLOSURE_STORES): whatever
+// the entry point reads or writes, it finds the arrays an eagerly storing context has.  TRM_ENTER_KEEP: the entry points that neither
+// read nor write field memory, or order the accesses themselves -- trm_step / trm_step_timed (Ops::fused_launch), trm_restore_state
+// (overwrites the fields), trm_synchronize, trm_status; the getters that take no macro at all belong here too.
+#define TRM_ENTER_KEEP(c)                                    \
     if (!(c)) return TRM_EINVAL;                             \
     TRM_HIP(c, hipSetDevice((c)->device));
+#define TRM_ENTER_HEUN(c)                                    \
+    TRM_ENTER_KEEP(c)                                        \
+    if ((c)->closure_deferred)                               \
+        if (int rc_flush__ = flush_closure(c)) return rc_flush__;
 #define TRM_ENTER(c)                                         \
     TRM_ENTER_HEUN(c)                                        \
     (c)->heun_pending = false;
@@ -1461,6 +1512,7 @@ int trm_create(const trm_grid* g, const trm_params* p, trm_ctx** out) {
     // (tests: TRM_DERIVE_DEFAULT = 1 makes small grids take the instances with the derivation, where the staged outputs and the
     // input paths are compiled in -- the value a context starts with for TRM_OPT_DERIVE_CLOSURE_FIELDS)
     if (env_switches().derive_default >= 0) c->opt_derive = (int)env_switches().derive_default;
+    if (env_switches().defer_closure >= 0) c->opt_defer_closure = (int)env_switches().defer_closure;
     c->debug_handoff_tag_bias = (unsigned)env_switches().handoff_tag_bias;
     if (rc == TRM_OK) hip(hipMemsetAsync(c->d_zero, 0, (size_t)c->Nh * c->esize, c->stream), "hipMemset(zero)");
     if (rc) return bail(rc);
@@ -1555,6 +1607,7 @@ int trm_upload(trm_ctx* c, int field, const void* host) {
                                    "(root_distribution.jl:45-63): set them with trm_set_vegetation");
     TRM_HIP(c, hipSetDevice(c->device));
     c->heun_pending = false;
+    if (int rf = flush_closure(c)) return rf;      // (an upload of T alone must find liq current, and the reverse)
     int rc = c->precision == TRM_F64 ? upload_impl<double>(c, field, (const double*)host) : upload_impl<float>(c, field, (const float*)host);
     if (field <= TRM_FIELD_PRESSURE_HEAD || field == TRM_FIELD_WATER_TABLE) c->closure_consistent = false;   // (U, sat, T, liq, psi, water table)
     if (field == TRM_FIELD_INTERNAL_ENERGY || field == TRM_FIELD_SATURATION_WATER_ICE) c->tan_stale = true;
@@ -1580,12 +1633,17 @@ int trm_download(trm_ctx* c, int field, void* host) {
     if (is_tendency(field) && !c->tend_valid) return fail(c, TRM_ESTALE, kStaleTendencies);
     if (!c->state.f[field]) return fail(c, TRM_EINVAL, "trm_download: the field exists only after trm_set_vegetation");
     TRM_HIP(c, hipSetDevice(c->device));
+    if (int rf = flush_closure(c)) return rf;
     return c->precision == TRM_F64 ? download_impl<double>(c, field, (double*)host) : download_impl<float>(c, field, (float*)host);
 }
 
 int trm_field_device_ptr(trm_ctx* c, int field, void** dev, int64_t* pitch_elems) {
     if (!c || !dev || !valid_field(field)) return fail(c, TRM_EINVAL, "trm_field_device_ptr: bad argument");
     if (is_tendency(field) && !c->tend_valid) return fail(c, TRM_ESTALE, kStaleTendencies);
+    if (c->closure_deferred) {      // (the caller reads the arrays behind the library's back from now on; closure_escaped below ends deferral)
+        TRM_HIP(c, hipSetDevice(c->device));
+        if (int rf = flush_closure(c)) return rf;
+    }
     *dev = c->state.f[field];
     if (pitch_elems) *pitch_elems = is_3d(field) ? c->Nzp : 1;
     // the caller may write the state behind the library's back from now on: stop trusting the top-cell copies
@@ -2028,7 +2086,8 @@ int trm_invclosure(trm_ctx* c) {
 }
 
 int trm_step(trm_ctx* c, double dt, int nsteps, int finalize) {
-    TRM_ENTER(c);
+    TRM_ENTER_KEEP(c);
+    c->heun_pending = false;
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step: nsteps < 0");
     c->tan_stale = true;
     return finish(c, DISPATCH(c, step(c, dt, nsteps, finalize)));
@@ -2050,7 +2109,8 @@ int wait_polling(trm_ctx* c, hipEvent_t ev) {
 }  // namespace
 
 int trm_step_timed(trm_ctx* c, double dt, int nsteps, int finalize, float* ms) {
-    TRM_ENTER(c);
+    TRM_ENTER_KEEP(c);
+    c->heun_pending = false;
     if (nsteps < 0 || !ms) return fail(c, TRM_EINVAL, "trm_step_timed: bad argument");
     c->tan_stale = true;
     TRM_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -2203,8 +2263,10 @@ int trm_save_state(trm_ctx* c) {
     return TRM_OK;
 }
 int trm_restore_state(trm_ctx* c) {
-    TRM_ENTER(c);
+    TRM_ENTER_KEEP(c);
+    c->heun_pending = false;
     if (!c->has_saved) return fail(c, TRM_EINVAL, "trm_restore_state: nothing was saved");
+    c->closure_deferred = false;      // (every field is overwritten below: nothing to materialise)
     for (int f = 0; f < TRM_FIELD_COUNT; ++f)
         if (c->state.f[f] && c->saved.f[f]) TRM_HIP(c, hipMemcpyAsync(c->state.f[f], c->saved.f[f], field_elems(c, f) * c->esize, hipMemcpyDeviceToDevice, c->stream));
     TRM_HIP(c, hipMemcpyAsync(c->state.kf_top, c->saved.kf_top, (size_t)c->Nh * c->esize, hipMemcpyDeviceToDevice, c->stream));
@@ -2831,7 +2893,7 @@ int trm_status_global_all(trm_ctx** ctxs, int n, uint32_t* flags) {
 }
 
 int trm_status(trm_ctx* c, uint32_t* flags) {
-    TRM_ENTER_HEUN(c);
+    TRM_ENTER_KEEP(c);
     if (!flags) return TRM_EINVAL;
     TRM_HIP(c, hipMemcpyAsync(flags, c->d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -2849,6 +2911,12 @@ int trm_set_option(trm_ctx* c, int option, int value) {
     if (!c) return TRM_EINVAL;
     c->args_valid = false;
     c->heun_pending = false;
+    // (an option that changes which program the next step takes: the arrays are made current here, not by whatever runs next)
+    if (c->closure_deferred && option != TRM_OPT_ASYNC && option != TRM_OPT_WRITE_KF_EVERY_STEP &&
+        !(option == TRM_OPT_DEFER_CLOSURE_STORES && value != 0)) {
+        TRM_HIP(c, hipSetDevice(c->device));
+        if (int rf = flush_closure(c)) return rf;
+    }
     switch (option) {
         case TRM_OPT_ASYNC: c->opt_async = value != 0; return TRM_OK;
         case TRM_OPT_STEP_KERNEL:
@@ -2880,6 +2948,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
             if (value < 0 || value > 2) break;
             c->opt_front = value;
             return TRM_OK;
+        case TRM_OPT_DEFER_CLOSURE_STORES: c->opt_defer_closure = value != 0; return TRM_OK;
         default: break;
     }
     return fail(c, TRM_EINVAL, "trm_set_option: unknown option or value");
@@ -2899,6 +2968,9 @@ int trm_get_option(const trm_ctx* c, int option, int* value) {
         case TRM_OPT_BC_SIGNATURE: *value = c->opt_bc_signature; return TRM_OK;
         case TRM_OPT_ZERO_GRADIENT_FAST: *value = c->opt_zero_gradient_fast; return TRM_OK;
         case TRM_OPT_SURFACE_IN_LAUNCH: *value = c->opt_front; return TRM_OK;
+        case TRM_OPT_DEFER_CLOSURE_STORES: *value = c->opt_defer_closure; return TRM_OK;
+        case TRM_INFO_CLOSURE_STORED: *value = c->closure_deferred ? 0 : 1; return TRM_OK;
+        case TRM_INFO_MATERIALIZATIONS: *value = (int)c->materializations; return TRM_OK;
         case TRM_INFO_LAST_PROGRAM: *value = c->last_program; return TRM_OK;
         case TRM_INFO_GENERIC_BOUNDARY_KERNELS: *value = (c->precision == TRM_F64 ? trmh::Policy<double>::generic_bcs(c) : trmh::Policy<float>::generic_bcs(c)) ? 1 : 0; return TRM_OK;
         case TRM_INFO_BC_SIGNATURE: *value = trmh::bc_signature_of(c); return TRM_OK;
@@ -2915,7 +2987,7 @@ int trm_set_stream(trm_ctx* c, void* hip_stream) {
     return TRM_OK;
 }
 int trm_synchronize(trm_ctx* c) {
-    TRM_ENTER_HEUN(c);
+    TRM_ENTER_KEEP(c);
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
 }

@@ -260,6 +260,10 @@ template <class NF> struct ColumnArgs {
     const SeriesTable<NF>* series;
     const SeriesRow* series_rows;
     int nseries;
+    // 0: the launch does not store temperature / liquid_water_fraction (a deriving per-step launch, Ops::defer_closure_now: the next
+    // step derives them from the stored (U, sat) again and k_materialize_closure forms them for whoever reads the arrays); 1: as ever.
+    // (in the padding behind nseries: the kernarg layout does not move)
+    int store_closure;
     // Heun of the vegetation-coupled LandModel: the stage's saturation, liquid fraction, temperature ([Nh][Nzp]) and surface
     // excess water ([Nh]) are stored for the 0-D processes that are evaluated AT the stage (null otherwise)
     NF *stage_sat, *stage_liq, *stage_T, *stage_S;
@@ -738,15 +742,16 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
         // every base pointer the store phase may need in ONE batch of scalar loads: fetched where they are used -- inside the
         // finalize / write_kf / top-lane branches -- each is a scalar load and a wait of its own in front of its store
         NF* const pGU = v.G_U; NF* const pGS3 = v.G_sat; NF* const pKf = v.Kf; NF* const pKft = v.Kf_top; NF* const pS = v.S; NF* const pwt = v.wt;
-        asm volatile("" : : "s"(pGU), "s"(pGS3), "s"(pKf), "s"(pKft), "s"(pS), "s"(pwt));
+        const int store_closure = kernarg_reload<ColumnArgs<NF>>(off_args).store_closure;      // (in the same batch)
+        asm volatile("" : : "s"(pGU), "s"(pGS3), "s"(pKf), "s"(pKft), "s"(pS), "s"(pwt), "s"(store_closure));
         // (block_local in EVERY block that stores: an offset defined in another block has been widened to 64 bits there.  One
         //  variable per offset, re-materialised in place: a fresh `block_local(cb0)` per block keeps cb0 alive beside it -- a
         //  vector move per block)
         unsigned cb = block_local(cb0);
         stg(v.U, cb, n.U);
-        stg(v.T, cb, n.T);
-        stg(v.liq, cb, n.liq);
-        if (RICHARDS) { stg(v.sat, cb, n.sat); stg(v.psi, cb, n.psi); }
+        // (T / liq are a pure function of the stored (U, sat): a deferring launch leaves them to k_materialize_closure -- 2 of 9 streams)
+        if (uniform_flag(store_closure)) { cb = block_local(cb); stg(v.T, cb, n.T); stg(v.liq, cb, n.liq); }
+        if (RICHARDS) { cb = block_local(cb); stg(v.sat, cb, n.sat); stg(v.psi, cb, n.psi); }
         // (the flags are tested afresh in every block: a wave-uniform bool carried into the divergent top-lane block becomes a
         //  lane mask there, formed by a v_cndmask and a v_cmp)
         if (uniform_flag(finalize)) {   // state.tendencies as the reference leaves them after its last step
@@ -827,6 +832,27 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK)
 #endif
     k_column(View<NF> v_arg, DevParams<NF> p_arg, ColumnArgs<NF> a) {
     column_program<NF, RICHARDS, HYD, LPC, DERIVE, PROG, SEB_INLINE, SERIES, STAGED, SCALAR_IN, BCSIG>(v_arg, p_arg, a, xcd_block<TRM_XCD_REMAP != 0>(blockIdx.x, gridDim.x));
+}
+
+// temperature and liquid_water_fraction of the stored (internal_energy, saturation) after launches that did not store them
+// (ColumnArgs::store_closure = 0): the derivation a deriving step runs at entry (energy_closure_wave<NF, 0>), on the same lanes of the
+// same waves -- lane = level, LPC lanes per column, tail lanes clamped as there, so its wave-wide decisions are the step's -- and
+// nothing else: no saturation repair, no pressure head, no water table, no status bits.  2 reads + 2 writes per cell.
+template <class NF, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_materialize_closure(View<NF> v, DevParams<NF> p) {
+    constexpr int CPW = 64 / LPC;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = (int)((blockIdx.x * (unsigned)TRM_STEP_BLOCK + threadIdx.x) >> 6);
+    const int k = lane % LPC, i = wave * CPW + lane / LPC;
+    const int Nz = v.Nz, Nh = (int)v.Nh;
+    const bool act = i < Nh && k < Nz;
+    const int ii = i < Nh ? i : Nh - 1;
+    const unsigned cb = ((unsigned)ii * (unsigned)v.Nzp + (unsigned)(k < Nz ? k : Nz - 1)) * (unsigned)sizeof(NF);
+    const NF U = ldg(v.U, cb), sat = ldg(v.sat, cb);
+    NF liq, T;
+    uint32_t viol = 0;
+    energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol);
+    if (act) { stg(v.T, cb, T); stg(v.liq, cb, liq); }
 }
 
 // The multi-step program with time averages accumulated in the launch (ACCUM): the kinds read at run time, nothing derived, the

@@ -94,6 +94,13 @@ struct trm_ctx {
     // true after a fused step / closure!, false after anything else wrote one of the four fields.  Lets the step derive
     // them in registers instead of reading them (k_column<DERIVE>).
     bool closure_consistent = false, closure_escaped = false, saved_closure_consistent = false;
+    // TRM_OPT_DEFER_CLOSURE_STORES: a deriving per-step launch does not store T / liq (nothing reads them before the next step derives
+    // them again).  `closure_deferred`: the T / liq arrays are stale and the stored (U, sat) define them -- every entry point that may
+    // read or write field memory materialises them first (flush_closure, k_materialize_closure).  `defer_launch`: the launch being
+    // issued may pass ColumnArgs::store_closure = 0 (set by Ops::fused_launch for its step launch only); `launch_deferred`: it has.
+    int opt_defer_closure = 1;
+    bool closure_deferred = false, defer_launch = false, launch_deferred = false;
+    int64_t materializations = 0;   // TRM_INFO_MATERIALIZATIONS: k_materialize_closure launches so far
     void* d_zero = nullptr;  // [Nh] zeros: stands in for the value array of every unset boundary condition
     double* d_reduce = nullptr;  // scratch for trm_reduce
     size_t reduce_cap = 0;
@@ -450,6 +457,7 @@ template <class NF> ColumnArgs<NF> column_args(trm_ctx* c, double dt, int finali
     a.series = (const SeriesTable<NF>*)c->d_series_table;
     a.series_rows = (const SeriesRow*)c->d_series_rows;
     a.nseries = (int)c->series.size();
+    a.store_closure = 1;      // (0: take_deferral, by the launchers of the deriving per-step instances alone)
     if (prog == PROG_HEUN && Policy<NF>::coupled(c)) {
         a.stage_sat = (NF*)c->stage.f[TRM_FIELD_SATURATION_WATER_ICE];
         a.stage_liq = (NF*)c->stage.f[TRM_FIELD_LIQUID_WATER_FRACTION];
@@ -457,6 +465,14 @@ template <class NF> ColumnArgs<NF> column_args(trm_ctx* c, double dt, int finali
         a.stage_S = (NF*)c->stage.f[TRM_FIELD_SURFACE_EXCESS_WATER];
     }
     return a;
+}
+
+// A launcher of a deriving (DERIVE_T_LIQ) per-step instance of k_column / k_column_land asks here whether this launch leaves
+// T / liq unstored: yes where Ops::fused_launch has allowed it for the launch being issued.  Records that it has.
+template <class NF> void take_deferral(trm_ctx* c, ColumnArgs<NF>& a) {
+    if (!c->defer_launch) return;
+    a.store_closure = 0;
+    c->launch_deferred = true;
 }
 
 // ---- the launchers: declared here, defined and explicitly instantiated in the trm_launch_*.hip files ------------------------
@@ -494,6 +510,8 @@ struct TangentLaunch {
     static int step(trm_ctx* c, double dt, int nsteps);
     static int closure(trm_ctx* c);
 };
+// k_materialize_closure (trm_launch_materialize.hip)
+template <class NF> struct MaterializeLaunch { static int run(trm_ctx* c); };
 // k_accumulate (trm_launch_average.hip)
 template <class NF> struct AverageLaunch { static int accumulate(trm_ctx* c, const AccumBatch& b); };
 constexpr int TRM_PROGRAM_BIT_AVERAGES_IN_LAUNCH = TRM_PROGRAM_AVERAGES_IN_LAUNCH;

@@ -8,9 +8,10 @@ template <class NF, bool RICH, int H, int LPC, int PROG> static int launch_colum
     using P = Policy<NF>;
     const View<NF>& v = state_view<NF>(c);
     const DevParams<NF>& p = launch_args<NF>(c).p;
-    const ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, nsteps, PROG);
+    ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, nsteps, PROG);
     const dim3 grid = column_grid(c, LPC), block(TRM_STEP_BLOCK);
     const int derive = P::template derive_now<RICH>(c);     // (for this kernel: DERIVE_NONE or DERIVE_T_LIQ)
+    if (PROG == PROG_EULER && derive == DERIVE_T_LIQ) take_deferral(c, a);      // (every instance below that derives)
     if (derive != DERIVE_NONE && derive != DERIVE_T_LIQ) return fail(c, TRM_EINVAL, "k_column: no instance for this derivation mode");
     int pid = 0;    // TRM_INFO_LAST_PROGRAM of the instance that is launched below
     if constexpr (PROG == PROG_MULTI) {

@@ -12,7 +12,7 @@ template <int H, int LPC> static int launch_column_land(trm_ctx* c, double dt, i
     const View<NF>& v = la.state;
     FrontArgs fa;
     if (int rc = front_args(c, "k_column_land", fa)) return rc;
-    const ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, 1, heun ? PROG_HEUN : PROG_EULER);
+    ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, 1, heun ? PROG_HEUN : PROG_EULER);
     dim3 grid = column_grid(c, LPC);
     grid.x += (unsigned)fa.chain_blocks;
     const dim3 block(TRM_STEP_BLOCK);
@@ -23,6 +23,7 @@ template <int H, int LPC> static int launch_column_land(trm_ctx* c, double dt, i
         return TRM_OK;
     }
     const int derive = P::derive_now<true>(c);
+    if (derive == DERIVE_T_LIQ) take_deferral(c, a);
     int staged = derive == DERIVE_T_LIQ ? P::staged_now<true>(c) : 0, scalar_in = derive == DERIVE_T_LIQ ? P::scalar_inputs_now<true>(c) : 1;
     P::io_paths(true, staged, scalar_in);
 #define TRM_LAND1(D, ST, SC) hipLaunchKernelGGL((k_column_land<NF, true, H, LPC, D, ST, SC>), grid, block, 0, c->stream, v, la.p, a, fa)

@@ -551,11 +551,11 @@ class DeviceState:
     def set_option(self, option, value):
         if option == "step_kernel" and isinstance(value, str):
             value = _capi.KERNEL[value]
-        self._check(self._lib.trm_set_option(self._ctx, _capi.OPTION[option], int(value)), "trm_set_option")
+        self._check(self._lib.trm_set_option(self._ctx, _capi.option_id(option), int(value)), "trm_set_option")
 
     def get_option(self, option) -> int:
         v = C.c_int()
-        self._check(self._lib.trm_get_option(self._ctx, _capi.OPTION[option], C.byref(v)), "trm_get_option")
+        self._check(self._lib.trm_get_option(self._ctx, _capi.option_id(option), C.byref(v)), "trm_get_option")
         return int(v.value)
 
     def last_program(self) -> dict:
