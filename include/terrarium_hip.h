@@ -243,7 +243,8 @@ enum {
     TRM_PROGRAM_NONE = 0, TRM_PROGRAM_COLUMN_EULER = 1, TRM_PROGRAM_COLUMN_HEUN = 2, TRM_PROGRAM_COLUMN_MULTI = 3,
     TRM_PROGRAM_PACKED_F32 = 4, TRM_PROGRAM_GENERIC_EULER = 5, TRM_PROGRAM_GENERIC_HEUN = 6, TRM_PROGRAM_COLUMN_LAND = 7,
     TRM_PROGRAM_DEEP = 8, TRM_PROGRAM_WIDE = 9, TRM_PROGRAM_LAND_INTERLEAVED = 10, TRM_PROGRAM_UNFUSED = 11, TRM_PROGRAM_VEGETATION = 12,
-    TRM_PROGRAM_PACKED_LAND = 13, TRM_PROGRAM_COLUMN_TANGENT = 14
+    TRM_PROGRAM_PACKED_LAND = 13, TRM_PROGRAM_COLUMN_TANGENT = 14,
+    TRM_PROGRAM_COLUMN_ADJOINT = 15
 };
 /* bits of TRM_INFO_LAST_PROGRAM beside the ones above (25-27 are per family: surface processes inline / time series in the multi-step
  * program, the program and the generic boundaries of the deep and wide columns): how the step's time averages were accumulated
@@ -613,6 +614,48 @@ int trm_tangent_download(trm_ctx* ctx, int which, void* host);
 int trm_tangent_device_ptr(trm_ctx* ctx, int which, void** dev, int64_t* pitch_elems);
 int trm_tangent_closure(trm_ctx* ctx);
 int trm_step_tangent(trm_ctx* ctx, double dt, int nsteps);
+
+/* ---- reverse-mode gradients of the heat-only run (the reference pulls a seed back through run! with Enzyme's Reverse mode) ---------
+ * The gradient g = dL/dU_0 of L = <wU, U_n> + <wT, T_n> + <wliq, liq_n> with respect to the initial internal energy, for what the
+ * tangent covers (above): the transpose of the linear map trm_step_tangent applies, one backward sweep for any number of inputs.
+ * Boundary values and parameters are constants.
+ *   trm_adjoint_open(ctx, capacity_steps)   allocates the cotangent fields of U, T, liq (zero) and a tape of capacity_steps slots; one
+ *                                           slot is Nh x Nzp x 8 bytes (the internal energy before a step).  Opening again starts a
+ *                                           fresh tape and zeroes the cotangents.
+ *   trm_adjoint_close(ctx)                  frees them
+ *   trm_adjoint_upload(ctx, which, host)    the cotangents wU / wT / wliq of the final U / T / liq, host layout [Nz][Nh]
+ *   trm_adjoint_download(ctx, which, host)  after trm_adjoint_backward: TRM_ADJOINT_INTERNAL_ENERGY is g, the other two are zero
+ *                                           (folded in)
+ *   trm_adjoint_device_ptr(ctx, which, &dev, &pitch)
+ *                                           device layout as trm_field_device_ptr
+ *   trm_adjoint_tape(ctx, &recorded, &capacity)
+ *   trm_step_record(ctx, dt, nsteps)        nsteps ForwardEuler steps, the internal energy before each stored in the next tape slot, dt
+ *                                           kept per step on the host.  The state afterwards -- every field, the status word, the clock
+ *                                           -- is that of trm_step(ctx, dt, nsteps, 1), bit for bit, in the launches trm_step would
+ *                                           issue on the multi-step program.  The stored T and liq are taken to be the closure of the
+ *                                           stored U, as for trm_step_tangent.
+ *   trm_adjoint_backward(ctx)               pulls the cotangents back through every taped step, newest first, and empties the tape:
+ *                                           one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt.  With
+ *                                           an empty tape it is the closure's transpose alone: g = wU + a wT + b wliq, a and b the
+ *                                           slopes dT/dU and dliq/dU of trm_tangent_closure at the stored state.
+ * TRM_INFO_LAST_PROGRAM of both is TRM_PROGRAM_COLUMN_ADJOINT: bit 25 as for the tangent family (Gradient halos on temperature, the
+ * generic halo form), bit 26 set for a backward launch and clear for a record launch.
+ * Errors: TRM_EINVAL without a context or an open adjoint, for a bad `which`, capacity_steps < 1, nsteps < 0, and for a trm_step_record
+ * of more steps than the tape has slots left (nothing is stepped; state and tape are unchanged).  TRM_EUNSUPPORTED for what the tangent
+ * refuses.  TRM_ENOMEM when the tape does not fit.  TRM_ESTALE from trm_adjoint_backward and trm_step_record when anything but
+ * trm_step_record has changed the state since the first taped step (the calls listed for the tangent, and trm_step_tangent), or
+ * trm_set_bc / trm_set_bc_series a boundary condition: the sweep reads the boundary values the context holds when it runs, which must be
+ * the ones the record ran with.  Nothing is stepped or pulled back then.  trm_adjoint_open, or a trm_adjoint_backward that succeeded,
+ * starts a fresh tape.  trm_step_record is a state-changing call for an open tangent.  A tangent and an adjoint may be open at once. */
+enum { TRM_ADJOINT_INTERNAL_ENERGY = 0, TRM_ADJOINT_TEMPERATURE = 1, TRM_ADJOINT_LIQUID_WATER_FRACTION = 2 };
+int trm_adjoint_open(trm_ctx* ctx, int capacity_steps);
+int trm_adjoint_close(trm_ctx* ctx);
+int trm_adjoint_upload(trm_ctx* ctx, int which, const void* host);
+int trm_adjoint_download(trm_ctx* ctx, int which, void* host);
+int trm_adjoint_device_ptr(trm_ctx* ctx, int which, void** dev, int64_t* pitch_elems);
+int trm_adjoint_tape(const trm_ctx* ctx, int* recorded, int* capacity);
+int trm_step_record(trm_ctx* ctx, double dt, int nsteps);
+int trm_adjoint_backward(trm_ctx* ctx);
 
 int trm_clock(const trm_ctx* ctx, double* time, int64_t* iteration);
 int trm_set_clock(trm_ctx* ctx, double time, int64_t iteration);

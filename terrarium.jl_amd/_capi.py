@@ -55,7 +55,7 @@ def option_id(name: str) -> int:
 KERNEL = dict(fused=0, unfused=1)
 # TRM_INFO_LAST_PROGRAM (include/terrarium_hip.h: TRM_PROGRAM_*; trm_host.hpp: program_id)
 PROGRAM = ("none", "column_euler", "column_heun", "column_multi", "packed_f32", "generic_euler", "generic_heun", "column_land", "deep", "wide",
-           "land_interleaved", "unfused", "vegetation", "packed_land", "column_tangent")
+           "land_interleaved", "unfused", "vegetation", "packed_land", "column_tangent", "column_adjoint")
 DERIVE = ("none", "T_liq", "liq", "liq_psi", "all")
 
 
@@ -69,6 +69,8 @@ def decode_program(pid: int) -> dict:
         d.update(program=("euler", "heun", "multi")[extra & 3])
     if d["family"] == "column_tangent":
         d.update(generic_boundaries=bool(extra & 1))
+    if d["family"] == "column_adjoint":
+        d.update(generic_boundaries=bool(extra & 1), backward=bool(extra & 2))
     if d["family"] in ("deep", "wide"):
         d.update(program=("euler", "heun", "multi")[extra & 3], generic_boundaries=bool(extra & 4))
     if pid & (PROGRAM_AVERAGES_IN_LAUNCH | PROGRAM_AVERAGES_AFTER_LAUNCH):
@@ -94,7 +96,9 @@ EXPORTS = (
     "trm_series_window trm_comm_init_all trm_step_all trm_step_heun_all trm_synchronize_all trm_reduce_global_all trm_status_global_all "
     "trm_average_open trm_average_reset trm_average_read trm_average_close "
     "trm_tangent_open trm_tangent_close trm_tangent_upload trm_tangent_download trm_tangent_device_ptr trm_tangent_closure "
-    "trm_step_tangent").split()
+    "trm_step_tangent "
+    "trm_adjoint_open trm_adjoint_close trm_adjoint_upload trm_adjoint_download trm_adjoint_device_ptr trm_adjoint_tape "
+    "trm_step_record trm_adjoint_backward").split()
 # forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
 TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
 TIME_INDEXING = dict(linear=0, clamp=1, cyclical=2, raster=3)
@@ -251,6 +255,14 @@ def lib():
     L.trm_tangent_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
     L.trm_tangent_closure.argtypes = [vp]
     L.trm_step_tangent.argtypes = [vp, dbl, i32]
+    L.trm_adjoint_open.argtypes = [vp, i32]
+    L.trm_adjoint_close.argtypes = [vp]
+    L.trm_adjoint_upload.argtypes = [vp, i32, vp]
+    L.trm_adjoint_download.argtypes = [vp, i32, vp]
+    L.trm_adjoint_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
+    L.trm_adjoint_tape.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.trm_step_record.argtypes = [vp, dbl, i32]
+    L.trm_adjoint_backward.argtypes = [vp]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

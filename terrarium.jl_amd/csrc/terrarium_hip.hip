@@ -377,6 +377,16 @@ bool averageable(const trm_ctx* c, int field) {
 }
 
 // tick! per step: the same sequence of sums as per-step calls (restarts compare the clock bit for bit)
+// The state has changed behind the derivatives' backs: an open tangent needs a new seed, a tape that holds steps no longer leads to the
+// stored state.  bc_changed: a boundary condition has (the backward sweep reads the values the context holds when it runs).
+void bc_changed(trm_ctx* c) {
+    if (!c->tape_dt.empty()) c->adj_stale = true;
+}
+void state_changed(trm_ctx* c) {
+    c->tan_stale = true;
+    bc_changed(c);
+}
+
 void tick(trm_ctx* c, double dt, int nsteps) {
     for (int j = 0; j < nsteps; ++j) c->time += dt;
     c->iteration += nsteps;
@@ -1577,6 +1587,9 @@ int trm_destroy(trm_ctx* c) {
         if (q) (void)hipFree(q);
     for (double* q : c->d_tan)
         if (q) (void)hipFree(q);
+    for (double* q : c->d_adj)
+        if (q) (void)hipFree(q);
+    if (c->d_tape) (void)hipFree(c->d_tape);
 
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->args && c->args_free) c->args_free(c->args);
@@ -1610,7 +1623,7 @@ int trm_upload(trm_ctx* c, int field, const void* host) {
     if (int rf = flush_closure(c)) return rf;      // (an upload of T alone must find liq current, and the reverse)
     int rc = c->precision == TRM_F64 ? upload_impl<double>(c, field, (const double*)host) : upload_impl<float>(c, field, (const float*)host);
     if (field <= TRM_FIELD_PRESSURE_HEAD || field == TRM_FIELD_WATER_TABLE) c->closure_consistent = false;   // (U, sat, T, liq, psi, water table)
-    if (field == TRM_FIELD_INTERNAL_ENERGY || field == TRM_FIELD_SATURATION_WATER_ICE) c->tan_stale = true;
+    if (field == TRM_FIELD_INTERNAL_ENERGY || field == TRM_FIELD_SATURATION_WATER_ICE) state_changed(c);
     if (!rc && field == TRM_FIELD_VWC_FORCING) {
         c->opt_vwc_field = 1;
         c->args_valid = false;
@@ -1683,6 +1696,7 @@ int trm_set_bc(trm_ctx* c, int var, int side, int kind, const void* values, doub
     c->bc_zero_gradient[var][side] = false;
     c->args_valid = false;
     c->heun_pending = false;
+    bc_changed(c);
     if (kind == TRM_BC_NOFLUX) return TRM_OK;
     size_t bytes = (size_t)c->Nh * c->esize;
     if (!c->bc_value[var][side]) TRM_HIP(c, hipMalloc(&c->bc_value[var][side], bytes));
@@ -1776,6 +1790,7 @@ int trm_set_bc_series(trm_ctx* c, int var, int side, int kind, int nt, const dou
     c->bc_kind[var][side] = kind;
     c->bc_zero_gradient[var][side] = false;      // (the values come from the series from now on)
     c->args_valid = false;
+    bc_changed(c);
     if (!c->bc_value[var][side]) {
         TRM_HIP(c, hipMalloc(&c->bc_value[var][side], (size_t)c->Nh * c->esize));
         TRM_HIP(c, hipMemsetAsync(c->bc_value[var][side], 0, (size_t)c->Nh * c->esize, c->stream));
@@ -1946,7 +1961,7 @@ int trm_reset(trm_ctx* c) {
     c->top_valid = false;
     c->tend_valid = true;
     c->closure_consistent = false;
-    c->tan_stale = true;
+    state_changed(c);
     return finish(c, TRM_OK);
 }
 
@@ -2010,7 +2025,7 @@ static int gather_ring(trm_ctx* c, int field, const void* full, bool device, con
     if (field == TRM_FIELD_ROOT_FRACTION) return fail(c, TRM_EINVAL, std::string(who) + ": root_fraction is derived from the root distribution parameters");
     int rc = c->precision == TRM_F64 ? gather_ring_impl<double>(c, field, full, device) : gather_ring_impl<float>(c, field, full, device);
     if (field <= TRM_FIELD_PRESSURE_HEAD || field == TRM_FIELD_WATER_TABLE) c->closure_consistent = false;
-    if (field == TRM_FIELD_INTERNAL_ENERGY || field == TRM_FIELD_SATURATION_WATER_ICE) c->tan_stale = true;
+    if (field == TRM_FIELD_INTERNAL_ENERGY || field == TRM_FIELD_SATURATION_WATER_ICE) state_changed(c);
     if (!rc && field == TRM_FIELD_VWC_FORCING) { c->opt_vwc_field = 1; c->args_valid = false; }
     c->top_valid = false;
     if (!rc && is_tendency(field)) c->tend_valid = true;
@@ -2029,7 +2044,7 @@ int trm_initialize(trm_ctx* c) {
     TRM_ENTER(c);
     c->top_valid = false;
     c->closure_consistent = false;   // temperature is the user's, internal_energy follows from it
-    c->tan_stale = true;
+    state_changed(c);
     return finish(c, DISPATCH(c, initialize(c)));
 }
 int trm_update_inputs(trm_ctx* c) {
@@ -2068,7 +2083,7 @@ int trm_explicit_step(trm_ctx* c, double dt) {
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, vegetation(c, c->state, VEG_EXPLICIT, dt, 1, 0)));
     c->top_valid = false;
     c->closure_consistent = false;
-    c->tan_stale = true;
+    state_changed(c);
     return finish(c, DISPATCH(c, explicit_step(c, c->state, dt)));
 }
 int trm_closure(trm_ctx* c) {
@@ -2081,7 +2096,7 @@ int trm_invclosure(trm_ctx* c) {
     TRM_ENTER(c);
     c->top_valid = false;
     c->closure_consistent = false;
-    c->tan_stale = true;
+    state_changed(c);
     return finish(c, DISPATCH(c, invclosure(c, c->state)));
 }
 
@@ -2089,7 +2104,7 @@ int trm_step(trm_ctx* c, double dt, int nsteps, int finalize) {
     TRM_ENTER_KEEP(c);
     c->heun_pending = false;
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step: nsteps < 0");
-    c->tan_stale = true;
+    state_changed(c);
     return finish(c, DISPATCH(c, step(c, dt, nsteps, finalize)));
 }
 
@@ -2112,7 +2127,7 @@ int trm_step_timed(trm_ctx* c, double dt, int nsteps, int finalize, float* ms) {
     TRM_ENTER_KEEP(c);
     c->heun_pending = false;
     if (nsteps < 0 || !ms) return fail(c, TRM_EINVAL, "trm_step_timed: bad argument");
-    c->tan_stale = true;
+    state_changed(c);
     TRM_HIP(c, hipEventRecord(c->ev0, c->stream));
     int rc = DISPATCH(c, step(c, dt, nsteps, finalize));
     if (rc) return rc;
@@ -2136,7 +2151,7 @@ int ensure_stage(trm_ctx* c) {
 int trm_step_heun(trm_ctx* c, double dt, int nsteps, int finalize) {
     TRM_ENTER(c);
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_heun: nsteps < 0");
-    c->tan_stale = true;
+    state_changed(c);
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, veg_step(c, dt, nsteps, finalize, true)));
     // (HeunPath: the stage's fields exist for every path but the one launch of <= 64 levels, which keeps the stage in registers)
     if (DISPATCH(c, heun_path(c)) != HEUN_ONE_LAUNCH)
@@ -2173,7 +2188,7 @@ int trm_heun_predict(trm_ctx* c, double dt) {
     c->top_valid = false;
     c->tend_valid = true;
     c->closure_consistent = false;     // (the state is untouched so far; the flag is set again by trm_heun_correct)
-    c->tan_stale = true;
+    state_changed(c);
     const int rc = DISPATCH(c, heun_predict(c, dt, true));
     if (rc) return rc;
     c->heun_pending = true;
@@ -2197,7 +2212,7 @@ int trm_heun_correct(trm_ctx* c, double dt, int finalize) {
     if (!c->heun_pending) return fail(c, TRM_EINVAL, "trm_heun_correct: call trm_heun_predict first");
     if (dt != c->heun_dt) return fail(c, TRM_EINVAL, "trm_heun_correct: dt differs from the dt of trm_heun_predict");
     c->heun_pending = false;
-    c->tan_stale = true;
+    state_changed(c);
     const int rc = DISPATCH(c, heun_correct(c, dt, finalize, c->heun_stage_aux));
     c->heun_stage_aux = false;
     if (rc) return rc;
@@ -2276,7 +2291,7 @@ int trm_restore_state(trm_ctx* c) {
     c->tend_valid = c->saved_tend_valid;
     c->closure_consistent = c->saved_closure_consistent;
     c->top_valid = false;
-    c->tan_stale = true;
+    state_changed(c);
     return finish(c, TRM_OK);
 }
 
@@ -2350,8 +2365,8 @@ int trm_average_close(trm_ctx* c, int handle) {
 
 // ---- forward-mode tangents of the heat-only step (trm_column_tangent.hpp) ---------------------------------------------------
 namespace {
-// what the tangent program covers: the heat-only fp64 SoilModel in columns of one level per lane
-const char* tangent_unsupported(const trm_ctx* c) {
+// what the tangent and adjoint programs cover: the heat-only fp64 SoilModel in columns of one level per lane
+const char* derivative_unsupported(const trm_ctx* c) {
     if (c->precision != TRM_F64) return "fp64 contexts only";
     if (c->params.flow == TRM_FLOW_RICHARDS) return "the heat-only SoilModel (NoFlow) only";
     if (c->params.seb || c->veg_mode != TRM_VEGETATION_OFF) return "not the LandModel or vegetation";
@@ -2359,8 +2374,8 @@ const char* tangent_unsupported(const trm_ctx* c) {
     return nullptr;
 }
 // ... and what a step needs besides: constant inputs, no accumulation, the temperature halos of the heat-only programs
-const char* tangent_step_unsupported(const trm_ctx* c) {
-    if (const char* why = tangent_unsupported(c)) return why;
+const char* derivative_step_unsupported(const trm_ctx* c) {
+    if (const char* why = derivative_unsupported(c)) return why;
     if (!c->series.empty()) return "no time series may be attached";
     for (const auto& a : c->averages)
         if (a.field >= 0) return "no time average may be open";
@@ -2380,7 +2395,7 @@ const char* kStaleTangent = ": the state has changed since the tangent was seede
 
 int trm_tangent_open(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
-    if (const char* why = tangent_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_open: ") + why);
+    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_open: ") + why);
     const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double);
     for (double*& q : c->d_tan) {
         if (!q) TRM_HIP(c, hipMalloc((void**)&q, bytes));
@@ -2440,7 +2455,7 @@ int trm_tangent_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_ele
 int trm_tangent_closure(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_closure: no tangent is open (trm_tangent_open)");
-    if (const char* why = tangent_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_closure: ") + why);
+    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_closure: ") + why);
     if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_closure") + kStaleTangent);
     return finish(c, TangentLaunch::closure(c));
 }
@@ -2448,8 +2463,9 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     TRM_ENTER(c);
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_step_tangent: no tangent is open (trm_tangent_open)");
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_tangent: nsteps < 0");
-    if (const char* why = tangent_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + why);
+    if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + why);
     if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_step_tangent") + kStaleTangent);
+    bc_changed(c);             // (a state-changing call for an open tape)
     // the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to TRM_OPT_STEPS_PER_LAUNCH steps each
     const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);
     int n = 0;
@@ -2464,6 +2480,166 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     c->closure_consistent = true;
     c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
     c->top_valid = false;
+    return finish(c, TRM_OK);
+}
+
+// ---- reverse-mode gradients of the heat-only run (trm_column_adjoint.hpp) -----------------------------------------------------
+namespace {
+int adjoint_args_ok(trm_ctx* c, int which, const void* ptr, const char* who) {
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no adjoint is open (trm_adjoint_open)");
+    if (which < 0 || which > TRM_ADJOINT_LIQUID_WATER_FRACTION || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument");
+    return TRM_OK;
+}
+const char* kStaleTape = ": the state or a boundary condition has changed since the first taped step: trm_adjoint_open starts a new tape";
+void free_adjoint(trm_ctx* c) {
+    for (double*& q : c->d_adj) {
+        if (q) (void)hipFree(q);
+        q = nullptr;
+    }
+    if (c->d_tape) (void)hipFree(c->d_tape);
+    c->d_tape = nullptr;
+    c->tape_cap = 0;
+    c->tape_dt.clear();
+    c->adj_stale = false;
+}
+}  // namespace
+
+int trm_adjoint_open(trm_ctx* c, int capacity_steps) {
+    TRM_ENTER_HEUN(c);
+    if (capacity_steps < 1) return fail(c, TRM_EINVAL, "trm_adjoint_open: capacity_steps < 1");
+    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_open: ") + why);
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double);
+    if (capacity_steps != c->tape_cap) {
+        if (c->d_tape) (void)hipFree(c->d_tape);
+        c->d_tape = nullptr;
+        c->tape_cap = 0;
+        c->tape_dt.clear();
+        c->adj_stale = false;
+        if (hipMalloc((void**)&c->d_tape, (size_t)capacity_steps * bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            c->d_tape = nullptr;
+            const bool was_open = c->d_adj[0] != nullptr;
+            free_adjoint(c);
+            return fail(c, TRM_ENOMEM, "trm_adjoint_open: a tape of " + std::to_string(capacity_steps) + " steps x " + std::to_string(bytes) +
+                                           " bytes does not fit" + (was_open ? " (the adjoint that was open is closed)" : ""));
+        }
+        c->tape_cap = capacity_steps;
+    }
+    for (double*& q : c->d_adj) {
+        if (!q && hipMalloc((void**)&q, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            q = nullptr;
+            free_adjoint(c);
+            return fail(c, TRM_ENOMEM, "trm_adjoint_open: the cotangent fields do not fit");
+        }
+        TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+    }
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    c->tape_dt.clear();        // (a fresh tape)
+    c->adj_stale = false;
+    return TRM_OK;
+}
+int trm_adjoint_close(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_close: no adjoint is open");
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    free_adjoint(c);
+    return TRM_OK;
+}
+int trm_adjoint_upload(trm_ctx* c, int which, const void* host) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = adjoint_args_ok(c, which, host, "trm_adjoint_upload")) return rc;
+    const long Nh = c->Nh;
+    const size_t bytes = (size_t)c->Nz * Nh * sizeof(double);
+    if (int rc = io_buffer(c, bytes)) return rc;
+    TRM_HIP(c, hipMemcpyAsync(c->d_io, host, bytes, hipMemcpyHostToDevice, c->stream));
+    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
+    hipLaunchKernelGGL((k_transpose<double, true>), grid, dim3(256), 0, c->stream, (const double*)c->d_io, c->d_adj[which], Nh, c->Nz, c->Nzp);
+    TRM_HIP(c, hipGetLastError());
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_download(trm_ctx* c, int which, void* host) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = adjoint_args_ok(c, which, host, "trm_adjoint_download")) return rc;
+    const long Nh = c->Nh;
+    const size_t bytes = (size_t)c->Nz * Nh * sizeof(double);
+    if (int rc = io_buffer(c, bytes)) return rc;
+    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
+    hipLaunchKernelGGL((k_transpose<double, false>), grid, dim3(256), 0, c->stream, (const double*)c->d_adj[which], (double*)c->d_io, Nh, c->Nz, c->Nzp);
+    TRM_HIP(c, hipGetLastError());
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_io, bytes, hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_elems) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = adjoint_args_ok(c, which, dev, "trm_adjoint_device_ptr")) return rc;
+    if (!pitch_elems) return fail(c, TRM_EINVAL, "trm_adjoint_device_ptr: bad argument");
+    *dev = c->d_adj[which];
+    *pitch_elems = c->Nzp;
+    return TRM_OK;
+}
+int trm_adjoint_tape(const trm_ctx* c, int* recorded, int* capacity) {
+    if (!c) return TRM_EINVAL;
+    if (!c->d_adj[0]) return fail(const_cast<trm_ctx*>(c), TRM_EINVAL, "trm_adjoint_tape: no adjoint is open (trm_adjoint_open)");
+    if (recorded) *recorded = (int)c->tape_dt.size();
+    if (capacity) *capacity = c->tape_cap;
+    return TRM_OK;
+}
+int trm_step_record(trm_ctx* c, double dt, int nsteps) {
+    TRM_ENTER(c);
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_step_record: no adjoint is open (trm_adjoint_open)");
+    if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_record: nsteps < 0");
+    const int recorded = (int)c->tape_dt.size();
+    if (nsteps > c->tape_cap - recorded)
+        return fail(c, TRM_EINVAL, "trm_step_record: " + std::to_string(nsteps) + " steps do not fit the tape (" + std::to_string(recorded) + " of " +
+                                       std::to_string(c->tape_cap) + " slots taken)");
+    if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + why);
+    if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_step_record") + kStaleTape);
+    if (nsteps > 0) c->tan_stale = true;       // (a state-changing call for an open tangent)
+    // the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to TRM_OPT_STEPS_PER_LAUNCH steps each
+    const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);
+    int n = 0;
+    while (n < nsteps) {
+        const int m = std::min(spl, nsteps - n);
+        int rc = Ops<double>::update_inputs(c, c->state, c->time);
+        if (!rc) rc = AdjointLaunch::record(c, dt, m, (int)c->tape_dt.size());
+        if (rc) {
+            c->adj_stale = !c->tape_dt.empty();
+            return rc;
+        }
+        c->tape_dt.insert(c->tape_dt.end(), (size_t)m, dt);
+        tick(c, dt, m);
+        n += m;
+    }
+    c->closure_consistent = true;
+    c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
+    c->top_valid = false;
+    return finish(c, TRM_OK);
+}
+int trm_adjoint_backward(trm_ctx* c) {
+    TRM_ENTER(c);
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_backward: no adjoint is open (trm_adjoint_open)");
+    if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + why);
+    if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_adjoint_backward") + kStaleTape);
+    // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch folds
+    // the cotangents of T and liq in (an empty tape: that launch alone)
+    const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);
+    int end = (int)c->tape_dt.size(), fold = 1;
+    do {
+        int begin = end;
+        while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
+        if (int rc = AdjointLaunch::backward(c, end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0, end - begin, begin, fold)) {
+            c->adj_stale = true;       // (lam is part way down the tape)
+            return rc;
+        }
+        end = begin;
+        fold = 0;
+    } while (end > 0);
+    c->tape_dt.clear();
+    c->adj_stale = false;
     return finish(c, TRM_OK);
 }
 

@@ -1,0 +1,236 @@
+// trm_column_adjoint.hpp -- reverse-mode gradients of the heat-only ForwardEuler run (trm_step_record, trm_adjoint_backward).
+//
+// The adjoint is the transpose of the linear map k_column_tangent applies (trm_column_tangent.hpp): with the closure slopes
+// dT = a dU, dliq = b dU of the branch the primal took and dkappa = c dliq, one forward step is dU' = dU + dt dgU(dT, dliq).  Backwards,
+// for the cotangent lam' of dU':
+//   mu      = lam' dt rdzc                                   (the cotangent of -(dq_hi - dq_lo))
+//   phi     = mu - mu_below  (mu at the bottom face)         (the cotangent of a cell's lower face flux dq_lo; -mu of the top face flux)
+//   dq_lo   = A (dkappa + dkappa_m) + B (dT - dT_m),  A = -0.5 (T - T_m) rdzf,  B = -0.5 (kappa + kappa_m) rdzf
+//   kappa~  = phi A + (phi A)_above,   T~ = phi B - (phi B)_above
+//   lam     = lam' + a T~ + b c kappa~
+// The boundary faces use the transposed halo rules: a Value halo extrapolates through a constant (dT - dT_halo = +-dT dzf / (dzf / 2)),
+// a Gradient halo copies the edge cell (no term), the mirror policy's halo conductivity is the edge cell's (its A counts twice), the dry
+// halo cell of the reference-zero policy has dkappa = 0.  Flux boundary terms are constants.
+// Every coefficient is a function of the state U_k BEFORE step k: k_column_record is the multi-step primal that stores U_k into tape
+// slot k (the field layout [Nh][Nzp]) before every step; k_column_adjoint walks a block of slots backwards with lam in registers.
+// closure_tangent and conductivity_tangent are linear in their seed, one scalar slope per cell: applied to a cotangent they are their
+// own transposes, and the slopes are formed by the tangent's expressions.  No operation has an additive constant, so scaling the
+// cotangents by a power of two scales the gradient bit for bit, and a zero cotangent gives a zero gradient.
+#pragma once
+// (trm_column_tangent.hpp defines the non-template kernel k_closure_tangent, which trm_launch_column_tangent.hip owns: this translation
+// unit takes the header for closure_tangent and conductivity_tangent and gives its copy of that kernel a name of its own)
+#define k_closure_tangent k_closure_tangent_in_adjoint_unit
+#include "trm_column_tangent.hpp"
+#undef k_closure_tangent
+
+namespace trm {
+
+// Fourth kernel argument of k_column_record / k_column_adjoint
+struct AdjointArgs {
+    double *lU, *lT, *lliq;   // the cotangent fields ([Nh][Nzp] like the state); lU carries lam between launches
+    double* tape;             // the slot of the first step of this launch; slot s of the launch at tape + s * slot_elems
+    long long slot_elems;     // Nh * Nzp
+    int generic;              // 1: Gradient on temperature off the branch-free kinds (k_step_wave's halos, column_tendencies_generic)
+    int fold;                 // backward: 1 in the first launch of a sweep: lam_n = wU + a_n wT + b_n wliq of the stored state, wT = wliq = 0 after
+};
+
+// what the lane-per-level kernels of this file know about their lane (as k_column_tangent forms it)
+template <int LPC> TRM_DEV LaneInfo adjoint_lane(const View<double>& v, int& ii, size_t& e) {
+    constexpr int CPW = 64 / LPC;
+    LaneInfo ln;
+    ln.lane = threadIdx.x & 63;
+    const int wave = (int)((blockIdx.x * (unsigned)TRM_STEP_BLOCK + threadIdx.x) >> 6);
+    ln.k = ln.lane % LPC;
+    const int sub = ln.lane / LPC;
+    const int Nz = v.Nz, Nh = (int)v.Nh;
+    ln.is_bot = ln.k == 0;
+    ln.is_top = ln.k == Nz - 1;
+    ln.m_bot = wave_ballot(ln.is_bot);
+    ln.m_top = wave_ballot(ln.is_top);
+    const int i = wave * CPW + sub;
+    const bool colok = i < Nh;
+    ln.act = colok && ln.k < Nz;
+    ln.m_act = wave_ballot(colok) & wave_ballot(ln.k < Nz);
+    ii = colok ? i : Nh - 1;                             // (tail lanes carry clamped copies and store nothing)
+    e = (size_t)ii * (size_t)v.Nzp + (size_t)(ln.k < Nz ? ln.k : Nz - 1);
+    return ln;
+}
+
+// `a.nsteps` ForwardEuler steps of the state, U_k stored into tape slot k before step k; the outputs are those of a finalizing trm_step
+template <int HYD, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, AdjointArgs aa) {
+    using NF = double;
+    int ii;
+    size_t e;
+    const LaneInfo ln = adjoint_lane<LPC>(v, ii, e);
+    const int Nz = v.Nz;
+    const bool generic = aa.generic != 0;
+    uint32_t viol = 0;
+    bool bad = false;
+
+    Cell<NF> c;
+    c.U = v.U[e];
+    c.sat = v.sat[e];
+    c.T = v.T[e];
+    c.liq = v.liq[e];
+    c.psi = 0.0;
+    const LevelGeom<NF> L = level_geom(v, ln.k);
+    // boundary inputs: constants over the launch
+    const NF bTb = v.bc.kind[2][0] == 1 ? bcval(v, 2, 0)[ii] : 0.0, bTt = v.bc.kind[2][1] == 1 ? bcval(v, 2, 1)[ii] : 0.0;
+    ColumnBC<NF> bc;
+    bc.bTb = bTb;
+    bc.bTt = bTt;
+    bc.flux_S = 0.0;
+    bc.has_U = true;
+    bc.has_S = false;
+    {   // compute_z_bcs! terms as each program forms them (k_step_wave: flux_term_*; the column program: flux_term_*_nsz, selects)
+        const bool bU = v.bc.kind[0][0] == 2, tU = v.bc.kind[0][1] == 2;
+        if (generic) {
+            NF fU = 0.0;
+            if (ln.is_bot && bU) fU = flux_term_bottom(bcval(v, 0, 0)[ii], v.g);
+            if (ln.is_top && tU) fU = -flux_term_top(bcval(v, 0, 1)[ii], v.g);
+            bc.flux_U = fU;
+        } else {
+            NF eU_b = 0.0, eU_t = 0.0;
+            if (bU) eU_b = flux_term_bottom_nsz(bcval(v, 0, 0)[ii], v.g);
+            if (tU) eU_t = -flux_term_top_nsz(bcval(v, 0, 1)[ii], v.g);
+            const NF tU_term = ln.is_top ? eU_t : NF(0);
+            bc.flux_U = ln.is_bot ? eU_b : tU_term;
+        }
+    }
+
+    Cell<NF> n = c;
+    Frac<NF> f_new{};
+    NF gU_out = 0.0;
+    NF* slot = aa.tape + e;
+    for (int step = 0; step < a.nsteps; ++step) {
+        if (step > 0) c = n;
+        if (ln.act) *slot = c.U;
+        slot += aa.slot_elems;
+        const Frac<NF>* pre = step > 0 ? &f_new : nullptr;
+        const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
+                                       : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
+        NF gU = t.gU, gS = t.gS, z0;
+        column_advance<NF, false, LPC>(v, L, ln, Nz, bc, c.U, c.sat, gU, gS, a.dt, n, z0, bad);
+        f_new = column_closure<NF, false, HYD>(p, L, z0, n, viol);
+        gU_out = gU;
+    }
+    // hydraulic_conductivity of the new state (a finalizing step: compute_auxiliary!)
+    const NF Kc_new = conductivity_hydraulic<NF, HYD, false>(p, n.liq, f_new);
+    const NF Kc_new_m = shfl_up1<NF, LPC>(Kc_new);
+    const NF Kmin_new = jl_min(Kc_new, Kc_new_m);
+    const NF Kf_out = (ln.is_bot || ln.is_top) ? Kc_new : Kmin_new;
+    if (ln.act) {
+        v.U[e] = n.U;
+        v.T[e] = n.T;
+        v.liq[e] = n.liq;
+        v.G_U[e] = gU_out;
+        v.Kf[e] = Kf_out;
+        if (ln.is_top) v.Kf_top[ii] = Kc_new;
+        viol |= bad ? 1u : 0u;
+    }
+    if (viol && ln.act) atomicOr(v.status, viol);
+}
+
+// the transposed step at the state U (the tape's U_k): lam' -> lam
+template <int LPC>
+TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, const LevelGeom<double>& L, const LaneInfo& ln, int ii,
+                            double U, double sat, double lam, double dt, double bTb, double bTt, bool generic) {
+    // T, liq, C and kappa of the cell, as the tangent recomputes them
+    uint32_t viol_in = 0;
+    double liq, T;
+    const Frac<double> f = energy_closure_wave<double, 0>(p, U, sat, liq, T, viol_in);
+    const double C = heat_capacity(p, f);
+    const double kap = conductivity(p, f);
+    const double T_sh = shfl_up1<double, LPC>(T), kap_sh = shfl_up1<double, LPC>(kap);
+    // temperature halos as the primal forms them
+    double T_b = T, T_t = T;
+    const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
+    if (generic) {      // (k_step_wave's halos from the boundary values the kernel has loaded: no load inside the sweep but the tape's)
+        T_b = halo_bottom(kb, &bTb, 0, T, v.g);
+        T_t = halo_top(kt, &bTt, 0, T, v.g);
+    } else {
+        if (kb == 1) T_b = T + div_const_nsz(T - bTb, v.g.hdzf_bot, v.g.rhdzf_bot) * (-v.g.dzf_bot);
+        if (kt == 1) T_t = T + div_const_nsz(bTt - T, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top;
+    }
+    const bool mirror = p.halo_policy == 1;
+    const double kap_halo = mirror ? kap : conductivity(p, fractions_unchecked(p, 0.0, liq));
+    const double T_m = ln.is_bot ? T_b : T_sh, kap_m = ln.is_bot ? kap_halo : kap_sh;
+    // cotangents of the face fluxes
+    const double mu = lam * dt * L.rdzc;
+    const double mu_sh = shfl_up1<double, LPC>(mu);
+    const double phi_lo = ln.is_bot ? mu : mu - mu_sh;
+    const double phi_top = -mu;
+    // the lower face: pA is the cotangent of (dkappa + dkappa_m), pB of (dT - dT_m)
+    const double pA = phi_lo * (-0.5 * ((T - T_m) * L.rdzf_lo));
+    const double pB = phi_lo * (-(0.5 * (kap + kap_m)) * L.rdzf_lo);
+    // the top boundary face (used by the top lane alone)
+    const double pA_t = phi_top * (-0.5 * ((T_t - T) * L.rdzf_hi));
+    const double pB_t = phi_top * (-(0.5 * (kap_halo + kap)) * L.rdzf_hi);
+    const double pA_sh = shfl_dn1<double, LPC>(pA), pB_sh = shfl_dn1<double, LPC>(pB);
+    // own share of the lower face: an interior cell is the `+` side; the bottom cell owns its halo (Value: dT - dT_b = dT dzf / (dzf / 2),
+    // else 0; mirror: dkappa_halo = dkappa, else 0)
+    const double pB_val_b = kb == 1 ? -(div_const(pB, v.g.hdzf_bot, v.g.rhdzf_bot) * (-v.g.dzf_bot)) : 0.0;
+    const double own_B = ln.is_bot ? pB_val_b : pB;
+    const double own_A = (ln.is_bot && mirror) ? pA + pA : pA;
+    // share of the face above: the cell below a face is its `-` side in dT and its `+` side in dkappa; the top cell owns its halo
+    // (Value: dT_t - dT = -dT dzf / (dzf / 2))
+    const double pB_val_t = kt == 1 ? div_const(-pB_t, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top : 0.0;
+    const double up_B = ln.is_top ? pB_val_t : -pB_sh;
+    const double up_A = ln.is_top ? (mirror ? pA_t + pA_t : pA_t) : pA_sh;
+    const double Tbar = own_B + up_B;
+    const double kbar = own_A + up_A;
+    // through the slopes: liq~ = c kappa~, U~ = a T~ + b liq~ (closure_tangent and conductivity_tangent are their own transposes)
+    const double lbar = conductivity_tangent(p, f, sat * p.por, kbar);
+    double via_T, via_liq, unused_liq, unused_T;
+    closure_tangent(p, U, sat, C, Tbar, unused_liq, via_T);
+    closure_tangent(p, U, sat, C, lbar, via_liq, unused_T);
+    return lam + via_T + via_liq;
+}
+
+// The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt
+template <int HYD, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, AdjointArgs aa) {
+    using NF = double;
+    int ii;
+    size_t e;
+    const LaneInfo ln = adjoint_lane<LPC>(v, ii, e);
+    const bool generic = aa.generic != 0;
+    const NF sat = v.sat[e];
+    NF lam = aa.lU[e];
+    // the newest slot first; the load of the slot below is issued before the arithmetic of a step
+    const NF* slot = aa.tape + (size_t)(a.nsteps > 0 ? a.nsteps - 1 : 0) * (size_t)aa.slot_elems + e;
+    NF U_next = a.nsteps > 0 ? *slot : 0.0;
+    const LevelGeom<NF> L = level_geom(v, ln.k);
+    // the temperature boundary values: of a Value condition, and of a Gradient condition where the generic halo form reads them
+    const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
+    const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
+    if (aa.fold) {   // the end of the run: the cotangents of T_n and liq_n through the closure of the stored U_n
+        const NF U = v.U[e], wT = aa.lT[e], wliq = aa.lliq[e];
+        uint32_t viol_in = 0;
+        NF liq, T, via_T, via_liq, unused_liq, unused_T;
+        const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
+        const NF C = heat_capacity(p, f);
+        closure_tangent(p, U, sat, C, wT, unused_liq, via_T);
+        closure_tangent(p, U, sat, C, wliq, via_liq, unused_T);
+        lam = lam + via_T + via_liq;
+        if (ln.act) {
+            aa.lT[e] = 0.0;
+            aa.lliq[e] = 0.0;
+        }
+    }
+    // Everything loaded so far is used here, in front of the loop: inside it the next slot's load is the only one in flight, and the wait
+    // for it sits where its value is taken, behind the arithmetic of the step
+    asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt));
+    for (int step = a.nsteps - 1; step >= 0; --step) {
+        const NF U = U_next;
+        if (step > 0) {
+            slot -= aa.slot_elems;
+            U_next = *slot;
+        }
+        lam = adjoint_step<LPC>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic);
+    }
+    if (ln.act) aa.lU[e] = lam;
+}
+
+}  // namespace trm

@@ -157,6 +157,14 @@ struct trm_ctx {
     // `tan_stale`: another call has changed the state since the tangent was seeded (trm_tangent_upload of dU clears it).
     double* d_tan[3] = {};
     bool tan_stale = false;
+    // reverse-mode gradients (trm_adjoint_*): the cotangent fields of U, T, liq in the same layout, and the tape of trm_step_record --
+    // `tape_cap` slots of [Nh][Nzp] doubles, slot k the internal energy before taped step k, `tape_dt[k]` that step's dt.  `adj_stale`:
+    // another call has changed the state or a boundary condition since the first taped step (state_changed / bc_changed below).
+    double* d_adj[3] = {};
+    double* d_tape = nullptr;
+    int tape_cap = 0;
+    std::vector<double> tape_dt;
+    bool adj_stale = false;
     bool args_valid = false;
     void* args = nullptr;   // LaunchArgs<NF>*, owned
     void (*args_free)(void*) = nullptr;
@@ -509,6 +517,11 @@ template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx
 struct TangentLaunch {
     static int step(trm_ctx* c, double dt, int nsteps);
     static int closure(trm_ctx* c);
+};
+// k_column_record / k_column_adjoint (trm_launch_column_adjoint.hip, fp64 NoFlow only): `slot` is the tape slot of the launch's first step
+struct AdjointLaunch {
+    static int record(trm_ctx* c, double dt, int nsteps, int slot);
+    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
 };
 // k_materialize_closure (trm_launch_materialize.hip)
 template <class NF> struct MaterializeLaunch { static int run(trm_ctx* c); };

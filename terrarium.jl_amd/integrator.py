@@ -441,6 +441,43 @@ class DeviceState:
         """`nsteps` ForwardEuler steps of the state and its tangent; the state ends as after step(dt, nsteps, finalize=True)."""
         self._check(self._lib.trm_step_tangent(self._ctx, float(dt), int(nsteps)), "trm_step_tangent")
 
+    # -- reverse-mode gradients (trm_adjoint_*) with respect to the initial internal energy: what the tangent covers ---------------
+    def open_adjoint(self, capacity_steps):
+        """Cotangent fields of internal energy, temperature and liquid fraction (zero) and a tape of `capacity_steps` slots, one
+        internal-energy field each (trm_adjoint_open).  Opening again starts a fresh tape."""
+        self._check(self._lib.trm_adjoint_open(self._ctx, int(capacity_steps)), "trm_adjoint_open")
+        self._adjoint_open = True
+
+    def close_adjoint(self):
+        self._check(self._lib.trm_adjoint_close(self._ctx), "trm_adjoint_close")
+        self._adjoint_open = False
+
+    def set_cotangent(self, name, value):
+        """The cotangent of a final field ([Nz][Nh], or anything that broadcasts to it)."""
+        a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
+        a[...] = value
+        self._check(self._lib.trm_adjoint_upload(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_adjoint_upload")
+
+    def cotangent(self, name) -> np.ndarray:
+        """A cotangent field as [Nz][Nh] (row 0 = bottom layer); after adjoint_backward `internal_energy` is dL/dU_0."""
+        a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
+        self._check(self._lib.trm_adjoint_download(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_adjoint_download")
+        return a
+
+    def step_record(self, dt, nsteps=1):
+        """`nsteps` ForwardEuler steps, each taped; the state ends as after step(dt, nsteps, finalize=True)."""
+        self._check(self._lib.trm_step_record(self._ctx, float(dt), int(nsteps)), "trm_step_record")
+
+    def adjoint_backward(self):
+        """Pulls the cotangents back through every taped step and empties the tape (trm_adjoint_backward)."""
+        self._check(self._lib.trm_adjoint_backward(self._ctx), "trm_adjoint_backward")
+
+    def adjoint_tape(self):
+        """(steps recorded, capacity) of the tape."""
+        n, cap = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.trm_adjoint_tape(self._ctx, C.byref(n), C.byref(cap)), "trm_adjoint_tape")
+        return int(n.value), int(cap.value)
+
     def step(self, dt, nsteps=1, finalize=True):
         self._check(self._lib.trm_step(self._ctx, float(dt), int(nsteps), int(finalize)), "trm_step")
 
@@ -852,6 +889,31 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int) -> dict:
     finally:
         if opened:
             st.close_tangent()
+
+
+def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=None, liquid_water_fraction=None) -> np.ndarray:
+    """Reverse-mode derivative of `run!(integ; steps)`: the integrator is stepped `steps` times with its own dt (state and clock end
+    where `run` leaves them), then the given cotangents of the final temperature, internal energy and liquid water fraction ([Nz][Nh],
+    or anything that broadcasts to it; None: zero) are pulled back.  Returns dL/dU_0 as [Nz][Nh], L the sum of the three inner
+    products.  One tape slot per step (trm_step_record, trm_adjoint_backward); the coverage and refusals of `jvp`."""
+    if not isinstance(integ.timestepper, ForwardEuler):
+        raise ValueError("vjp: ForwardEuler only")
+    if integ._has_time_dependence() or integ._windowed():
+        raise ValueError("vjp: boundary conditions and inputs must be constant over the run")
+    st = integ.state
+    steps = int(steps)
+    opened = not getattr(st, "_adjoint_open", False)
+    if opened or st.adjoint_tape() != (0, max(steps, 1)):
+        st.open_adjoint(max(steps, 1))
+    try:
+        st.step_record(integ.timestepper.dt, steps)
+        for name, w in (("internal_energy", internal_energy), ("temperature", temperature), ("liquid_water_fraction", liquid_water_fraction)):
+            st.set_cotangent(name, 0.0 if w is None else w)
+        st.adjoint_backward()
+        return st.cotangent("internal_energy")
+    finally:
+        if opened:
+            st.close_adjoint()
 
 
 def current_time(integrator: ModelIntegrator) -> float:
