@@ -87,6 +87,10 @@ def _lib(omp=False):
         lib.trm_oracle_set_threads.argtypes = [C.c_int]
         lib.trm_oracle_create.restype = C.c_void_p
         lib.trm_oracle_create.argtypes = [C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_double, C.POINTER(ParamsD)]
+        lib.trm_oracle_create_wide.restype = C.c_void_p
+        lib.trm_oracle_create_wide.argtypes = [C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_double, C.POINTER(ParamsD)]
+        lib.trm_oracle_wide_digits.restype = C.c_int
+        lib.trm_oracle_safediv_wide.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.trm_oracle_destroy.argtypes = [C.c_void_p]
         lib.trm_oracle_field_rows.restype = C.c_long
         lib.trm_oracle_field_rows.argtypes = [C.c_void_p, C.c_int]
@@ -166,19 +170,52 @@ def volumetric_fractions(por, sat, liq, org=0.0):
     return dict(zip(("water", "ice", "air", "mineral", "organic"), out))
 
 
-class Oracle:
-    """Reference-order CPU driver.  Arrays cross as [rows][Nh], k = 0 bottom."""
+def wide_available():
+    """True where np.longdouble is the C library's `long double` with at least 64 significand bits (x86-64 Linux: the 80-bit
+    x87 format), so that arrays cross to the wide instance unchanged and it is wider than both model precisions."""
+    return np.finfo(np.longdouble).nmant >= 63 and _lib().trm_oracle_wide_digits() == np.finfo(np.longdouble).nmant + 1
 
-    def __init__(self, num_columns, thickness, params=None, dtype=np.float64, dx=0.0, omp=False):
+
+def safediv_wide(x, y, model=np.float64):
+    """safediv (utils.jl:25) in wide arithmetic with eps of the model precision."""
+    a, b, out = (np.array([v], dtype=np.longdouble) for v in (x, y, 0))
+    _lib().trm_oracle_safediv_wide(_MODEL_CODE[np.dtype(model)], a.ctypes.data, b.ctypes.data, out.ctypes.data)
+    return out[0]
+
+
+_MODEL_CODE = {np.dtype(np.float64): 0, np.dtype(np.float32): 1}
+
+
+class Oracle:
+    """Reference-order CPU driver.  Arrays cross as [rows][Nh], k = 0 bottom.
+
+    dtype = np.float64 / np.float32: the model in its own arithmetic (precision codes 0 / 1).  dtype = np.longdouble
+    (precision code 2): the model of precision `model` (np.float64 or np.float32) evaluated in long double -- its
+    parameters, grid, eps and literals stay the model's, and every array handed in is rounded to `model` first, so all
+    three instances start from identical values; results come back as np.longdouble."""
+
+    def __init__(self, num_columns, thickness, params=None, dtype=np.float64, dx=0.0, omp=False, model=None):
         self.lib = _lib(omp)
         self.dtype = np.dtype(dtype)
+        self.wide = self.dtype == np.dtype(np.longdouble) and self.dtype != np.float64
+        self.model = np.dtype(model) if model is not None else (np.dtype(np.float64) if self.wide else self.dtype)
+        assert self.wide or self.model == self.dtype, "a model precision other than the arithmetic's needs dtype=np.longdouble"
         self.Nh = int(num_columns)
         self.thickness = np.ascontiguousarray(thickness, dtype=np.float64)
         self.Nz = int(self.thickness.size)
         self.params = params if params is not None else default_params()
-        prec = 0 if self.dtype == np.float64 else 1
-        self.h = self.lib.trm_oracle_create(prec, self.Nh, self.Nz, self.thickness.ctypes.data, float(dx),
-                                            C.byref(self.params))
+        if self.wide:
+            assert wide_available(), "np.longdouble is not a wider format than float64 on this platform"
+            self.h = self.lib.trm_oracle_create_wide(_MODEL_CODE[self.model], self.Nh, self.Nz, self.thickness.ctypes.data,
+                                                     float(dx), C.byref(self.params))
+        else:
+            prec = 0 if self.dtype == np.float64 else 1
+            self.h = self.lib.trm_oracle_create(prec, self.Nh, self.Nz, self.thickness.ctypes.data, float(dx),
+                                                C.byref(self.params))
+
+    def _input(self, value):
+        """`value` as the model precision holds it, in the arithmetic type"""
+        return np.asarray(value, dtype=self.model).astype(self.dtype) if self.wide else np.asarray(value, dtype=self.dtype)
 
     def __del__(self):
         try:
@@ -195,7 +232,7 @@ class Oracle:
     def set(self, name, value):
         rows = self.rows(name)
         a = np.empty((rows, self.Nh), dtype=self.dtype)
-        a[...] = np.asarray(value, dtype=self.dtype).reshape((-1, 1)) if np.ndim(value) == 1 and np.size(value) == rows and rows != self.Nh else value
+        a[...] = self._input(value).reshape((-1, 1)) if np.ndim(value) == 1 and np.size(value) == rows and rows != self.Nh else self._input(value)
         a = np.ascontiguousarray(a)
         rc = self.lib.trm_oracle_set_field(self.h, FIELDS[name], a.ctypes.data)
         assert rc == 0, name
@@ -215,7 +252,7 @@ class Oracle:
         if np.ndim(value) == 0:
             ptr, scalar_v = None, float(value)
         else:
-            arr = np.ascontiguousarray(value, dtype=self.dtype)
+            arr = np.ascontiguousarray(self._input(value))
             assert arr.shape == (self.Nh,)
             ptr, scalar_v = arr.ctypes.data, 0.0
         rc = self.lib.trm_oracle_set_bc(self.h, BC_VARS[var], top, BC_KINDS[kind], ptr, scalar_v)
@@ -224,7 +261,7 @@ class Oracle:
     # -- time series input sources (input_sources.jl:142-171) -----------------
     def _series(self, times, values):
         t = np.ascontiguousarray(times, dtype=np.float64)
-        v = np.ascontiguousarray(values, dtype=self.dtype)
+        v = np.ascontiguousarray(self._input(values))
         if v.ndim == 1:
             v = np.ascontiguousarray(np.broadcast_to(v[:, None], (v.size, self.Nh)))
         assert v.shape == (t.size, self.Nh)
@@ -286,7 +323,8 @@ class Oracle:
     def clone(self):
         """`deepcopy(state)` (heun.jl:24): an independent oracle with the same fields, clock, boundary values and parameters"""
         c = object.__new__(Oracle)
-        c.__dict__.update(lib=self.lib, dtype=self.dtype, Nh=self.Nh, thickness=self.thickness, Nz=self.Nz, params=self.params)
+        c.__dict__.update(lib=self.lib, dtype=self.dtype, Nh=self.Nh, thickness=self.thickness, Nz=self.Nz, params=self.params,
+                          wide=self.wide, model=self.model)
         c.h = self.lib.trm_oracle_clone(self.h)
         return c
 
@@ -412,7 +450,7 @@ class VegetationOracle:
         self.Nh = int(num_columns)
         self.veg_params = veg_params if veg_params is not None else default_vegetation_params()
         self.params = params if params is not None else default_params()
-        self.h = self.lib.trm_oracle_veg_create(0 if self.dtype == np.float64 else 1, self.Nh, C.byref(self.veg_params), C.byref(self.params))
+        self.h = self.lib.trm_oracle_veg_create({np.dtype(np.float64): 0, np.dtype(np.float32): 1}.get(self.dtype, 2), self.Nh, C.byref(self.veg_params), C.byref(self.params))
 
     def __del__(self):
         try:

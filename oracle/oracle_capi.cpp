@@ -9,21 +9,46 @@
 
 using namespace trm_oracle;
 
+// Precision codes of the handles: 0 = f64, 1 = f32, 2 = wide (long double arithmetic: the 80-bit x87 format on x86-64, 64
+// significand bits).  The wide instance exists to measure the other two against (tests/accuracy.py); it restates the SAME
+// model, so it is created with the model precision it stands for -- `model` 0 = the Float64 model, 1 = the Float32 model:
+// eps(NF) of safediv, the converted literals, parameters and grid coordinates are the model's (terrarium_oracle.hpp).
+// Arrays of a wide handle cross as long double.
+typedef long double wide_t;
+enum { PREC_F64 = 0, PREC_F32 = 1, PREC_WIDE = 2 };
+
 struct OracleHandle {
-    int precision;  // 0 = f64, 1 = f32
+    int precision;  // PREC_*
+    int model;      // wide only: 0 = Float64 model (w), 1 = Float32 model (wf)
     Oracle<double>* d;
     Oracle<float>* f;
+    Oracle<wide_t, double>* w;
+    Oracle<wide_t, float>* wf;
 };
 
-#define DISPATCH(h, expr)            \
-    do {                             \
-        if ((h)->precision == 0) {   \
-            auto* o = (h)->d;        \
-            expr;                    \
-        } else {                     \
-            auto* o = (h)->f;        \
-            expr;                    \
-        }                            \
+#define DISPATCH(h, expr)                     \
+    do {                                      \
+        if ((h)->precision == PREC_F64) {     \
+            auto* o = (h)->d;                 \
+            expr;                             \
+        } else if ((h)->precision == PREC_F32) { \
+            auto* o = (h)->f;                 \
+            expr;                             \
+        } else if ((h)->model == 0) {         \
+            auto* o = (h)->w;                 \
+            expr;                             \
+        } else {                              \
+            auto* o = (h)->wf;                \
+            expr;                             \
+        }                                     \
+    } while (0)
+// the same for calls that take arrays or scalars of the handle's own type: T is that type inside `expr`
+#define DISPATCH_T(h, expr)                                                      \
+    do {                                                                         \
+        if ((h)->precision == PREC_F64) { typedef double T; auto* o = (h)->d; expr; }       \
+        else if ((h)->precision == PREC_F32) { typedef float T; auto* o = (h)->f; expr; }   \
+        else if ((h)->model == 0) { typedef wide_t T; auto* o = (h)->w; expr; }             \
+        else { typedef wide_t T; auto* o = (h)->wf; expr; }                                 \
     } while (0)
 
 extern "C" {
@@ -39,16 +64,28 @@ int trm_oracle_set_threads(int n) {
 #endif
 }
 
-OracleHandle* trm_oracle_create(int precision, long nh, int nz, const double* thickness, double dx, const ParamsD* params) {
-    OracleHandle* h = new OracleHandle{precision, nullptr, nullptr};
-    if (precision == 0) h->d = new Oracle<double>(nh, nz, thickness, dx, *params);
-    else h->f = new Oracle<float>(nh, nz, thickness, dx, *params);
+static OracleHandle* create(int precision, int model, long nh, int nz, const double* thickness, double dx, const ParamsD* params) {
+    OracleHandle* h = new OracleHandle{precision, model != 0, nullptr, nullptr, nullptr, nullptr};
+    if (precision == PREC_F64) h->d = new Oracle<double>(nh, nz, thickness, dx, *params);
+    else if (precision == PREC_F32) h->f = new Oracle<float>(nh, nz, thickness, dx, *params);
+    else if (model == 0) h->w = new Oracle<wide_t, double>(nh, nz, thickness, dx, *params);
+    else h->wf = new Oracle<wide_t, float>(nh, nz, thickness, dx, *params);
     return h;
 }
+OracleHandle* trm_oracle_create(int precision, long nh, int nz, const double* thickness, double dx, const ParamsD* params) {
+    return create(precision, 0, nh, nz, thickness, dx, params);
+}
+// precision code 2 with the model precision it restates (0 = Float64, 1 = Float32)
+OracleHandle* trm_oracle_create_wide(int model, long nh, int nz, const double* thickness, double dx, const ParamsD* params) {
+    return create(PREC_WIDE, model, nh, nz, thickness, dx, params);
+}
+int trm_oracle_wide_digits(void) { return std::numeric_limits<wide_t>::digits; }
 void trm_oracle_destroy(OracleHandle* h) {
     if (!h) return;
     delete h->d;
     delete h->f;
+    delete h->w;
+    delete h->wf;
     delete h;
 }
 // LandModel(grid; soil, vegetation = VegetationCarbon): couple the vegetation and canopy processes (land_model.jl:24-34)
@@ -59,12 +96,14 @@ long trm_oracle_field_rows(OracleHandle* h, int id) {
     return r;
 }
 int trm_oracle_set_field(OracleHandle* h, int id, const void* src) {
-    if (h->precision == 0) return h->d->set_field(id, (const double*)src);
-    return h->f->set_field(id, (const float*)src);
+    int rc = 1;
+    DISPATCH_T(h, rc = o->set_field(id, (const T*)src));
+    return rc;
 }
 int trm_oracle_get_field(OracleHandle* h, int id, void* dst) {
-    if (h->precision == 0) return h->d->get_field(id, (double*)dst);
-    return h->f->get_field(id, (float*)dst);
+    int rc = 1;
+    DISPATCH_T(h, rc = o->get_field(id, (T*)dst));
+    return rc;
 }
 double trm_oracle_get_halo(OracleHandle* h, int id, int top, long i) {
     double r = 0;
@@ -72,12 +111,15 @@ double trm_oracle_get_halo(OracleHandle* h, int id, int top, long i) {
     return r;
 }
 int trm_oracle_set_bc(OracleHandle* h, int var, int top, int kind, const void* values, double scalar) {
-    if (h->precision == 0) return h->d->set_bc(var, top, kind, (const double*)values, scalar);
-    return h->f->set_bc(var, top, kind, (const float*)values, (float)scalar);
+    int rc = 1;
+    const bool f32_model = h->precision == PREC_F32 || (h->precision == PREC_WIDE && h->model != 0);
+    DISPATCH_T(h, rc = o->set_bc(var, top, kind, (const T*)values, f32_model ? (T)(float)scalar : (T)scalar));
+    return rc;
 }
 int trm_oracle_set_series(OracleHandle* h, int is_bc, int field, int var, int top, int kind, long nt, const double* times, const void* values, int indexing) {
-    if (h->precision == 0) return h->d->set_series(is_bc != 0, field, var, top, kind, nt, times, (const double*)values, indexing);
-    return h->f->set_series(is_bc != 0, field, var, top, kind, nt, times, (const float*)values, indexing);
+    int rc = 1;
+    DISPATCH_T(h, rc = o->set_series(is_bc != 0, field, var, top, kind, nt, times, (const T*)values, indexing));
+    return rc;
 }
 void trm_oracle_clear_series(OracleHandle* h) { DISPATCH(h, o->series.clear()); }
 void trm_oracle_update_inputs(OracleHandle* h) { DISPATCH(h, o->update_inputs()); }
@@ -99,8 +141,8 @@ void trm_oracle_reset_tendencies(OracleHandle* h) { DISPATCH(h, o->reset_tendenc
 void trm_oracle_compute_auxiliary(OracleHandle* h) { DISPATCH(h, o->compute_auxiliary()); }
 void trm_oracle_compute_tendencies(OracleHandle* h) { DISPATCH(h, o->compute_tendencies()); }
 void trm_oracle_explicit_step(OracleHandle* h, double dt) {
-    if (h->precision == 0) h->d->explicit_step(dt);
-    else h->f->explicit_step((float)dt);
+    const bool f32_model = h->precision == PREC_F32 || (h->precision == PREC_WIDE && h->model != 0);
+    DISPATCH_T(h, o->explicit_step(f32_model ? (T)(float)dt : (T)dt));
 }
 void trm_oracle_closure(OracleHandle* h) { DISPATCH(h, o->closure()); }
 void trm_oracle_invclosure(OracleHandle* h) { DISPATCH(h, o->invclosure()); }
@@ -111,15 +153,19 @@ void trm_oracle_timestep_heun(OracleHandle* h, double dt, int finalize) { DISPAT
 // Heun stepped BY HAND from the test harness (heun.jl:37-71), so that a test can evaluate a state-dependent forcing / boundary
 // value at the stage between the two halves: `stage = deepcopy(state)` (heun.jl:24, 45), tick!(clock), average_tendencies!
 OracleHandle* trm_oracle_clone(OracleHandle* h) {
-    OracleHandle* c = new OracleHandle{h->precision, nullptr, nullptr};
-    if (h->precision == 0) c->d = new Oracle<double>(*h->d);
-    else c->f = new Oracle<float>(*h->f);
+    OracleHandle* c = new OracleHandle{h->precision, h->model, nullptr, nullptr, nullptr, nullptr};
+    if (h->precision == PREC_F64) c->d = new Oracle<double>(*h->d);
+    else if (h->precision == PREC_F32) c->f = new Oracle<float>(*h->f);
+    else if (h->model == 0) c->w = new Oracle<wide_t, double>(*h->w);
+    else c->wf = new Oracle<wide_t, float>(*h->wf);
     return c;
 }
 void trm_oracle_tick(OracleHandle* h, double dt) { DISPATCH(h, o->tick(dt)); }
 void trm_oracle_average_tendencies(OracleHandle* h, OracleHandle* stage) {
-    if (h->precision == 0) h->d->average_tendencies(*stage->d);
-    else h->f->average_tendencies(*stage->f);
+    if (h->precision == PREC_F64) h->d->average_tendencies(*stage->d);
+    else if (h->precision == PREC_F32) h->f->average_tendencies(*stage->f);
+    else if (h->model == 0) h->w->average_tendencies(*stage->w);
+    else h->wf->average_tendencies(*stage->wf);
 }
 void trm_oracle_run(OracleHandle* h, double dt, long steps) { DISPATCH(h, o->run(dt, steps)); }
 // `steps` Euler steps without the trailing compute_auxiliary (timing leg)
@@ -171,6 +217,10 @@ double trm_oracle_longwave_up(const ParamsD* pd, double lw_down, double Ts, doub
 double trm_oracle_saturation_vapor_pressure(double T) { return saturation_vapor_pressure(T); }
 double trm_oracle_pow(double x, double y) { return jl_pow(x, y); }
 double trm_oracle_safediv(double x, double y) { return safediv(x, y); }
+// safediv in wide arithmetic with the model's eps (model 0 = Float64, 1 = Float32); arguments and result as long double
+void trm_oracle_safediv_wide(int model, const wide_t* x, const wide_t* y, wide_t* out) {
+    *out = model == 0 ? safediv<wide_t, double>(*x, *y) : safediv<wide_t, float>(*x, *y);
+}
 
 // Generic explicit integrators on the 0-D model du/dt = u + v used by the
 // reference's time-stepper test (test/timestepping/heun.jl:6-49): restates
@@ -207,24 +257,26 @@ void trm_oracle_update_skin_temperature(OracleHandle* h) { DISPATCH(h, o->update
 // ---- vegetation (oracle/vegetation_oracle.hpp) ---------------------------------------------------------------------
 struct VegHandle {
     int precision;
+    int model;      // (DISPATCH reads it; the vegetation oracle has one wide instance)
     VegetationOracle<double>* d;
     VegetationOracle<float>* f;
+    VegetationOracle<wide_t>* w;
+    VegetationOracle<wide_t>* wf;   // never set: the Float32-model slot of DISPATCH
 };
 VegHandle* trm_oracle_veg_create(int precision, long nh, const VegParamsD* vp, const ParamsD* cp) {
-    VegHandle* h = new VegHandle{precision, nullptr, nullptr};
-    if (precision == 0) h->d = new VegetationOracle<double>(nh, *vp, *cp);
-    else h->f = new VegetationOracle<float>(nh, *vp, *cp);
+    VegHandle* h = new VegHandle{precision, 0, nullptr, nullptr, nullptr, nullptr};
+    if (precision == PREC_F64) h->d = new VegetationOracle<double>(nh, *vp, *cp);
+    else if (precision == PREC_F32) h->f = new VegetationOracle<float>(nh, *vp, *cp);
+    else h->w = new VegetationOracle<wide_t>(nh, *vp, *cp);
     return h;
 }
-void trm_oracle_veg_destroy(VegHandle* h) { if (h) { delete h->d; delete h->f; delete h; } }
+void trm_oracle_veg_destroy(VegHandle* h) { if (h) { delete h->d; delete h->f; delete h->w; delete h; } }
 int trm_oracle_veg_set(VegHandle* h, int id, const void* src) {
-    if (h->precision == 0) { auto* v = h->d->field(id); if (!v) return 1; std::memcpy(v->data(), src, sizeof(double) * h->d->Nh); }
-    else { auto* v = h->f->field(id); if (!v) return 1; std::memcpy(v->data(), src, sizeof(float) * h->f->Nh); }
+    DISPATCH_T(h, { auto* v = o->field(id); if (!v) return 1; std::memcpy(v->data(), src, sizeof(T) * o->Nh); });
     return 0;
 }
 int trm_oracle_veg_get(VegHandle* h, int id, void* dst) {
-    if (h->precision == 0) { auto* v = h->d->field(id); if (!v) return 1; std::memcpy(dst, v->data(), sizeof(double) * h->d->Nh); }
-    else { auto* v = h->f->field(id); if (!v) return 1; std::memcpy(dst, v->data(), sizeof(float) * h->f->Nh); }
+    DISPATCH_T(h, { auto* v = o->field(id); if (!v) return 1; std::memcpy(dst, v->data(), sizeof(T) * o->Nh); });
     return 0;
 }
 void trm_oracle_veg_compute_auxiliary(VegHandle* h) { DISPATCH(h, o->compute_auxiliary()); }

@@ -17,6 +17,10 @@
 //   * FreezeCurves.jl 0.9: BrooksCorey / VanGenuchten SWRC and inverses
 //   * Julia Base: min/max, x^n (compensated power by squaring), false*x
 //
+// THREE INSTANCES: Oracle<double> and Oracle<float> are the Float64 and Float32 models in their own arithmetic (what the
+// device is compared with); Oracle<long double, double> and Oracle<long double, float> are the same two models evaluated
+// in long double -- the measure of how much either loses to rounding (tests/accuracy.py).  See model_literal below.
+//
 // Layout mirrors the reference Field storage: one plane per z level, x fastest,
 // one halo level below (k = 0) and above (k = Nz+1); k = 1 is the BOTTOM cell
 // and k = Nz the surface cell (src/grids/column_grid.jl:31).  The driver runs
@@ -24,6 +28,7 @@
 // (src/timesteppers/forward_euler.jl:19-31, src/state_variables.jl:72-80).
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <limits>
@@ -121,9 +126,17 @@ template <class NF> inline NF jl_pow(NF x, NF y) {
     return std::pow(x, y);
 }
 
-// src/utils/utils.jl:25
-template <class NF> inline NF safediv(NF x, NF y) {
-    return (y == NF(0)) ? std::numeric_limits<NF>::infinity() : x / (y + std::numeric_limits<NF>::epsilon());
+// ARITHMETIC TYPE AND MODEL PRECISION.  `NF` is the type every operation is carried out in; `MF` is the number format of
+// the model being restated (Float32 or Float64 in the reference) and defaults to `NF`.  Whatever the reference takes from
+// its number format rather than computes -- eps(NF) in safediv, the literals it converts to NF, the parameters, the grid
+// coordinates and the inputs -- is part of the model and keeps MF's value when NF is wider: Oracle<long double, float> is
+// the Float32 model evaluated without Float32's rounding, the yardstick of tests/accuracy.py.  With MF = NF every
+// expression below is the one it was before MF existed (NF(NF(x)) == NF(x)).
+template <class NF, class MF> inline NF model_literal(double x) { return NF(MF(x)); }
+
+// src/utils/utils.jl:25 (eps(NF) is the model's)
+template <class NF, class MF = NF> inline NF safediv(NF x, NF y) {
+    return (y == NF(0)) ? std::numeric_limits<NF>::infinity() : x / (y + NF(std::numeric_limits<MF>::epsilon()));
 }
 
 // ---------------------------------------------------------------------------
@@ -150,6 +163,13 @@ struct ParamsD {  // plain doubles + ints across the C API
     double albedo, emissivity, kappa_s, C_h, min_windspeed, tau_r, beta_evap, field_capacity;
     int32_t flow, swrc, unsat_k, seb, halo_policy, prescribed_albedo, evap_resistance, reserved;
 };
+
+// the parameters as the model's number format holds them (convert(MF, x)); the identity for MF = double
+template <class MF> inline ParamsD model_params(ParamsD d) {
+    double* q = &d.rho_w;
+    for (size_t n = 0; n < offsetof(ParamsD, flow) / sizeof(double); ++n) q[n] = (double)MF(q[n]);
+    return d;
+}
 
 template <class NF> struct Params {
     NF rho_w, rho_i, rho_a, c_a, Lsl, Llg, Lsg, g, Tref, sigma, kappa_vk, eps_mw, R_a;
@@ -230,9 +250,9 @@ template <class NF> inline NF heat_capacity(const Params<NF>& p, const Fractions
 }
 
 // soil_energy_closures.jl:131-141 liquid_water_fraction(::FreeWater, U, Lθ, sat)
-template <class NF> inline NF liquid_water_fraction(NF U, NF Ltheta) {
+template <class NF, class MF = NF> inline NF liquid_water_fraction(NF U, NF Ltheta) {
     if (U >= NF(0)) return NF(1);
-    return jl_boolmul(U >= -Ltheta, NF(1) - safediv(U, -Ltheta));
+    return jl_boolmul(U >= -Ltheta, NF(1) - safediv<NF, MF>(U, -Ltheta));
 }
 // soil_energy_closures.jl:147-159 energy_to_temperature(::FreeWater, U, Lθ, C)
 template <class NF> inline NF energy_to_temperature(NF U, NF Ltheta, NF C) {
@@ -308,15 +328,16 @@ template <class NF> inline NF hydraulic_conductivity_cell(const Params<NF>& p, N
 }
 
 // physics_utils.jl:54,67-73 saturation_vapor_pressure (August-Roche-Magnus)
-template <class NF> inline NF saturation_vapor_pressure(NF T) {
-    if (T <= NF(0)) return NF(611.0) * std::exp(NF(22.46) * T / (T + NF(272.62)));
-    return NF(611.0) * std::exp(NF(17.62) * T / (T + NF(243.12)));
+template <class NF, class MF = NF> inline NF saturation_vapor_pressure(NF T) {
+    auto c = [](double x) { return model_literal<NF, MF>(x); };
+    if (T <= NF(0)) return c(611.0) * std::exp(c(22.46) * T / (T + c(272.62)));
+    return c(611.0) * std::exp(c(17.62) * T / (T + c(243.12)));
 }
 // physical_constants.jl:83-97 compute_vpd
-template <class NF> inline NF compute_vpd(const Params<NF>& p, NF pres, NF q_air, NF T) {
-    NF e_sat = saturation_vapor_pressure(T);
+template <class NF, class MF = NF> inline NF compute_vpd(const Params<NF>& p, NF pres, NF q_air, NF T) {
+    NF e_sat = saturation_vapor_pressure<NF, MF>(T);
     NF e_air = q_air * pres / (p.eps_mw + (NF(1) - p.eps_mw) * q_air);
-    return jl_max(e_sat - e_air, NF(0.1));
+    return jl_max(e_sat - e_air, model_literal<NF, MF>(0.1));
 }
 // physical_constants.jl:68 stefan_boltzmann: ϵ * σ * T^4 (T^4 = pow_body(T, 4))
 template <class NF> inline NF stefan_boltzmann(const Params<NF>& p, NF T, NF emis) {
@@ -360,7 +381,8 @@ template <class NF> struct Grid {
 
     // `thickness` is get_spacing(vert) (vertical_discretization.jl:20): index 0
     // is the SURFACE layer.  dx <= 0 selects the ColumnGrid default x = (0, 1).
-    void build(long nh, int nz, const double* thickness, double dx_in) {
+    // MF: the number format the coordinates are converted to (column_grid.jl:31 `convert.(NF, ...)`), NF by default
+    template <class MF = NF> void build(long nh, int nz, const double* thickness, double dx_in) {
         Nh = nh;
         Nz = nz;
         // z_coords = convert.(NF, vcat(-reverse(cumsum(z_thick)), 0))   (column_grid.jl:31)
@@ -369,7 +391,7 @@ template <class NF> struct Grid {
         cs[0] = s;
         for (int i = 1; i < nz; ++i) { s = s + thickness[i]; cs[i] = s; }
         zF.assign(nz + 3, NF(0));
-        for (int k = 1; k <= nz; ++k) zF[k] = NF(-cs[nz - k]);
+        for (int k = 1; k <= nz; ++k) zF[k] = NF(MF(-cs[nz - k]));
         zF[nz + 1] = NF(0);
         // Bounded halo faces continue with the boundary cell's spacing
         NF dlo = zF[2] - zF[1], dhi = zF[nz + 1] - zF[nz];
@@ -385,7 +407,7 @@ template <class NF> struct Grid {
         rdzf.assign(nz + 2, NF(0));
         for (int k = 0; k <= nz + 1; ++k) rdzc[k] = NF(1) / dzc[k];
         for (int k = 1; k <= nz + 1; ++k) rdzf[k] = NF(1) / dzf[k];
-        dx = dx_in > 0 ? NF(dx_in) : NF(1.0 / (double)nh);
+        dx = dx_in > 0 ? NF(MF(dx_in)) : NF(MF(1.0 / (double)nh));
     }
 };
 
@@ -420,8 +442,9 @@ template <class NF> struct Bc {
 #include "vegetation_oracle.hpp"   // the 0-D vegetation / canopy processes the coupled LandModel below steps
 namespace trm_oracle {
 
-template <class NF> class Oracle {
+template <class NF, class MF = NF> class Oracle {
   public:
+    static NF lit(double x) { return model_literal<NF, MF>(x); }   // a literal the reference converts to its number format
     Grid<NF> g;
     ParamsD pd;
     Params<NF> p;
@@ -457,8 +480,8 @@ template <class NF> class Oracle {
     FieldVec<NF> w_can, G_w_can, I_can, R_can, f_can, rain_ground, E_can, transp, SAI, paw;
     std::vector<NF> root_frac;
 
-    Oracle(long nh, int nz, const double* thickness, double dx, const ParamsD& pd_in) : pd(pd_in), p(pd_in), Nh(nh), Nz(nz) {
-        g.build(nh, nz, thickness, dx);
+    Oracle(long nh, int nz, const double* thickness, double dx, const ParamsD& pd_in) : pd(pd_in), p(model_params<MF>(pd_in)), Nh(nh), Nz(nz) {
+        g.template build<MF>(nh, nz, thickness, dx);
         size_t n3 = (size_t)(nz + 2) * nh, nf = (size_t)(nz + 3) * nh, n2 = (size_t)nh;
         (void)n3; (void)nf; (void)n2;
         for (auto* v : {&U, &sat, &T, &liq, &psi, &G_U, &G_sat, &Fvwc}) first_touch(*v, nz + 2, NF(0));
@@ -467,8 +490,8 @@ template <class NF> class Oracle {
         // input defaults (prescribed_atmosphere.jl:90-92,148,221-223)
         first_touch(Tair, 1, NF(10));
         first_touch(pres, 1, NF(101325));
-        first_touch(wind, 1, NF(0.1));
-        first_touch(qair, 1, NF(1.0e-3));
+        first_touch(wind, 1, lit(0.1));
+        first_touch(qair, 1, lit(1.0e-3));
         first_touch(rain, 1, NF(0));
         first_touch(swd, 1, NF(300));
         first_touch(lwd, 1, NF(50));
@@ -683,6 +706,8 @@ template <class NF> class Oracle {
         series.push_back(std::move(sr));
         return 0;
     }
+    // (the interpolation weights are Float64 in the reference; the products below are formed in double for every NF, so a
+    // wide instance gains nothing on a time series -- the accuracy suite uses constant inputs)
     void update_inputs() {
         for (const Series& sr : series) {
             double f; long n1, n2;
@@ -785,11 +810,11 @@ template <class NF> class Oracle {
     // ---- surface processes (Appendix A-9) -----------------------------------
     inline NF aerodynamic_resistance(long i) const {  // prescribed_atmosphere.jl:110-116,137
         NF V = jl_max(wind[i], p.min_windspeed);
-        NF Va = jl_max(V, NF(1.0e-6));
+        NF Va = jl_max(V, lit(1.0e-6));
         return NF(1) / (p.C_h * Va);
     }
     inline NF humidity_vpd(long i, NF Tsurf) const {  // prescribed_atmosphere.jl:163-182, physics_utils.jl:38
-        NF de = compute_vpd(p, pres[i], qair[i], Tsurf);
+        NF de = compute_vpd<NF, MF>(p, pres[i], qair[i], Tsurf);
         return p.eps_mw * de / pres[i];
     }
     // ground_evaporation_resistance_factor (ground_resistance_factor.jl:12,36-56)
@@ -800,7 +825,7 @@ template <class NF> class Oracle {
             Fractions<NF> fr = volumetric_fractions(por, sat[C(Nz, i)], liq[C(Nz, i)], organic_fraction(p));
             NF fc = p.field_capacity;
             if (fr.water < fc) {
-                NF t = NF(1) - std::cos(NF(3.141592653589793) * fr.water / fc);
+                NF t = NF(1) - std::cos(lit(3.141592653589793) * fr.water / fc);
                 beta = (t * t) / NF(4);
             } else {
                 beta = NF(1);
@@ -1109,7 +1134,7 @@ template <class NF> class Oracle {
             for (long i = i0_; i < i1_; ++i) {
                 NF u = U[C(k, i)], s = sat[C(k, i)];
                 NF Ltheta = L * s * por;
-                NF l = liquid_water_fraction(u, Ltheta);
+                NF l = liquid_water_fraction<NF, MF>(u, Ltheta);
                 liq[C(k, i)] = l;
                 NF Cv = heat_capacity(p, volumetric_fractions(por, s, l, org, &status));
                 T[C(k, i)] = energy_to_temperature(u, Ltheta, Cv);
