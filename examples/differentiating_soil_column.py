@@ -37,8 +37,10 @@ def jacobian(steps=N_T):
     return tangents["temperature"], tangents["internal_energy"], grid.z_centers()
 
 
-def gradient(steps=N_T):
-    """dT_f[second-lowest layer] / dU_0 after `steps` steps, [Nz]: the reference's Enzyme.autodiff(Reverse, ...) call."""
+def gradient(steps=N_T, checkpoint_every=None):
+    """dT_f[second-lowest layer] / dU_0 after `steps` steps, [Nz]: the reference's Enzyme.autodiff(Reverse, ...) call.
+    `checkpoint_every` = K: the tape keeps every K-th state and the sweep forms the rest again (the reference's Checkpointing.jl
+    scheme passed to run!) -- the same gradient bit for bit."""
     spacing = trm.ExponentialSpacing()
     Nz = len(spacing.get_spacing())
     grid = trm.ColumnGrid(spacing, num_columns=1)
@@ -47,7 +49,7 @@ def gradient(steps=N_T):
     integrator = trm.initialize(model, trm.ForwardEuler(), boundary_conditions=bcs)
     seed = np.zeros((Nz, 1))
     seed[1] = 1.0                                                  # the final temperature of the second-lowest layer
-    return trm.vjp(integrator, steps, temperature=seed)[:, 0]
+    return trm.vjp(integrator, steps, temperature=seed, checkpoint_every=checkpoint_every)[:, 0]
 
 
 def main():

@@ -646,7 +646,25 @@ int trm_step_tangent(trm_ctx* ctx, double dt, int nsteps);
  * trm_step_record has changed the state since the first taped step (the calls listed for the tangent, and trm_step_tangent), or
  * trm_set_bc / trm_set_bc_series a boundary condition: the sweep reads the boundary values the context holds when it runs, which must be
  * the ones the record ran with.  Nothing is stepped or pulled back then.  trm_adjoint_open, or a trm_adjoint_backward that succeeded,
- * starts a fresh tape.  trm_step_record is a state-changing call for an open tangent.  A tangent and an adjoint may be open at once. */
+ * starts a fresh tape.  trm_step_record is a state-changing call for an open tangent.  A tangent and an adjoint may be open at once.
+ *
+ * The checkpointed tape keeps the internal energy before every `interval`-th step alone; trm_adjoint_backward forms the states in
+ * between again, inside its launches, by re-running the recorded steps bit for bit.  The gradient is the per-step tape's bit for bit;
+ * the tape is `interval` times smaller, and the sweep runs interval - 1 of every interval steps a second time.
+ *   trm_adjoint_open_checkpointed(ctx, capacity_slots, interval)
+ *                                           allocates the cotangent fields as trm_adjoint_open does and capacity_slots checkpoint
+ *                                           slots of Nh x Nzp x 8 bytes.  interval is 1 ... TRM_ADJOINT_MAX_INTERVAL;
+ *                                           TRM_ADJOINT_DEFAULT_INTERVAL is the largest that costs the sweep no occupancy.  Opening
+ *                                           in either mode replaces an open adjoint of the other mode.
+ *   trm_adjoint_checkpoints(ctx, &interval, &slots_used, &slots_capacity)
+ *                                           interval is 0 for a per-step tape, whose slots are steps
+ * Every other call above works on either tape.  Segments: the taped steps are split into segments of up to `interval` steps under
+ * one dt, each with its first state in one slot.  A trm_step_record call opens a new segment -- and takes a slot -- when the tape
+ * is empty, when the open segment holds `interval` steps, or when its dt differs from the call's.  The call works out the slots it
+ * needs before it launches anything: TRM_EINVAL with nothing stepped if they do not fit.  Its launches are still those of trm_step, so
+ * one may straddle segment boundaries.  trm_adjoint_backward issues one launch per segment, newest first.  trm_adjoint_tape reports
+ * the steps taped and capacity_slots x interval.  TRM_INFO_LAST_PROGRAM carries bit 27 for the launches of a checkpointed tape.
+ * Errors as above; TRM_EINVAL for capacity_slots < 1 or an interval out of range. */
 enum { TRM_ADJOINT_INTERNAL_ENERGY = 0, TRM_ADJOINT_TEMPERATURE = 1, TRM_ADJOINT_LIQUID_WATER_FRACTION = 2 };
 int trm_adjoint_open(trm_ctx* ctx, int capacity_steps);
 int trm_adjoint_close(trm_ctx* ctx);
@@ -654,6 +672,10 @@ int trm_adjoint_upload(trm_ctx* ctx, int which, const void* host);
 int trm_adjoint_download(trm_ctx* ctx, int which, void* host);
 int trm_adjoint_device_ptr(trm_ctx* ctx, int which, void** dev, int64_t* pitch_elems);
 int trm_adjoint_tape(const trm_ctx* ctx, int* recorded, int* capacity);
+#define TRM_ADJOINT_MAX_INTERVAL 32      /* 64 KiB of LDS per workgroup in the backward launch: 2 KiB per step of a segment */
+#define TRM_ADJOINT_DEFAULT_INTERVAL 16
+int trm_adjoint_open_checkpointed(trm_ctx* ctx, int capacity_slots, int interval);
+int trm_adjoint_checkpoints(const trm_ctx* ctx, int* interval, int* slots_used, int* slots_capacity);
 int trm_step_record(trm_ctx* ctx, double dt, int nsteps);
 int trm_adjoint_backward(trm_ctx* ctx);
 

@@ -380,7 +380,7 @@ bool averageable(const trm_ctx* c, int field) {
 // The state has changed behind the derivatives' backs: an open tangent needs a new seed, a tape that holds steps no longer leads to the
 // stored state.  bc_changed: a boundary condition has (the backward sweep reads the values the context holds when it runs).
 void bc_changed(trm_ctx* c) {
-    if (!c->tape_dt.empty()) c->adj_stale = true;
+    if (!c->tape_dt.empty() || !c->tape_segs.empty()) c->adj_stale = true;
 }
 void state_changed(trm_ctx* c) {
     c->tan_stale = true;
@@ -2491,53 +2491,80 @@ int adjoint_args_ok(trm_ctx* c, int which, const void* ptr, const char* who) {
     return TRM_OK;
 }
 const char* kStaleTape = ": the state or a boundary condition has changed since the first taped step: trm_adjoint_open starts a new tape";
+void free_tape(trm_ctx* c) {
+    if (c->d_tape) (void)hipFree(c->d_tape);
+    c->d_tape = nullptr;
+    c->tape_cap = 0;
+    c->ckpt_interval = 0;
+    c->tape_dt.clear();
+    c->tape_segs.clear();
+    c->adj_stale = false;
+}
 void free_adjoint(trm_ctx* c) {
     for (double*& q : c->d_adj) {
         if (q) (void)hipFree(q);
         q = nullptr;
     }
-    if (c->d_tape) (void)hipFree(c->d_tape);
-    c->d_tape = nullptr;
-    c->tape_cap = 0;
-    c->tape_dt.clear();
-    c->adj_stale = false;
+    free_tape(c);
 }
-}  // namespace
-
-int trm_adjoint_open(trm_ctx* c, int capacity_steps) {
-    TRM_ENTER_HEUN(c);
-    if (capacity_steps < 1) return fail(c, TRM_EINVAL, "trm_adjoint_open: capacity_steps < 1");
-    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_open: ") + why);
+// steps on the tape, per-step or checkpointed
+int taped_steps(const trm_ctx* c) {
+    if (c->ckpt_interval == 0) return (int)c->tape_dt.size();
+    return c->tape_segs.empty() ? 0 : c->tape_segs.back().first + c->tape_segs.back().len;
+}
+// trm_adjoint_open (`interval` 0: `capacity` slots, one per step) and trm_adjoint_open_checkpointed (`capacity` checkpoint slots)
+int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who) {
+    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, who + ": " + why);
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double);
-    if (capacity_steps != c->tape_cap) {
-        if (c->d_tape) (void)hipFree(c->d_tape);
-        c->d_tape = nullptr;
-        c->tape_cap = 0;
-        c->tape_dt.clear();
-        c->adj_stale = false;
-        if (hipMalloc((void**)&c->d_tape, (size_t)capacity_steps * bytes) != hipSuccess) {
+    if (capacity != c->tape_cap || interval != c->ckpt_interval) {
+        free_tape(c);
+        if (hipMalloc((void**)&c->d_tape, (size_t)capacity * bytes) != hipSuccess) {
             (void)hipGetLastError();
             c->d_tape = nullptr;
             const bool was_open = c->d_adj[0] != nullptr;
             free_adjoint(c);
-            return fail(c, TRM_ENOMEM, "trm_adjoint_open: a tape of " + std::to_string(capacity_steps) + " steps x " + std::to_string(bytes) +
+            return fail(c, TRM_ENOMEM, who + ": a tape of " + std::to_string(capacity) + (interval ? " checkpoints x " : " steps x ") + std::to_string(bytes) +
                                            " bytes does not fit" + (was_open ? " (the adjoint that was open is closed)" : ""));
         }
-        c->tape_cap = capacity_steps;
+        c->tape_cap = capacity;
+        c->ckpt_interval = interval;
     }
     for (double*& q : c->d_adj) {
         if (!q && hipMalloc((void**)&q, bytes) != hipSuccess) {
             (void)hipGetLastError();
             q = nullptr;
             free_adjoint(c);
-            return fail(c, TRM_ENOMEM, "trm_adjoint_open: the cotangent fields do not fit");
+            return fail(c, TRM_ENOMEM, who + ": the cotangent fields do not fit");
         }
         TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
     }
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     c->tape_dt.clear();        // (a fresh tape)
+    c->tape_segs.clear();
     c->adj_stale = false;
+    return TRM_OK;
+}
+}  // namespace
+
+int trm_adjoint_open(trm_ctx* c, int capacity_steps) {
+    TRM_ENTER_HEUN(c);
+    if (capacity_steps < 1) return fail(c, TRM_EINVAL, "trm_adjoint_open: capacity_steps < 1");
+    return open_adjoint(c, capacity_steps, 0, "trm_adjoint_open");
+}
+int trm_adjoint_open_checkpointed(trm_ctx* c, int capacity_slots, int interval) {
+    TRM_ENTER_HEUN(c);
+    if (capacity_slots < 1) return fail(c, TRM_EINVAL, "trm_adjoint_open_checkpointed: capacity_slots < 1");
+    if (interval < 1 || interval > TRM_ADJOINT_MAX_INTERVAL)
+        return fail(c, TRM_EINVAL, "trm_adjoint_open_checkpointed: the interval is 1 ... " + std::to_string(TRM_ADJOINT_MAX_INTERVAL));
+    return open_adjoint(c, capacity_slots, interval, "trm_adjoint_open_checkpointed");
+}
+int trm_adjoint_checkpoints(const trm_ctx* c, int* interval, int* slots_used, int* slots_capacity) {
+    if (!c) return TRM_EINVAL;
+    if (!c->d_adj[0]) return fail(const_cast<trm_ctx*>(c), TRM_EINVAL, "trm_adjoint_checkpoints: no adjoint is open (trm_adjoint_open)");
+    if (interval) *interval = c->ckpt_interval;
+    if (slots_used) *slots_used = c->ckpt_interval ? (int)c->tape_segs.size() : (int)c->tape_dt.size();
+    if (slots_capacity) *slots_capacity = c->tape_cap;
     return TRM_OK;
 }
 int trm_adjoint_close(trm_ctx* c) {
@@ -2584,18 +2611,34 @@ int trm_adjoint_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_ele
 int trm_adjoint_tape(const trm_ctx* c, int* recorded, int* capacity) {
     if (!c) return TRM_EINVAL;
     if (!c->d_adj[0]) return fail(const_cast<trm_ctx*>(c), TRM_EINVAL, "trm_adjoint_tape: no adjoint is open (trm_adjoint_open)");
-    if (recorded) *recorded = (int)c->tape_dt.size();
-    if (capacity) *capacity = c->tape_cap;
+    if (recorded) *recorded = taped_steps(c);
+    if (capacity) *capacity = (int)std::min<long long>((long long)c->tape_cap * std::max(c->ckpt_interval, 1), std::numeric_limits<int>::max());
     return TRM_OK;
 }
+namespace {
+// the steps the open segment of a checkpointed tape still takes under `dt` (0: the next step opens a segment)
+int open_segment_room(const trm_ctx* c, double dt) {
+    if (c->tape_segs.empty() || c->tape_segs.back().dt != dt) return 0;
+    return c->ckpt_interval - c->tape_segs.back().len;
+}
+}  // namespace
 int trm_step_record(trm_ctx* c, double dt, int nsteps) {
     TRM_ENTER(c);
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_step_record: no adjoint is open (trm_adjoint_open)");
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_record: nsteps < 0");
-    const int recorded = (int)c->tape_dt.size();
-    if (nsteps > c->tape_cap - recorded)
-        return fail(c, TRM_EINVAL, "trm_step_record: " + std::to_string(nsteps) + " steps do not fit the tape (" + std::to_string(recorded) + " of " +
-                                       std::to_string(c->tape_cap) + " slots taken)");
+    const int K = c->ckpt_interval;
+    if (K == 0) {
+        const int recorded = (int)c->tape_dt.size();
+        if (nsteps > c->tape_cap - recorded)
+            return fail(c, TRM_EINVAL, "trm_step_record: " + std::to_string(nsteps) + " steps do not fit the tape (" + std::to_string(recorded) + " of " +
+                                           std::to_string(c->tape_cap) + " slots taken)");
+    } else {   // the checkpoints this call takes: the steps the open segment has no room for, K to a slot
+        const long long room = open_segment_room(c, dt), used = (long long)c->tape_segs.size();
+        const long long need = nsteps > room ? (nsteps - room + K - 1) / K : 0;
+        if (need > c->tape_cap - used)
+            return fail(c, TRM_EINVAL, "trm_step_record: " + std::to_string(nsteps) + " steps need " + std::to_string(need) + " checkpoints (" +
+                                           std::to_string(used) + " of " + std::to_string(c->tape_cap) + " slots taken)");
+    }
     if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + why);
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_step_record") + kStaleTape);
     if (nsteps > 0) c->tan_stale = true;       // (a state-changing call for an open tangent)
@@ -2605,12 +2648,28 @@ int trm_step_record(trm_ctx* c, double dt, int nsteps) {
     while (n < nsteps) {
         const int m = std::min(spl, nsteps - n);
         int rc = Ops<double>::update_inputs(c, c->state, c->time);
-        if (!rc) rc = AdjointLaunch::record(c, dt, m, (int)c->tape_dt.size());
+        // (checkpointed: the launch stores before its steps room, room + K, ... -- the starts of the segments it opens)
+        const int room = K ? open_segment_room(c, dt) : 0;
+        if (!rc) rc = K ? CheckpointLaunch::record(c, dt, m, (int)c->tape_segs.size(), room, K) : AdjointLaunch::record(c, dt, m, (int)c->tape_dt.size());
         if (rc) {
-            c->adj_stale = !c->tape_dt.empty();
+            c->adj_stale = taped_steps(c) > 0;
             return rc;
         }
-        c->tape_dt.insert(c->tape_dt.end(), (size_t)m, dt);
+        if (K) {
+            int left = m, at = taped_steps(c);
+            if (room > 0 && left > 0) {
+                const int take = std::min(room, left);
+                c->tape_segs.back().len += take;
+                left -= take;
+                at += take;
+            }
+            while (left > 0) {
+                const int take = std::min(K, left);
+                c->tape_segs.push_back({at, take, dt, (int)c->tape_segs.size()});
+                left -= take;
+                at += take;
+            }
+        } else c->tape_dt.insert(c->tape_dt.end(), (size_t)m, dt);
         tick(c, dt, m);
         n += m;
     }
@@ -2624,6 +2683,22 @@ int trm_adjoint_backward(trm_ctx* c) {
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_backward: no adjoint is open (trm_adjoint_open)");
     if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + why);
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_adjoint_backward") + kStaleTape);
+    if (c->ckpt_interval) {   // one launch per segment, newest first; the first launch folds (an empty tape: that launch alone, no step)
+        int fold = 1;
+        size_t s = c->tape_segs.size();
+        do {
+            const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
+            if (int rc = CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold)) {
+                c->adj_stale = true;       // (lam is part way down the tape)
+                return rc;
+            }
+            fold = 0;
+            if (s > 0) --s;
+        } while (s > 0);
+        c->tape_segs.clear();
+        c->adj_stale = false;
+        return finish(c, TRM_OK);
+    }
     // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch folds
     // the cotangents of T and liq in (an empty tape: that launch alone)
     const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);

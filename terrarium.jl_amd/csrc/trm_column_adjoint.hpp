@@ -56,9 +56,32 @@ template <int LPC> TRM_DEV LaneInfo adjoint_lane(const View<double>& v, int& ii,
     return ln;
 }
 
-// `a.nsteps` ForwardEuler steps of the state, U_k stored into tape slot k before step k; the outputs are those of a finalizing trm_step
-template <int HYD, int LPC>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, AdjointArgs aa) {
+// compute_z_bcs! terms as each program forms them (k_step_wave: flux_term_*; the column program: flux_term_*_nsz, selects)
+TRM_DEV void record_flux_U(const View<double>& v, const LaneInfo& ln, int ii, bool generic, ColumnBC<double>& bc) {
+    using NF = double;
+    const bool bU = v.bc.kind[0][0] == 2, tU = v.bc.kind[0][1] == 2;
+    if (generic) {
+        NF fU = 0.0;
+        if (ln.is_bot && bU) fU = flux_term_bottom(bcval(v, 0, 0)[ii], v.g);
+        if (ln.is_top && tU) fU = -flux_term_top(bcval(v, 0, 1)[ii], v.g);
+        bc.flux_U = fU;
+    } else {
+        NF eU_b = 0.0, eU_t = 0.0;
+        if (bU) eU_b = flux_term_bottom_nsz(bcval(v, 0, 0)[ii], v.g);
+        if (tU) eU_t = -flux_term_top_nsz(bcval(v, 0, 1)[ii], v.g);
+        const NF tU_term = ln.is_top ? eU_t : NF(0);
+        bc.flux_U = ln.is_bot ? eU_b : tU_term;
+    }
+}
+
+// `a.nsteps` ForwardEuler steps of the state, U_k stored into tape slot k before step k; the outputs are those of a finalizing trm_step.
+// STRIDED (Args = CheckpointArgs, trm_column_adjoint_ckpt.hpp: the record of a checkpointed tape): U_k is stored before the steps
+// aa.first, aa.first + aa.every, ... of the launch alone, into the slots from aa.tape on -- a wave-uniform branch, everything else the
+// same.  (One kernel template and not a device function under two kernels: behind a call the existing instances came out of the
+// register allocator with other registers and three more instructions; as a defaulted template parameter they compile to the code
+// they had.)
+template <int HYD, int LPC, bool STRIDED = false, class Args = AdjointArgs>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args aa) {
     using NF = double;
     int ii;
     size_t e;
@@ -83,30 +106,26 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v
     bc.flux_S = 0.0;
     bc.has_U = true;
     bc.has_S = false;
-    {   // compute_z_bcs! terms as each program forms them (k_step_wave: flux_term_*; the column program: flux_term_*_nsz, selects)
-        const bool bU = v.bc.kind[0][0] == 2, tU = v.bc.kind[0][1] == 2;
-        if (generic) {
-            NF fU = 0.0;
-            if (ln.is_bot && bU) fU = flux_term_bottom(bcval(v, 0, 0)[ii], v.g);
-            if (ln.is_top && tU) fU = -flux_term_top(bcval(v, 0, 1)[ii], v.g);
-            bc.flux_U = fU;
-        } else {
-            NF eU_b = 0.0, eU_t = 0.0;
-            if (bU) eU_b = flux_term_bottom_nsz(bcval(v, 0, 0)[ii], v.g);
-            if (tU) eU_t = -flux_term_top_nsz(bcval(v, 0, 1)[ii], v.g);
-            const NF tU_term = ln.is_top ? eU_t : NF(0);
-            bc.flux_U = ln.is_bot ? eU_b : tU_term;
-        }
-    }
+    record_flux_U(v, ln, ii, generic, bc);
 
     Cell<NF> n = c;
     Frac<NF> f_new{};
     NF gU_out = 0.0;
     NF* slot = aa.tape + e;
+    int next = 0;
+    if constexpr (STRIDED) next = aa.first;
     for (int step = 0; step < a.nsteps; ++step) {
         if (step > 0) c = n;
-        if (ln.act) *slot = c.U;
-        slot += aa.slot_elems;
+        if constexpr (STRIDED) {
+            if (step == next) {
+                if (ln.act) *slot = c.U;
+                slot += aa.slot_elems;
+                next += aa.every;
+            }
+        } else {
+            if (ln.act) *slot = c.U;
+            slot += aa.slot_elems;
+        }
         const Frac<NF>* pre = step > 0 ? &f_new : nullptr;
         const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
                                        : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
@@ -188,6 +207,24 @@ TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, c
     return lam + via_T + via_liq;
 }
 
+// the end of the run: the cotangents of T_n and liq_n through the closure of the stored U_n, lam_n = wU + a_n wT + b_n wliq; wT = wliq = 0 after
+TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, const LaneInfo& ln, size_t e, double sat, double& lam, double* lT,
+                          double* lliq) {
+    using NF = double;
+    const NF U = v.U[e], wT = lT[e], wliq = lliq[e];
+    uint32_t viol_in = 0;
+    NF liq, T, via_T, via_liq, unused_liq, unused_T;
+    const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
+    const NF C = heat_capacity(p, f);
+    closure_tangent(p, U, sat, C, wT, unused_liq, via_T);
+    closure_tangent(p, U, sat, C, wliq, via_liq, unused_T);
+    lam = lam + via_T + via_liq;
+    if (ln.act) {
+        lT[e] = 0.0;
+        lliq[e] = 0.0;
+    }
+}
+
 // The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt
 template <int HYD, int LPC>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, AdjointArgs aa) {
@@ -205,20 +242,7 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> 
     // the temperature boundary values: of a Value condition, and of a Gradient condition where the generic halo form reads them
     const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
     const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
-    if (aa.fold) {   // the end of the run: the cotangents of T_n and liq_n through the closure of the stored U_n
-        const NF U = v.U[e], wT = aa.lT[e], wliq = aa.lliq[e];
-        uint32_t viol_in = 0;
-        NF liq, T, via_T, via_liq, unused_liq, unused_T;
-        const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
-        const NF C = heat_capacity(p, f);
-        closure_tangent(p, U, sat, C, wT, unused_liq, via_T);
-        closure_tangent(p, U, sat, C, wliq, via_liq, unused_T);
-        lam = lam + via_T + via_liq;
-        if (ln.act) {
-            aa.lT[e] = 0.0;
-            aa.lliq[e] = 0.0;
-        }
-    }
+    if (aa.fold) adjoint_fold(v, p, ln, e, sat, lam, aa.lT, aa.lliq);
     // Everything loaded so far is used here, in front of the loop: inside it the next slot's load is the only one in flight, and the wait
     // for it sits where its value is taken, behind the arithmetic of the step
     asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt));

@@ -1,0 +1,89 @@
+// trm_column_adjoint_ckpt.hpp -- the checkpointed tape of the reverse-mode gradients (trm_adjoint_open_checkpointed).
+//
+// The per-step tape of trm_column_adjoint.hpp keeps U_k of every step.  Here the record keeps U_c of every K-th step alone (a segment
+// start), and the backward launch of a segment of m <= K steps forms the m - 1 states behind its checkpoint again before it walks
+// them backwards: the primal step is re-run bit for bit (the library is built -ffp-contract=off, and the step is the sequence of
+// column_tendencies / column_advance / column_closure the record ran), so the U_k adjoint_step sees are the recorded ones and the
+// gradient is the per-step tape's bit for bit.
+// The recomputed states live in dynamic LDS, seg[j * TRM_STEP_BLOCK + threadIdx.x]: 2 KiB per step and workgroup in both layouts.  A
+// thread reads back only what it wrote: no barrier.  Lanes are 8 bytes apart: a ds_write_b64 group of 16 lanes covers 32 banks once, a
+// ds_read_b64 group of 32 lanes 64 banks once -- conflict-free.
+// Restart: (T_c, liq_c, Frac) of a checkpoint are the closure of (U_c, sat), column_closure<double, false, HYD>, which is what the
+// record chain entered step c with for every c > 0 (the closure the step before ended with, or its stored result), and for the first
+// state of a tape under the contract of trm_step_record: the stored T and liq are the closure of the stored U.
+#pragma once
+// (as trm_column_adjoint.hpp: this translation unit's copy of the non-template kernel of trm_column_tangent.hpp gets a name of its own)
+#define k_closure_tangent k_closure_tangent_in_adjoint_ckpt_unit
+#include "trm_column_tangent.hpp"
+#undef k_closure_tangent
+#include "trm_column_adjoint.hpp"
+
+namespace trm {
+
+// Fourth kernel argument of k_column_record<HYD, LPC, true, CheckpointArgs> (the strided record) / k_column_adjoint_ckpt
+struct CheckpointArgs {
+    double *lU, *lT, *lliq;   // the cotangent fields; lU carries lam between launches
+    double* tape;             // record: the slot of the launch's first store; backward: the segment's checkpoint slot
+    long long slot_elems;     // Nh * Nzp
+    int generic;              // as AdjointArgs
+    int fold;                 // backward: 1 in the first launch of a sweep
+    int first, every;         // record: the step of the launch that stores first (>= nsteps: none does), and the interval K
+};
+
+// lam pulled back through one segment: the checkpoint U_c at ca.tape and the a.nsteps - 1 states behind it under a.dt.
+// Dynamic LDS: a.nsteps * TRM_STEP_BLOCK doubles.
+template <int HYD, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<double> v, DevParams<double> p, ColumnArgs<double> a, CheckpointArgs ca) {
+    using NF = double;
+    extern __shared__ double seg[];
+    int ii;
+    size_t e;
+    const LaneInfo ln = adjoint_lane<LPC>(v, ii, e);
+    const bool generic = ca.generic != 0;
+    const int Nz = v.Nz, m = a.nsteps;
+    const NF sat = v.sat[e];
+    NF lam = ca.lU[e];
+    Cell<NF> c;
+    c.U = m > 0 ? ca.tape[e] : 0.0;
+    c.sat = sat;
+    c.T = 0.0;
+    c.liq = 0.0;
+    c.psi = 0.0;
+    const LevelGeom<NF> L = level_geom(v, ln.k);
+    // the temperature boundary values as k_column_adjoint loads them (the non-generic primal reads those of a Value condition alone)
+    const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
+    const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
+    if (ca.fold) adjoint_fold(v, p, ln, e, sat, lam, ca.lT, ca.lliq);
+
+    // ---- recompute: U_c ... U_{c+m-1} into LDS; nothing is stored to memory and no flag is raised (the record run has raised them)
+    NF* mine = seg + threadIdx.x;
+    if (m > 1) {
+        ColumnBC<NF> bc;
+        bc.bTb = bTb;
+        bc.bTt = bTt;
+        bc.flux_S = 0.0;
+        bc.has_U = true;
+        bc.has_S = false;
+        record_flux_U(v, ln, ii, generic, bc);
+        uint32_t viol = 0;
+        bool bad = false;
+        Frac<NF> f = column_closure<NF, false, HYD>(p, L, 0.0, c, viol);
+        for (int j = 0; j < m - 1; ++j) {
+            mine[j * TRM_STEP_BLOCK] = c.U;
+            const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
+                                           : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, &f);
+            NF gU = t.gU, gS = t.gS, z0;
+            Cell<NF> n = c;
+            column_advance<NF, false, LPC>(v, L, ln, Nz, bc, c.U, c.sat, gU, gS, a.dt, n, z0, bad);
+            f = column_closure<NF, false, HYD>(p, L, z0, n, viol);
+            c = n;
+        }
+    }
+    if (m > 0) mine[(m - 1) * TRM_STEP_BLOCK] = c.U;
+
+    // ---- backward: the transposed steps at U_{c+m-1} ... U_c
+    for (int j = m - 1; j >= 0; --j) lam = adjoint_step<LPC>(v, p, L, ln, ii, mine[j * TRM_STEP_BLOCK], sat, lam, a.dt, bTb, bTt, generic);
+    if (ln.act) ca.lU[e] = lam;
+}
+
+}  // namespace trm

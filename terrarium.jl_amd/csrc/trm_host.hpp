@@ -165,6 +165,16 @@ struct trm_ctx {
     int tape_cap = 0;
     std::vector<double> tape_dt;
     bool adj_stale = false;
+    // the checkpointed tape (trm_adjoint_open_checkpointed): `ckpt_interval` K > 0, `tape_cap` counts checkpoint slots, tape_dt stays
+    // empty and `tape_segs` lists the taped steps instead -- a segment is up to K consecutive steps under one dt, its first state in
+    // `slot` (segments take the slots in order)
+    struct TapeSegment {
+        int first, len;
+        double dt;
+        int slot;
+    };
+    int ckpt_interval = 0;
+    std::vector<TapeSegment> tape_segs;
     bool args_valid = false;
     void* args = nullptr;   // LaunchArgs<NF>*, owned
     void (*args_free)(void*) = nullptr;
@@ -521,6 +531,13 @@ struct TangentLaunch {
 // k_column_record / k_column_adjoint (trm_launch_column_adjoint.hip, fp64 NoFlow only): `slot` is the tape slot of the launch's first step
 struct AdjointLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot);
+    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+};
+// the strided k_column_record / k_column_adjoint_ckpt (trm_launch_column_adjoint_ckpt.hip): the record stores before the steps `first`,
+// `first + every`, ... of the launch into the slots from `slot` on; the backward launch pulls lam through the segment of `nsteps`
+// steps whose checkpoint is in `slot`
+struct CheckpointLaunch {
+    static int record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
 };
 // k_materialize_closure (trm_launch_materialize.hip)

@@ -442,10 +442,15 @@ class DeviceState:
         self._check(self._lib.trm_step_tangent(self._ctx, float(dt), int(nsteps)), "trm_step_tangent")
 
     # -- reverse-mode gradients (trm_adjoint_*) with respect to the initial internal energy: what the tangent covers ---------------
-    def open_adjoint(self, capacity_steps):
-        """Cotangent fields of internal energy, temperature and liquid fraction (zero) and a tape of `capacity_steps` slots, one
-        internal-energy field each (trm_adjoint_open).  Opening again starts a fresh tape."""
-        self._check(self._lib.trm_adjoint_open(self._ctx, int(capacity_steps)), "trm_adjoint_open")
+    def open_adjoint(self, capacity, checkpoint_every=None):
+        """Cotangent fields of internal energy, temperature and liquid fraction (zero) and a tape of `capacity` slots, one
+        internal-energy field each (trm_adjoint_open): one slot per taped step.  With `checkpoint_every` = K a slot holds the state
+        before every K-th step alone and the backward sweep forms the others again (trm_adjoint_open_checkpointed): the same gradient
+        bit for bit from a tape K times smaller.  Opening again starts a fresh tape."""
+        if checkpoint_every is None:
+            self._check(self._lib.trm_adjoint_open(self._ctx, int(capacity)), "trm_adjoint_open")
+        else:
+            self._check(self._lib.trm_adjoint_open_checkpointed(self._ctx, int(capacity), int(checkpoint_every)), "trm_adjoint_open_checkpointed")
         self._adjoint_open = True
 
     def close_adjoint(self):
@@ -472,8 +477,14 @@ class DeviceState:
         """Pulls the cotangents back through every taped step and empties the tape (trm_adjoint_backward)."""
         self._check(self._lib.trm_adjoint_backward(self._ctx), "trm_adjoint_backward")
 
+    def adjoint_checkpoints(self):
+        """(interval, slots used, slot capacity) of the tape (trm_adjoint_checkpoints); interval 0: a per-step tape, its slots are steps."""
+        k, n, cap = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.trm_adjoint_checkpoints(self._ctx, C.byref(k), C.byref(n), C.byref(cap)), "trm_adjoint_checkpoints")
+        return int(k.value), int(n.value), int(cap.value)
+
     def adjoint_tape(self):
-        """(steps recorded, capacity) of the tape."""
+        """(steps recorded, capacity in steps) of the tape."""
         n, cap = C.c_int32(0), C.c_int32(0)
         self._check(self._lib.trm_adjoint_tape(self._ctx, C.byref(n), C.byref(cap)), "trm_adjoint_tape")
         return int(n.value), int(cap.value)
@@ -891,11 +902,13 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int) -> dict:
             st.close_tangent()
 
 
-def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=None, liquid_water_fraction=None) -> np.ndarray:
+def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=None, liquid_water_fraction=None,
+        checkpoint_every=None) -> np.ndarray:
     """Reverse-mode derivative of `run!(integ; steps)`: the integrator is stepped `steps` times with its own dt (state and clock end
     where `run` leaves them), then the given cotangents of the final temperature, internal energy and liquid water fraction ([Nz][Nh],
     or anything that broadcasts to it; None: zero) are pulled back.  Returns dL/dU_0 as [Nz][Nh], L the sum of the three inner
-    products.  One tape slot per step (trm_step_record, trm_adjoint_backward); the coverage and refusals of `jvp`."""
+    products.  One tape slot per step (trm_step_record, trm_adjoint_backward); with `checkpoint_every` = K one slot per K steps, the
+    states in between formed again by the backward sweep -- the same gradient bit for bit.  The coverage and refusals of `jvp`."""
     if not isinstance(integ.timestepper, ForwardEuler):
         raise ValueError("vjp: ForwardEuler only")
     if integ._has_time_dependence() or integ._windowed():
@@ -903,8 +916,14 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
     st = integ.state
     steps = int(steps)
     opened = not getattr(st, "_adjoint_open", False)
-    if opened or st.adjoint_tape() != (0, max(steps, 1)):
-        st.open_adjoint(max(steps, 1))
+    if checkpoint_every is None:
+        if opened or st.adjoint_checkpoints() != (0, 0, max(steps, 1)):
+            st.open_adjoint(max(steps, 1))
+    else:
+        K = int(checkpoint_every)
+        slots = max(-(-steps // max(K, 1)), 1)
+        if opened or st.adjoint_checkpoints() != (K, 0, slots):
+            st.open_adjoint(slots, K)
     try:
         st.step_record(integ.timestepper.dt, steps)
         for name, w in (("internal_energy", internal_energy), ("temperature", temperature), ("liquid_water_fraction", liquid_water_fraction)):
