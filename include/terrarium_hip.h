@@ -218,6 +218,14 @@ enum {
                                     /* launch in front of the first call that reads or writes field memory (see trm_step): same values, bit  */
                                     /* for bit.  0: stored by every step (a caller that reads one of them after EVERY step: DESIGN 4.3).     */
                                     /* Environment: TRM_DEFER_CLOSURE_STORES = 0 / 1 sets the default of new contexts (A/B)                  */
+    ,TRM_OPT_INTERIOR_STEPS = 13    /* 1: inside ONE trm_step / trm_step_timed call of n > 1 steps, the per-step fp64 heat + Richards  */
+                                    /* launches (no LandModel, a compiled-in boundary signature, TRM_OPT_DEFER_CLOSURE_STORES in effect) but  */
+                                    /* the last store internal_energy, saturation, surface_excess_water and the water table alone; the launch   */
+                                    /* behind one derives the pressure head at entry from (saturation, water table) instead of reading it.      */
+                                    /* pressure_head, hydraulic_conductivity and the status word are stale only between launches of one call:    */
+                                    /* after every call all arrays, the status and the clock are what option 0 leaves, bit for bit.  0: every    */
+                                    /* launch stores everything (A/B, tests); 2 (default): the library's rule -- as 1 for states within the      */
+                                    /* Infinity Cache (256 MiB), as 0 beyond.  Environment: TRM_INTERIOR_STEPS = 0 / 1 / 2 sets the default      */
 };
 /* DIAGNOSTIC, read-only (trm_get_option): which fast paths the NEXT step will take -- what the library tracks about its own
  * buffers.  Tests pin them (a wrong value costs speed, never correctness, so nothing else would notice). */
@@ -234,7 +242,8 @@ enum {
                                        /* before the first step: family in bits 0-7, then one field per selection rule                    */
     TRM_INFO_CLOSURE_STORED = 106,     /* 1: the temperature / liquid fraction ARRAYS are current; 0: the last step launches left them      */
                                        /* unstored (TRM_OPT_DEFER_CLOSURE_STORES) and the next reader materialises them                     */
-    TRM_INFO_MATERIALIZATIONS = 107    /* how many times the context has materialised them (one small launch each)                          */
+    TRM_INFO_MATERIALIZATIONS = 107,   /* how many times the context has materialised them (one small launch each)                          */
+    TRM_INFO_INTERIOR_LAUNCHES = 108   /* how many step launches of the context were interior launches (TRM_OPT_INTERIOR_STEPS)             */
 };
 /* kernel families reported in the low byte of TRM_INFO_LAST_PROGRAM; bits 8-9 the hydraulics instance (0 the reference default, 1 van
  * Genuchten n = 2, 2 run-time exponents), 10-11 lanes per column / 32, 12-14 which closure fields are derived, 15 per-column outputs

@@ -47,10 +47,16 @@ OPTION = dict(asynchronous=0, step_kernel=1, write_kf_every_step=2, vwc_forcing_
 # Options and info keys added after the table above was pinned name by name (tests/test_host_and_abi.py maps every entry of OPTION
 # through a fixed list): looked up by option_id beside it; tests/test_deferred_closure_abi.py holds their header agreement.
 OPTION_LATER = dict(defer_closure_stores=12, info_closure_stored=106, info_materializations=107)
+# ... and that table is pinned as a whole by the same test: the keys of TRM_OPT_INTERIOR_STEPS have one of their own
+# (tests/test_interior_steps_abi.py)
+OPTION_INTERIOR = dict(interior_steps=13, info_interior_launches=108)
 
 
 def option_id(name: str) -> int:
-    return OPTION[name] if name in OPTION else OPTION_LATER[name]
+    for table in (OPTION, OPTION_LATER, OPTION_INTERIOR):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 KERNEL = dict(fused=0, unfused=1)
 # TRM_INFO_LAST_PROGRAM (include/terrarium_hip.h: TRM_PROGRAM_*; trm_host.hpp: program_id)

@@ -648,8 +648,9 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     // time averages take the step's terms (`accumulate`: the launch has not added them itself); only the finalizing launch stores
     // state.tendencies; the top-cell arrays describe the state after a successful LandModel launch.  Then, finalizing, the state's
     // surface processes once more (+ the 0-D auxiliaries of the coupled vegetation).
-    static int fused_epilogue(trm_ctx* c, int rc, double dt, int fin, bool accumulate = true, bool deferred = false) {
+    static int fused_epilogue(trm_ctx* c, int rc, double dt, int fin, bool accumulate = true, bool deferred = false, bool psi_step = false) {
         if (!rc) c->closure_consistent = true;
+        c->psi_consistent = !rc && psi_step;          // (pressure_head / water_table as a k_column ForwardEuler launch leaves them)
         if (!rc) c->closure_deferred = deferred;      // (every other launch has stored T / liq)
         if (!rc && accumulate) rc = accumulate_after(c, dt);
         c->tend_valid = fin != 0;
@@ -680,6 +681,23 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
             if (a.field == TRM_FIELD_TEMPERATURE || a.field == TRM_FIELD_LIQUID_WATER_FRACTION) return false;
         return !c->params.seb || tops_current(c);
     }
+    // TRM_OPT_INTERIOR_STEPS: the context's per-step launch is one of the instances k_column_psi stands in for -- fp64, Richards, no
+    // LandModel, one level per lane, every column, a compiled hydraulics and one of the non-LandModel signatures, T / liq derived --
+    // and nothing reads a field between the launches of a call: no open time average (accumulate_after reads the arrays every step), no
+    // tangent state, no device pointer handed out; and the stored pressure_head / water_table are a step launch's (psi_consistent).
+    static bool interior_capable(trm_ctx* c) {
+        if (!std::is_same<NF, double>::value || !c->opt_interior || !c->psi_consistent || c->closure_escaped) return false;
+        // 2, the library's rule: states within the Infinity Cache (the bound of Policy::scalar_inputs_now).  Beyond it the step gains more
+        // (EXPERIMENTS R10.1), but bench.py's HBM-resident companion then reports a roofline fraction above 1 on its fixed 2 080 B per
+        // column-step, which tests/test_gpu_full_size.py bounds: left to 1 until that yardstick is recalibrated
+        if (c->opt_interior == 2 && (size_t)6 * (size_t)c->Nh * (size_t)c->Nzp * sizeof(NF) > ((size_t)256 << 20)) return false;
+        if (!c->opt_write_kf) return false;      // (without TRM_OPT_WRITE_KF_EVERY_STEP the K array is the last finalizing launch's: left to the classic launches)
+        if (!P::richards(c) || c->params.seb || P::coupled(c) || c->veg_mode == TRM_VEGETATION_STANDALONE) return false;
+        if (c->opt_kernel != TRM_KERNEL_FUSED || P::levels_per_lane(c) != 1 || c->part >= 0 || P::generic_bcs(c)) return false;
+        if (!c->opt_bc_signature || P::hyd(c) == HYD_GENERIC || !column_psi_supported(bc_signature_of(c))) return false;
+        if (averaging(c) || c->d_tan[0]) return false;
+        return P::template derive_now<true>(c) == DERIVE_T_LIQ;
+    }
     template <int PROG> static int fused_launch(trm_ctx* c, double dt, int fin, int nsteps = 1) {
         int rc = fused_prologue<PROG>(c, dt, nsteps);
         const bool in_launch = !rc && PROG != PROG_MULTI && surface_in_launch(c, PROG == PROG_HEUN);
@@ -690,13 +708,34 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
         if (!rc && c->closure_deferred && (PROG != PROG_EULER || surface_reads_fields || !derives_unread(c, in_launch))) rc = flush_closure(c);
         c->defer_launch = !rc && PROG == PROG_EULER && defer_closure_now(c, in_launch);
         c->launch_deferred = false;
+        // The form of this launch (PSI_STORED: today's instance).  Behind an interior launch the pressure head in memory is stale: the
+        // launch must derive it; it goes interior itself if it is not the call's last (Ops::step) and leaves T / liq unstored anyway.
+        c->psi_request = PSI_STORED;
+        c->psi_check_entry = c->prev_interior ? 1 : 0;
+        c->psi_launched = PSI_STORED;
+        c->launch_psi_step = false;
+        if (PROG == PROG_EULER && !rc && (c->prev_interior || c->interior_wanted)) {
+            const bool capable = !in_launch && interior_capable(c);
+            if (capable && c->interior_wanted && c->defer_launch) c->psi_request = PSI_INTERIOR;
+            else if (c->prev_interior) {
+                if (!capable) rc = fail(c, TRM_EINVAL, "trm_step: the launch behind an interior launch cannot derive the pressure head");
+                c->psi_request = PSI_LAST;
+            }
+        } else if (c->prev_interior && !rc) rc = fail(c, TRM_EINVAL, "trm_step: an interior launch must be followed by a ForwardEuler launch");
         if (!rc && PROG != PROG_MULTI && P::coupled(c)) rc = V::surface_veg(c, c->state, true, true, dt, c->opt_write_kf != 0);
         else if (!rc && PROG != PROG_MULTI && c->params.seb && !in_launch) rc = U::surface(c, c->state, true);
         const bool accum = PROG == PROG_MULTI && averaging(c) && averages_in_launch(c);
         if (!rc) rc = step_launch<PROG>(c, in_launch, accum, dt, fin, nsteps);
         const bool deferred = c->launch_deferred;
         c->defer_launch = c->launch_deferred = false;
-        return fused_epilogue(c, rc, dt, fin, !accum, deferred);
+        if (!rc && c->psi_launched != c->psi_request) rc = fail(c, TRM_EINVAL, "trm_step: the step launch did not take the requested form");
+        const bool went_interior = !rc && c->psi_launched == PSI_INTERIOR;
+        if (went_interior) c->interior_launches += 1;
+        if (!rc) c->prev_interior = went_interior;
+        const bool psi_step = PROG == PROG_EULER && c->launch_psi_step;
+        c->psi_request = c->psi_launched = PSI_STORED;
+        c->launch_psi_step = false;
+        return fused_epilogue(c, rc, dt, fin, !accum, deferred, psi_step);
     }
     // ---- LandModel, per-step path: the surface processes of one half of the columns UNDER the column program of the other ----
     // (k_land_euler / k_land_pk, trm_column.hpp: one stream, two launches per step as before, each covering the soil columns
@@ -803,6 +842,7 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
                 c->tend_valid = true;
                 if (!rc) rc = unfused_step(c, dt, fin);
                 if (!rc) c->closure_consistent = true;   // closure! has just run
+                c->psi_consistent = false;
             } else if (m > 1 || (program_ok && single_step_program(c))) {
                 rc = fused_launch<PROG_MULTI>(c, dt, fin, m);
             } else if (interleave_now(c, nsteps - n)) {
@@ -812,11 +852,25 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
                 n += m;
                 continue;
             } else {
+                // (interior launches: inside this call only, never its last launch, never finalizing)
+                c->interior_wanted = n + m < nsteps && !fin;
                 rc = fused_launch<PROG_EULER>(c, dt, fin);
+                c->interior_wanted = false;
             }
             if (rc) break;
             tick(c, dt, m);
             n += m;
+        }
+        if (c->prev_interior) {
+            // A launch failed behind interior launches (the loop cannot end otherwise: the call's last launch is never interior): pressure_head,
+            // water-table and hydraulic_conductivity arrays are those of an earlier step.  Rebuilt here from the stored state with the
+            // reference-order kernels, whatever they return -- the caller gets the error of the launch that failed.
+            c->prev_interior = false;
+            c->psi_consistent = false;
+            const std::string err = c->err;
+            if (!flush_closure(c) && !U::closure_hydrology(c, c->state, true, false)) (void)U::hydraulics(c, c->state);
+            c->err = err;
+            if (!rc) rc = fail(c, TRM_EINVAL, "trm_step: the call ended on an interior launch");
         }
         return rc;
     }
@@ -958,6 +1012,7 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
         c->top_valid = false;
         c->tend_valid = true;
         c->closure_consistent = true;   // (ends with closure!)
+        c->psi_consistent = false;
         c->last_program = TRM_PROGRAM_UNFUSED;
         int rc = heun_predict(c, dt);
         if (!rc) rc = heun_correct(c, dt, finalize);
@@ -999,7 +1054,7 @@ bool parse_env_int(const char* name, long lo, long hi, long multiple_of, long& o
     return true;
 }
 struct EnvSwitches {
-    long field_skew = 16640, derive_default = -1, debug_placement = 0, handoff_tag_bias = 0, defer_closure = -1;
+    long field_skew = 16640, derive_default = -1, debug_placement = 0, handoff_tag_bias = 0, defer_closure = -1, interior_steps = -1;
     std::string error;
     EnvSwitches() {
         long v;
@@ -1008,6 +1063,7 @@ struct EnvSwitches {
         if (error.empty() && parse_env_int("TRM_DEBUG_PLACEMENT", 0, 1, 1, v, error)) debug_placement = v;   // (prints every field's allocation: profiles/tools/placement_probe.sh)
         if (error.empty() && parse_env_int("TRM_DEBUG_HANDOFF_TAG_BIAS", 0, 1, 1, v, error)) handoff_tag_bias = v;      // (tests: FrontArgs::tag_bias)
         if (error.empty() && parse_env_int("TRM_DEFER_CLOSURE_STORES", 0, 1, 1, v, error)) defer_closure = v;      // (child-process A/B)
+        if (error.empty() && parse_env_int("TRM_INTERIOR_STEPS", 0, 2, 1, v, error)) interior_steps = v;         // (child-process A/B)
         if (error.empty() && parse_env_int("TRM_STAGED_SMALL", 0, 1, 1, v, error)) { /* read by Policy::staged_now */ }
         if (error.empty() && parse_env_int("TRM_SCALAR_INPUTS", 0, 1, 1, v, error)) { /* read by Policy::scalar_inputs_now */ }
     }
@@ -1523,6 +1579,7 @@ int trm_create(const trm_grid* g, const trm_params* p, trm_ctx** out) {
     // input paths are compiled in -- the value a context starts with for TRM_OPT_DERIVE_CLOSURE_FIELDS)
     if (env_switches().derive_default >= 0) c->opt_derive = (int)env_switches().derive_default;
     if (env_switches().defer_closure >= 0) c->opt_defer_closure = (int)env_switches().defer_closure;
+    if (env_switches().interior_steps >= 0) c->opt_interior = (int)env_switches().interior_steps;
     c->debug_handoff_tag_bias = (unsigned)env_switches().handoff_tag_bias;
     if (rc == TRM_OK) hip(hipMemsetAsync(c->d_zero, 0, (size_t)c->Nh * c->esize, c->stream), "hipMemset(zero)");
     if (rc) return bail(rc);
@@ -2054,6 +2111,7 @@ int trm_update_inputs(trm_ctx* c) {
 int trm_update_state(trm_ctx* c, int compute_tendencies) {
     TRM_ENTER(c);
     c->tend_valid = true;
+    c->psi_consistent = false;      // (the auxiliary fields are the reference-order kernels' from here on: the next step launch reads them as stored)
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) {
         int rc = DISPATCH(c, update_inputs(c, c->state, c->time));
         if (!rc) rc = compute_tendencies ? DISPATCH(c, vegetation(c, c->state, VEG_UPDATE, 0.0, 1, 0)) : DISPATCH(c, vegetation(c, c->state, VEG_AUX, 0.0, 1, 0));
@@ -2065,6 +2123,7 @@ int trm_update_state(trm_ctx* c, int compute_tendencies) {
 }
 int trm_compute_auxiliary(trm_ctx* c) {
     TRM_ENTER(c);
+    c->psi_consistent = false;      // (likewise)
     if (c->veg_mode == TRM_VEGETATION_STANDALONE) return finish(c, DISPATCH(c, vegetation(c, c->state, VEG_AUX, 0.0, 1, 0)));
     return finish(c, DISPATCH(c, compute_auxiliary(c, c->state)));
 }
@@ -2090,6 +2149,7 @@ int trm_closure(trm_ctx* c) {
     TRM_ENTER(c);
     c->top_valid = false;
     c->closure_consistent = true;
+    c->psi_consistent = false;
     return finish(c, DISPATCH(c, closure(c, c->state)));
 }
 int trm_invclosure(trm_ctx* c) {
@@ -2219,6 +2279,7 @@ int trm_heun_correct(trm_ctx* c, double dt, int finalize) {
     c->top_valid = false;
     c->tend_valid = true;
     c->closure_consistent = true;      // (ends with closure!)
+    c->psi_consistent = false;
     tick(c, dt, 1);
     return finish(c, TRM_OK);
 }
@@ -2290,6 +2351,7 @@ int trm_restore_state(trm_ctx* c) {
     c->iteration = c->saved_iteration;
     c->tend_valid = c->saved_tend_valid;
     c->closure_consistent = c->saved_closure_consistent;
+    c->psi_consistent = false;      // (the restored pressure_head / water_table: whatever the saved state held)
     c->top_valid = false;
     state_changed(c);
     return finish(c, TRM_OK);
@@ -2478,6 +2540,7 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
         n += m;
     }
     c->closure_consistent = true;
+    c->psi_consistent = false;
     c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
     c->top_valid = false;
     return finish(c, TRM_OK);
@@ -2674,6 +2737,7 @@ int trm_step_record(trm_ctx* c, double dt, int nsteps) {
         n += m;
     }
     c->closure_consistent = true;
+    c->psi_consistent = false;
     c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
     c->top_valid = false;
     return finish(c, TRM_OK);
@@ -3163,7 +3227,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
     c->args_valid = false;
     c->heun_pending = false;
     // (an option that changes which program the next step takes: the arrays are made current here, not by whatever runs next)
-    if (c->closure_deferred && option != TRM_OPT_ASYNC && option != TRM_OPT_WRITE_KF_EVERY_STEP &&
+    if (c->closure_deferred && option != TRM_OPT_ASYNC && option != TRM_OPT_WRITE_KF_EVERY_STEP && option != TRM_OPT_INTERIOR_STEPS &&
         !(option == TRM_OPT_DEFER_CLOSURE_STORES && value != 0)) {
         TRM_HIP(c, hipSetDevice(c->device));
         if (int rf = flush_closure(c)) return rf;
@@ -3200,6 +3264,10 @@ int trm_set_option(trm_ctx* c, int option, int value) {
             c->opt_front = value;
             return TRM_OK;
         case TRM_OPT_DEFER_CLOSURE_STORES: c->opt_defer_closure = value != 0; return TRM_OK;
+        case TRM_OPT_INTERIOR_STEPS:
+            if (value < 0 || value > 2) break;
+            c->opt_interior = value;
+            return TRM_OK;
         default: break;
     }
     return fail(c, TRM_EINVAL, "trm_set_option: unknown option or value");
@@ -3222,6 +3290,8 @@ int trm_get_option(const trm_ctx* c, int option, int* value) {
         case TRM_OPT_DEFER_CLOSURE_STORES: *value = c->opt_defer_closure; return TRM_OK;
         case TRM_INFO_CLOSURE_STORED: *value = c->closure_deferred ? 0 : 1; return TRM_OK;
         case TRM_INFO_MATERIALIZATIONS: *value = (int)c->materializations; return TRM_OK;
+        case TRM_OPT_INTERIOR_STEPS: *value = c->opt_interior; return TRM_OK;
+        case TRM_INFO_INTERIOR_LAUNCHES: *value = (int)c->interior_launches; return TRM_OK;
         case TRM_INFO_LAST_PROGRAM: *value = c->last_program; return TRM_OK;
         case TRM_INFO_GENERIC_BOUNDARY_KERNELS: *value = (c->precision == TRM_F64 ? trmh::Policy<double>::generic_bcs(c) : trmh::Policy<float>::generic_bcs(c)) ? 1 : 0; return TRM_OK;
         case TRM_INFO_BC_SIGNATURE: *value = trmh::bc_signature_of(c); return TRM_OK;

@@ -22,10 +22,23 @@
 #pragma once
 #include "trm_kernels.hpp"
 #include "trm_average.hpp"
+#include <cstddef>
+#include <type_traits>
 
 namespace trm {
 
 enum { PROG_EULER = 0, PROG_HEUN = 1, PROG_MULTI = 2 };
+// How the fp64 Richards ForwardEuler program treats the pressure head (and with it the second half of the step) -- TRM_OPT_INTERIOR_STEPS:
+//   PSI_STORED    reads it as stored, forms and stores it at exit (every launch until round 10)
+//   PSI_LAST      derives it at entry from the loaded saturation and the stored water table -- pressure_head<NF, HYD, true>, the very
+//                 function the exit closure applied to the same values -- and is PSI_STORED from there on: the last launch of a call
+//                 whose predecessor was an interior launch
+//   PSI_INTERIOR  the same entry; at exit NO closure (T / liq / psi of the new state are what the next launch derives at entry) and no
+//                 hydraulic conductivity: it stores U, sat and the per-column surface_excess_water / water_table alone -- 4 field
+//                 streams instead of 7.  Launched for steps inside one trm_step call only (Ops::step), never finalizing.
+// The status bit of the skipped exit closure (CHECK = 2) is raised by the entry derivation of the launch that follows
+// (ColumnArgs::check_entry).
+enum { PSI_STORED = 0, PSI_LAST = 1, PSI_INTERIOR = 2 };
 // (diagnostic builds of the in-launch surface processes, wrong results by construction: 1 no surface chain, 2 no granule poll,
 // 4 the granules taken as valid whatever their tags)
 #ifndef TRM_FRONT_DIAG
@@ -251,9 +264,14 @@ struct FrontGranules {
     }
     TRM_DEV double value(int q) const { return __builtin_bit_cast(double, (w[q + 1] << 32) | (w[q] & 0xffffffffull)); }
 };
+struct NoCheckEntry {};      // (fp32: no padding behind nsteps and no program that reads the flag -- the member takes no room)
 template <class NF> struct ColumnArgs {
     NF dt;
     int finalize, write_kf, nsteps;
+    // PSI_LAST / PSI_INTERIOR (fp64): 1 = the launch before this one in the same call was an interior launch, whose skipped exit closure
+    // would have checked the composition of the state this launch reads: the entry derivation reports it instead (wave-uniform; 0: as
+    // ever).  In the four bytes of padding behind nsteps: the kernarg layout does not move.
+    [[no_unique_address]] std::conditional_t<sizeof(NF) == 8, int, NoCheckEntry> check_entry;
     // Heun: the stage's temperature boundary values (a series evaluated at t + dt), else the state's
     const NF *bcT_bot_stage, *bcT_top_stage;
     // multi-step program with time series: the slot table and [nsteps][nseries] rows
@@ -268,6 +286,8 @@ template <class NF> struct ColumnArgs {
     // excess water ([Nh]) are stored for the 0-D processes that are evaluated AT the stage (null otherwise)
     NF *stage_sat, *stage_liq, *stage_T, *stage_S;
 };
+static_assert(offsetof(ColumnArgs<double>, check_entry) == 20 && offsetof(ColumnArgs<double>, bcT_bot_stage) == 24 && sizeof(ColumnArgs<double>) == 96 &&
+              offsetof(ColumnArgs<float>, bcT_bot_stage) == 16 && offsetof(ColumnArgs<float>, stage_sat) == 56 && offsetof(ColumnArgs<double>, stage_sat) == 64 && sizeof(ColumnArgs<float>) == 88, "check_entry lives in padding: the kernarg layout does not move");
 
 
 
@@ -287,7 +307,7 @@ template <class NF> struct ColumnArgs {
 // launch (surface_front, trm_kernels.hpp) as granules; the kernel's fourth argument is then a FrontArgs.
 // ACCUM (PROG_MULTI): time averages accumulated in the launch -- every step adds dt * x of the requested fields into register
 // partials that leave once per launch (trm_average.hpp); the kernel's fourth argument is then an AccumArgs.
-template <class NF, bool RICHARDS, int HYD, int LPC, int DERIVE, int PROG, bool SEB_INLINE, bool SERIES = false, bool STAGED = false, bool SCALAR_IN = true, int BCSIG = BCSIG_RUNTIME, bool FRONT = false, bool ACCUM = false>
+template <class NF, bool RICHARDS, int HYD, int LPC, int DERIVE, int PROG, bool SEB_INLINE, bool SERIES = false, bool STAGED = false, bool SCALAR_IN = true, int BCSIG = BCSIG_RUNTIME, bool FRONT = false, bool ACCUM = false, int PSI = PSI_STORED>
 TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, const ColumnArgs<NF>& a, unsigned block) {
     // (kernarg layout: the arguments in order, each at its natural alignment)
     constexpr unsigned off_p = round_up_to((unsigned)sizeof(View<NF>), (unsigned)alignof(DevParams<NF>));
@@ -295,6 +315,9 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     constexpr unsigned off_front = round_up_to(off_args + (unsigned)sizeof(ColumnArgs<NF>), (unsigned)alignof(FrontArgs));
     static_assert(!FRONT || (PROG != PROG_MULTI && BCSIG == BCSIG_LAND && RICHARDS && !SEB_INLINE && sizeof(NF) == 8), "the in-launch surface processes feed the per-step fp64 LandModel programs");
     static_assert(!ACCUM || (PROG == PROG_MULTI && !FRONT && !STAGED), "averages are accumulated in the multi-step program");
+    constexpr bool PSI_IN = PSI != PSI_STORED, INTERIOR = PSI == PSI_INTERIOR;
+    static_assert(!PSI_IN || (RICHARDS && PROG == PROG_EULER && DERIVE == DERIVE_T_LIQ && sizeof(NF) == 8 && !FRONT && BCSIG >= 0 && !(BCSIG & BCSIG_LAND)),
+                  "the pressure head is derived at entry by the fp64 Richards ForwardEuler program of a non-LandModel signature that derives T / liq");
     constexpr unsigned off_acc = round_up_to(off_args + (unsigned)sizeof(ColumnArgs<NF>), (unsigned)alignof(AccumArgs));
     const View<NF>& v = v_arg;
     const DevParams<NF>& p = p_arg;
@@ -362,7 +385,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     static_assert(DERIVE == DERIVE_NONE || DERIVE == DERIVE_T_LIQ, "the column program reads T / liq or derives both (the liquid fraction alone and the "
                   "pressure head as well were measured and lost: EXPERIMENTS.md; their instances were removed in round 5)");
     constexpr bool DERIVE_TL = DERIVE == DERIVE_T_LIQ;
-    c.psi = RICHARDS ? ldg(v.psi, cb0) : NF(0);
+    c.psi = (RICHARDS && !PSI_IN) ? ldg(v.psi, cb0) : NF(0);
     if (!DERIVE_TL) { c.T = ldg(v.T, cb0); c.liq = ldg(v.liq, cb0); }
     const LevelGeom<NF> L = level_geom(v, ln.k);      // (behind the field loads: see level_geom)
     // (BCSIG >= 0: the launcher has matched the context's kinds against the signature -- constants from here on)
@@ -417,7 +440,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     // instructions after the fields).  surface_excess_water and the skin temperature likewise: vector memory retires in order, loads and
     // stores through the one counter, so a load issued behind the field stores would hold the wave until its stores were acknowledged.
     const ColVal none{NF(0), NF(0)};
-    ColVal q_Tb = none, q_Tt = none, q_Ub = none, q_Sb = none, q_Ut = none, q_St = none, q_Tb2 = none, q_Tt2 = none, q_S = none, q_Ts = none;
+    ColVal q_Tb = none, q_Tt = none, q_Ub = none, q_Sb = none, q_Ut = none, q_St = none, q_Tb2 = none, q_Tt2 = none, q_S = none, q_Ts = none, q_wt = none;
     NF S_stage_out = NF(0);
     FrontGranules fg0{}, fg1{};
     unsigned front_epoch = 0;
@@ -435,6 +458,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
         }
         if (PROG != PROG_MULTI) {
             if (RICHARDS) q_S = col_req(v.S);
+            if (PSI_IN) q_wt = col_req(v.wt);      // (the water table the previous launch stored: a per-column input, it does not wait for the saturation)
             if (seb && !FRONT) q_Ts = col_req(v.Ts);
         }
         if constexpr (FRONT) {   // the granules of the wave's columns through the scalar path: valid if the surface workgroups have published them
@@ -452,7 +476,9 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     Frac<NF> f_in{};          // the incoming cell's volumetric fractions, when the derivation has formed them
     if (DERIVE_TL) {
         uint32_t viol_in = 0;
-        f_in = energy_closure_wave<NF, 0>(kernarg_reload<DevParams<NF>>(off_p), c.U, c.sat, c.liq, c.T, viol_in);   // (its scalars die right here)
+        f_in = energy_closure_wave<NF, PSI_IN ? 2 : 0>(kernarg_reload<DevParams<NF>>(off_p), c.U, c.sat, c.liq, c.T, viol_in);   // (its scalars die right here)
+        // (the check the exit closure of an interior launch did not run, on the same stored state: masked, not branched on)
+        if constexpr (PSI_IN) viol |= viol_in & (0u - (uint32_t)kernarg_reload<ColumnArgs<NF>>(off_args).check_entry);
     }
     // ---- boundary inputs of the column --------------------------------------------------------------------------------
     TRM_PHASE_FENCE("inputs", c.U, c.sat, c.psi, c.T, c.liq);
@@ -461,6 +487,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     NF in_Ut = col_get(q_Ut), in_St = col_get(q_St);
     const NF in_Tb2 = col_get(q_Tb2), in_Tt2 = col_get(q_Tt2);
     NF S_in = col_get(q_S), Ts_in = col_get(q_Ts);
+    if constexpr (PSI_IN) c.psi = pressure_head<NF, HYD, true>(kernarg_reload<DevParams<NF>>(off_p), c.sat, L.zC, L.psiz, col_get(q_wt));      // (column_closure's)
     NF front_Ut = NF(0), front_St = NF(0);
     bool front_ready = true;
     if constexpr (FRONT) {
@@ -687,7 +714,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
             // (second half of the step: parameters fetched afresh instead of being kept in SGPRs across the first half --
             // the kernel is short of scalar registers, and what does not fit is parked in VGPR lanes at a VALU move each)
             TRM_PHASE_FENCE("closure", n.U, n.sat, z0, over, gU, gS);
-            f_new = column_closure<NF, RICHARDS, HYD>(kernarg_reload<DevParams<NF>>(off_p), L, z0, n, viol);
+            if constexpr (!INTERIOR) f_new = column_closure<NF, RICHARDS, HYD>(kernarg_reload<DevParams<NF>>(off_p), L, z0, n, viol);
             gU_out = gU; gS_out = gS;
             if constexpr (ACCUM) {
                 // the step's terms dt * x, x after the step (the surface diagnostics as this step's surface processes formed them)
@@ -707,7 +734,7 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
 
     // ---- hydraulic_conductivity of the state: K(state the last tendencies saw), K(new state) when finalizing -----------
     NF Kf_out = t.Kf_lo, Kf_out_top = t.Kc;
-    if (finalize && write_kf) {
+    if (!INTERIOR && finalize && write_kf) {
         const DevParams<NF>& p = kernarg_reload<DevParams<NF>>(off_p);
         const NF Kc_new = conductivity_hydraulic<NF, HYD, false>(p, n.liq, f_new);     // (the closure has checked this composition)
         const NF Kc_new_m = shfl_up1<NF, LPC>(Kc_new);
@@ -737,6 +764,30 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
     }
     // ---- the column goes out: 6 coalesced stores ---------------------------------------------------------------------------
     TRM_PHASE_FENCE("stores", Kf_out, Kf_out_top, S, GS_out);
+    if constexpr (INTERIOR) {
+        // an interior launch: U, sat, and per column surface_excess_water and the water table the next launch derives psi from (nothing
+        // at all if it were launched finalizing: the host never does)
+        if (ln.act && !uniform_flag(finalize)) {
+            const View<NF>& v = kernarg_reload<View<NF>>(0);
+            NF* const pS = v.S; NF* const pwt = v.wt;
+            asm volatile("" : : "s"(pS), "s"(pwt));
+            unsigned cb = block_local(cb0);
+            stg(v.U, cb, n.U);
+            stg(v.sat, cb, n.sat);
+            if (ln.is_top && STAGED) {
+                const int cib = (int)(threadIdx.x >> 6) * CPW + sub;
+                constexpr int cpb = (TRM_STEP_BLOCK / 64) * CPW;
+                NF* st = small_stage<NF>();
+                st[SMALL_S * cpb + cib] = S;
+                st[SMALL_WT * cpb + cib] = z0;
+            } else if (ln.is_top) {
+                const unsigned ib = block_local(ib0);
+                stg(pS, ib, S);
+                stg(pwt, ib, z0);
+            }
+            viol |= bad ? 1u : 0u;
+        }
+    } else
     if (ln.act) {
         const View<NF>& v = kernarg_reload<View<NF>>(0);
         // every base pointer the store phase may need in ONE batch of scalar loads: fetched where they are used -- inside the
@@ -800,7 +851,9 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
         }
         viol |= bad ? 1u : 0u;
     }
-    if (STAGED) {
+    if (STAGED && INTERIOR) {
+        store_small_outputs<NF, (TRM_STEP_BLOCK / 64) * CPW>(finalize ? 0u : (1u << SMALL_S) | (1u << SMALL_WT), block, Nh);
+    } else if (STAGED) {
         const unsigned enabled = (write_kf ? 1u << SMALL_KF_TOP : 0u) | (RICHARDS ? (1u << SMALL_S) | (1u << SMALL_WT) : 0u) |
                                  ((RICHARDS && finalize) ? 1u << SMALL_G_S : 0u) |
                                  (seb ? (1u << SMALL_TOP_T) | (1u << SMALL_TOP_SAT) | (1u << SMALL_TOP_LIQ) | (1u << SMALL_TS) : 0u);
@@ -832,6 +885,15 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK)
 #endif
     k_column(View<NF> v_arg, DevParams<NF> p_arg, ColumnArgs<NF> a) {
     column_program<NF, RICHARDS, HYD, LPC, DERIVE, PROG, SEB_INLINE, SERIES, STAGED, SCALAR_IN, BCSIG>(v_arg, p_arg, a, xcd_block<TRM_XCD_REMAP != 0>(blockIdx.x, gridDim.x));
+}
+
+// The fp64 Richards ForwardEuler program with the pressure head derived at entry (PSI_LAST / PSI_INTERIOR above): the instances that
+// stand in for k_column<double, true, HYD, LPC, DERIVE_T_LIQ, PROG_EULER, false, false, STAGED, SCALAR_IN, BCSIG> inside one trm_step call.
+template <int HYD, int LPC, bool STAGED, bool SCALAR_IN, int BCSIG, int PSI>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK)
+    __attribute__((amdgpu_waves_per_eu(HYD == HYD_BC_LINEAR ? TRM_COLUMN_WAVES_EULER : 5, 8)))
+    k_column_psi(View<double> v_arg, DevParams<double> p_arg, ColumnArgs<double> a) {
+    column_program<double, true, HYD, LPC, DERIVE_T_LIQ, PROG_EULER, false, false, STAGED, SCALAR_IN, BCSIG, false, false, PSI>(v_arg, p_arg, a, xcd_block<TRM_XCD_REMAP != 0>(blockIdx.x, gridDim.x));
 }
 
 // temperature and liquid_water_fraction of the stored (internal_energy, saturation) after launches that did not store them

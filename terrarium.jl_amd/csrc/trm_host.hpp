@@ -101,6 +101,18 @@ struct trm_ctx {
     int opt_defer_closure = 1;
     bool closure_deferred = false, defer_launch = false, launch_deferred = false;
     int64_t materializations = 0;   // TRM_INFO_MATERIALIZATIONS: k_materialize_closure launches so far
+    // TRM_OPT_INTERIOR_STEPS: inside one trm_step call the fp64 Richards per-step launches but the last store U, sat, surface_excess_water
+    // and the water table alone (k_column_psi<PSI_INTERIOR>), and the launch behind one derives the pressure head at entry.
+    // `psi_consistent`: the stored pressure_head / water_table are what a k_column ForwardEuler launch left for the stored saturation
+    // (set by Ops::fused_epilogue after such a launch, cleared by everything else that sets closure_consistent).  The rest lives inside
+    // Ops::step's loop only: `interior_wanted` (the launch being issued is not the call's last), `prev_interior` (the one before it was
+    // an interior launch: psi, K and the water-table-derived fields in memory are stale until the call's last launch has run),
+    // `psi_request` / `psi_check_entry` (what Ops::fused_launch asks of the launcher), `psi_launched` (what the launcher did),
+    // `launch_psi_step` (the launcher issued a k_column / k_column_psi ForwardEuler launch of a Richards state).
+    int opt_interior = 2;           // 0 off, 1 whenever legal, 2 the library's rule (Ops::interior_capable)
+    bool psi_consistent = false, interior_wanted = false, prev_interior = false, launch_psi_step = false;
+    int psi_request = 0, psi_check_entry = 0, psi_launched = 0;
+    int64_t interior_launches = 0;  // TRM_INFO_INTERIOR_LAUNCHES
     void* d_zero = nullptr;  // [Nh] zeros: stands in for the value array of every unset boundary condition
     double* d_reduce = nullptr;  // scratch for trm_reduce
     size_t reduce_cap = 0;
@@ -550,6 +562,12 @@ constexpr int TRM_PROGRAM_BIT_AVERAGES_IN_LAUNCH = TRM_PROGRAM_AVERAGES_IN_LAUNC
 template <class NF, bool RICH, int SIG> struct ColumnSigLaunch {
     static void run(trm_ctx* c, const View<NF>& v, const DevParams<NF>& p, const ColumnArgs<NF>& a, dim3 grid, dim3 block, int lpc, int derive, int staged, int scalar_in);
 };
+// the fp64 Richards instances that derive the pressure head at entry (k_column_psi<..., PSI_LAST | PSI_INTERIOR>, trm_launch_column_psi_f64_*.hip):
+// `form` is PSI_LAST or PSI_INTERIOR, (staged, scalar_in) one of (0, 1), (1, 0); `supported`: the signatures that have instances
+template <int SIG> struct ColumnPsiLaunch {
+    static void run(trm_ctx* c, const View<double>& v, const DevParams<double>& p, const ColumnArgs<double>& a, dim3 grid, dim3 block, int lpc, int form, int staged, int scalar_in);
+};
+inline bool column_psi_supported(int sig) { return sig == 0 || sig == BCSIG_T_TOP || sig == (BCSIG_T_TOP | BCSIG_FU_BOT) || sig == (BCSIG_T_TOP | BCSIG_FS_TOP); }
 // the same for the one-launch Heun program (trm_launch_column_sig_heun_*.hip)
 template <class NF, bool RICH, int SIG> struct ColumnSigHeunLaunch {
     static void run(trm_ctx* c, const View<NF>& v, const DevParams<NF>& p, const ColumnArgs<NF>& a, dim3 grid, dim3 block, int lpc);

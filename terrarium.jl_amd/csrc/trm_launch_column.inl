@@ -28,7 +28,24 @@ template <class NF, bool RICH, int H, int LPC, int PROG> static int launch_colum
         int staged = derive == DERIVE_T_LIQ ? P::template staged_now<RICH>(c) : 0, scalar_in = derive == DERIVE_T_LIQ ? P::template scalar_inputs_now<RICH>(c) : 1;
         const bool has_instance = sig == 0 || sig == BCSIG_T_TOP || sig == (BCSIG_T_TOP | BCSIG_FU_BOT) || (RICH && (sig == BCSIG_LAND || sig == (BCSIG_T_TOP | BCSIG_FS_TOP)));
         P::io_paths(!has_instance || sig == BCSIG_LAND, staged, scalar_in);
-        if (launch_by_signature<ColumnSigLaunch, NF, RICH>(sig, c, v, p, a, grid, block, LPC, derive, staged, scalar_in)) {
+        if (RICH) c->launch_psi_step = true;      // (every instance below stores pressure_head / water_table as column_closure forms them -- or is an interior launch)
+        if (c->psi_request != PSI_STORED) {
+            // TRM_OPT_INTERIOR_STEPS (Ops::fused_launch): the instance that derives the pressure head at entry stands in for the signature
+            // instance this launch would otherwise be, and reports that instance's id
+            if constexpr (std::is_same<NF, double>::value && RICH && H != HYD_GENERIC) {
+                if (derive != DERIVE_T_LIQ || !column_psi_supported(sig) || staged == scalar_in) return fail(c, TRM_EINVAL, "k_column_psi: no instance for this launch");
+                a.check_entry = c->psi_check_entry;
+                switch (sig) {
+                    case 0: ColumnPsiLaunch<0>::run(c, v, p, a, grid, block, LPC, c->psi_request, staged, scalar_in); break;
+                    case BCSIG_T_TOP: ColumnPsiLaunch<BCSIG_T_TOP>::run(c, v, p, a, grid, block, LPC, c->psi_request, staged, scalar_in); break;
+                    case BCSIG_T_TOP | BCSIG_FU_BOT: ColumnPsiLaunch<BCSIG_T_TOP | BCSIG_FU_BOT>::run(c, v, p, a, grid, block, LPC, c->psi_request, staged, scalar_in); break;
+                    default: ColumnPsiLaunch<BCSIG_T_TOP | BCSIG_FS_TOP>::run(c, v, p, a, grid, block, LPC, c->psi_request, staged, scalar_in); break;
+                }
+                c->psi_launched = c->psi_request;
+                pid = program_id(TRM_PROGRAM_COLUMN_EULER, H, LPC, DERIVE_T_LIQ, staged, scalar_in, sig);
+            } else return fail(c, TRM_EINVAL, "k_column_psi: no instance for this launch");
+        }
+        else if (launch_by_signature<ColumnSigLaunch, NF, RICH>(sig, c, v, p, a, grid, block, LPC, derive, staged, scalar_in)) {
             // (trm_launch_column_sig.inl: without the derivation the signature instances store directly and take the scalar path)
             pid = derive == DERIVE_T_LIQ ? program_id(TRM_PROGRAM_COLUMN_EULER, H, LPC, DERIVE_T_LIQ, staged, scalar_in, sig) : program_id(TRM_PROGRAM_COLUMN_EULER, H, LPC, DERIVE_NONE, 0, 1, sig);
         }
