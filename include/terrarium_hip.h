@@ -593,7 +593,7 @@ int trm_average_close(trm_ctx* ctx, int handle);
 /* ---- forward-mode tangents of the heat-only step (the reference differentiates timestep! with Enzyme) -----------------------------
  * Tangents with respect to the initial internal energy of a SoilModel with NoFlow, ForwardEuler, fp64, Nz <= 64, every boundary kind
  * of the heat-only programs (NoFlux, Value / Gradient on temperature, Flux on energy) and both halo policies.  Boundary values are
- * constants: their tangent is 0.
+ * constants: their tangent is 0 unless trm_tangent_bc_upload seeds them (below).
  *   trm_tangent_open(ctx)                   allocates the three tangent fields below, Nz rows each, zero
  *   trm_tangent_close(ctx)                  frees them
  *   trm_tangent_upload / _download(ctx, which, host)
@@ -623,11 +623,25 @@ int trm_tangent_download(trm_ctx* ctx, int which, void* host);
 int trm_tangent_device_ptr(trm_ctx* ctx, int which, void** dev, int64_t* pitch_elems);
 int trm_tangent_closure(trm_ctx* ctx);
 int trm_step_tangent(trm_ctx* ctx, double dt, int nsteps);
+/* Seeds on the boundary values: the tangent with respect to what drives the run.  A boundary value enters the heat-only step as a Value
+ * or a Gradient on temperature (also a zero Gradient at the bottom, which the primal skips: its derivative is not zero) or as a Flux on
+ * internal energy; the values are constant over the steps, and so are their seeds.
+ *   trm_tangent_bc_upload(ctx, bc_var, side, host)
+ *                                           host[num_columns] doubles: the seed d(value) of the pair (bc_var, side), bc_var
+ *                                           TRM_BCV_TEMPERATURE or TRM_BCV_INTERNAL_ENERGY, side TRM_BOTTOM or TRM_TOP.  The four seed
+ *                                           arrays are allocated by the first upload, zeroed by trm_tangent_open and freed by
+ *                                           trm_tangent_close.  A pair whose current kind reads no value contributes nothing, whatever
+ *                                           its seed.  Seeds are not state: no call makes them stale, and the upload does not seed dU
+ *                                           (a stale tangent stays stale).
+ * Once a seed has been uploaded since trm_tangent_open, trm_step_tangent runs the seeded instances: TRM_INFO_LAST_PROGRAM carries
+ * bit 26.  The state afterwards is still that of trm_step, bit for bit, and zero seeds give the tangents of the unseeded run.
+ * Errors: TRM_EINVAL without a context or an open tangent, for any other bc_var, a side other than 0 / 1, or a NULL pointer. */
+int trm_tangent_bc_upload(trm_ctx* ctx, int bc_var, int side, const void* host);
 
 /* ---- reverse-mode gradients of the heat-only run (the reference pulls a seed back through run! with Enzyme's Reverse mode) ---------
  * The gradient g = dL/dU_0 of L = <wU, U_n> + <wT, T_n> + <wliq, liq_n> with respect to the initial internal energy, for what the
  * tangent covers (above): the transpose of the linear map trm_step_tangent applies, one backward sweep for any number of inputs.
- * Boundary values and parameters are constants.
+ * Parameters are constants; the gradient with respect to the boundary values comes from trm_adjoint_bc_open (below).
  *   trm_adjoint_open(ctx, capacity_steps)   allocates the cotangent fields of U, T, liq (zero) and a tape of capacity_steps slots; one
  *                                           slot is Nh x Nzp x 8 bytes (the internal energy before a step).  Opening again starts a
  *                                           fresh tape and zeroes the cotangents.
@@ -687,6 +701,26 @@ int trm_adjoint_open_checkpointed(trm_ctx* ctx, int capacity_slots, int interval
 int trm_adjoint_checkpoints(const trm_ctx* ctx, int* interval, int* slots_used, int* slots_capacity);
 int trm_step_record(trm_ctx* ctx, double dt, int nsteps);
 int trm_adjoint_backward(trm_ctx* ctx);
+/* Boundary gradients: dL/d(value) of the boundary values that drove the taped steps -- the surface temperature, a temperature gradient,
+ * the ground or geothermal heat flux -- from the same sweep, for the pairs trm_tangent_bc_upload seeds.
+ *   trm_adjoint_bc_open(ctx)                allocates four accumulators of num_columns doubles, zero; from then on trm_adjoint_backward
+ *                                           runs the accumulating instances (TRM_INFO_LAST_PROGRAM: bit 30) on either tape.
+ *                                           trm_adjoint_open keeps them (zeroed); trm_adjoint_close frees them.
+ *   trm_adjoint_bc_download(ctx, bc_var, side, host)
+ *                                           host[num_columns] doubles.  After a trm_adjoint_backward that succeeded: dL/d(value) of the
+ *                                           pair of that sweep -- the sum over all taped steps, the value being constant over the tape
+ *                                           (a trm_set_bc in between makes the tape stale) -- and exact zeros for a pair whose kind
+ *                                           reads no value.  After a sweep that failed the content is unspecified.
+ *   trm_adjoint_bc_device_ptr(ctx, bc_var, side, &dev)
+ *                                           the accumulator on the device, num_columns contiguous doubles
+ * The sum runs over the taped steps newest first, one step at a time in a register of the column's edge lane, and is carried from launch
+ * to launch: it does not depend on TRM_OPT_STEPS_PER_LAUNCH or on the checkpoint interval, the checkpointed tape gives the per-step
+ * tape's bits, and g = dL/dU_0 is bit for bit what the sweep without boundary gradients gives.
+ * Errors: TRM_EINVAL without a context or an open adjoint, for _download / _device_ptr before trm_adjoint_bc_open, for a bc_var other
+ * than TRM_BCV_TEMPERATURE / TRM_BCV_INTERNAL_ENERGY, a side other than 0 / 1, or a NULL pointer; TRM_ENOMEM. */
+int trm_adjoint_bc_open(trm_ctx* ctx);
+int trm_adjoint_bc_download(trm_ctx* ctx, int bc_var, int side, void* host);
+int trm_adjoint_bc_device_ptr(trm_ctx* ctx, int bc_var, int side, void** dev);
 
 int trm_clock(const trm_ctx* ctx, double* time, int64_t* iteration);
 int trm_set_clock(trm_ctx* ctx, double time, int64_t iteration);

@@ -74,9 +74,9 @@ def decode_program(pid: int) -> dict:
     if d["family"] == "column_land":
         d.update(program=("euler", "heun", "multi")[extra & 3])
     if d["family"] == "column_tangent":
-        d.update(generic_boundaries=bool(extra & 1))
+        d.update(generic_boundaries=bool(extra & 1), boundary_seeds=bool(extra & 2))
     if d["family"] == "column_adjoint":
-        d.update(generic_boundaries=bool(extra & 1), backward=bool(extra & 2), checkpointed=bool(extra & 4))
+        d.update(generic_boundaries=bool(extra & 1), backward=bool(extra & 2), checkpointed=bool(extra & 4), boundary_gradient=bool(extra & 32))
     if d["family"] in ("deep", "wide"):
         d.update(program=("euler", "heun", "multi")[extra & 3], generic_boundaries=bool(extra & 4))
     if pid & (PROGRAM_AVERAGES_IN_LAUNCH | PROGRAM_AVERAGES_AFTER_LAUNCH):
@@ -104,7 +104,8 @@ EXPORTS = (
     "trm_tangent_open trm_tangent_close trm_tangent_upload trm_tangent_download trm_tangent_device_ptr trm_tangent_closure "
     "trm_step_tangent "
     "trm_adjoint_open trm_adjoint_close trm_adjoint_upload trm_adjoint_download trm_adjoint_device_ptr trm_adjoint_tape "
-    "trm_step_record trm_adjoint_backward trm_adjoint_open_checkpointed trm_adjoint_checkpoints").split()
+    "trm_step_record trm_adjoint_backward trm_adjoint_open_checkpointed trm_adjoint_checkpoints "
+    "trm_tangent_bc_upload trm_adjoint_bc_open trm_adjoint_bc_download trm_adjoint_bc_device_ptr").split()
 # forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
 TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
 # the checkpointed tape of the adjoint (trm_adjoint_open_checkpointed): TRM_ADJOINT_MAX_INTERVAL, TRM_ADJOINT_DEFAULT_INTERVAL
@@ -273,6 +274,10 @@ def lib():
     L.trm_adjoint_backward.argtypes = [vp]
     L.trm_adjoint_open_checkpointed.argtypes = [vp, i32, i32]
     L.trm_adjoint_checkpoints.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.trm_tangent_bc_upload.argtypes = [vp, i32, i32, vp]
+    L.trm_adjoint_bc_open.argtypes = [vp]
+    L.trm_adjoint_bc_download.argtypes = [vp, i32, i32, vp]
+    L.trm_adjoint_bc_device_ptr.argtypes = [vp, i32, i32, C.POINTER(vp)]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

@@ -1646,6 +1646,10 @@ int trm_destroy(trm_ctx* c) {
         if (q) (void)hipFree(q);
     for (double* q : c->d_adj)
         if (q) (void)hipFree(q);
+    for (double* q : c->d_tan_bc)
+        if (q) (void)hipFree(q);
+    for (double* q : c->d_adj_bc)
+        if (q) (void)hipFree(q);
     if (c->d_tape) (void)hipFree(c->d_tape);
 
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -2452,6 +2456,13 @@ int tangent_args_ok(trm_ctx* c, int which, const void* ptr, const char* who) {
     if (which < 0 || which > TRM_TANGENT_LIQUID_WATER_FRACTION || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument");
     return TRM_OK;
 }
+// the slot of a (boundary variable, side) pair in d_tan_bc / d_adj_bc, -1 for a pair the heat-only step reads no value of
+int bc_pair_index(int bc_var, int side) {
+    if (side != TRM_BOTTOM && side != TRM_TOP) return -1;
+    if (bc_var == TRM_BCV_TEMPERATURE) return side == TRM_TOP ? 1 : 0;
+    if (bc_var == TRM_BCV_INTERNAL_ENERGY) return side == TRM_TOP ? 3 : 2;
+    return -1;
+}
 const char* kStaleTangent = ": the state has changed since the tangent was seeded: trm_tangent_upload a new dU first";
 }  // namespace
 
@@ -2463,6 +2474,9 @@ int trm_tangent_open(trm_ctx* c) {
         if (!q) TRM_HIP(c, hipMalloc((void**)&q, bytes));
         TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
     }
+    for (double* q : c->d_tan_bc)
+        if (q) TRM_HIP(c, hipMemsetAsync(q, 0, (size_t)c->Nh * sizeof(double), c->stream));
+    c->tan_bc_seeded = false;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     c->tan_stale = false;      // (a zero seed: zero tangents)
     return TRM_OK;
@@ -2475,7 +2489,32 @@ int trm_tangent_close(trm_ctx* c) {
         TRM_HIP(c, hipFree(q));
         q = nullptr;
     }
+    for (double*& q : c->d_tan_bc) {
+        if (q) TRM_HIP(c, hipFree(q));
+        q = nullptr;
+    }
+    c->tan_bc_seeded = false;
     c->tan_stale = false;
+    return TRM_OK;
+}
+int trm_tangent_bc_upload(trm_ctx* c, int bc_var, int side, const void* host) {
+    TRM_ENTER_HEUN(c);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: no tangent is open (trm_tangent_open)");
+    const int slot = bc_pair_index(bc_var, side);
+    if (slot < 0 || !host) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: bad argument (internal energy or temperature, bottom or top)");
+    const size_t bytes = (size_t)c->Nh * sizeof(double);
+    for (double*& q : c->d_tan_bc)
+        if (!q) {
+            if (hipMalloc((void**)&q, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                q = nullptr;
+                return fail(c, TRM_ENOMEM, "trm_tangent_bc_upload: the seed arrays do not fit");
+            }
+            TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+        }
+    TRM_HIP(c, hipMemcpyAsync(c->d_tan_bc[slot], host, bytes, hipMemcpyHostToDevice, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    c->tan_bc_seeded = true;   // (seeds are not state: tan_stale stays as it is)
     return TRM_OK;
 }
 int trm_tangent_upload(trm_ctx* c, int which, const void* host) {
@@ -2534,7 +2573,7 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     while (n < nsteps) {
         const int m = std::min(spl, nsteps - n);
         int rc = Ops<double>::update_inputs(c, c->state, c->time);
-        if (!rc) rc = TangentLaunch::step(c, dt, m);
+        if (!rc) rc = c->tan_bc_seeded ? TangentLaunch::step_bc(c, dt, m) : TangentLaunch::step(c, dt, m);
         if (rc) return rc;
         tick(c, dt, m);
         n += m;
@@ -2565,6 +2604,10 @@ void free_tape(trm_ctx* c) {
 }
 void free_adjoint(trm_ctx* c) {
     for (double*& q : c->d_adj) {
+        if (q) (void)hipFree(q);
+        q = nullptr;
+    }
+    for (double*& q : c->d_adj_bc) {
         if (q) (void)hipFree(q);
         q = nullptr;
     }
@@ -2602,6 +2645,8 @@ int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who)
         }
         TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
     }
+    for (double* q : c->d_adj_bc)   // (opening again keeps open boundary gradients, zero)
+        if (q) TRM_HIP(c, hipMemsetAsync(q, 0, (size_t)c->Nh * sizeof(double), c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     c->tape_dt.clear();        // (a fresh tape)
     c->tape_segs.clear();
@@ -2635,6 +2680,49 @@ int trm_adjoint_close(trm_ctx* c) {
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_close: no adjoint is open");
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     free_adjoint(c);
+    return TRM_OK;
+}
+int trm_adjoint_bc_open(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_bc_open: no adjoint is open (trm_adjoint_open)");
+    const size_t bytes = (size_t)c->Nh * sizeof(double);
+    for (double*& q : c->d_adj_bc) {
+        if (!q && hipMalloc((void**)&q, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            q = nullptr;
+            for (double*& r : c->d_adj_bc) {
+                if (r) (void)hipFree(r);
+                r = nullptr;
+            }
+            return fail(c, TRM_ENOMEM, "trm_adjoint_bc_open: the accumulators do not fit");
+        }
+        TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+    }
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+namespace {
+int adjoint_bc_args(trm_ctx* c, int bc_var, int side, const void* ptr, const char* who, int& slot) {
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no adjoint is open (trm_adjoint_open)");
+    if (!c->d_adj_bc[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no boundary gradients are open (trm_adjoint_bc_open)");
+    slot = bc_pair_index(bc_var, side);
+    if (slot < 0 || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument (internal energy or temperature, bottom or top)");
+    return TRM_OK;
+}
+}  // namespace
+int trm_adjoint_bc_download(trm_ctx* c, int bc_var, int side, void* host) {
+    TRM_ENTER_HEUN(c);
+    int slot = -1;
+    if (int rc = adjoint_bc_args(c, bc_var, side, host, "trm_adjoint_bc_download", slot)) return rc;
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_adj_bc[slot], (size_t)c->Nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_bc_device_ptr(trm_ctx* c, int bc_var, int side, void** dev) {
+    TRM_ENTER_HEUN(c);
+    int slot = -1;
+    if (int rc = adjoint_bc_args(c, bc_var, side, dev, "trm_adjoint_bc_device_ptr", slot)) return rc;
+    *dev = c->d_adj_bc[slot];
     return TRM_OK;
 }
 int trm_adjoint_upload(trm_ctx* c, int which, const void* host) {
@@ -2752,7 +2840,8 @@ int trm_adjoint_backward(trm_ctx* c) {
         size_t s = c->tape_segs.size();
         do {
             const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
-            if (int rc = CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold)) {
+            if (int rc = c->d_adj_bc[0] ? CheckpointLaunch::backward_bc(c, seg.dt, seg.len, seg.slot, fold)
+                                        : CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold)) {
                 c->adj_stale = true;       // (lam is part way down the tape)
                 return rc;
             }
@@ -2770,7 +2859,8 @@ int trm_adjoint_backward(trm_ctx* c) {
     do {
         int begin = end;
         while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
-        if (int rc = AdjointLaunch::backward(c, end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0, end - begin, begin, fold)) {
+        const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
+        if (int rc = c->d_adj_bc[0] ? AdjointLaunch::backward_bc(c, dt_block, end - begin, begin, fold) : AdjointLaunch::backward(c, dt_block, end - begin, begin, fold)) {
             c->adj_stale = true;       // (lam is part way down the tape)
             return rc;
         }

@@ -11,6 +11,14 @@
 // The boundary faces use the transposed halo rules: a Value halo extrapolates through a constant (dT - dT_halo = +-dT dzf / (dzf / 2)),
 // a Gradient halo copies the edge cell (no term), the mirror policy's halo conductivity is the edge cell's (its A counts twice), the dry
 // halo cell of the reference-zero policy has dkappa = 0.  Flux boundary terms are constants.
+// BCGRAD (trm_adjoint_bc_open): the sweep also forms dL/d(boundary value) of the four pairs (temperature, internal-energy flux) x (bottom,
+// top), the transposes of the seed terms of k_column_tangent<.., BCSEED>: with pB / pB_t the cotangents of the boundary-face differences
+//   Value     top  += div_const(pB_t, dzf / 2) dzf,   bottom += -(div_const(pB, dzf / 2) dzf)
+//   Gradient  top  += pB_t dzf,                      bottom += pB dzf
+//   Flux      top  += -flux_term_top(lam' dt),       bottom += flux_term_bottom(lam' dt)
+// summed in registers of the edge lanes over the taped steps, newest first: the launch that folds starts from 0, every other launch from
+// what the launch before stored, and the owning edge lane stores once at the end -- one strictly sequential sum per column and pair,
+// whatever the split into launches or segments.  No atomics.  lam is formed by the operations it was.
 // Every coefficient is a function of the state U_k BEFORE step k: k_column_record is the multi-step primal that stores U_k into tape
 // slot k (the field layout [Nh][Nzp]) before every step; k_column_adjoint walks a block of slots backwards with lam in registers.
 // closure_tangent and conductivity_tangent are linear in their seed, one scalar slope per cell: applied to a cotangent they are their
@@ -33,6 +41,40 @@ struct AdjointArgs {
     int generic;              // 1: Gradient on temperature off the branch-free kinds (k_step_wave's halos, column_tendencies_generic)
     int fold;                 // backward: 1 in the first launch of a sweep: lam_n = wU + a_n wT + b_n wliq of the stored state, wT = wliq = 0 after
 };
+// the boundary-gradient accumulators of a BCGRAD sweep, [Nh] each: dL/d(temperature value) and dL/d(internal-energy flux), bottom / top
+struct BcGradPtrs {
+    double *gTb, *gTt, *gUb, *gUt;
+};
+// ... of k_column_adjoint<HYD, LPC, true, AdjointBcArgs>
+struct AdjointBcArgs : AdjointArgs {
+    BcGradPtrs g;
+};
+// a lane's running sums (the bottom lane owns Tb and Ub, the top lane Tt and Ut; the other lanes carry zeros)
+struct BcGrad {
+    double Tb = 0.0, Tt = 0.0, Ub = 0.0, Ut = 0.0;
+};
+// in front of the loop: 0 in the launch that folds, else what the launch before stored
+TRM_DEV BcGrad bc_grad_load(const BcGradPtrs& g, int ii, int fold) {
+    BcGrad acc;
+    if (!fold) {
+        acc.Tb = g.gTb[ii];
+        acc.Tt = g.gTt[ii];
+        acc.Ub = g.gUb[ii];
+        acc.Ut = g.gUt[ii];
+    }
+    return acc;
+}
+// behind it: the owning edge lane alone (tail lanes carry clamped copies)
+TRM_DEV void bc_grad_store(const BcGradPtrs& g, const LaneInfo& ln, int ii, const BcGrad& acc) {
+    if (ln.act && ln.is_bot) {
+        g.gTb[ii] = acc.Tb;
+        g.gUb[ii] = acc.Ub;
+    }
+    if (ln.act && ln.is_top) {
+        g.gTt[ii] = acc.Tt;
+        g.gUt[ii] = acc.Ut;
+    }
+}
 
 // what the lane-per-level kernels of this file know about their lane (as k_column_tangent forms it)
 template <int LPC> TRM_DEV LaneInfo adjoint_lane(const View<double>& v, int& ii, size_t& e) {
@@ -151,10 +193,10 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v
     if (viol && ln.act) atomicOr(v.status, viol);
 }
 
-// the transposed step at the state U (the tape's U_k): lam' -> lam
-template <int LPC>
+// the transposed step at the state U (the tape's U_k): lam' -> lam.  BCGRAD: and this step's terms onto `acc`
+template <int LPC, bool BCGRAD = false>
 TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, const LevelGeom<double>& L, const LaneInfo& ln, int ii,
-                            double U, double sat, double lam, double dt, double bTb, double bTt, bool generic) {
+                            double U, double sat, double lam, double dt, double bTb, double bTt, bool generic, BcGrad& acc) {
     // T, liq, C and kappa of the cell, as the tangent recomputes them
     uint32_t viol_in = 0;
     double liq, T;
@@ -197,6 +239,20 @@ TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, c
     const double pB_val_t = kt == 1 ? div_const(-pB_t, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top : 0.0;
     const double up_B = ln.is_top ? pB_val_t : -pB_sh;
     const double up_A = ln.is_top ? (mirror ? pA_t + pA_t : pA_t) : pA_sh;
+    if constexpr (BCGRAD) {
+        double tb = 0.0, tt = 0.0, ub = 0.0, ut = 0.0;
+        if (kb == 1) tb = -(div_const(pB, v.g.hdzf_bot, v.g.rhdzf_bot) * v.g.dzf_bot);
+        if (kb == 3) tb = pB * v.g.dzf_bot;
+        if (kt == 1) tt = div_const(pB_t, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top;
+        if (kt == 3) tt = pB_t * v.g.dzf_top;
+        const double lam_dt = lam * dt;
+        if (v.bc.kind[0][0] == 2) ub = flux_term_bottom(lam_dt, v.g);
+        if (v.bc.kind[0][1] == 2) ut = -flux_term_top(lam_dt, v.g);
+        acc.Tb = acc.Tb + (ln.is_bot ? tb : 0.0);
+        acc.Ub = acc.Ub + (ln.is_bot ? ub : 0.0);
+        acc.Tt = acc.Tt + (ln.is_top ? tt : 0.0);
+        acc.Ut = acc.Ut + (ln.is_top ? ut : 0.0);
+    }
     const double Tbar = own_B + up_B;
     const double kbar = own_A + up_A;
     // through the slopes: liq~ = c kappa~, U~ = a T~ + b liq~ (closure_tangent and conductivity_tangent are their own transposes)
@@ -225,9 +281,10 @@ TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, con
     }
 }
 
-// The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt
-template <int HYD, int LPC>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, AdjointArgs aa) {
+// The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
+// BCGRAD (Args = AdjointBcArgs): the boundary gradients ride along; the instances without are the code they were.
+template <int HYD, int LPC, bool BCGRAD = false, class Args = AdjointArgs>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args aa) {
     using NF = double;
     int ii;
     size_t e;
@@ -245,16 +302,22 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> 
     if (aa.fold) adjoint_fold(v, p, ln, e, sat, lam, aa.lT, aa.lliq);
     // Everything loaded so far is used here, in front of the loop: inside it the next slot's load is the only one in flight, and the wait
     // for it sits where its value is taken, behind the arithmetic of the step
-    asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt));
+    BcGrad acc;
+    if constexpr (BCGRAD) {
+        acc = bc_grad_load(aa.g, ii, aa.fold);
+        asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt), "v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub),
+                     "v"(acc.Ut));
+    } else asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt));
     for (int step = a.nsteps - 1; step >= 0; --step) {
         const NF U = U_next;
         if (step > 0) {
             slot -= aa.slot_elems;
             U_next = *slot;
         }
-        lam = adjoint_step<LPC>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic);
+        lam = adjoint_step<LPC, BCGRAD>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc);
     }
     if (ln.act) aa.lU[e] = lam;
+    if constexpr (BCGRAD) bc_grad_store(aa.g, ln, ii, acc);
 }
 
 }  // namespace trm

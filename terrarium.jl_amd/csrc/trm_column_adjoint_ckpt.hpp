@@ -29,11 +29,16 @@ struct CheckpointArgs {
     int fold;                 // backward: 1 in the first launch of a sweep
     int first, every;         // record: the step of the launch that stores first (>= nsteps: none does), and the interval K
 };
+// ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointBcArgs>: and the boundary-gradient accumulators (trm_column_adjoint.hpp)
+struct CheckpointBcArgs : CheckpointArgs {
+    BcGradPtrs g;
+};
 
 // lam pulled back through one segment: the checkpoint U_c at ca.tape and the a.nsteps - 1 states behind it under a.dt.
 // Dynamic LDS: a.nsteps * TRM_STEP_BLOCK doubles.
-template <int HYD, int LPC>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<double> v, DevParams<double> p, ColumnArgs<double> a, CheckpointArgs ca) {
+// BCGRAD (Args = CheckpointBcArgs): the boundary gradients as in k_column_adjoint, added in the same order -- the per-step tape's sums.
+template <int HYD, int LPC, bool BCGRAD = false, class Args = CheckpointArgs>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ca) {
     using NF = double;
     extern __shared__ double seg[];
     int ii;
@@ -54,6 +59,8 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<dou
     const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
     const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
     if (ca.fold) adjoint_fold(v, p, ln, e, sat, lam, ca.lT, ca.lliq);
+    BcGrad acc;
+    if constexpr (BCGRAD) acc = bc_grad_load(ca.g, ii, ca.fold);
 
     // ---- recompute: U_c ... U_{c+m-1} into LDS; nothing is stored to memory and no flag is raised (the record run has raised them)
     NF* mine = seg + threadIdx.x;
@@ -82,8 +89,9 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<dou
     if (m > 0) mine[(m - 1) * TRM_STEP_BLOCK] = c.U;
 
     // ---- backward: the transposed steps at U_{c+m-1} ... U_c
-    for (int j = m - 1; j >= 0; --j) lam = adjoint_step<LPC>(v, p, L, ln, ii, mine[j * TRM_STEP_BLOCK], sat, lam, a.dt, bTb, bTt, generic);
+    for (int j = m - 1; j >= 0; --j) lam = adjoint_step<LPC, BCGRAD>(v, p, L, ln, ii, mine[j * TRM_STEP_BLOCK], sat, lam, a.dt, bTb, bTt, generic, acc);
     if (ln.act) ca.lU[e] = lam;
+    if constexpr (BCGRAD) bc_grad_store(ca.g, ln, ii, acc);
 }
 
 }  // namespace trm

@@ -11,7 +11,13 @@
 //   conductivity kappa = s^2 with s = sum_i sqrt(k_i) theta_i:  dkappa = 2 s (sqrt(k_water) dwater + sqrt(k_ice) dice),
 //                dwater = sat por dliq = -dice (NoFlow: sat is constant); the dry halo cell of the reference-zero policy has dkappa = 0
 //   face flux    qT = -(kappa + kappa_m) / 2 * (T - T_m) * rdz: the product rule, halo values formed as the primal forms them
-//   step         dU' = dU + dgU * dt (boundary values are constants: their tangent is 0)
+//   step         dU' = dU + dgU * dt (boundary values are constants: their tangent is 0 -- unless BCSEED, below)
+// BCSEED (TangentBcArgs: trm_tangent_bc_upload has seeded a boundary value): the per-column seeds dbTb, dbTt of the temperature values
+// and dF_b, dF_t of the internal-energy fluxes enter where the primal reads the value,
+//   Value     dT_t = dT + div_const(dbTt - dT, dzf / 2) dzf,   dT_b = dT + div_const(dT - dbTb, dzf / 2) (-dzf)
+//   Gradient  dT_t = dT + dbTt dzf,   dT_b = dT + dbTb (-dzf)   (also where the primal knows a zero Gradient at the bottom and skips it)
+//   Flux      dU' = dU + (dgU + dflux_U) dt,  dflux_U = flux_term_bottom(dF_b) on the bottom lane, -flux_term_top(dF_t) on the top lane
+// and a pair whose kind reads no value has none.  The primal half is the same code.
 // Every tangent operation is linear in (dU, dT, dliq) with no additive constant, so scaling a seed by a power of two scales every
 // tangent bit for bit.
 #pragma once
@@ -23,6 +29,11 @@ namespace trm {
 struct TangentArgs {
     double *dU, *dT, *dliq;
     int generic;      // 1: Gradient on temperature off the branch-free kinds (k_step_wave's halos, column_tendencies_generic)
+};
+// ... of k_column_tangent<HYD, LPC, true, TangentBcArgs>: and the seeds of the boundary values, [Nh] each
+struct TangentBcArgs : TangentArgs {
+    const double *sTb, *sTt;   // d(temperature value) at the bottom / top: of a Value or a Gradient condition
+    const double *sUb, *sUt;   // d(internal-energy flux) at the bottom / top
 };
 
 // tangent of the energy closure at (U, sat) -- C is the heat capacity the primal closure formed
@@ -46,10 +57,12 @@ TRM_DEV double conductivity_tangent(const DevParams<double>& p, const Frac<doubl
 }
 
 // dgU: the tangent of column_tendencies' (or column_tendencies_generic's) heat tendency, without the constant boundary flux terms.
-// The primal intermediates (kappa, the halos) are formed again with the primal's operations.
-template <int LPC>
+// The primal intermediates (kappa, the halos) are formed again with the primal's operations.  BCSEED: dbTb, dbTt are the column's seeds of
+// the temperature boundary values (0 for a kind that reads none).
+template <int LPC, bool BCSEED = false>
 TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& p, const LevelGeom<double>& L, const LaneInfo& ln, int ii,
-                                const Cell<double>& c, double dT, double dliq, double bTb, double bTt, bool generic) {
+                                const Cell<double>& c, double dT, double dliq, double bTb, double bTt, bool generic, double dbTb = 0.0,
+                                double dbTt = 0.0) {
     const Frac<double> f = fractions_unchecked(p, c.sat, c.liq);
     const double kap = conductivity(p, f);
     const double dkap = conductivity_tangent(p, f, c.sat * p.por, dliq);
@@ -65,8 +78,15 @@ TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& 
         if (kb == 1) T_b = c.T + div_const_nsz(c.T - bTb, v.g.hdzf_bot, v.g.rhdzf_bot) * (-v.g.dzf_bot);
         if (kt == 1) T_t = c.T + div_const_nsz(bTt - c.T, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top;
     }
-    if (kb == 1) dT_b = dT + div_const(dT, v.g.hdzf_bot, v.g.rhdzf_bot) * (-v.g.dzf_bot);
-    if (kt == 1) dT_t = dT + div_const(-dT, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top;
+    if constexpr (BCSEED) {
+        if (kb == 1) dT_b = dT + div_const(dT - dbTb, v.g.hdzf_bot, v.g.rhdzf_bot) * (-v.g.dzf_bot);
+        if (kt == 1) dT_t = dT + div_const(dbTt - dT, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top;
+        if (kb == 3) dT_b = dT + dbTb * (-v.g.dzf_bot);
+        if (kt == 3) dT_t = dT + dbTt * v.g.dzf_top;
+    } else {
+        if (kb == 1) dT_b = dT + div_const(dT, v.g.hdzf_bot, v.g.rhdzf_bot) * (-v.g.dzf_bot);
+        if (kt == 1) dT_t = dT + div_const(-dT, v.g.hdzf_top, v.g.rhdzf_top) * v.g.dzf_top;
+    }
     // halo conductivity: the edge cell's under the mirror policy, the dry cell's (sat = 0: no water, no ice) otherwise
     const bool mirror = p.halo_policy == 1;
     const double kap_halo = mirror ? kap : conductivity(p, fractions_unchecked(p, 0.0, c.liq));
@@ -82,8 +102,9 @@ TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& 
 
 // `a.nsteps` ForwardEuler steps of the state and its tangent; the outputs are those of a finalizing trm_step (the tendency of the
 // last step, hydraulic_conductivity of the new state) and the three tangents.
-template <int HYD, int LPC>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> v, DevParams<double> p, ColumnArgs<double> a, TangentArgs ta) {
+// BCSEED (Args = TangentBcArgs): the boundary seeds are loaded once in front of the step loop; the instances without are the code they were.
+template <int HYD, int LPC, bool BCSEED = false, class Args = TangentArgs>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ta) {
     using NF = double;
     constexpr int CPW = 64 / LPC;
     LaneInfo ln;
@@ -145,6 +166,18 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
             bc.flux_U = ln.is_bot ? eU_b : tU_term;
         }
     }
+    // the seeds of the boundary values this column's kinds read: constants over the launch
+    NF dbTb = 0.0, dbTt = 0.0, dflux_U = 0.0;
+    if constexpr (BCSEED) {
+        const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
+        if (kb == 1 || kb == 3) dbTb = ta.sTb[ii];
+        if (kt == 1 || kt == 3) dbTt = ta.sTt[ii];
+        NF dU_b = 0.0, dU_t = 0.0;
+        if (v.bc.kind[0][0] == 2) dU_b = flux_term_bottom(ta.sUb[ii], v.g);
+        if (v.bc.kind[0][1] == 2) dU_t = -flux_term_top(ta.sUt[ii], v.g);
+        const NF top_term = ln.is_top ? dU_t : NF(0);
+        dflux_U = ln.is_bot ? dU_b : top_term;
+    }
 
     Cell<NF> n = c;
     Frac<NF> f_new{};
@@ -154,11 +187,12 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
         const Frac<NF>* pre = step > 0 ? &f_new : nullptr;
         const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
                                        : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
-        const NF dgU = tendency_tangent<LPC>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic);
+        const NF dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt);
         NF gU = t.gU, gS = t.gS, z0;
         column_advance<NF, false, LPC>(v, L, ln, Nz, bc, c.U, c.sat, gU, gS, a.dt, n, z0, bad);
         f_new = column_closure<NF, false, HYD>(p, L, z0, n, viol);
-        dU = dU + dgU * a.dt;
+        if constexpr (BCSEED) dU = dU + (dgU + dflux_U) * a.dt;
+        else dU = dU + dgU * a.dt;
         closure_tangent(p, n.U, n.sat, heat_capacity(p, f_new), dU, dliq, dT);
         gU_out = gU;
     }

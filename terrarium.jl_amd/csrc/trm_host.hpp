@@ -169,10 +169,18 @@ struct trm_ctx {
     // `tan_stale`: another call has changed the state since the tangent was seeded (trm_tangent_upload of dU clears it).
     double* d_tan[3] = {};
     bool tan_stale = false;
+    // the seeds of the boundary values (trm_tangent_bc_upload), [Nh] doubles each: d(temperature value) bottom, top, d(internal-energy
+    // flux) bottom, top.  Allocated by the first upload, zeroed by trm_tangent_open; `tan_bc_seeded`: one has been uploaded since
+    // trm_tangent_open, and trm_step_tangent runs the seeded instances.  Seeds are not state: nothing makes them stale.
+    double* d_tan_bc[4] = {};
+    bool tan_bc_seeded = false;
     // reverse-mode gradients (trm_adjoint_*): the cotangent fields of U, T, liq in the same layout, and the tape of trm_step_record --
     // `tape_cap` slots of [Nh][Nzp] doubles, slot k the internal energy before taped step k, `tape_dt[k]` that step's dt.  `adj_stale`:
     // another call has changed the state or a boundary condition since the first taped step (state_changed / bc_changed below).
     double* d_adj[3] = {};
+    // the boundary-gradient accumulators (trm_adjoint_bc_open), [Nh] doubles each, in the order of d_tan_bc; null: the sweep runs the
+    // instances without
+    double* d_adj_bc[4] = {};
     double* d_tape = nullptr;
     int tape_cap = 0;
     std::vector<double> tape_dt;
@@ -538,12 +546,14 @@ template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx
 // k_column_tangent / k_closure_tangent (trm_launch_column_tangent.hip, fp64 NoFlow only)
 struct TangentLaunch {
     static int step(trm_ctx* c, double dt, int nsteps);
+    static int step_bc(trm_ctx* c, double dt, int nsteps);   // with boundary seeds (trm_launch_column_tangent_bc.hip)
     static int closure(trm_ctx* c);
 };
 // k_column_record / k_column_adjoint (trm_launch_column_adjoint.hip, fp64 NoFlow only): `slot` is the tape slot of the launch's first step
 struct AdjointLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot);
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int backward_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // with boundary gradients (trm_launch_column_adjoint_bc.hip)
 };
 // the strided k_column_record / k_column_adjoint_ckpt (trm_launch_column_adjoint_ckpt.hip): the record stores before the steps `first`,
 // `first + every`, ... of the launch into the slots from `slot` on; the backward launch pulls lam through the segment of `nsteps`
@@ -551,6 +561,7 @@ struct AdjointLaunch {
 struct CheckpointLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int backward_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // with boundary gradients (trm_launch_column_adjoint_ckpt_bc.hip)
 };
 // k_materialize_closure (trm_launch_materialize.hip)
 template <class NF> struct MaterializeLaunch { static int run(trm_ctx* c); };

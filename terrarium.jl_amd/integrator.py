@@ -427,6 +427,14 @@ class DeviceState:
         a[...] = value
         self._check(self._lib.trm_tangent_upload(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_tangent_upload")
 
+    def set_bc_tangent(self, var, side, values):
+        """Seeds the boundary value of (`var`, `side`) -- `temperature` (a Value or a Gradient condition) or `internal_energy` (a Flux),
+        `bottom` or `top`: [Nh], or a scalar for every column (trm_tangent_bc_upload).  The seed holds for every step_tangent until
+        open_tangent zeroes it; a pair whose kind reads no value contributes nothing."""
+        a = np.empty(self.grid.Nh, dtype=np.float64)
+        a[...] = values
+        self._check(self._lib.trm_tangent_bc_upload(self._ctx, _capi.BC_VAR[var], _capi.SIDE[side], a.ctypes.data), "trm_tangent_bc_upload")
+
     def tangent(self, name) -> np.ndarray:
         """A tangent field as [Nz][Nh] (row 0 = bottom layer)."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
@@ -467,6 +475,17 @@ class DeviceState:
         """A cotangent field as [Nz][Nh] (row 0 = bottom layer); after adjoint_backward `internal_energy` is dL/dU_0."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
         self._check(self._lib.trm_adjoint_download(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_adjoint_download")
+        return a
+
+    def open_bc_gradient(self):
+        """From now on adjoint_backward also forms dL/d(boundary value) per column (trm_adjoint_bc_open); needs an open adjoint."""
+        self._check(self._lib.trm_adjoint_bc_open(self._ctx), "trm_adjoint_bc_open")
+
+    def bc_gradient(self, var, side) -> np.ndarray:
+        """dL/d(value) of the boundary condition on (`var`, `side`) as [Nh], after adjoint_backward: `temperature` (a Value or a
+        Gradient condition) or `internal_energy` (a Flux).  Zeros where the pair's kind reads no value (trm_adjoint_bc_download)."""
+        a = np.empty(self.grid.Nh, dtype=np.float64)
+        self._check(self._lib.trm_adjoint_bc_download(self._ctx, _capi.BC_VAR[var], _capi.SIDE[side], a.ctypes.data), "trm_adjoint_bc_download")
         return a
 
     def step_record(self, dt, nsteps=1):
@@ -880,10 +899,16 @@ class ModelIntegrator:
             any(callable(v) for v in self.inputs.values())
 
 
-def jvp(integ: ModelIntegrator, d_internal_energy, steps: int) -> dict:
+# the (variable, side) pairs whose boundary value the heat-only step reads, and the kinds that read it
+_BOUNDARY_DERIVATIVE_KINDS = {"temperature": ("value", "gradient"), "internal_energy": ("flux",)}
+
+
+def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None) -> dict:
     """Forward-mode derivative of `run!(integ; steps)` with respect to the initial internal energy: the integrator is stepped `steps`
     times with its own dt, its state carrying the tangent seeded by `d_internal_energy` ([Nz][Nh], or anything that broadcasts to
     it).  Returns {"internal_energy", "temperature", "liquid_water_fraction"}: the tangents of those fields after the last step.
+    `d_boundary` = {(var, side): values}: seeds d(value) of boundary conditions, [Nh] or a scalar each -- a Value or a Gradient on
+    `temperature`, a Flux on `internal_energy` -- held over the run like the values themselves (trm_tangent_bc_upload).
     The heat-only SoilModel in fp64 with ForwardEuler and constant boundary conditions and inputs (trm_step_tangent)."""
     if not isinstance(integ.timestepper, ForwardEuler):
         raise ValueError("jvp: ForwardEuler only")
@@ -895,6 +920,8 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int) -> dict:
         st.open_tangent()
     try:
         st.set_tangent("internal_energy", d_internal_energy)
+        for (var, side), values in (d_boundary or {}).items():
+            st.set_bc_tangent(var, side, values)
         st.step_tangent(integ.timestepper.dt, int(steps))
         return {name: st.tangent(name) for name in _capi.TANGENT}
     finally:
@@ -903,12 +930,15 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int) -> dict:
 
 
 def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=None, liquid_water_fraction=None,
-        checkpoint_every=None) -> np.ndarray:
+        checkpoint_every=None, wrt_boundary=False):
     """Reverse-mode derivative of `run!(integ; steps)`: the integrator is stepped `steps` times with its own dt (state and clock end
     where `run` leaves them), then the given cotangents of the final temperature, internal energy and liquid water fraction ([Nz][Nh],
     or anything that broadcasts to it; None: zero) are pulled back.  Returns dL/dU_0 as [Nz][Nh], L the sum of the three inner
     products.  One tape slot per step (trm_step_record, trm_adjoint_backward); with `checkpoint_every` = K one slot per K steps, the
-    states in between formed again by the backward sweep -- the same gradient bit for bit.  The coverage and refusals of `jvp`."""
+    states in between formed again by the backward sweep -- the same gradient bit for bit.  The coverage and refusals of `jvp`.
+    With `wrt_boundary` it returns (dL/dU_0, {(var, side): dL/d(value) as [Nh]}) for the boundary conditions of the integrator whose
+    value the run reads -- a Value or a Gradient on `temperature`, a Flux on `internal_energy` -- from the same sweep
+    (trm_adjoint_bc_open)."""
     if not isinstance(integ.timestepper, ForwardEuler):
         raise ValueError("vjp: ForwardEuler only")
     if integ._has_time_dependence() or integ._windowed():
@@ -928,8 +958,14 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
         st.step_record(integ.timestepper.dt, steps)
         for name, w in (("internal_energy", internal_energy), ("temperature", temperature), ("liquid_water_fraction", liquid_water_fraction)):
             st.set_cotangent(name, 0.0 if w is None else w)
+        if wrt_boundary:
+            st.open_bc_gradient()
         st.adjoint_backward()
-        return st.cotangent("internal_energy")
+        g = st.cotangent("internal_energy")
+        if not wrt_boundary:
+            return g
+        pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
+        return g, {(var, side): st.bc_gradient(var, side) for var, side in pairs}
     finally:
         if opened:
             st.close_adjoint()
