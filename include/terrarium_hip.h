@@ -260,6 +260,10 @@ enum {
  * (trm_average_open) -- by the step launch itself (the resident multi-step program), or by a k_accumulate launch behind it.  Neither is
  * set while no accumulator is open. */
 enum { TRM_PROGRAM_AVERAGES_IN_LAUNCH = 268435456 /* 1 << 28 */, TRM_PROGRAM_AVERAGES_AFTER_LAUNCH = 536870912 /* 1 << 29 */ };
+/* ... and bit 31, the last one the two derivative families leave free (25-27 and 30 are taken there, 28-29 above): the launch carried
+ * seeds on, or formed the gradient with respect to, the thermal parameters (trm_tangent_param_set, trm_adjoint_param_open).  The id is an
+ * int: with this bit it reads as a negative number, and the bits are those of its two's complement. */
+enum { TRM_PROGRAM_PARAMETERS = (-2147483647 - 1) /* bit 31 */ };
 enum {
     TRM_KERNEL_FUSED = 0,       /* one launch per step: lane = soil level, a column per (half-)wavefront,     */
                                 /* wavefront shuffles for the vertical stencil (Nz <= 64; two levels per lane */
@@ -637,11 +641,30 @@ int trm_step_tangent(trm_ctx* ctx, double dt, int nsteps);
  * bit 26.  The state afterwards is still that of trm_step, bit for bit, and zero seeds give the tangents of the unseeded run.
  * Errors: TRM_EINVAL without a context or an open tangent, for any other bc_var, a side other than 0 / 1, or a NULL pointer. */
 int trm_tangent_bc_upload(trm_ctx* ctx, int bc_var, int side, const void* host);
+/* Seeds on the thermal parameters: the tangent with respect to the five conductivities and five heat capacities of trm_params
+ * (SoilThermalConductivities, SoilHeatCapacities; Enzyme gives the reference these through Duplicated(integrator, dintegrator)), in the
+ * order of trm_params.  Porosity, rho_soc, Lsl and the saturation are not differentiated.
+ *   trm_tangent_param_set(ctx, seed)        seed[TRM_THERMAL_PARAM_COUNT] doubles, d(parameter); the same for every column.  They are
+ *                                           constants like the boundary seeds: not state, nothing makes them stale, trm_tangent_open
+ *                                           zeroes them.  The call allocates the four boundary seed arrays (zero) if no
+ *                                           trm_tangent_bc_upload has: parameter seeds always ride with the boundary-seeded instances.
+ * Once it has been called since trm_tangent_open, trm_step_tangent runs the parameter-seeded instances (TRM_INFO_LAST_PROGRAM: bits 26
+ * and 31, TRM_PROGRAM_PARAMETERS), and trm_tangent_closure and the incoming closure of trm_step_tangent add the heat-capacity term
+ * dT += -(T / C) dC.  The state afterwards is still that of trm_step, bit for bit; ten zero seeds give the tangents of the unseeded run.
+ * Errors: TRM_EUNSUPPORTED where the tangent is; TRM_EINVAL without a context or an open tangent, for a NULL pointer, and when one of
+ * the five conductivities is <= 0 (the kernels hold sqrt(k), which has no derivative there). */
+enum {
+    TRM_THERMAL_PARAM_K_WATER = 0, TRM_THERMAL_PARAM_K_ICE = 1, TRM_THERMAL_PARAM_K_AIR = 2, TRM_THERMAL_PARAM_K_MINERAL = 3,
+    TRM_THERMAL_PARAM_K_ORGANIC = 4, TRM_THERMAL_PARAM_C_WATER = 5, TRM_THERMAL_PARAM_C_ICE = 6, TRM_THERMAL_PARAM_C_AIR = 7,
+    TRM_THERMAL_PARAM_C_MINERAL = 8, TRM_THERMAL_PARAM_C_ORGANIC = 9, TRM_THERMAL_PARAM_COUNT = 10
+};
+int trm_tangent_param_set(trm_ctx* ctx, const double seed[TRM_THERMAL_PARAM_COUNT]);
 
 /* ---- reverse-mode gradients of the heat-only run (the reference pulls a seed back through run! with Enzyme's Reverse mode) ---------
  * The gradient g = dL/dU_0 of L = <wU, U_n> + <wT, T_n> + <wliq, liq_n> with respect to the initial internal energy, for what the
  * tangent covers (above): the transpose of the linear map trm_step_tangent applies, one backward sweep for any number of inputs.
- * Parameters are constants; the gradient with respect to the boundary values comes from trm_adjoint_bc_open (below).
+ * The gradient with respect to the boundary values comes from trm_adjoint_bc_open, with respect to the thermal parameters from
+ * trm_adjoint_param_open (both below); every other parameter is a constant.
  *   trm_adjoint_open(ctx, capacity_steps)   allocates the cotangent fields of U, T, liq (zero) and a tape of capacity_steps slots; one
  *                                           slot is Nh x Nzp x 8 bytes (the internal energy before a step).  Opening again starts a
  *                                           fresh tape and zeroes the cotangents.
@@ -721,6 +744,27 @@ int trm_adjoint_backward(trm_ctx* ctx);
 int trm_adjoint_bc_open(trm_ctx* ctx);
 int trm_adjoint_bc_download(trm_ctx* ctx, int bc_var, int side, void* host);
 int trm_adjoint_bc_device_ptr(trm_ctx* ctx, int bc_var, int side, void** dev);
+/* Parameter gradients: dL/d(parameter) of the ten thermal parameters trm_tangent_param_set seeds (TRM_THERMAL_PARAM_*), per column, from
+ * the same sweep.
+ *   trm_adjoint_param_open(ctx)             allocates eight per-cell accumulators (Nh x Nzp doubles each) and the result, zero, and
+ *                                           implies trm_adjoint_bc_open: from then on trm_adjoint_backward runs the instances that
+ *                                           accumulate both (TRM_INFO_LAST_PROGRAM: bits 30 and 31) on either tape, and ends with one
+ *                                           reduction launch.  trm_adjoint_open keeps them (zeroed); trm_adjoint_close frees them.
+ *   trm_adjoint_param_download(ctx, which, host)
+ *                                           host[num_columns] doubles.  After a trm_adjoint_backward that succeeded: dL/d(parameter
+ *                                           `which`) of each column's share of L (the parameter is one number for all columns: their
+ *                                           sum is the gradient of the scalar L).  After a sweep that failed the content is unspecified.
+ *   trm_adjoint_param_device_ptr(ctx, which, &dev)
+ *                                           the same on the device, num_columns contiguous doubles
+ * Every lane sums its own cell's terms over the taped steps newest first, carried from launch to launch; the reduction adds a column's
+ * cells from the bottom up.  The sums do not depend on TRM_OPT_STEPS_PER_LAUNCH or on the checkpoint interval, and g = dL/dU_0 and the
+ * boundary gradients are bit for bit what the sweep without parameter gradients gives.
+ * Errors: TRM_EUNSUPPORTED where the adjoint is; TRM_EINVAL without a context or an open adjoint, for _download / _device_ptr before
+ * trm_adjoint_param_open, a `which` outside 0 ... TRM_THERMAL_PARAM_COUNT - 1, a NULL pointer, and for trm_adjoint_param_open when one
+ * of the five conductivities is <= 0; TRM_ENOMEM. */
+int trm_adjoint_param_open(trm_ctx* ctx);
+int trm_adjoint_param_download(trm_ctx* ctx, int which, void* host);
+int trm_adjoint_param_device_ptr(trm_ctx* ctx, int which, void** dev);
 
 int trm_clock(const trm_ctx* ctx, double* time, int64_t* iteration);
 int trm_set_clock(trm_ctx* ctx, double time, int64_t iteration);

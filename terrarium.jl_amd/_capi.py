@@ -66,6 +66,7 @@ DERIVE = ("none", "T_liq", "liq", "liq_psi", "all")
 
 
 def decode_program(pid: int) -> dict:
+    pid &= 0xffffffff          # (the id is a C int: with TRM_PROGRAM_PARAMETERS, bit 31, it arrives negative)
     d = dict(family=PROGRAM[pid & 0xff], hydraulics=("default", "vg_n2", "generic")[(pid >> 8) & 3], lanes_per_column=32 * ((pid >> 10) & 3),
              derive=DERIVE[(pid >> 12) & 7], staged=bool((pid >> 15) & 1), scalar_inputs=bool((pid >> 16) & 1), bc_signature=((pid >> 17) & 0xff) - 1)
     extra = pid >> 25
@@ -74,9 +75,10 @@ def decode_program(pid: int) -> dict:
     if d["family"] == "column_land":
         d.update(program=("euler", "heun", "multi")[extra & 3])
     if d["family"] == "column_tangent":
-        d.update(generic_boundaries=bool(extra & 1), boundary_seeds=bool(extra & 2))
+        d.update(generic_boundaries=bool(extra & 1), boundary_seeds=bool(extra & 2), parameter_seeds=bool(pid & PROGRAM_PARAMETERS))
     if d["family"] == "column_adjoint":
-        d.update(generic_boundaries=bool(extra & 1), backward=bool(extra & 2), checkpointed=bool(extra & 4), boundary_gradient=bool(extra & 32))
+        d.update(generic_boundaries=bool(extra & 1), backward=bool(extra & 2), checkpointed=bool(extra & 4), boundary_gradient=bool(extra & 32),
+                 parameter_gradient=bool(pid & PROGRAM_PARAMETERS))
     if d["family"] in ("deep", "wide"):
         d.update(program=("euler", "heun", "multi")[extra & 3], generic_boundaries=bool(extra & 4))
     if pid & (PROGRAM_AVERAGES_IN_LAUNCH | PROGRAM_AVERAGES_AFTER_LAUNCH):
@@ -84,6 +86,8 @@ def decode_program(pid: int) -> dict:
     return d
 # TRM_PROGRAM_AVERAGES_*: how the last step accumulated the open time averages (trm_average_open)
 PROGRAM_AVERAGES_IN_LAUNCH, PROGRAM_AVERAGES_AFTER_LAUNCH = 1 << 28, 1 << 29
+# TRM_PROGRAM_PARAMETERS: a derivative launch that carried the thermal parameters (trm_tangent_param_set, trm_adjoint_param_open)
+PROGRAM_PARAMETERS = 1 << 31
 STATUS_NAN, STATUS_COMPOSITION, STATUS_HANDOFF_TIMEOUT = 1, 2, 4
 TRM_OK, TRM_EINVAL, TRM_EHIP, TRM_ENOMEM, TRM_EUNSUPPORTED, TRM_ESTALE, TRM_ECOMM = range(7)
 
@@ -105,7 +109,10 @@ EXPORTS = (
     "trm_step_tangent "
     "trm_adjoint_open trm_adjoint_close trm_adjoint_upload trm_adjoint_download trm_adjoint_device_ptr trm_adjoint_tape "
     "trm_step_record trm_adjoint_backward trm_adjoint_open_checkpointed trm_adjoint_checkpoints "
-    "trm_tangent_bc_upload trm_adjoint_bc_open trm_adjoint_bc_download trm_adjoint_bc_device_ptr").split()
+    "trm_tangent_bc_upload trm_adjoint_bc_open trm_adjoint_bc_download trm_adjoint_bc_device_ptr "
+    "trm_tangent_param_set trm_adjoint_param_open trm_adjoint_param_download trm_adjoint_param_device_ptr").split()
+# the thermal parameters the tangent and the adjoint differentiate (TRM_THERMAL_PARAM_*), in the order of trm_params
+THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
 # forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
 TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
 # the checkpointed tape of the adjoint (trm_adjoint_open_checkpointed): TRM_ADJOINT_MAX_INTERVAL, TRM_ADJOINT_DEFAULT_INTERVAL
@@ -278,6 +285,10 @@ def lib():
     L.trm_adjoint_bc_open.argtypes = [vp]
     L.trm_adjoint_bc_download.argtypes = [vp, i32, i32, vp]
     L.trm_adjoint_bc_device_ptr.argtypes = [vp, i32, i32, C.POINTER(vp)]
+    L.trm_tangent_param_set.argtypes = [vp, C.POINTER(C.c_double)]
+    L.trm_adjoint_param_open.argtypes = [vp]
+    L.trm_adjoint_param_download.argtypes = [vp, i32, vp]
+    L.trm_adjoint_param_device_ptr.argtypes = [vp, i32, C.POINTER(vp)]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

@@ -1650,6 +1650,9 @@ int trm_destroy(trm_ctx* c) {
         if (q) (void)hipFree(q);
     for (double* q : c->d_adj_bc)
         if (q) (void)hipFree(q);
+    for (double* q : c->d_adj_param)
+        if (q) (void)hipFree(q);
+    if (c->d_adj_param_out) (void)hipFree(c->d_adj_param_out);
     if (c->d_tape) (void)hipFree(c->d_tape);
 
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -2463,6 +2466,13 @@ int bc_pair_index(int bc_var, int side) {
     if (bc_var == TRM_BCV_INTERNAL_ENERGY) return side == TRM_TOP ? 3 : 2;
     return -1;
 }
+// the square roots of the five conductivities have no derivative at 0
+const char* thermal_params_not_differentiable(const trm_ctx* c) {
+    const trm_params& q = c->params;
+    if (!(q.k_water > 0.0 && q.k_ice > 0.0 && q.k_air > 0.0 && q.k_mineral > 0.0 && q.k_organic > 0.0))
+        return "every thermal conductivity must be > 0 (sqrt has no derivative at 0)";
+    return nullptr;
+}
 const char* kStaleTangent = ": the state has changed since the tangent was seeded: trm_tangent_upload a new dU first";
 }  // namespace
 
@@ -2477,6 +2487,8 @@ int trm_tangent_open(trm_ctx* c) {
     for (double* q : c->d_tan_bc)
         if (q) TRM_HIP(c, hipMemsetAsync(q, 0, (size_t)c->Nh * sizeof(double), c->stream));
     c->tan_bc_seeded = false;
+    std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
+    c->tan_param_seeded = false;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     c->tan_stale = false;      // (a zero seed: zero tangents)
     return TRM_OK;
@@ -2494,27 +2506,54 @@ int trm_tangent_close(trm_ctx* c) {
         q = nullptr;
     }
     c->tan_bc_seeded = false;
+    std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
+    c->tan_param_seeded = false;
     c->tan_stale = false;
     return TRM_OK;
 }
-int trm_tangent_bc_upload(trm_ctx* c, int bc_var, int side, const void* host) {
-    TRM_ENTER_HEUN(c);
-    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: no tangent is open (trm_tangent_open)");
-    const int slot = bc_pair_index(bc_var, side);
-    if (slot < 0 || !host) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: bad argument (internal energy or temperature, bottom or top)");
+namespace {
+// the four boundary seed arrays, zeroed where this call allocates them
+int alloc_tangent_bc_seeds(trm_ctx* c, const char* who) {
     const size_t bytes = (size_t)c->Nh * sizeof(double);
     for (double*& q : c->d_tan_bc)
         if (!q) {
             if (hipMalloc((void**)&q, bytes) != hipSuccess) {
                 (void)hipGetLastError();
                 q = nullptr;
-                return fail(c, TRM_ENOMEM, "trm_tangent_bc_upload: the seed arrays do not fit");
+                return fail(c, TRM_ENOMEM, std::string(who) + ": the seed arrays do not fit");
             }
             TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
         }
+    return TRM_OK;
+}
+}  // namespace
+int trm_tangent_bc_upload(trm_ctx* c, int bc_var, int side, const void* host) {
+    TRM_ENTER_HEUN(c);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: no tangent is open (trm_tangent_open)");
+    const int slot = bc_pair_index(bc_var, side);
+    if (slot < 0 || !host) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: bad argument (internal energy or temperature, bottom or top)");
+    const size_t bytes = (size_t)c->Nh * sizeof(double);
+    if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_bc_upload")) return rc;
     TRM_HIP(c, hipMemcpyAsync(c->d_tan_bc[slot], host, bytes, hipMemcpyHostToDevice, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     c->tan_bc_seeded = true;   // (seeds are not state: tan_stale stays as it is)
+    return TRM_OK;
+}
+int trm_tangent_param_set(trm_ctx* c, const double seed[TRM_THERMAL_PARAM_COUNT]) {
+    TRM_ENTER_HEUN(c);
+    // (a context the tangent does not cover has none open: it is told why, not to open one)
+    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_param_set: ") + why);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_param_set: no tangent is open (trm_tangent_open)");
+    if (!seed) return fail(c, TRM_EINVAL, "trm_tangent_param_set: bad argument");
+    if (const char* why = thermal_params_not_differentiable(c)) return fail(c, TRM_EINVAL, std::string("trm_tangent_param_set: ") + why);
+    if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_param_set")) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    // the chain rule to the eight numbers the kernels hold (thermal_param_chain): a sum per derived number, in the order of trm_params
+    double w[TRM_THERMAL_PARAM_COUNT];
+    thermal_param_chain(c->params, launch_args<double>(c).p, w);
+    std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
+    for (int q = 0; q < TRM_THERMAL_PARAM_COUNT; ++q) c->tan_param[thermal_param_target(q)] += w[q] * seed[q];
+    c->tan_param_seeded = true;   // (seeds are not state: tan_stale stays as it is)
     return TRM_OK;
 }
 int trm_tangent_upload(trm_ctx* c, int which, const void* host) {
@@ -2558,7 +2597,7 @@ int trm_tangent_closure(trm_ctx* c) {
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_closure: no tangent is open (trm_tangent_open)");
     if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_closure: ") + why);
     if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_closure") + kStaleTangent);
-    return finish(c, TangentLaunch::closure(c));
+    return finish(c, c->tan_param_seeded ? TangentLaunch::closure_param(c) : TangentLaunch::closure(c));
 }
 int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     TRM_ENTER(c);
@@ -2573,7 +2612,7 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     while (n < nsteps) {
         const int m = std::min(spl, nsteps - n);
         int rc = Ops<double>::update_inputs(c, c->state, c->time);
-        if (!rc) rc = c->tan_bc_seeded ? TangentLaunch::step_bc(c, dt, m) : TangentLaunch::step(c, dt, m);
+        if (!rc) rc = c->tan_param_seeded ? TangentLaunch::step_param(c, dt, m) : c->tan_bc_seeded ? TangentLaunch::step_bc(c, dt, m) : TangentLaunch::step(c, dt, m);
         if (rc) return rc;
         tick(c, dt, m);
         n += m;
@@ -2602,6 +2641,14 @@ void free_tape(trm_ctx* c) {
     c->tape_segs.clear();
     c->adj_stale = false;
 }
+void free_adjoint_params(trm_ctx* c) {
+    for (double*& q : c->d_adj_param) {
+        if (q) (void)hipFree(q);
+        q = nullptr;
+    }
+    if (c->d_adj_param_out) (void)hipFree(c->d_adj_param_out);
+    c->d_adj_param_out = nullptr;
+}
 void free_adjoint(trm_ctx* c) {
     for (double*& q : c->d_adj) {
         if (q) (void)hipFree(q);
@@ -2611,6 +2658,7 @@ void free_adjoint(trm_ctx* c) {
         if (q) (void)hipFree(q);
         q = nullptr;
     }
+    free_adjoint_params(c);
     free_tape(c);
 }
 // steps on the tape, per-step or checkpointed
@@ -2647,6 +2695,9 @@ int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who)
     }
     for (double* q : c->d_adj_bc)   // (opening again keeps open boundary gradients, zero)
         if (q) TRM_HIP(c, hipMemsetAsync(q, 0, (size_t)c->Nh * sizeof(double), c->stream));
+    for (double* q : c->d_adj_param)   // (... and open parameter gradients)
+        if (q) TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+    if (c->d_adj_param_out) TRM_HIP(c, hipMemsetAsync(c->d_adj_param_out, 0, (size_t)TRM_THERMAL_PARAM_COUNT * (size_t)c->Nh * sizeof(double), c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     c->tape_dt.clear();        // (a fresh tape)
     c->tape_segs.clear();
@@ -2723,6 +2774,55 @@ int trm_adjoint_bc_device_ptr(trm_ctx* c, int bc_var, int side, void** dev) {
     int slot = -1;
     if (int rc = adjoint_bc_args(c, bc_var, side, dev, "trm_adjoint_bc_device_ptr", slot)) return rc;
     *dev = c->d_adj_bc[slot];
+    return TRM_OK;
+}
+int trm_adjoint_param_open(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    // (a context the adjoint does not cover has none open: it is told why, not to open one)
+    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_param_open: ") + why);
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_param_open: no adjoint is open (trm_adjoint_open)");
+    if (const char* why = thermal_params_not_differentiable(c)) return fail(c, TRM_EINVAL, std::string("trm_adjoint_param_open: ") + why);
+    if (int rc = trm_adjoint_bc_open(c)) return rc;   // (the accumulating instances carry both)
+    const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double), out_bytes = (size_t)TRM_THERMAL_PARAM_COUNT * (size_t)c->Nh * sizeof(double);
+    bool ok = true;
+    for (double*& q : c->d_adj_param)
+        if (ok && !q && hipMalloc((void**)&q, bytes) != hipSuccess) {
+            q = nullptr;
+            ok = false;
+        }
+    if (ok && !c->d_adj_param_out && hipMalloc((void**)&c->d_adj_param_out, out_bytes) != hipSuccess) {
+        c->d_adj_param_out = nullptr;
+        ok = false;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        free_adjoint_params(c);
+        return fail(c, TRM_ENOMEM, "trm_adjoint_param_open: the accumulators do not fit");
+    }
+    for (double* q : c->d_adj_param) TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+    TRM_HIP(c, hipMemsetAsync(c->d_adj_param_out, 0, out_bytes, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+namespace {
+int adjoint_param_args(trm_ctx* c, int which, const void* ptr, const char* who) {
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no adjoint is open (trm_adjoint_open)");
+    if (!c->d_adj_param_out) return fail(c, TRM_EINVAL, std::string(who) + ": no parameter gradients are open (trm_adjoint_param_open)");
+    if (which < 0 || which >= TRM_THERMAL_PARAM_COUNT || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument (TRM_THERMAL_PARAM_*)");
+    return TRM_OK;
+}
+}  // namespace
+int trm_adjoint_param_download(trm_ctx* c, int which, void* host) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = adjoint_param_args(c, which, host, "trm_adjoint_param_download")) return rc;
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_adj_param_out + (size_t)which * (size_t)c->Nh, (size_t)c->Nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_param_device_ptr(trm_ctx* c, int which, void** dev) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = adjoint_param_args(c, which, dev, "trm_adjoint_param_device_ptr")) return rc;
+    *dev = c->d_adj_param_out + (size_t)which * (size_t)c->Nh;
     return TRM_OK;
 }
 int trm_adjoint_upload(trm_ctx* c, int which, const void* host) {
@@ -2840,8 +2940,9 @@ int trm_adjoint_backward(trm_ctx* c) {
         size_t s = c->tape_segs.size();
         do {
             const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
-            if (int rc = c->d_adj_bc[0] ? CheckpointLaunch::backward_bc(c, seg.dt, seg.len, seg.slot, fold)
-                                        : CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold)) {
+            if (int rc = c->d_adj_param_out ? CheckpointLaunch::backward_param(c, seg.dt, seg.len, seg.slot, fold)
+                         : c->d_adj_bc[0]   ? CheckpointLaunch::backward_bc(c, seg.dt, seg.len, seg.slot, fold)
+                                            : CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold)) {
                 c->adj_stale = true;       // (lam is part way down the tape)
                 return rc;
             }
@@ -2850,7 +2951,7 @@ int trm_adjoint_backward(trm_ctx* c) {
         } while (s > 0);
         c->tape_segs.clear();
         c->adj_stale = false;
-        return finish(c, TRM_OK);
+        return finish(c, c->d_adj_param_out ? AdjointLaunch::param_reduce(c) : TRM_OK);
     }
     // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch folds
     // the cotangents of T and liq in (an empty tape: that launch alone)
@@ -2860,7 +2961,9 @@ int trm_adjoint_backward(trm_ctx* c) {
         int begin = end;
         while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
         const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
-        if (int rc = c->d_adj_bc[0] ? AdjointLaunch::backward_bc(c, dt_block, end - begin, begin, fold) : AdjointLaunch::backward(c, dt_block, end - begin, begin, fold)) {
+        if (int rc = c->d_adj_param_out ? AdjointLaunch::backward_param(c, dt_block, end - begin, begin, fold)
+                     : c->d_adj_bc[0]   ? AdjointLaunch::backward_bc(c, dt_block, end - begin, begin, fold)
+                                        : AdjointLaunch::backward(c, dt_block, end - begin, begin, fold)) {
             c->adj_stale = true;       // (lam is part way down the tape)
             return rc;
         }
@@ -2869,7 +2972,7 @@ int trm_adjoint_backward(trm_ctx* c) {
     } while (end > 0);
     c->tape_dt.clear();
     c->adj_stale = false;
-    return finish(c, TRM_OK);
+    return finish(c, c->d_adj_param_out ? AdjointLaunch::param_reduce(c) : TRM_OK);
 }
 
 int trm_clock(const trm_ctx* c, double* time, int64_t* iteration) {

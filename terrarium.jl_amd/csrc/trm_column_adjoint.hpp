@@ -19,6 +19,15 @@
 // summed in registers of the edge lanes over the taped steps, newest first: the launch that folds starts from 0, every other launch from
 // what the launch before stored, and the owning edge lane stores once at the end -- one strictly sequential sum per column and pair,
 // whatever the split into launches or segments.  No atomics.  lam is formed by the operations it was.
+// PGRAD (trm_adjoint_param_open, always with BCGRAD): the sweep also forms the cotangents of the eight thermal numbers of DevParams, the
+// transposes of the seed terms of k_column_tangent<.., PSEED>, per cell: with T~ and kappa~ of the cell as above, m = -(T / C) and s of
+// kappa = s^2,
+//   C~ = m T~        onto c_water (x water), c_ice (x ice), c_air (x air), C0          (the fold: m wT of the stored state)
+//   s~ = 2 s kappa~  onto sk_water (x water), sk_ice (x ice), sk_air (x air), s0
+//   dry halo (reference-zero policy): 2 s_halo pA on the bottom lane, 2 s_halo pA_t on the top lane, onto s0 and (x por) sk_air
+// Each lane sums its own cell's eight values in registers over the taped steps, newest first, carried from launch to launch in eight
+// fields [Nh][Nzp] like the boundary sums: strictly sequential per cell.  k_param_reduce sums a column's cells in ascending order and
+// applies the host's chain rule to the ten parameters.
 // Every coefficient is a function of the state U_k BEFORE step k: k_column_record is the multi-step primal that stores U_k into tape
 // slot k (the field layout [Nh][Nzp]) before every step; k_column_adjoint walks a block of slots backwards with lam in registers.
 // closure_tangent and conductivity_tangent are linear in their seed, one scalar slope per cell: applied to a cotangent they are their
@@ -74,6 +83,55 @@ TRM_DEV void bc_grad_store(const BcGradPtrs& g, const LaneInfo& ln, int ii, cons
         g.gTt[ii] = acc.Tt;
         g.gUt[ii] = acc.Ut;
     }
+}
+
+// the per-cell parameter accumulators of a PGRAD sweep, [Nh][Nzp] each, in the order of ParamSeeds
+struct ParamGradPtrs {
+    double* g[8];
+};
+// ... of k_column_adjoint<HYD, LPC, true, AdjointParamArgs, true>
+struct AdjointParamArgs : AdjointBcArgs {
+    ParamGradPtrs pg;
+};
+// a lane's running sums for its own cell
+struct ParamGrad {
+    double sk_water = 0.0, sk_ice = 0.0, sk_air = 0.0, s0 = 0.0;
+    double c_water = 0.0, c_ice = 0.0, c_air = 0.0, C0 = 0.0;
+};
+// in front of the loop: 0 in the launch that folds, else what the launch before stored
+TRM_DEV ParamGrad param_grad_load(const ParamGradPtrs& g, size_t e, int fold) {
+    ParamGrad acc;
+    if (!fold) {
+        acc.sk_water = g.g[0][e];
+        acc.sk_ice = g.g[1][e];
+        acc.sk_air = g.g[2][e];
+        acc.s0 = g.g[3][e];
+        acc.c_water = g.g[4][e];
+        acc.c_ice = g.g[5][e];
+        acc.c_air = g.g[6][e];
+        acc.C0 = g.g[7][e];
+    }
+    return acc;
+}
+// behind it: every active lane owns its cell
+TRM_DEV void param_grad_store(const ParamGradPtrs& g, const LaneInfo& ln, size_t e, const ParamGrad& acc) {
+    if (ln.act) {
+        g.g[0][e] = acc.sk_water;
+        g.g[1][e] = acc.sk_ice;
+        g.g[2][e] = acc.sk_air;
+        g.g[3][e] = acc.s0;
+        g.g[4][e] = acc.c_water;
+        g.g[5][e] = acc.c_ice;
+        g.g[6][e] = acc.c_air;
+        g.g[7][e] = acc.C0;
+    }
+}
+// C~ of a cell onto the heat-capacity sums
+TRM_DEV void param_grad_add_C(ParamGrad& acc, const Frac<double>& f, double Cbar) {
+    acc.c_water = acc.c_water + Cbar * f.water;
+    acc.c_ice = acc.c_ice + Cbar * f.ice;
+    acc.c_air = acc.c_air + Cbar * f.air;
+    acc.C0 = acc.C0 + Cbar;
 }
 
 // what the lane-per-level kernels of this file know about their lane (as k_column_tangent forms it)
@@ -193,10 +251,10 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v
     if (viol && ln.act) atomicOr(v.status, viol);
 }
 
-// the transposed step at the state U (the tape's U_k): lam' -> lam.  BCGRAD: and this step's terms onto `acc`
-template <int LPC, bool BCGRAD = false>
+// the transposed step at the state U (the tape's U_k): lam' -> lam.  BCGRAD: and this step's terms onto `acc`; PGRAD: and onto `pacc`
+template <int LPC, bool BCGRAD = false, bool PGRAD = false>
 TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, const LevelGeom<double>& L, const LaneInfo& ln, int ii,
-                            double U, double sat, double lam, double dt, double bTb, double bTt, bool generic, BcGrad& acc) {
+                            double U, double sat, double lam, double dt, double bTb, double bTt, bool generic, BcGrad& acc, ParamGrad& pacc) {
     // T, liq, C and kappa of the cell, as the tangent recomputes them
     uint32_t viol_in = 0;
     double liq, T;
@@ -255,6 +313,22 @@ TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, c
     }
     const double Tbar = own_B + up_B;
     const double kbar = own_A + up_A;
+    if constexpr (PGRAD) {
+        param_grad_add_C(pacc, f, closure_param_slope(T, C) * Tbar);
+        const double sbar = 2.0 * conductivity_root(p, f) * kbar;
+        double s_air = sbar * f.air, s_0 = sbar;
+        if (!mirror) {   // the dry halo cells of the edge lanes
+            const Frac<double> f_dry = fractions_unchecked(p, 0.0, liq);
+            const double two_s = 2.0 * conductivity_root(p, f_dry);
+            const double h = (ln.is_bot ? two_s * pA : 0.0) + (ln.is_top ? two_s * pA_t : 0.0);
+            s_air = s_air + h * f_dry.air;
+            s_0 = s_0 + h;
+        }
+        pacc.sk_water = pacc.sk_water + sbar * f.water;
+        pacc.sk_ice = pacc.sk_ice + sbar * f.ice;
+        pacc.sk_air = pacc.sk_air + s_air;
+        pacc.s0 = pacc.s0 + s_0;
+    }
     // through the slopes: liq~ = c kappa~, U~ = a T~ + b liq~ (closure_tangent and conductivity_tangent are their own transposes)
     const double lbar = conductivity_tangent(p, f, sat * p.por, kbar);
     double via_T, via_liq, unused_liq, unused_T;
@@ -263,9 +337,11 @@ TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, c
     return lam + via_T + via_liq;
 }
 
-// the end of the run: the cotangents of T_n and liq_n through the closure of the stored U_n, lam_n = wU + a_n wT + b_n wliq; wT = wliq = 0 after
+// the end of the run: the cotangents of T_n and liq_n through the closure of the stored U_n, lam_n = wU + a_n wT + b_n wliq; wT = wliq = 0 after.
+// PGRAD: and wT through the heat capacity of that closure onto `pacc`
+template <bool PGRAD = false>
 TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, const LaneInfo& ln, size_t e, double sat, double& lam, double* lT,
-                          double* lliq) {
+                          double* lliq, ParamGrad& pacc) {
     using NF = double;
     const NF U = v.U[e], wT = lT[e], wliq = lliq[e];
     uint32_t viol_in = 0;
@@ -275,6 +351,7 @@ TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, con
     closure_tangent(p, U, sat, C, wT, unused_liq, via_T);
     closure_tangent(p, U, sat, C, wliq, via_liq, unused_T);
     lam = lam + via_T + via_liq;
+    if constexpr (PGRAD) param_grad_add_C(pacc, f, closure_param_slope(T, C) * wT);
     if (ln.act) {
         lT[e] = 0.0;
         lliq[e] = 0.0;
@@ -283,7 +360,8 @@ TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, con
 
 // The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
 // BCGRAD (Args = AdjointBcArgs): the boundary gradients ride along; the instances without are the code they were.
-template <int HYD, int LPC, bool BCGRAD = false, class Args = AdjointArgs>
+// PGRAD (Args = AdjointParamArgs, with BCGRAD): and the per-cell parameter sums.
+template <int HYD, int LPC, bool BCGRAD = false, class Args = AdjointArgs, bool PGRAD = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args aa) {
     using NF = double;
     int ii;
@@ -299,11 +377,18 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> 
     // the temperature boundary values: of a Value condition, and of a Gradient condition where the generic halo form reads them
     const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
     const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
-    if (aa.fold) adjoint_fold(v, p, ln, e, sat, lam, aa.lT, aa.lliq);
+    ParamGrad pacc;
+    if constexpr (PGRAD) pacc = param_grad_load(aa.pg, e, aa.fold);
+    if (aa.fold) adjoint_fold<PGRAD>(v, p, ln, e, sat, lam, aa.lT, aa.lliq, pacc);
     // Everything loaded so far is used here, in front of the loop: inside it the next slot's load is the only one in flight, and the wait
     // for it sits where its value is taken, behind the arithmetic of the step
     BcGrad acc;
-    if constexpr (BCGRAD) {
+    if constexpr (PGRAD) {
+        acc = bc_grad_load(aa.g, ii, aa.fold);
+        asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt), "v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub),
+                     "v"(acc.Ut), "v"(pacc.sk_water), "v"(pacc.sk_ice), "v"(pacc.sk_air), "v"(pacc.s0), "v"(pacc.c_water), "v"(pacc.c_ice),
+                     "v"(pacc.c_air), "v"(pacc.C0));
+    } else if constexpr (BCGRAD) {
         acc = bc_grad_load(aa.g, ii, aa.fold);
         asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt), "v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub),
                      "v"(acc.Ut));
@@ -314,10 +399,32 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> 
             slot -= aa.slot_elems;
             U_next = *slot;
         }
-        lam = adjoint_step<LPC, BCGRAD>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc);
+        lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc, pacc);
     }
     if (ln.act) aa.lU[e] = lam;
     if constexpr (BCGRAD) bc_grad_store(aa.g, ln, ii, acc);
+    if constexpr (PGRAD) param_grad_store(aa.pg, ln, e, pacc);
+}
+
+// trm_adjoint_backward's last launch under PGRAD: one thread per column sums each of the eight fields over k = 0 ... Nz-1 in ascending
+// order and applies the transposed chain rule of the host (ParamChain: the factors of make_dev_params) -- out[q][Nh], q in the order of
+// trm_params (TRM_THERMAL_PARAM_*).  A template, so that only the translation unit that launches it holds a copy.
+struct ParamChain {
+    double w[10];   // d(derived number) / d(parameter q): 1 / (2 sk_i), frac / (2 sqrt(k)), 1, frac
+};
+template <class Ptrs> __global__ void __launch_bounds__(256) k_param_reduce(Ptrs g, ParamChain ch, double* out, long long Nh, int Nz, int Nzp) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= Nh) return;
+    double sum[8];
+    for (int q = 0; q < 8; ++q) {
+        const double* col = g.g[q] + (size_t)i * (size_t)Nzp;
+        double s = 0.0;
+        for (int k = 0; k < Nz; ++k) s = s + col[k];
+        sum[q] = s;
+    }
+    // k_water, k_ice, k_air, k_mineral, k_organic, c_water, c_ice, c_air, c_mineral, c_organic
+    const int from[10] = {0, 1, 2, 3, 3, 4, 5, 6, 7, 7};
+    for (int q = 0; q < 10; ++q) out[(size_t)q * (size_t)Nh + (size_t)i] = sum[from[q]] * ch.w[q];
 }
 
 }  // namespace trm

@@ -33,11 +33,16 @@ struct CheckpointArgs {
 struct CheckpointBcArgs : CheckpointArgs {
     BcGradPtrs g;
 };
+// ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointParamArgs, true>: and the per-cell parameter accumulators
+struct CheckpointParamArgs : CheckpointBcArgs {
+    ParamGradPtrs pg;
+};
 
 // lam pulled back through one segment: the checkpoint U_c at ca.tape and the a.nsteps - 1 states behind it under a.dt.
 // Dynamic LDS: a.nsteps * TRM_STEP_BLOCK doubles.
 // BCGRAD (Args = CheckpointBcArgs): the boundary gradients as in k_column_adjoint, added in the same order -- the per-step tape's sums.
-template <int HYD, int LPC, bool BCGRAD = false, class Args = CheckpointArgs>
+// PGRAD (Args = CheckpointParamArgs, with BCGRAD): and the per-cell parameter sums, likewise.
+template <int HYD, int LPC, bool BCGRAD = false, class Args = CheckpointArgs, bool PGRAD = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ca) {
     using NF = double;
     extern __shared__ double seg[];
@@ -58,7 +63,9 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<dou
     // the temperature boundary values as k_column_adjoint loads them (the non-generic primal reads those of a Value condition alone)
     const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
     const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
-    if (ca.fold) adjoint_fold(v, p, ln, e, sat, lam, ca.lT, ca.lliq);
+    ParamGrad pacc;
+    if constexpr (PGRAD) pacc = param_grad_load(ca.pg, e, ca.fold);
+    if (ca.fold) adjoint_fold<PGRAD>(v, p, ln, e, sat, lam, ca.lT, ca.lliq, pacc);
     BcGrad acc;
     if constexpr (BCGRAD) acc = bc_grad_load(ca.g, ii, ca.fold);
 
@@ -89,9 +96,10 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<dou
     if (m > 0) mine[(m - 1) * TRM_STEP_BLOCK] = c.U;
 
     // ---- backward: the transposed steps at U_{c+m-1} ... U_c
-    for (int j = m - 1; j >= 0; --j) lam = adjoint_step<LPC, BCGRAD>(v, p, L, ln, ii, mine[j * TRM_STEP_BLOCK], sat, lam, a.dt, bTb, bTt, generic, acc);
+    for (int j = m - 1; j >= 0; --j) lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, mine[j * TRM_STEP_BLOCK], sat, lam, a.dt, bTb, bTt, generic, acc, pacc);
     if (ln.act) ca.lU[e] = lam;
     if constexpr (BCGRAD) bc_grad_store(ca.g, ln, ii, acc);
+    if constexpr (PGRAD) param_grad_store(ca.pg, ln, e, pacc);
 }
 
 }  // namespace trm

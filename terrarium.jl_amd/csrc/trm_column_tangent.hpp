@@ -18,8 +18,15 @@
 //   Gradient  dT_t = dT + dbTt dzf,   dT_b = dT + dbTb (-dzf)   (also where the primal knows a zero Gradient at the bottom and skips it)
 //   Flux      dU' = dU + (dgU + dflux_U) dt,  dflux_U = flux_term_bottom(dF_b) on the bottom lane, -flux_term_top(dF_t) on the top lane
 // and a pair whose kind reads no value has none.  The primal half is the same code.
-// Every tangent operation is linear in (dU, dT, dliq) with no additive constant, so scaling a seed by a power of two scales every
-// tangent bit for bit.
+// PSEED (TangentParamArgs: trm_tangent_param_set has seeded a thermal parameter; always together with BCSEED): the seeds of the eight
+// numbers DevParams holds -- dsk_i of the square roots sk_i, ds0 of s0 = kterm_mineral + kterm_organic, dc_i, dC0 of C0 = cterm_mineral +
+// cterm_organic -- ride in scalar registers and enter where the primal reads the parameter,
+//   closure      thawed / frozen: T = N / C with N free of the parameters: dT += m dC_p, m = -(T / C), dC_p = dc_w water + dc_i ice +
+//                dc_a air + dC0; phase change: T = 0 and liq is free of C: nothing
+//   conductivity dkappa += 2 s (dsk_w water + dsk_i ice + dsk_a air + ds0)
+//   dry halo     of the reference-zero policy: s_halo = sk_air por + s0, dkappa_halo = 2 s_halo (dsk_a por + ds0)
+// Every tangent operation is linear in (dU, dT, dliq) and the seeds with no additive constant, so scaling the seeds by a power of two
+// scales every tangent bit for bit.
 #pragma once
 #include "trm_column.hpp"
 
@@ -35,6 +42,15 @@ struct TangentBcArgs : TangentArgs {
     const double *sTb, *sTt;   // d(temperature value) at the bottom / top: of a Value or a Gradient condition
     const double *sUb, *sUt;   // d(internal-energy flux) at the bottom / top
 };
+// the seeds of the eight thermal numbers of DevParams (the host's chain rule has taken the ten parameters there): wave-uniform, by value
+struct ParamSeeds {
+    double dsk_water, dsk_ice, dsk_air, ds0;
+    double dc_water, dc_ice, dc_air, dC0;
+};
+// ... of k_column_tangent<HYD, LPC, true, TangentParamArgs, true>
+struct TangentParamArgs : TangentBcArgs {
+    ParamSeeds s;
+};
 
 // tangent of the energy closure at (U, sat) -- C is the heat capacity the primal closure formed
 TRM_DEV void closure_tangent(const DevParams<double>& p, double U, double sat, double C, double dU, double& dliq, double& dT) {
@@ -43,6 +59,25 @@ TRM_DEV void closure_tangent(const DevParams<double>& p, double U, double sat, d
     const bool thawed = U >= 0.0, frozen = U < nLth;
     dT = (thawed || frozen) ? div_nr(dU, C) : 0.0;
     dliq = (thawed || frozen || nLth == 0.0) ? 0.0 : -div_nr(dU, nLth + Limits<double>::eps());
+}
+
+// PSEED: what the heat-capacity seeds add to the closure's dT -- m dC_p with the slope m = -(T / C) (T = 0 in phase change: nothing)
+TRM_DEV double closure_param_slope(double T, double C) { return -div_nr(T, C); }
+TRM_DEV double heat_capacity_seed(const ParamSeeds& s, const Frac<double>& f) {
+    return s.dc_water * f.water + s.dc_ice * f.ice + s.dc_air * f.air + s.dC0;
+}
+// s of kappa = s^2, as conductivity() forms it
+TRM_DEV double conductivity_root(const DevParams<double>& p, const Frac<double>& f) {
+    double s = p.sk_water * f.water;
+    s = s + p.sk_ice * f.ice;
+    s = s + p.sk_air * f.air;
+    s = s + p.kterm_mineral;
+    s = s + p.kterm_organic;
+    return s;
+}
+// PSEED: what the conductivity seeds add to dkappa of a cell with fractions f
+TRM_DEV double conductivity_seed(const DevParams<double>& p, const ParamSeeds& s, const Frac<double>& f) {
+    return 2.0 * conductivity_root(p, f) * (s.dsk_water * f.water + s.dsk_ice * f.ice + s.dsk_air * f.air + s.ds0);
 }
 
 // dkappa of a cell with fractions f and tangent liquid fraction dliq (wi = sat * por)
@@ -58,14 +93,15 @@ TRM_DEV double conductivity_tangent(const DevParams<double>& p, const Frac<doubl
 
 // dgU: the tangent of column_tendencies' (or column_tendencies_generic's) heat tendency, without the constant boundary flux terms.
 // The primal intermediates (kappa, the halos) are formed again with the primal's operations.  BCSEED: dbTb, dbTt are the column's seeds of
-// the temperature boundary values (0 for a kind that reads none).
-template <int LPC, bool BCSEED = false>
+// the temperature boundary values (0 for a kind that reads none).  PSEED: `ps` are the parameter seeds.
+template <int LPC, bool BCSEED = false, bool PSEED = false>
 TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& p, const LevelGeom<double>& L, const LaneInfo& ln, int ii,
                                 const Cell<double>& c, double dT, double dliq, double bTb, double bTt, bool generic, double dbTb = 0.0,
-                                double dbTt = 0.0) {
+                                double dbTt = 0.0, const ParamSeeds* ps = nullptr) {
     const Frac<double> f = fractions_unchecked(p, c.sat, c.liq);
     const double kap = conductivity(p, f);
-    const double dkap = conductivity_tangent(p, f, c.sat * p.por, dliq);
+    double dkap = conductivity_tangent(p, f, c.sat * p.por, dliq);
+    if constexpr (PSEED) dkap = dkap + conductivity_seed(p, *ps, f);
     const double T_sh = shfl_up1<double, LPC>(c.T), kap_sh = shfl_up1<double, LPC>(kap);
     const double dT_sh = shfl_up1<double, LPC>(dT), dkap_sh = shfl_up1<double, LPC>(dkap);
     // temperature halos and their tangents (a Value condition extrapolates through a constant, a Gradient adds one)
@@ -90,7 +126,11 @@ TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& 
     // halo conductivity: the edge cell's under the mirror policy, the dry cell's (sat = 0: no water, no ice) otherwise
     const bool mirror = p.halo_policy == 1;
     const double kap_halo = mirror ? kap : conductivity(p, fractions_unchecked(p, 0.0, c.liq));
-    const double dkap_halo = mirror ? dkap : 0.0;
+    double dkap_halo = mirror ? dkap : 0.0;
+    if constexpr (PSEED) {   // (the dry cell's conductivity is constant in the state, not in the parameters)
+        const double dkap_dry = conductivity_seed(p, *ps, fractions_unchecked(p, 0.0, c.liq));
+        dkap_halo = mirror ? dkap : dkap_dry;
+    }
     const double T_m = ln.is_bot ? T_b : T_sh, kap_m = ln.is_bot ? kap_halo : kap_sh;
     const double dT_m = ln.is_bot ? dT_b : dT_sh, dkap_m = ln.is_bot ? dkap_halo : dkap_sh;
     const double dq_lo = -(0.5 * (dkap + dkap_m)) * ((c.T - T_m) * L.rdzf_lo) + -(0.5 * (kap + kap_m)) * ((dT - dT_m) * L.rdzf_lo);
@@ -103,7 +143,8 @@ TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& 
 // `a.nsteps` ForwardEuler steps of the state and its tangent; the outputs are those of a finalizing trm_step (the tendency of the
 // last step, hydraulic_conductivity of the new state) and the three tangents.
 // BCSEED (Args = TangentBcArgs): the boundary seeds are loaded once in front of the step loop; the instances without are the code they were.
-template <int HYD, int LPC, bool BCSEED = false, class Args = TangentArgs>
+// PSEED (Args = TangentParamArgs, with BCSEED): the parameter seeds are kernel arguments.
+template <int HYD, int LPC, bool BCSEED = false, class Args = TangentArgs, bool PSEED = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ta) {
     using NF = double;
     constexpr int CPW = 64 / LPC;
@@ -141,7 +182,9 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
         uint32_t viol_in = 0;
         NF liq0, T0;
         const Frac<NF> f0 = energy_closure_wave<NF, 0>(p, c.U, c.sat, liq0, T0, viol_in);
-        closure_tangent(p, c.U, c.sat, heat_capacity(p, f0), dU, dliq, dT);
+        const NF C0 = heat_capacity(p, f0);
+        closure_tangent(p, c.U, c.sat, C0, dU, dliq, dT);
+        if constexpr (PSEED) dT = dT + closure_param_slope(T0, C0) * heat_capacity_seed(ta.s, f0);
     }
     // boundary inputs: constants over the launch
     const NF bTb = v.bc.kind[2][0] == 1 ? bcval(v, 2, 0)[ii] : 0.0, bTt = v.bc.kind[2][1] == 1 ? bcval(v, 2, 1)[ii] : 0.0;
@@ -187,13 +230,19 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
         const Frac<NF>* pre = step > 0 ? &f_new : nullptr;
         const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
                                        : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
-        const NF dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt);
+        NF dgU;
+        if constexpr (PSEED) dgU = tendency_tangent<LPC, BCSEED, true>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt, &ta.s);
+        else dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt);
         NF gU = t.gU, gS = t.gS, z0;
         column_advance<NF, false, LPC>(v, L, ln, Nz, bc, c.U, c.sat, gU, gS, a.dt, n, z0, bad);
         f_new = column_closure<NF, false, HYD>(p, L, z0, n, viol);
         if constexpr (BCSEED) dU = dU + (dgU + dflux_U) * a.dt;
         else dU = dU + dgU * a.dt;
-        closure_tangent(p, n.U, n.sat, heat_capacity(p, f_new), dU, dliq, dT);
+        if constexpr (PSEED) {
+            const NF C_new = heat_capacity(p, f_new);
+            closure_tangent(p, n.U, n.sat, C_new, dU, dliq, dT);
+            dT = dT + closure_param_slope(n.T, C_new) * heat_capacity_seed(ta.s, f_new);
+        } else closure_tangent(p, n.U, n.sat, heat_capacity(p, f_new), dU, dliq, dT);
         gU_out = gU;
     }
     // hydraulic_conductivity of the new state (a finalizing step: compute_auxiliary!)
@@ -228,6 +277,22 @@ __global__ void __launch_bounds__(256) k_closure_tangent(View<double> v, DevPara
     double dliq, dT;
     closure_tangent(p, U, sat, heat_capacity(p, f), ta.dU[e], dliq, dT);
     ta.dT[e] = dT;
+    ta.dliq[e] = dliq;
+}
+// ... with parameter seeds (trm_tangent_param_set): and the heat-capacity term.  A template, so that only the translation unit that
+// launches it holds a copy.
+template <class Args> __global__ void __launch_bounds__(256) k_closure_tangent_param(View<double> v, DevParams<double> p, Args ta) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)v.Nh * (size_t)v.Nzp || (int)(e % (size_t)v.Nzp) >= v.Nz) return;
+    const double U = v.U[e], sat = v.sat[e];
+    double liq, T;
+    uint32_t viol = 0;
+    energy_closure(p, U, sat, liq, T, viol);
+    Frac<double> f = fractions_unchecked(p, sat, liq);
+    const double C = heat_capacity(p, f);
+    double dliq, dT;
+    closure_tangent(p, U, sat, C, ta.dU[e], dliq, dT);
+    ta.dT[e] = dT + closure_param_slope(T, C) * heat_capacity_seed(ta.s, f);
     ta.dliq[e] = dliq;
 }
 

@@ -174,6 +174,11 @@ struct trm_ctx {
     // trm_tangent_open, and trm_step_tangent runs the seeded instances.  Seeds are not state: nothing makes them stale.
     double* d_tan_bc[4] = {};
     bool tan_bc_seeded = false;
+    // the seeds of the thermal parameters (trm_tangent_param_set) as the kernels take them: of the eight numbers DevParams holds, in the
+    // order sk_water, sk_ice, sk_air, s0, c_water, c_ice, c_air, C0 (thermal_param_chain below).  Zeroed by trm_tangent_open;
+    // `tan_param_seeded`: set since trm_tangent_open, and trm_step_tangent / trm_tangent_closure run the parameter-seeded instances.
+    double tan_param[8] = {};
+    bool tan_param_seeded = false;
     // reverse-mode gradients (trm_adjoint_*): the cotangent fields of U, T, liq in the same layout, and the tape of trm_step_record --
     // `tape_cap` slots of [Nh][Nzp] doubles, slot k the internal energy before taped step k, `tape_dt[k]` that step's dt.  `adj_stale`:
     // another call has changed the state or a boundary condition since the first taped step (state_changed / bc_changed below).
@@ -181,6 +186,10 @@ struct trm_ctx {
     // the boundary-gradient accumulators (trm_adjoint_bc_open), [Nh] doubles each, in the order of d_tan_bc; null: the sweep runs the
     // instances without
     double* d_adj_bc[4] = {};
+    // the thermal-parameter accumulators (trm_adjoint_param_open): eight per-cell fields [Nh][Nzp] in the order of tan_param, and the
+    // result of k_param_reduce, [TRM_THERMAL_PARAM_COUNT][Nh]; null: the sweep runs the instances without
+    double* d_adj_param[8] = {};
+    double* d_adj_param_out = nullptr;
     double* d_tape = nullptr;
     int tape_cap = 0;
     std::vector<double> tape_dt;
@@ -547,13 +556,18 @@ template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx
 struct TangentLaunch {
     static int step(trm_ctx* c, double dt, int nsteps);
     static int step_bc(trm_ctx* c, double dt, int nsteps);   // with boundary seeds (trm_launch_column_tangent_bc.hip)
+    static int step_param(trm_ctx* c, double dt, int nsteps);   // with boundary and parameter seeds (trm_launch_column_tangent_param.hip)
     static int closure(trm_ctx* c);
+    static int closure_param(trm_ctx* c);                    // with parameter seeds (trm_launch_column_tangent_param.hip)
 };
 // k_column_record / k_column_adjoint (trm_launch_column_adjoint.hip, fp64 NoFlow only): `slot` is the tape slot of the launch's first step
 struct AdjointLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot);
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
     static int backward_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // with boundary gradients (trm_launch_column_adjoint_bc.hip)
+    // with boundary and parameter gradients, and k_param_reduce that ends a sweep on either tape (trm_launch_column_adjoint_param.hip)
+    static int backward_param(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int param_reduce(trm_ctx* c);
 };
 // the strided k_column_record / k_column_adjoint_ckpt (trm_launch_column_adjoint_ckpt.hip): the record stores before the steps `first`,
 // `first + every`, ... of the launch into the slots from `slot` on; the backward launch pulls lam through the segment of `nsteps`
@@ -562,7 +576,26 @@ struct CheckpointLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
     static int backward_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // with boundary gradients (trm_launch_column_adjoint_ckpt_bc.hip)
+    static int backward_param(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // ... and parameter gradients (trm_launch_column_adjoint_ckpt_param.hip)
 };
+// The chain rule between the ten thermal parameters (TRM_THERMAL_PARAM_*, the order of trm_params) and the eight numbers the kernels
+// differentiate (make_dev_params): w[q] = d(derived number) / d(parameter q), with sk_i = sqrt(k_i), s0 = sqrt(k_mineral) frac_mineral +
+// sqrt(k_organic) frac_organic, C0 = c_mineral frac_mineral + c_organic frac_organic.  Parameter q feeds derived number
+// thermal_param_target(q).  Forward for seeds, transposed for gradients (k_param_reduce), with the same factors.
+inline int thermal_param_target(int q) {
+    const int to[10] = {0, 1, 2, 3, 3, 4, 5, 6, 7, 7};
+    return to[q];
+}
+inline void thermal_param_chain(const trm_params& q, const trm::DevParams<double>& p, double w[10]) {
+    w[0] = 1.0 / (2.0 * p.sk_water);
+    w[1] = 1.0 / (2.0 * p.sk_ice);
+    w[2] = 1.0 / (2.0 * p.sk_air);
+    w[3] = p.frac_mineral / (2.0 * std::sqrt(q.k_mineral));
+    w[4] = p.frac_organic / (2.0 * std::sqrt(q.k_organic));
+    w[5] = w[6] = w[7] = 1.0;
+    w[8] = p.frac_mineral;
+    w[9] = p.frac_organic;
+}
 // k_materialize_closure (trm_launch_materialize.hip)
 template <class NF> struct MaterializeLaunch { static int run(trm_ctx* c); };
 // k_accumulate (trm_launch_average.hip)

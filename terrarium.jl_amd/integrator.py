@@ -435,6 +435,16 @@ class DeviceState:
         a[...] = values
         self._check(self._lib.trm_tangent_bc_upload(self._ctx, _capi.BC_VAR[var], _capi.SIDE[side], a.ctypes.data), "trm_tangent_bc_upload")
 
+    def set_param_tangent(self, seeds):
+        """Seeds thermal parameters: {name: d(parameter)} over `k_water, k_ice, k_air, k_mineral, k_organic, c_water, c_ice, c_air,
+        c_mineral, c_organic` (the ones left out are 0), one number each for all columns (trm_tangent_param_set).  The seeds hold for
+        every step_tangent and tangent_closure until open_tangent zeroes them."""
+        unknown = sorted(set(seeds) - set(_capi.THERMAL_PARAMS))
+        if unknown:
+            raise KeyError(f"set_param_tangent: no thermal parameter {unknown[0]!r} (one of {', '.join(_capi.THERMAL_PARAMS)})")
+        a = (C.c_double * len(_capi.THERMAL_PARAMS))(*[float(seeds.get(name, 0.0)) for name in _capi.THERMAL_PARAMS])
+        self._check(self._lib.trm_tangent_param_set(self._ctx, a), "trm_tangent_param_set")
+
     def tangent(self, name) -> np.ndarray:
         """A tangent field as [Nz][Nh] (row 0 = bottom layer)."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
@@ -486,6 +496,18 @@ class DeviceState:
         Gradient condition) or `internal_energy` (a Flux).  Zeros where the pair's kind reads no value (trm_adjoint_bc_download)."""
         a = np.empty(self.grid.Nh, dtype=np.float64)
         self._check(self._lib.trm_adjoint_bc_download(self._ctx, _capi.BC_VAR[var], _capi.SIDE[side], a.ctypes.data), "trm_adjoint_bc_download")
+        return a
+
+    def open_param_gradient(self):
+        """From now on adjoint_backward also forms dL/d(thermal parameter) per column, and the boundary gradients with it
+        (trm_adjoint_param_open); needs an open adjoint."""
+        self._check(self._lib.trm_adjoint_param_open(self._ctx), "trm_adjoint_param_open")
+
+    def param_gradient(self, name) -> np.ndarray:
+        """dL/d(parameter `name`) of each column's share of L as [Nh], after adjoint_backward; the sum over the columns is the
+        gradient of the scalar L (trm_adjoint_param_download)."""
+        a = np.empty(self.grid.Nh, dtype=np.float64)
+        self._check(self._lib.trm_adjoint_param_download(self._ctx, _capi.THERMAL_PARAMS.index(name), a.ctypes.data), "trm_adjoint_param_download")
         return a
 
     def step_record(self, dt, nsteps=1):
@@ -903,12 +925,13 @@ class ModelIntegrator:
 _BOUNDARY_DERIVATIVE_KINDS = {"temperature": ("value", "gradient"), "internal_energy": ("flux",)}
 
 
-def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None) -> dict:
+def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, d_params=None) -> dict:
     """Forward-mode derivative of `run!(integ; steps)` with respect to the initial internal energy: the integrator is stepped `steps`
     times with its own dt, its state carrying the tangent seeded by `d_internal_energy` ([Nz][Nh], or anything that broadcasts to
     it).  Returns {"internal_energy", "temperature", "liquid_water_fraction"}: the tangents of those fields after the last step.
     `d_boundary` = {(var, side): values}: seeds d(value) of boundary conditions, [Nh] or a scalar each -- a Value or a Gradient on
     `temperature`, a Flux on `internal_energy` -- held over the run like the values themselves (trm_tangent_bc_upload).
+    `d_params` = {name: value}: seeds on the thermal parameters (`k_mineral`, `c_water`, ...: trm_tangent_param_set).
     The heat-only SoilModel in fp64 with ForwardEuler and constant boundary conditions and inputs (trm_step_tangent)."""
     if not isinstance(integ.timestepper, ForwardEuler):
         raise ValueError("jvp: ForwardEuler only")
@@ -922,6 +945,8 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None) 
         st.set_tangent("internal_energy", d_internal_energy)
         for (var, side), values in (d_boundary or {}).items():
             st.set_bc_tangent(var, side, values)
+        if d_params is not None:
+            st.set_param_tangent(d_params)
         st.step_tangent(integ.timestepper.dt, int(steps))
         return {name: st.tangent(name) for name in _capi.TANGENT}
     finally:
@@ -930,7 +955,7 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None) 
 
 
 def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=None, liquid_water_fraction=None,
-        checkpoint_every=None, wrt_boundary=False):
+        checkpoint_every=None, wrt_boundary=False, wrt_params=False):
     """Reverse-mode derivative of `run!(integ; steps)`: the integrator is stepped `steps` times with its own dt (state and clock end
     where `run` leaves them), then the given cotangents of the final temperature, internal energy and liquid water fraction ([Nz][Nh],
     or anything that broadcasts to it; None: zero) are pulled back.  Returns dL/dU_0 as [Nz][Nh], L the sum of the three inner
@@ -938,7 +963,8 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
     states in between formed again by the backward sweep -- the same gradient bit for bit.  The coverage and refusals of `jvp`.
     With `wrt_boundary` it returns (dL/dU_0, {(var, side): dL/d(value) as [Nh]}) for the boundary conditions of the integrator whose
     value the run reads -- a Value or a Gradient on `temperature`, a Flux on `internal_energy` -- from the same sweep
-    (trm_adjoint_bc_open)."""
+    (trm_adjoint_bc_open).  With `wrt_params` it appends {name: dL/d(parameter) as [Nh]} for the ten thermal parameters, each column's
+    share (trm_adjoint_param_open): (dL/dU_0, params), or (dL/dU_0, boundary, params) with `wrt_boundary` as well."""
     if not isinstance(integ.timestepper, ForwardEuler):
         raise ValueError("vjp: ForwardEuler only")
     if integ._has_time_dependence() or integ._windowed():
@@ -960,12 +986,19 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
             st.set_cotangent(name, 0.0 if w is None else w)
         if wrt_boundary:
             st.open_bc_gradient()
+        if wrt_params:
+            st.open_param_gradient()
         st.adjoint_backward()
         g = st.cotangent("internal_energy")
-        if not wrt_boundary:
+        if not wrt_boundary and not wrt_params:
             return g
-        pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
-        return g, {(var, side): st.bc_gradient(var, side) for var, side in pairs}
+        out = [g]
+        if wrt_boundary:
+            pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
+            out.append({(var, side): st.bc_gradient(var, side) for var, side in pairs})
+        if wrt_params:
+            out.append({name: st.param_gradient(name) for name in _capi.THERMAL_PARAMS})
+        return tuple(out)
     finally:
         if opened:
             st.close_adjoint()
