@@ -79,25 +79,35 @@ __global__ void __launch_bounds__(256) k_e(Ptrs p, int Nh, double dt) {
     p.f[0][c] = a0 + dt; p.f[1][c] = a1 + dt; p.f[2][c] = a0 * dt; p.f[3][c] = a1 * dt; p.f[4][c] = a0 - a1; p.f[5][c] = a0 + a1;
 }
 
-// G: 3 reads + 4 writes (round 9's deferring step: U, sat, psi read; U, sat, psi, K stored)
-__global__ void __launch_bounds__(256) k_g(Ptrs p, int Nh, double dt) {
+// An agent-scope relaxed store: write-through (global_store_dwordx2 ... sc1), no fence and no wait -- the line does not stay dirty in the
+// XCD's L2 for the end of the launch to write back (rows Gw, Hw, Hsw)
+template <bool THROUGH> __device__ inline void st(double* q, double x) {
+    if constexpr (THROUGH) __hip_atomic_store(q, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *q = x;
+}
+// G: 3 reads + 4 writes (round 9's deferring step: U, sat, psi read; U, sat, psi, K stored); Gw: the four stores written through
+template <bool THROUGH> __global__ void __launch_bounds__(256) k_g(Ptrs p, int Nh, double dt) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int i = wave * 2 + (lane >> 5), k = lane & 31;
     if (i >= Nh) return;
     const size_t c = (size_t)i * 32 + k;
     double a0 = p.f[0][c], a1 = p.f[1][c], a4 = p.f[4][c];
-    p.f[0][c] = a0 + dt; p.f[1][c] = a1 + dt; p.f[4][c] = a4 + dt; p.f[5][c] = a0 + a1;
+    st<THROUGH>(&p.f[0][c], a0 + dt); st<THROUGH>(&p.f[1][c], a1 + dt); st<THROUGH>(&p.f[4][c], a4 + dt); st<THROUGH>(&p.f[5][c], a0 + a1);
 }
-// H: 2 reads + 2 writes (round 10's interior step: U and sat read, U and sat stored)
-__global__ void __launch_bounds__(256) k_h(Ptrs p, int Nh, double dt) {
+// H: 2 reads + 2 writes (round 10's interior step: U and sat read, U and sat stored).  FIELDS: the two field stores written through
+// (Hw).  SMALL: the top lane of each column also stores 8 B into each of two [Nh] arrays, as the interior launch stores
+// surface_excess_water and the water table (Hs); SMALL_THROUGH: those written through as well (Hsw).
+struct Small { double* s[2]; };
+template <bool FIELDS, bool SMALL, bool SMALL_THROUGH> __global__ void __launch_bounds__(256) k_h(Ptrs p, Small q, int Nh, double dt) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int i = wave * 2 + (lane >> 5), k = lane & 31;
     if (i >= Nh) return;
     const size_t c = (size_t)i * 32 + k;
     double a0 = p.f[0][c], a1 = p.f[1][c];
-    p.f[0][c] = a0 + dt * a1; p.f[1][c] = a1 + dt;
+    st<FIELDS>(&p.f[0][c], a0 + dt * a1); st<FIELDS>(&p.f[1][c], a1 + dt);
+    if (SMALL && k == 0) { st<SMALL_THROUGH>(&q.s[0][i], a0 - a1); st<SMALL_THROUGH>(&q.s[1][i], a1 * dt); }
 }
 
 // F: as D (3 reads + 6 writes) on a TILED layout: the six fields of a workgroup's 8 columns adjacent in memory (8 x 32 x 8 B = 2 KB per
@@ -139,8 +149,15 @@ int main(int argc, char** argv) {
     run("A lane=level 8B/lane", [&] { hipLaunchKernelGGL(k_a, dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, Nh, 1.0); });
     run("D 3 reads 6 writes (x9/11)", [&] { hipLaunchKernelGGL(k_d, dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, Nh, 1.0); });
     run("E 2 reads 6 writes (x8/11)", [&] { hipLaunchKernelGGL(k_e, dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, Nh, 1.0); });
-    run("G 3 reads 4 writes (x7/11)", [&] { hipLaunchKernelGGL(k_g, dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, Nh, 1.0); });
-    run("H 2 reads 2 writes (x4/11)", [&] { hipLaunchKernelGGL(k_h, dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, Nh, 1.0); });
+    Small q;
+    for (int f = 0; f < 2; ++f) { CK(hipMalloc(&q.s[f], (size_t)Nh * 8 + 64)); CK(hipMemset(q.s[f], 0, (size_t)Nh * 8)); }
+    run("G 3 reads 4 writes (x7/11)", [&] { hipLaunchKernelGGL(k_g<false>, dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, Nh, 1.0); });
+    run("Gw G, stores written through", [&] { hipLaunchKernelGGL(k_g<true>, dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, Nh, 1.0); });
+    run("H 2 reads 2 writes (x4/11)", [&] { hipLaunchKernelGGL((k_h<false, false, false>), dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, q, Nh, 1.0); });
+    run("Hw H, stores written through", [&] { hipLaunchKernelGGL((k_h<true, false, false>), dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, q, Nh, 1.0); });
+    run("Hs H + 2 per-column stores", [&] { hipLaunchKernelGGL((k_h<false, true, false>), dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, q, Nh, 1.0); });
+    run("Hsw Hs, all 4 written through", [&] { hipLaunchKernelGGL((k_h<true, true, true>), dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, q, Nh, 1.0); });
+    run("H (again, after the others)", [&] { hipLaunchKernelGGL((k_h<false, false, false>), dim3((wavesA + 3) / 4), dim3(256), 0, 0, p, q, Nh, 1.0); });
     double* tiled; CK(hipMalloc(&tiled, 6 * n * 8 + (1 << 20))); CK(hipMemset(tiled, 0, 6 * n * 8));
     run("F 3 reads 6 writes, tiled layout (x9/11)", [&] { hipLaunchKernelGGL(k_f, dim3((wavesA + 3) / 4), dim3(256), 0, 0, tiled, Nh, 1.0); });
     run("B 4 levels/lane 2x16B", [&] { hipLaunchKernelGGL(k_b, dim3((wavesB + 3) / 4), dim3(256), 0, 0, p, Nh, 1.0); });

@@ -294,6 +294,12 @@ static_assert(offsetof(ColumnArgs<double>, check_entry) == 20 && offsetof(Column
 #ifndef TRM_PICK_EXEC
 #define TRM_PICK_EXEC 1
 #endif
+// How an interior launch (PSI_INTERIOR) stores: 0 plain stores; 1 U and sat written through the L2 (stg_through); 2 the two direct
+// per-column stores (surface_excess_water, water table) as well.  A compile-time choice, A/B by -DTRM_INTERIOR_STORE_THROUGH=...
+// (EXPERIMENTS R12.1: 1 ships, C3 0.911 of the parent's time per step); every other launch keeps plain stores.
+#ifndef TRM_INTERIOR_STORE_THROUGH
+#define TRM_INTERIOR_STORE_THROUGH 1
+#endif
 #ifndef TRM_COLUMN_WAVES_EULER
 #define TRM_COLUMN_WAVES_EULER 1
 #endif
@@ -771,9 +777,14 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
             const View<NF>& v = kernarg_reload<View<NF>>(0);
             NF* const pS = v.S; NF* const pwt = v.wt;
             asm volatile("" : : "s"(pS), "s"(pwt));
+            // (the store form of this instance.  The (direct, scalar) family takes the macro: C3 15.99 against 17.55 us per step with 1,
+            //  16.57 with 2 -- EXPERIMENTS R12.1.  The (staged, vector) family -- states beyond the L2, where written lines are evicted
+            //  while the kernel runs -- stays plain: 8 x N145 with interior_steps = 1 reads 0.988 with 1, inside overlapping sample
+            //  ranges; its per-column values leave through store_small_outputs, plain, either way)
+            constexpr int THROUGH = STAGED ? 0 : TRM_INTERIOR_STORE_THROUGH;
             unsigned cb = block_local(cb0);
-            stg(v.U, cb, n.U);
-            stg(v.sat, cb, n.sat);
+            if constexpr (THROUGH >= 1) { stg_through(v.U, cb, n.U); stg_through(v.sat, cb, n.sat); }
+            else { stg(v.U, cb, n.U); stg(v.sat, cb, n.sat); }
             if (ln.is_top && STAGED) {
                 const int cib = (int)(threadIdx.x >> 6) * CPW + sub;
                 constexpr int cpb = (TRM_STEP_BLOCK / 64) * CPW;
@@ -782,8 +793,8 @@ TRM_DEV void column_program(const View<NF>& v_arg, const DevParams<NF>& p_arg, c
                 st[SMALL_WT * cpb + cib] = z0;
             } else if (ln.is_top) {
                 const unsigned ib = block_local(ib0);
-                stg(pS, ib, S);
-                stg(pwt, ib, z0);
+                if constexpr (THROUGH >= 2) { stg_through(pS, ib, S); stg_through(pwt, ib, z0); }
+                else { stg(pS, ib, S); stg(pwt, ib, z0); }
             }
             viol |= bad ? 1u : 0u;
         }

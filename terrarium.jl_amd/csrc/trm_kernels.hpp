@@ -513,6 +513,11 @@ template <class T> TRM_DEV T sld_off(const void* base, unsigned byte_off_uniform
 template <class NF> TRM_DEV void stg(NF* base, unsigned byte_off, NF x) {
     *reinterpret_cast<NF*>(reinterpret_cast<char*>(base) + byte_off) = x;
 }
+// The same addressing, written THROUGH the XCD's L2 (an agent-scope relaxed store: `global_store_dwordx2 ..., s[..] sc1`, the saddr form
+// kept, no fence and no wait): the line does not stay dirty in L2 for the end of the launch to write back (EXPERIMENTS R12.1)
+template <class NF> TRM_DEV void stg_through(NF* base, unsigned byte_off, NF x) {
+    __hip_atomic_store(reinterpret_cast<NF*>(reinterpret_cast<char*>(base) + byte_off), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 // Instruction selection works one basic block at a time: an offset defined in another block has already been
 // widened to 64 bits there.  Re-materialising it (a no-op the optimiser cannot see through) keeps the
 // zero-extension, and with it the saddr form, inside the block that does the access.
