@@ -226,6 +226,12 @@ enum {
                                     /* after every call all arrays, the status and the clock are what option 0 leaves, bit for bit.  0: every    */
                                     /* launch stores everything (A/B, tests); 2 (default): the library's rule -- as 1 for states within the      */
                                     /* Infinity Cache (256 MiB), as 0 beyond.  Environment: TRM_INTERIOR_STEPS = 0 / 1 / 2 sets the default      */
+    ,TRM_OPT_DERIVATIVE_SERIES = 14 /* 1: trm_step_tangent, trm_step_record and trm_adjoint_backward accept boundary time series (whole       */
+                                    /* records, trm_set_bc_series) of kind Value on temperature and Flux on internal energy, bottom or top,      */
+                                    /* on the branch-free boundary kinds: the kernels evaluate them in front of every step, seeds and           */
+                                    /* gradients of such a pair have the series' shape (trm_tangent_bc_series_upload,                            */
+                                    /* trm_adjoint_bc_series_download).  0 (default): a context with a series attached is refused with          */
+                                    /* TRM_EUNSUPPORTED by those three calls                                                                      */
 };
 /* DIAGNOSTIC, read-only (trm_get_option): which fast paths the NEXT step will take -- what the library tracks about its own
  * buffers.  Tests pin them (a wrong value costs speed, never correctness, so nothing else would notice). */
@@ -243,7 +249,9 @@ enum {
     TRM_INFO_CLOSURE_STORED = 106,     /* 1: the temperature / liquid fraction ARRAYS are current; 0: the last step launches left them      */
                                        /* unstored (TRM_OPT_DEFER_CLOSURE_STORES) and the next reader materialises them                     */
     TRM_INFO_MATERIALIZATIONS = 107,   /* how many times the context has materialised them (one small launch each)                          */
-    TRM_INFO_INTERIOR_LAUNCHES = 108   /* how many step launches of the context were interior launches (TRM_OPT_INTERIOR_STEPS)             */
+    TRM_INFO_INTERIOR_LAUNCHES = 108,  /* how many step launches of the context were interior launches (TRM_OPT_INTERIOR_STEPS)             */
+    TRM_INFO_DERIVATIVE_SERIES = 109   /* how many time series the last derivative launch of the context (tangent, record or backward)      */
+                                       /* evaluated in the kernel (TRM_OPT_DERIVATIVE_SERIES); 0 otherwise                                  */
 };
 /* kernel families reported in the low byte of TRM_INFO_LAST_PROGRAM; bits 8-9 the hydraulics instance (0 the reference default, 1 van
  * Genuchten n = 2, 2 run-time exponents), 10-11 lanes per column / 32, 12-14 which closure fields are derived, 15 per-column outputs
@@ -641,6 +649,23 @@ int trm_step_tangent(trm_ctx* ctx, double dt, int nsteps);
  * bit 26.  The state afterwards is still that of trm_step, bit for bit, and zero seeds give the tangents of the unseeded run.
  * Errors: TRM_EINVAL without a context or an open tangent, for any other bc_var, a side other than 0 / 1, or a NULL pointer. */
 int trm_tangent_bc_upload(trm_ctx* ctx, int bc_var, int side, const void* host);
+/* Seeds on a boundary time series (TRM_OPT_DERIVATIVE_SERIES = 1): the tangent with respect to the record that drives the run.  With the
+ * option set, trm_step_tangent accepts boundary series on the four pairs above (Value on temperature, Flux on internal energy; whole
+ * records on the branch-free boundary kinds) and evaluates them in the launch, in front of every step, as trm_step does: the state
+ * afterwards is that of trm_step with the same series, bit for bit.
+ *   trm_tangent_bc_series_upload(ctx, bc_var, side, nt, host)
+ *                                           host[nt][num_columns] doubles: the seed d(node value) of every node of the pair's series; nt
+ *                                           must be the levels the series holds.  A step's seed is s[n1] w1 + s[n2] w2 over the two
+ *                                           nodes that bracket its time, with the weights of the primal's interpolation (w2 = f,
+ *                                           w1 = 1 - f; Raster: w2 = f / g; one node where the time is clamped or lands on a node).
+ *                                           Zeroed by trm_tangent_open, freed by trm_tangent_close; a series nobody has seeded has zero
+ *                                           seeds.  A pair without a series keeps its constant value and its trm_tangent_bc_upload seed.
+ * Every operation is linear in the seeds: doubling them doubles the tangents bit for bit.  TRM_INFO_DERIVATIVE_SERIES reports the
+ * series the last launch evaluated.  Refused with TRM_EUNSUPPORTED by trm_step_tangent: a series of kind Gradient, any series on the
+ * generic boundary kinds, an input (forcing) series, a windowed or trimmed series, parameter seeds together with a series.
+ * Errors: TRM_EINVAL without a context or an open tangent, for a pair without a series, an nt other than the series' levels or a NULL
+ * pointer; trm_tangent_bc_upload on a seriesed pair (option set) returns TRM_EINVAL and names this call; TRM_ENOMEM. */
+int trm_tangent_bc_series_upload(trm_ctx* ctx, int bc_var, int side, int nt, const void* host);
 /* Seeds on the thermal parameters: the tangent with respect to the five conductivities and five heat capacities of trm_params
  * (SoilThermalConductivities, SoilHeatCapacities; Enzyme gives the reference these through Duplicated(integrator, dintegrator)), in the
  * order of trm_params.  Porosity, rho_soc, Lsl and the saturation are not differentiated.
@@ -744,6 +769,26 @@ int trm_adjoint_backward(trm_ctx* ctx);
 int trm_adjoint_bc_open(trm_ctx* ctx);
 int trm_adjoint_bc_download(trm_ctx* ctx, int bc_var, int side, void* host);
 int trm_adjoint_bc_device_ptr(trm_ctx* ctx, int bc_var, int side, void** dev);
+/* Gradients through a boundary time series (TRM_OPT_DERIVATIVE_SERIES = 1): dL/d(node value) of every node of the series that drive the
+ * run, from the same sweep.  With the option set, trm_step_record accepts the boundary series trm_step_tangent accepts, evaluates them
+ * in the launch and keeps the rows (bracketing nodes and fractions) of every taped step; trm_adjoint_backward runs the accumulating
+ * instances (it opens the four per-column accumulators, zero, if nobody has) with those rows, never a clock of its own.
+ *   trm_adjoint_bc_series_download(ctx, bc_var, side, nt, host)
+ *                                           host[nt][num_columns] doubles.  After a trm_adjoint_backward that succeeded: the node
+ *                                           gradients of the pair's series of that sweep -- a step adds w1 term to node n1 and w2 term to
+ *                                           node n2 of its bracket -- and exact zeros for nodes no taped step touched (and before the
+ *                                           first sweep).  nt must be the levels the series holds.
+ *   trm_adjoint_bc_series_device_ptr(ctx, bc_var, side, &dev, &nt)
+ *                                           the accumulator on the device, nt x num_columns contiguous doubles
+ * Each (node, column) sum runs over the taped steps newest first and always continues from the stored value: it does not depend on
+ * TRM_OPT_STEPS_PER_LAUNCH, on how the trm_step_record calls were split or on the checkpoint interval.  A pair without a series keeps
+ * its per-column gradient (trm_adjoint_bc_download) in the same sweep.  trm_set_bc_series, trm_clear_series, trm_series_append,
+ * trm_series_window and trm_series_trim_before make a tape that holds steps stale.
+ * Errors: TRM_EINVAL without a context or an open adjoint, for a pair without a series, an nt other than the series' levels or a NULL
+ * pointer; trm_adjoint_bc_download / _device_ptr on a seriesed pair (option set) return TRM_EINVAL and name these calls; TRM_EUNSUPPORTED
+ * from trm_step_record / trm_adjoint_backward as for trm_step_tangent, and for an open parameter gradient together with a series. */
+int trm_adjoint_bc_series_download(trm_ctx* ctx, int bc_var, int side, int nt, void* host);
+int trm_adjoint_bc_series_device_ptr(trm_ctx* ctx, int bc_var, int side, void** dev, int* nt);
 /* Parameter gradients: dL/d(parameter) of the ten thermal parameters trm_tangent_param_set seeds (TRM_THERMAL_PARAM_*), per column, from
  * the same sweep.
  *   trm_adjoint_param_open(ctx)             allocates eight per-cell accumulators (Nh x Nzp doubles each) and the result, zero, and

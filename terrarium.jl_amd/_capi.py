@@ -50,10 +50,12 @@ OPTION_LATER = dict(defer_closure_stores=12, info_closure_stored=106, info_mater
 # ... and that table is pinned as a whole by the same test: the keys of TRM_OPT_INTERIOR_STEPS have one of their own
 # (tests/test_interior_steps_abi.py)
 OPTION_INTERIOR = dict(interior_steps=13, info_interior_launches=108)
+# ... and those of TRM_OPT_DERIVATIVE_SERIES (tests/test_series_derivative_host.py)
+OPTION_DERIVATIVE = dict(derivative_series=14, info_derivative_series=109)
 
 
 def option_id(name: str) -> int:
-    for table in (OPTION, OPTION_LATER, OPTION_INTERIOR):
+    for table in (OPTION, OPTION_LATER, OPTION_INTERIOR, OPTION_DERIVATIVE):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -110,7 +112,8 @@ EXPORTS = (
     "trm_adjoint_open trm_adjoint_close trm_adjoint_upload trm_adjoint_download trm_adjoint_device_ptr trm_adjoint_tape "
     "trm_step_record trm_adjoint_backward trm_adjoint_open_checkpointed trm_adjoint_checkpoints "
     "trm_tangent_bc_upload trm_adjoint_bc_open trm_adjoint_bc_download trm_adjoint_bc_device_ptr "
-    "trm_tangent_param_set trm_adjoint_param_open trm_adjoint_param_download trm_adjoint_param_device_ptr").split()
+    "trm_tangent_param_set trm_adjoint_param_open trm_adjoint_param_download trm_adjoint_param_device_ptr "
+    "trm_tangent_bc_series_upload trm_adjoint_bc_series_download trm_adjoint_bc_series_device_ptr").split()
 # the thermal parameters the tangent and the adjoint differentiate (TRM_THERMAL_PARAM_*), in the order of trm_params
 THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
 # forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
@@ -289,6 +292,9 @@ def lib():
     L.trm_adjoint_param_open.argtypes = [vp]
     L.trm_adjoint_param_download.argtypes = [vp, i32, vp]
     L.trm_adjoint_param_device_ptr.argtypes = [vp, i32, C.POINTER(vp)]
+    L.trm_tangent_bc_series_upload.argtypes = [vp, i32, i32, i32, vp]
+    L.trm_adjoint_bc_series_download.argtypes = [vp, i32, i32, i32, vp]
+    L.trm_adjoint_bc_series_device_ptr.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(i32)]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

@@ -453,8 +453,9 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
             for (long i = 0; i < c->Nh; ++i) host[(size_t)k * c->Nh + i] = R[k] / total;
         return upload_impl<NF>(c, TRM_FIELD_ROOT_FRACTION, host.data());
     }
-    // slot table + [nsteps][nseries] rows for a multi-step launch that starts at the context clock
-    static int upload_series_rows(trm_ctx* c, double dt, int nsteps) {
+    // slot table + [nsteps][nseries] rows for a multi-step launch that starts at the context clock.  `keep`: the rows are appended there
+    // as well (trm_step_record's tape); `kept`: the rows are these, formed by an earlier call, and not the clock's (trm_adjoint_backward)
+    static int upload_series_rows(trm_ctx* c, double dt, int nsteps, std::vector<SeriesRow>* keep = nullptr, const SeriesRow* kept = nullptr) {
         const int ns = (int)c->series.size();
         const size_t nrows = (size_t)nsteps * ns, need = sizeof(SeriesTable<NF>) + nrows * sizeof(SeriesRow);
         trm_ctx::RowStage& st = c->row_stage[c->row_stage_next];
@@ -490,6 +491,7 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
             } else {
                 tb.dst[slot] = (NF*)c->state.f[sr.field];
             }
+            if (kept) continue;
             double t = c->time;
             if (sr.trimmed && t < sr.trimmed_before)
                 return fail(c, TRM_EINVAL, "a windowed time series was asked for a time before the levels it still holds (trm_series_trim_before released them)");
@@ -502,6 +504,8 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
                 t += dt;
             }
         }
+        if (kept && nrows > 0) std::memcpy(rows, kept, nrows * sizeof(SeriesRow));
+        if (keep) keep->insert(keep->end(), rows, rows + nrows);
         if (!c->d_series_table) TRM_HIP(c, hipMalloc(&c->d_series_table, sizeof(SeriesTable<double>)));
         if (nrows * sizeof(SeriesRow) > c->series_rows_cap) {
             if (c->d_series_rows) TRM_HIP(c, hipFree(c->d_series_rows));   // (waits for the launches that read it)
@@ -513,7 +517,7 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
         // in stream order behind the previous launch (which reads the device copies) and in front of the next one; the host
         // does not wait
         TRM_HIP(c, hipMemcpyAsync(c->d_series_table, &tb, sizeof(tb), hipMemcpyHostToDevice, c->stream));
-        TRM_HIP(c, hipMemcpyAsync(c->d_series_rows, rows, nrows * sizeof(SeriesRow), hipMemcpyHostToDevice, c->stream));
+        if (nrows > 0) TRM_HIP(c, hipMemcpyAsync(c->d_series_rows, rows, nrows * sizeof(SeriesRow), hipMemcpyHostToDevice, c->stream));
         TRM_HIP(c, hipEventRecord(st.done, c->stream));
         st.pending = true;
         return TRM_OK;
@@ -1650,6 +1654,10 @@ int trm_destroy(trm_ctx* c) {
         if (q) (void)hipFree(q);
     for (double* q : c->d_adj_bc)
         if (q) (void)hipFree(q);
+    for (double* q : c->d_tan_bcs)
+        if (q) (void)hipFree(q);
+    for (double* q : c->d_adj_bcs)
+        if (q) (void)hipFree(q);
     for (double* q : c->d_adj_param)
         if (q) (void)hipFree(q);
     if (c->d_adj_param_out) (void)hipFree(c->d_adj_param_out);
@@ -1871,6 +1879,7 @@ int trm_clear_series(trm_ctx* c) {
     for (auto& sr : c->series)
         if (sr.d_values) (void)hipFree(sr.d_values);
     c->series.clear();
+    bc_changed(c);
     return TRM_OK;
 }
 
@@ -1934,6 +1943,7 @@ int trm_series_append(trm_ctx* c, int is_bc, int id, int side, int nt, const dou
     if (sr->pending_from < 0) sr->pending_from = held;
     sr->windowed = true;
     sr->times.insert(sr->times.end(), times, times + nt);
+    bc_changed(c);     // (a taped step's rows name the levels the series held when it was recorded)
     return TRM_OK;
 }
 
@@ -1944,6 +1954,7 @@ int trm_series_window(trm_ctx* c, int is_bc, int id, int side, int levels) {
     if (sr->indexing == TRM_TIME_CYCLICAL) return fail(c, TRM_EINVAL, "trm_series_window: a cyclical series is periodic over its whole record and cannot be windowed");
     if (levels < 0) return fail(c, TRM_EINVAL, "trm_series_window: levels < 0");
     sr->windowed = true;
+    bc_changed(c);
     const long held = (long)sr->times.size();
     if (levels > sr->cap) {      // reserve: the levels held are laid out from slot 0 of the larger ring
         const size_t row = (size_t)c->Nh * c->esize;
@@ -1982,6 +1993,7 @@ int trm_series_trim_before(trm_ctx* c, double t) {
         }
     }
     if (released) {
+        bc_changed(c);
         if (hipSetDevice(c->device) != hipSuccess) return fail(c, TRM_EHIP, "trm_series_trim_before: hipSetDevice");
         if (!c->copy_order) TRM_HIP(c, hipEventCreateWithFlags(&c->copy_order, hipEventDisableTiming));
         TRM_HIP(c, hipEventRecord(c->copy_order, c->stream));
@@ -2442,10 +2454,37 @@ const char* derivative_unsupported(const trm_ctx* c) {
     if (c->Nz > 64) return "columns of at most 64 levels";
     return nullptr;
 }
+// TRM_OPT_DERIVATIVE_SERIES: the series the derivative kernels evaluate themselves -- boundary series of kind Value on temperature or
+// Flux on internal energy, whole records, on the branch-free boundary kinds
+const char* derivative_series_unsupported(const trm_ctx* c) {
+    if (Policy<double>::generic_bcs(c))
+        return "no time series with the generic boundary kinds (a Gradient condition on temperature off the branch-free kinds: that step reads its boundary values from memory)";
+    for (const auto& sr : c->series) {
+        if (!sr.is_bc) return "no input (forcing) time series: boundary series only";
+        const int slot = Policy<double>::series_slot(c, sr);
+        if (slot < SLOT_T_BOT || slot > SLOT_FU_TOP)
+            return "a boundary series of kind Value on temperature or Flux on internal energy only (not of kind Gradient, not on another variable)";
+        if (sr.windowed || sr.trimmed || sr.head != 0 || (long)sr.times.size() != sr.cap)
+            return "no windowed or trimmed time series: the sweep needs every level the tape spans";
+    }
+    return nullptr;
+}
+// the series of a (boundary variable, side) pair, or null
+const trm_ctx::Series* bc_series_of(const trm_ctx* c, int bc_var, int side) {
+    for (const auto& sr : c->series)
+        if (sr.is_bc && sr.var == bc_var && sr.side == side) return &sr;
+    return nullptr;
+}
+// series the derivative launches of this context evaluate in-kernel (0: none attached)
+int derivative_series_count(const trm_ctx* c) { return (int)c->series.size(); }
+const char* kSeriesWithParams = "no thermal-parameter seeds or gradients together with a time series (a follow-up: DESIGN 7 (8))";
 // ... and what a step needs besides: constant inputs, no accumulation, the temperature halos of the heat-only programs
 const char* derivative_step_unsupported(const trm_ctx* c) {
     if (const char* why = derivative_unsupported(c)) return why;
-    if (!c->series.empty()) return "no time series may be attached";
+    if (!c->series.empty()) {
+        if (!c->opt_derivative_series) return "no time series may be attached";
+        if (const char* why = derivative_series_unsupported(c)) return why;
+    }
     for (const auto& a : c->averages)
         if (a.field >= 0) return "no time average may be open";
     if (c->opt_vwc_field) return "no per-cell vwc_forcing field";
@@ -2486,6 +2525,8 @@ int trm_tangent_open(trm_ctx* c) {
     }
     for (double* q : c->d_tan_bc)
         if (q) TRM_HIP(c, hipMemsetAsync(q, 0, (size_t)c->Nh * sizeof(double), c->stream));
+    for (int s = 0; s < 4; ++s)
+        if (c->d_tan_bcs[s]) TRM_HIP(c, hipMemsetAsync(c->d_tan_bcs[s], 0, (size_t)c->tan_bcs_nt[s] * (size_t)c->Nh * sizeof(double), c->stream));
     c->tan_bc_seeded = false;
     std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
     c->tan_param_seeded = false;
@@ -2505,6 +2546,11 @@ int trm_tangent_close(trm_ctx* c) {
         if (q) TRM_HIP(c, hipFree(q));
         q = nullptr;
     }
+    for (double*& q : c->d_tan_bcs) {
+        if (q) TRM_HIP(c, hipFree(q));
+        q = nullptr;
+    }
+    std::fill(std::begin(c->tan_bcs_nt), std::end(c->tan_bcs_nt), 0L);
     c->tan_bc_seeded = false;
     std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
     c->tan_param_seeded = false;
@@ -2526,12 +2572,54 @@ int alloc_tangent_bc_seeds(trm_ctx* c, const char* who) {
         }
     return TRM_OK;
 }
+// a [nt][Nh] array shaped like the series of pair `slot`, zeroed where this call allocates it (a series of another length replaces it)
+int alloc_series_shaped(trm_ctx* c, double*& q, long& have_nt, long nt, const char* who) {
+    if (q && have_nt == nt) return TRM_OK;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    if (q) (void)hipFree(q);
+    q = nullptr;
+    have_nt = 0;
+    const size_t bytes = (size_t)nt * (size_t)c->Nh * sizeof(double);
+    if (hipMalloc((void**)&q, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        q = nullptr;
+        return fail(c, TRM_ENOMEM, std::string(who) + ": an array of the series' shape does not fit");
+    }
+    have_nt = nt;
+    TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+    return TRM_OK;
+}
+// the arguments of the three per-node calls: the pair's slot and its series
+int bc_series_args(trm_ctx* c, int bc_var, int side, const char* who, int& slot, const trm_ctx::Series*& sr) {
+    slot = bc_pair_index(bc_var, side);
+    if (slot < 0) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument (internal energy or temperature, bottom or top)");
+    sr = bc_series_of(c, bc_var, side);
+    if (!sr) return fail(c, TRM_EINVAL, std::string(who) + ": the pair has no time series (trm_set_bc_series)");
+    return TRM_OK;
+}
 }  // namespace
+int trm_tangent_bc_series_upload(trm_ctx* c, int bc_var, int side, int nt, const void* host) {
+    TRM_ENTER_HEUN(c);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_bc_series_upload: no tangent is open (trm_tangent_open)");
+    int slot = -1;
+    const trm_ctx::Series* sr = nullptr;
+    if (int rc = bc_series_args(c, bc_var, side, "trm_tangent_bc_series_upload", slot, sr)) return rc;
+    if (!host) return fail(c, TRM_EINVAL, "trm_tangent_bc_series_upload: bad argument");
+    if ((long)nt != sr->cap || (long)sr->times.size() != sr->cap)
+        return fail(c, TRM_EINVAL, "trm_tangent_bc_series_upload: nt must be the levels of the pair's series (" + std::to_string(sr->times.size()) + ")");
+    if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_bc_series_upload")) return rc;
+    if (int rc = alloc_series_shaped(c, c->d_tan_bcs[slot], c->tan_bcs_nt[slot], nt, "trm_tangent_bc_series_upload")) return rc;
+    TRM_HIP(c, hipMemcpyAsync(c->d_tan_bcs[slot], host, (size_t)nt * (size_t)c->Nh * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;             // (seeds are not state: tan_stale stays as it is)
+}
 int trm_tangent_bc_upload(trm_ctx* c, int bc_var, int side, const void* host) {
     TRM_ENTER_HEUN(c);
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: no tangent is open (trm_tangent_open)");
     const int slot = bc_pair_index(bc_var, side);
     if (slot < 0 || !host) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: bad argument (internal energy or temperature, bottom or top)");
+    if (c->opt_derivative_series && bc_series_of(c, bc_var, side))
+        return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: the pair is driven by a time series: its seeds have the series' shape (trm_tangent_bc_series_upload)");
     const size_t bytes = (size_t)c->Nh * sizeof(double);
     if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_bc_upload")) return rc;
     TRM_HIP(c, hipMemcpyAsync(c->d_tan_bc[slot], host, bytes, hipMemcpyHostToDevice, c->stream));
@@ -2545,6 +2633,7 @@ int trm_tangent_param_set(trm_ctx* c, const double seed[TRM_THERMAL_PARAM_COUNT]
     if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_param_set: ") + why);
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_param_set: no tangent is open (trm_tangent_open)");
     if (!seed) return fail(c, TRM_EINVAL, "trm_tangent_param_set: bad argument");
+    if (c->opt_derivative_series && !c->series.empty()) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_param_set: ") + kSeriesWithParams);
     if (const char* why = thermal_params_not_differentiable(c)) return fail(c, TRM_EINVAL, std::string("trm_tangent_param_set: ") + why);
     if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_param_set")) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -2604,16 +2693,29 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_step_tangent: no tangent is open (trm_tangent_open)");
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_tangent: nsteps < 0");
     if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + why);
+    const int nser = derivative_series_count(c);
+    if (nser && c->tan_param_seeded) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + kSeriesWithParams);
     if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_step_tangent") + kStaleTangent);
+    if (nser) {   // series ride with the boundary-seeded instances: the per-column seeds, and zeros for a series nobody has seeded
+        if (int rc = alloc_tangent_bc_seeds(c, "trm_step_tangent")) return rc;
+        for (const auto& sr : c->series) {
+            const int slot = bc_pair_index(sr.var, sr.side);
+            if (int rc = alloc_series_shaped(c, c->d_tan_bcs[slot], c->tan_bcs_nt[slot], sr.cap, "trm_step_tangent")) return rc;
+        }
+    }
     bc_changed(c);             // (a state-changing call for an open tape)
     // the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to TRM_OPT_STEPS_PER_LAUNCH steps each
     const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);
     int n = 0;
     while (n < nsteps) {
         const int m = std::min(spl, nsteps - n);
-        int rc = Ops<double>::update_inputs(c, c->state, c->time);
-        if (!rc) rc = c->tan_param_seeded ? TangentLaunch::step_param(c, dt, m) : c->tan_bc_seeded ? TangentLaunch::step_bc(c, dt, m) : TangentLaunch::step(c, dt, m);
+        int rc = nser ? Ops<double>::upload_series_rows(c, dt, m) : Ops<double>::update_inputs(c, c->state, c->time);
+        if (!rc) rc = nser                  ? TangentLaunch::step_series(c, dt, m)
+                      : c->tan_param_seeded ? TangentLaunch::step_param(c, dt, m)
+                      : c->tan_bc_seeded    ? TangentLaunch::step_bc(c, dt, m)
+                                            : TangentLaunch::step(c, dt, m);
         if (rc) return rc;
+        c->derivative_series = nser;
         tick(c, dt, m);
         n += m;
     }
@@ -2639,6 +2741,7 @@ void free_tape(trm_ctx* c) {
     c->ckpt_interval = 0;
     c->tape_dt.clear();
     c->tape_segs.clear();
+    c->tape_rows.clear();
     c->adj_stale = false;
 }
 void free_adjoint_params(trm_ctx* c) {
@@ -2658,6 +2761,11 @@ void free_adjoint(trm_ctx* c) {
         if (q) (void)hipFree(q);
         q = nullptr;
     }
+    for (double*& q : c->d_adj_bcs) {
+        if (q) (void)hipFree(q);
+        q = nullptr;
+    }
+    std::fill(std::begin(c->adj_bcs_nt), std::end(c->adj_bcs_nt), 0L);
     free_adjoint_params(c);
     free_tape(c);
 }
@@ -2695,12 +2803,15 @@ int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who)
     }
     for (double* q : c->d_adj_bc)   // (opening again keeps open boundary gradients, zero)
         if (q) TRM_HIP(c, hipMemsetAsync(q, 0, (size_t)c->Nh * sizeof(double), c->stream));
+    for (int s = 0; s < 4; ++s)     // (... and node gradients)
+        if (c->d_adj_bcs[s]) TRM_HIP(c, hipMemsetAsync(c->d_adj_bcs[s], 0, (size_t)c->adj_bcs_nt[s] * (size_t)c->Nh * sizeof(double), c->stream));
     for (double* q : c->d_adj_param)   // (... and open parameter gradients)
         if (q) TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
     if (c->d_adj_param_out) TRM_HIP(c, hipMemsetAsync(c->d_adj_param_out, 0, (size_t)TRM_THERMAL_PARAM_COUNT * (size_t)c->Nh * sizeof(double), c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     c->tape_dt.clear();        // (a fresh tape)
     c->tape_segs.clear();
+    c->tape_rows.clear();
     c->adj_stale = false;
     return TRM_OK;
 }
@@ -2733,11 +2844,13 @@ int trm_adjoint_close(trm_ctx* c) {
     free_adjoint(c);
     return TRM_OK;
 }
-int trm_adjoint_bc_open(trm_ctx* c) {
-    TRM_ENTER_HEUN(c);
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_bc_open: no adjoint is open (trm_adjoint_open)");
+namespace {
+// the four per-column accumulators, zeroed: all of them (trm_adjoint_bc_open) or the ones this call allocates (`only_new`: a sweep with
+// series, which rides with the accumulating instances, opens them if nobody has)
+int open_adjoint_bc(trm_ctx* c, bool only_new, const char* who) {
     const size_t bytes = (size_t)c->Nh * sizeof(double);
     for (double*& q : c->d_adj_bc) {
+        const bool fresh = !q;
         if (!q && hipMalloc((void**)&q, bytes) != hipSuccess) {
             (void)hipGetLastError();
             q = nullptr;
@@ -2745,12 +2858,18 @@ int trm_adjoint_bc_open(trm_ctx* c) {
                 if (r) (void)hipFree(r);
                 r = nullptr;
             }
-            return fail(c, TRM_ENOMEM, "trm_adjoint_bc_open: the accumulators do not fit");
+            return fail(c, TRM_ENOMEM, std::string(who) + ": the accumulators do not fit");
         }
-        TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+        if (fresh || !only_new) TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
     }
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
+}
+}  // namespace
+int trm_adjoint_bc_open(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_bc_open: no adjoint is open (trm_adjoint_open)");
+    return open_adjoint_bc(c, false, "trm_adjoint_bc_open");
 }
 namespace {
 int adjoint_bc_args(trm_ctx* c, int bc_var, int side, const void* ptr, const char* who, int& slot) {
@@ -2758,9 +2877,42 @@ int adjoint_bc_args(trm_ctx* c, int bc_var, int side, const void* ptr, const cha
     if (!c->d_adj_bc[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no boundary gradients are open (trm_adjoint_bc_open)");
     slot = bc_pair_index(bc_var, side);
     if (slot < 0 || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument (internal energy or temperature, bottom or top)");
+    if (c->opt_derivative_series && bc_series_of(c, bc_var, side))
+        return fail(c, TRM_EINVAL, std::string(who) + ": the pair is driven by a time series: its gradient has the series' shape (trm_adjoint_bc_series_download)");
+    return TRM_OK;
+}
+// the node accumulator of a seriesed pair (zeros until a sweep has run)
+int adjoint_bc_series_args(trm_ctx* c, int bc_var, int side, const void* ptr, const char* who, int& slot, long& nt) {
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no adjoint is open (trm_adjoint_open)");
+    const trm_ctx::Series* sr = nullptr;
+    if (int rc = bc_series_args(c, bc_var, side, who, slot, sr)) return rc;
+    if (!ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument");
+    nt = sr->cap;
+    if (int rc = alloc_series_shaped(c, c->d_adj_bcs[slot], c->adj_bcs_nt[slot], nt, who)) return rc;
     return TRM_OK;
 }
 }  // namespace
+int trm_adjoint_bc_series_download(trm_ctx* c, int bc_var, int side, int nt, void* host) {
+    TRM_ENTER_HEUN(c);
+    int slot = -1;
+    long have = 0;
+    if (int rc = adjoint_bc_series_args(c, bc_var, side, host, "trm_adjoint_bc_series_download", slot, have)) return rc;
+    if ((long)nt != have) return fail(c, TRM_EINVAL, "trm_adjoint_bc_series_download: nt must be the levels of the pair's series (" + std::to_string(have) + ")");
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_adj_bcs[slot], (size_t)nt * (size_t)c->Nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_bc_series_device_ptr(trm_ctx* c, int bc_var, int side, void** dev, int* nt) {
+    TRM_ENTER_HEUN(c);
+    int slot = -1;
+    long have = 0;
+    if (!nt) return fail(c, TRM_EINVAL, "trm_adjoint_bc_series_device_ptr: bad argument");
+    if (int rc = adjoint_bc_series_args(c, bc_var, side, dev, "trm_adjoint_bc_series_device_ptr", slot, have)) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    *dev = c->d_adj_bcs[slot];
+    *nt = (int)have;
+    return TRM_OK;
+}
 int trm_adjoint_bc_download(trm_ctx* c, int bc_var, int side, void* host) {
     TRM_ENTER_HEUN(c);
     int slot = -1;
@@ -2782,6 +2934,7 @@ int trm_adjoint_param_open(trm_ctx* c) {
     if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_param_open: ") + why);
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_param_open: no adjoint is open (trm_adjoint_open)");
     if (const char* why = thermal_params_not_differentiable(c)) return fail(c, TRM_EINVAL, std::string("trm_adjoint_param_open: ") + why);
+    if (c->opt_derivative_series && !c->series.empty()) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_param_open: ") + kSeriesWithParams);
     if (int rc = trm_adjoint_bc_open(c)) return rc;   // (the accumulating instances carry both)
     const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double), out_bytes = (size_t)TRM_THERMAL_PARAM_COUNT * (size_t)c->Nh * sizeof(double);
     bool ok = true;
@@ -2891,6 +3044,8 @@ int trm_step_record(trm_ctx* c, double dt, int nsteps) {
                                            std::to_string(used) + " of " + std::to_string(c->tape_cap) + " slots taken)");
     }
     if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + why);
+    const int nser = derivative_series_count(c);
+    if (nser && c->d_adj_param_out) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + kSeriesWithParams);
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_step_record") + kStaleTape);
     if (nsteps > 0) c->tan_stale = true;       // (a state-changing call for an open tangent)
     // the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to TRM_OPT_STEPS_PER_LAUNCH steps each
@@ -2898,14 +3053,19 @@ int trm_step_record(trm_ctx* c, double dt, int nsteps) {
     int n = 0;
     while (n < nsteps) {
         const int m = std::min(spl, nsteps - n);
-        int rc = Ops<double>::update_inputs(c, c->state, c->time);
+        // (with series: the rows of the launch's steps stay with the tape, [taped step][series])
+        const size_t rows_before = c->tape_rows.size();
+        int rc = nser ? Ops<double>::upload_series_rows(c, dt, m, &c->tape_rows) : Ops<double>::update_inputs(c, c->state, c->time);
         // (checkpointed: the launch stores before its steps room, room + K, ... -- the starts of the segments it opens)
         const int room = K ? open_segment_room(c, dt) : 0;
-        if (!rc) rc = K ? CheckpointLaunch::record(c, dt, m, (int)c->tape_segs.size(), room, K) : AdjointLaunch::record(c, dt, m, (int)c->tape_dt.size());
+        if (!rc && nser) rc = K ? CheckpointLaunch::record_series(c, dt, m, (int)c->tape_segs.size(), room, K) : AdjointLaunch::record_series(c, dt, m, (int)c->tape_dt.size());
+        else if (!rc) rc = K ? CheckpointLaunch::record(c, dt, m, (int)c->tape_segs.size(), room, K) : AdjointLaunch::record(c, dt, m, (int)c->tape_dt.size());
         if (rc) {
+            c->tape_rows.resize(rows_before);
             c->adj_stale = taped_steps(c) > 0;
             return rc;
         }
+        c->derivative_series = nser;
         if (K) {
             int left = m, at = taped_steps(c);
             if (room > 0 && left > 0) {
@@ -2934,22 +3094,43 @@ int trm_adjoint_backward(trm_ctx* c) {
     TRM_ENTER(c);
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_backward: no adjoint is open (trm_adjoint_open)");
     if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + why);
+    const int nser = derivative_series_count(c);
+    if (nser && c->d_adj_param_out) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + kSeriesWithParams);
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_adjoint_backward") + kStaleTape);
+    if (nser) {
+        // series ride with the accumulating instances: the per-column accumulators if nobody has opened them, and the node accumulators,
+        // zero in front of the sweep's first launch; every launch gets the rows the record kept for its steps
+        if (c->tape_rows.size() != (size_t)taped_steps(c) * (size_t)nser)
+            return fail(c, TRM_ESTALE, "trm_adjoint_backward: the tape was recorded without the series the context holds now: trm_adjoint_open starts a new tape");
+        if (int rc = open_adjoint_bc(c, true, "trm_adjoint_backward")) return rc;
+        for (const auto& sr : c->series) {
+            const int slot = bc_pair_index(sr.var, sr.side);
+            if (int rc = alloc_series_shaped(c, c->d_adj_bcs[slot], c->adj_bcs_nt[slot], sr.cap, "trm_adjoint_backward")) return rc;
+            TRM_HIP(c, hipMemsetAsync(c->d_adj_bcs[slot], 0, (size_t)sr.cap * (size_t)c->Nh * sizeof(double), c->stream));
+        }
+    }
+    // (the rows of taped steps [first, first + n), uploaded in front of the launch that walks them)
+    auto kept_rows = [&](int first, int n) { return Ops<double>::upload_series_rows(c, 0.0, n, nullptr, c->tape_rows.data() + (size_t)first * (size_t)nser); };
     if (c->ckpt_interval) {   // one launch per segment, newest first; the first launch folds (an empty tape: that launch alone, no step)
         int fold = 1;
         size_t s = c->tape_segs.size();
         do {
             const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
-            if (int rc = c->d_adj_param_out ? CheckpointLaunch::backward_param(c, seg.dt, seg.len, seg.slot, fold)
-                         : c->d_adj_bc[0]   ? CheckpointLaunch::backward_bc(c, seg.dt, seg.len, seg.slot, fold)
-                                            : CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold)) {
+            int rc = nser ? kept_rows(seg.first, seg.len) : TRM_OK;
+            if (!rc) rc = nser                 ? CheckpointLaunch::backward_series(c, seg.dt, seg.len, seg.slot, fold)
+                          : c->d_adj_param_out ? CheckpointLaunch::backward_param(c, seg.dt, seg.len, seg.slot, fold)
+                          : c->d_adj_bc[0]     ? CheckpointLaunch::backward_bc(c, seg.dt, seg.len, seg.slot, fold)
+                                               : CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold);
+            if (rc) {
                 c->adj_stale = true;       // (lam is part way down the tape)
                 return rc;
             }
+            c->derivative_series = nser;
             fold = 0;
             if (s > 0) --s;
         } while (s > 0);
         c->tape_segs.clear();
+        c->tape_rows.clear();
         c->adj_stale = false;
         return finish(c, c->d_adj_param_out ? AdjointLaunch::param_reduce(c) : TRM_OK);
     }
@@ -2961,16 +3142,21 @@ int trm_adjoint_backward(trm_ctx* c) {
         int begin = end;
         while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
         const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
-        if (int rc = c->d_adj_param_out ? AdjointLaunch::backward_param(c, dt_block, end - begin, begin, fold)
-                     : c->d_adj_bc[0]   ? AdjointLaunch::backward_bc(c, dt_block, end - begin, begin, fold)
-                                        : AdjointLaunch::backward(c, dt_block, end - begin, begin, fold)) {
+        int rc = nser ? kept_rows(begin, end - begin) : TRM_OK;
+        if (!rc) rc = nser                 ? AdjointLaunch::backward_series(c, dt_block, end - begin, begin, fold)
+                      : c->d_adj_param_out ? AdjointLaunch::backward_param(c, dt_block, end - begin, begin, fold)
+                      : c->d_adj_bc[0]     ? AdjointLaunch::backward_bc(c, dt_block, end - begin, begin, fold)
+                                           : AdjointLaunch::backward(c, dt_block, end - begin, begin, fold);
+        if (rc) {
             c->adj_stale = true;       // (lam is part way down the tape)
             return rc;
         }
+        c->derivative_series = nser;
         end = begin;
         fold = 0;
     } while (end > 0);
     c->tape_dt.clear();
+    c->tape_rows.clear();
     c->adj_stale = false;
     return finish(c, c->d_adj_param_out ? AdjointLaunch::param_reduce(c) : TRM_OK);
 }
@@ -3420,7 +3606,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
     c->args_valid = false;
     c->heun_pending = false;
     // (an option that changes which program the next step takes: the arrays are made current here, not by whatever runs next)
-    if (c->closure_deferred && option != TRM_OPT_ASYNC && option != TRM_OPT_WRITE_KF_EVERY_STEP && option != TRM_OPT_INTERIOR_STEPS &&
+    if (c->closure_deferred && option != TRM_OPT_ASYNC && option != TRM_OPT_WRITE_KF_EVERY_STEP && option != TRM_OPT_INTERIOR_STEPS && option != TRM_OPT_DERIVATIVE_SERIES &&
         !(option == TRM_OPT_DEFER_CLOSURE_STORES && value != 0)) {
         TRM_HIP(c, hipSetDevice(c->device));
         if (int rf = flush_closure(c)) return rf;
@@ -3461,6 +3647,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
             if (value < 0 || value > 2) break;
             c->opt_interior = value;
             return TRM_OK;
+        case TRM_OPT_DERIVATIVE_SERIES: c->opt_derivative_series = value != 0; return TRM_OK;
         default: break;
     }
     return fail(c, TRM_EINVAL, "trm_set_option: unknown option or value");
@@ -3485,6 +3672,8 @@ int trm_get_option(const trm_ctx* c, int option, int* value) {
         case TRM_INFO_MATERIALIZATIONS: *value = (int)c->materializations; return TRM_OK;
         case TRM_OPT_INTERIOR_STEPS: *value = c->opt_interior; return TRM_OK;
         case TRM_INFO_INTERIOR_LAUNCHES: *value = (int)c->interior_launches; return TRM_OK;
+        case TRM_OPT_DERIVATIVE_SERIES: *value = c->opt_derivative_series; return TRM_OK;
+        case TRM_INFO_DERIVATIVE_SERIES: *value = c->derivative_series; return TRM_OK;
         case TRM_INFO_LAST_PROGRAM: *value = c->last_program; return TRM_OK;
         case TRM_INFO_GENERIC_BOUNDARY_KERNELS: *value = (c->precision == TRM_F64 ? trmh::Policy<double>::generic_bcs(c) : trmh::Policy<float>::generic_bcs(c)) ? 1 : 0; return TRM_OK;
         case TRM_INFO_BC_SIGNATURE: *value = trmh::bc_signature_of(c); return TRM_OK;

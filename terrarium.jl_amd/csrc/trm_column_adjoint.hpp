@@ -28,6 +28,11 @@
 // Each lane sums its own cell's eight values in registers over the taped steps, newest first, carried from launch to launch in eight
 // fields [Nh][Nzp] like the boundary sums: strictly sequential per cell.  k_param_reduce sums a column's cells in ascending order and
 // applies the host's chain rule to the ten parameters.
+// SERIES (TRM_OPT_DERIVATIVE_SERIES, always with BCGRAD; trm_series_derivative.hpp): the record evaluates the boundary series in front of
+// every step as column_program<.., SERIES> does; the sweep takes each step's temperature values from the series again (fetched a step
+// ahead, with the next tape slot) and a seriesed pair's term goes w1 term onto node n1 and w2 term onto node n2 of a [nt][Nh]
+// accumulator instead of the per-column sum: the owning edge lane holds the two sums of the current bracket and stores / loads them
+// where a step's row names other nodes, and at the end of the launch.
 // Every coefficient is a function of the state U_k BEFORE step k: k_column_record is the multi-step primal that stores U_k into tape
 // slot k (the field layout [Nh][Nzp]) before every step; k_column_adjoint walks a block of slots backwards with lam in registers.
 // closure_tangent and conductivity_tangent are linear in their seed, one scalar slope per cell: applied to a cotangent they are their
@@ -58,6 +63,10 @@ struct BcGradPtrs {
 struct AdjointBcArgs : AdjointArgs {
     BcGradPtrs g;
 };
+// ... of k_column_adjoint<HYD, LPC, true, AdjointSeriesArgs, false, true>: and the node accumulators of the seriesed pairs
+struct AdjointSeriesArgs : AdjointBcArgs {
+    SeriesGradPtrs sg;
+};
 // a lane's running sums (the bottom lane owns Tb and Ub, the top lane Tt and Ut; the other lanes carry zeros)
 struct BcGrad {
     double Tb = 0.0, Tt = 0.0, Ub = 0.0, Ut = 0.0;
@@ -83,6 +92,32 @@ TRM_DEV void bc_grad_store(const BcGradPtrs& g, const LaneInfo& ln, int ii, cons
         g.gTt[ii] = acc.Tt;
         g.gUt[ii] = acc.Ut;
     }
+}
+
+// SERIES, behind adjoint_step: this step's four terms (`term`: zero off the owning lanes) onto the node sums of the seriesed pairs and
+// onto the per-column sums of the others
+TRM_DEV void series_grad_step(const ColumnArgs<double>& a, const SeriesGradPtrs& g, const LaneInfo& ln, int ii, int step, const BcGrad& term,
+                              BcGrad& acc, SeriesGrad& sg) {
+    const SeriesTable<double>* tb = a.series;
+    const SeriesRow* rows = a.series_rows + (size_t)step * (size_t)a.nseries;
+    const bool own_b = ln.act && ln.is_bot, own_t = ln.act && ln.is_top;
+    if (tb->base[SLOT_T_BOT]) series_sums_add(sg.s[SLOT_T_BOT], g.gn[SLOT_T_BOT], series_bracket(tb, rows, SLOT_T_BOT), own_b, ii, term.Tb);
+    else acc.Tb = acc.Tb + term.Tb;
+    if (tb->base[SLOT_T_TOP]) series_sums_add(sg.s[SLOT_T_TOP], g.gn[SLOT_T_TOP], series_bracket(tb, rows, SLOT_T_TOP), own_t, ii, term.Tt);
+    else acc.Tt = acc.Tt + term.Tt;
+    if (tb->base[SLOT_FU_BOT]) series_sums_add(sg.s[SLOT_FU_BOT], g.gn[SLOT_FU_BOT], series_bracket(tb, rows, SLOT_FU_BOT), own_b, ii, term.Ub);
+    else acc.Ub = acc.Ub + term.Ub;
+    if (tb->base[SLOT_FU_TOP]) series_sums_add(sg.s[SLOT_FU_TOP], g.gn[SLOT_FU_TOP], series_bracket(tb, rows, SLOT_FU_TOP), own_t, ii, term.Ut);
+    else acc.Ut = acc.Ut + term.Ut;
+}
+// behind the loop: the held sums back to their nodes
+TRM_DEV void series_grad_store(const ColumnArgs<double>& a, const SeriesGradPtrs& g, const LaneInfo& ln, int ii, const SeriesGrad& sg) {
+    const SeriesTable<double>* tb = a.series;
+    const bool own_b = ln.act && ln.is_bot, own_t = ln.act && ln.is_top;
+    if (tb->base[SLOT_T_BOT]) series_sums_store(sg.s[SLOT_T_BOT], g.gn[SLOT_T_BOT], own_b, ii);
+    if (tb->base[SLOT_T_TOP]) series_sums_store(sg.s[SLOT_T_TOP], g.gn[SLOT_T_TOP], own_t, ii);
+    if (tb->base[SLOT_FU_BOT]) series_sums_store(sg.s[SLOT_FU_BOT], g.gn[SLOT_FU_BOT], own_b, ii);
+    if (tb->base[SLOT_FU_TOP]) series_sums_store(sg.s[SLOT_FU_TOP], g.gn[SLOT_FU_TOP], own_t, ii);
 }
 
 // the per-cell parameter accumulators of a PGRAD sweep, [Nh][Nzp] each, in the order of ParamSeeds
@@ -180,7 +215,8 @@ TRM_DEV void record_flux_U(const View<double>& v, const LaneInfo& ln, int ii, bo
 // same.  (One kernel template and not a device function under two kernels: behind a call the existing instances came out of the
 // register allocator with other registers and three more instructions; as a defaulted template parameter they compile to the code
 // they had.)
-template <int HYD, int LPC, bool STRIDED = false, class Args = AdjointArgs>
+// SERIES: the seriesed boundary values are formed in front of every step (series_boundary_step), the last step writes them back.
+template <int HYD, int LPC, bool STRIDED = false, class Args = AdjointArgs, bool SERIES = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args aa) {
     using NF = double;
     int ii;
@@ -225,6 +261,10 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v
         } else {
             if (ln.act) *slot = c.U;
             slot += aa.slot_elems;
+        }
+        if constexpr (SERIES) {
+            NF unused_b = 0.0, unused_t = 0.0, unused_U = 0.0;
+            series_boundary_step<false, true>(v, a, ln, ii, step, bc, nullptr, unused_b, unused_t, unused_U);
         }
         const Frac<NF>* pre = step > 0 ? &f_new : nullptr;
         const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
@@ -361,7 +401,8 @@ TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, con
 // The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
 // BCGRAD (Args = AdjointBcArgs): the boundary gradients ride along; the instances without are the code they were.
 // PGRAD (Args = AdjointParamArgs, with BCGRAD): and the per-cell parameter sums.
-template <int HYD, int LPC, bool BCGRAD = false, class Args = AdjointArgs, bool PGRAD = false>
+// SERIES (Args = AdjointSeriesArgs, with BCGRAD): a.series_rows holds the rows of this launch's taped steps, oldest first.
+template <int HYD, int LPC, bool BCGRAD = false, class Args = AdjointArgs, bool PGRAD = false, bool SERIES = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args aa) {
     using NF = double;
     int ii;
@@ -393,13 +434,32 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> 
         asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt), "v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub),
                      "v"(acc.Ut));
     } else asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt));
-    for (int step = a.nsteps - 1; step >= 0; --step) {
-        const NF U = U_next;
-        if (step > 0) {
-            slot -= aa.slot_elems;
-            U_next = *slot;
+    if constexpr (SERIES) {
+        // the step's temperature values are fetched with the tape slot of the step, a step ahead of their use
+        SeriesGrad sg;
+        NF bTb_next = bTb, bTt_next = bTt;
+        if (a.nsteps > 0) series_temperatures(a, ii, a.nsteps - 1, bTb_next, bTt_next);
+        for (int step = a.nsteps - 1; step >= 0; --step) {
+            const NF U = U_next, sTb = bTb_next, sTt = bTt_next;
+            if (step > 0) {
+                slot -= aa.slot_elems;
+                U_next = *slot;
+                series_temperatures(a, ii, step - 1, bTb_next, bTt_next);
+            }
+            BcGrad term;
+            lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, U, sat, lam, a.dt, sTb, sTt, generic, term, pacc);
+            series_grad_step(a, aa.sg, ln, ii, step, term, acc, sg);
         }
-        lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc, pacc);
+        series_grad_store(a, aa.sg, ln, ii, sg);
+    } else {
+        for (int step = a.nsteps - 1; step >= 0; --step) {
+            const NF U = U_next;
+            if (step > 0) {
+                slot -= aa.slot_elems;
+                U_next = *slot;
+            }
+            lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc, pacc);
+        }
     }
     if (ln.act) aa.lU[e] = lam;
     if constexpr (BCGRAD) bc_grad_store(aa.g, ln, ii, acc);

@@ -33,6 +33,10 @@ struct CheckpointArgs {
 struct CheckpointBcArgs : CheckpointArgs {
     BcGradPtrs g;
 };
+// ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointSeriesArgs, false, true>: and the node accumulators of the seriesed pairs
+struct CheckpointSeriesArgs : CheckpointBcArgs {
+    SeriesGradPtrs sg;
+};
 // ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointParamArgs, true>: and the per-cell parameter accumulators
 struct CheckpointParamArgs : CheckpointBcArgs {
     ParamGradPtrs pg;
@@ -42,7 +46,9 @@ struct CheckpointParamArgs : CheckpointBcArgs {
 // Dynamic LDS: a.nsteps * TRM_STEP_BLOCK doubles.
 // BCGRAD (Args = CheckpointBcArgs): the boundary gradients as in k_column_adjoint, added in the same order -- the per-step tape's sums.
 // PGRAD (Args = CheckpointParamArgs, with BCGRAD): and the per-cell parameter sums, likewise.
-template <int HYD, int LPC, bool BCGRAD = false, class Args = CheckpointArgs, bool PGRAD = false>
+// SERIES (Args = CheckpointSeriesArgs, with BCGRAD): a.series_rows holds the rows of the segment's steps, oldest first; the recompute
+// loop evaluates the series as the record did, the backward loop takes the temperature values again and sums onto the nodes.
+template <int HYD, int LPC, bool BCGRAD = false, class Args = CheckpointArgs, bool PGRAD = false, bool SERIES = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ca) {
     using NF = double;
     extern __shared__ double seg[];
@@ -84,6 +90,10 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<dou
         Frac<NF> f = column_closure<NF, false, HYD>(p, L, 0.0, c, viol);
         for (int j = 0; j < m - 1; ++j) {
             mine[j * TRM_STEP_BLOCK] = c.U;
+            if constexpr (SERIES) {
+                NF unused_b = 0.0, unused_t = 0.0, unused_U = 0.0;
+                series_boundary_step<false, false>(v, a, ln, ii, j, bc, nullptr, unused_b, unused_t, unused_U);
+            }
             const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
                                            : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, &f);
             NF gU = t.gU, gS = t.gS, z0;
@@ -96,7 +106,21 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<dou
     if (m > 0) mine[(m - 1) * TRM_STEP_BLOCK] = c.U;
 
     // ---- backward: the transposed steps at U_{c+m-1} ... U_c
-    for (int j = m - 1; j >= 0; --j) lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, mine[j * TRM_STEP_BLOCK], sat, lam, a.dt, bTb, bTt, generic, acc, pacc);
+    if constexpr (SERIES) {
+        SeriesGrad sg;
+        NF sTb = bTb, sTt = bTt;
+        if (m > 0) series_temperatures(a, ii, m - 1, sTb, sTt);
+        for (int j = m - 1; j >= 0; --j) {
+            const NF uTb = sTb, uTt = sTt;
+            if (j > 0) series_temperatures(a, ii, j - 1, sTb, sTt);
+            BcGrad term;
+            lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, mine[j * TRM_STEP_BLOCK], sat, lam, a.dt, uTb, uTt, generic, term, pacc);
+            series_grad_step(a, ca.sg, ln, ii, j, term, acc, sg);
+        }
+        series_grad_store(a, ca.sg, ln, ii, sg);
+    } else {
+        for (int j = m - 1; j >= 0; --j) lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, mine[j * TRM_STEP_BLOCK], sat, lam, a.dt, bTb, bTt, generic, acc, pacc);
+    }
     if (ln.act) ca.lU[e] = lam;
     if constexpr (BCGRAD) bc_grad_store(ca.g, ln, ii, acc);
     if constexpr (PGRAD) param_grad_store(ca.pg, ln, e, pacc);

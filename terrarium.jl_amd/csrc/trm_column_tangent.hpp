@@ -27,8 +27,12 @@
 //   dry halo     of the reference-zero policy: s_halo = sk_air por + s0, dkappa_halo = 2 s_halo (dsk_a por + ds0)
 // Every tangent operation is linear in (dU, dT, dliq) and the seeds with no additive constant, so scaling the seeds by a power of two
 // scales every tangent bit for bit.
+// SERIES (TangentSeriesArgs, always together with BCSEED; trm_series_derivative.hpp): in front of every step the seriesed pairs among the four
+// take the value of their series (the primal: as column_program<.., SERIES>) and the seed s[n1] w1 + s[n2] w2 of seeds shaped like the
+// series, [nt][Nh]; a pair without a series keeps its constant value and its per-column seed.
 #pragma once
 #include "trm_column.hpp"
+#include "trm_series_derivative.hpp"
 
 namespace trm {
 
@@ -50,6 +54,11 @@ struct ParamSeeds {
 // ... of k_column_tangent<HYD, LPC, true, TangentParamArgs, true>
 struct TangentParamArgs : TangentBcArgs {
     ParamSeeds s;
+};
+// ... of k_column_tangent<HYD, LPC, true, TangentSeriesArgs, false, true>: and the seeds of the seriesed pairs, [nt][Nh] each, by slot
+// (null: the pair has no series)
+struct TangentSeriesArgs : TangentBcArgs {
+    const double* sn[4];
 };
 
 // tangent of the energy closure at (U, sat) -- C is the heat capacity the primal closure formed
@@ -144,7 +153,8 @@ TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& 
 // last step, hydraulic_conductivity of the new state) and the three tangents.
 // BCSEED (Args = TangentBcArgs): the boundary seeds are loaded once in front of the step loop; the instances without are the code they were.
 // PSEED (Args = TangentParamArgs, with BCSEED): the parameter seeds are kernel arguments.
-template <int HYD, int LPC, bool BCSEED = false, class Args = TangentArgs, bool PSEED = false>
+// SERIES (Args = TangentSeriesArgs, with BCSEED): values and seeds of the seriesed pairs are formed in front of every step.
+template <int HYD, int LPC, bool BCSEED = false, class Args = TangentArgs, bool PSEED = false, bool SERIES = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ta) {
     using NF = double;
     constexpr int CPW = 64 / LPC;
@@ -227,11 +237,13 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
     NF gU_out = 0.0;
     for (int step = 0; step < a.nsteps; ++step) {
         if (step > 0) c = n;
+        if constexpr (SERIES) series_boundary_step<true, true>(v, a, ln, ii, step, bc, ta.sn, dbTb, dbTt, dflux_U);
         const Frac<NF>* pre = step > 0 ? &f_new : nullptr;
         const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
                                        : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
         NF dgU;
         if constexpr (PSEED) dgU = tendency_tangent<LPC, BCSEED, true>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt, &ta.s);
+        else if constexpr (SERIES) dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bc.bTb, bc.bTt, generic, dbTb, dbTt);
         else dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt);
         NF gU = t.gU, gS = t.gS, z0;
         column_advance<NF, false, LPC>(v, L, ln, Nz, bc, c.U, c.sat, gU, gS, a.dt, n, z0, bad);

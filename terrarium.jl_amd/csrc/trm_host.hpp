@@ -179,6 +179,14 @@ struct trm_ctx {
     // `tan_param_seeded`: set since trm_tangent_open, and trm_step_tangent / trm_tangent_closure run the parameter-seeded instances.
     double tan_param[8] = {};
     bool tan_param_seeded = false;
+    // TRM_OPT_DERIVATIVE_SERIES: 1 lets trm_step_tangent / trm_step_record / trm_adjoint_backward run with boundary time series on the four
+    // pairs above, evaluated in the launch (trm_series_derivative.hpp); 0 (default): they refuse a context with a series attached.
+    // `derivative_series`: TRM_INFO_DERIVATIVE_SERIES, the series the last derivative launch evaluated in-kernel.
+    int opt_derivative_series = 0, derivative_series = 0;
+    // the seeds of the seriesed pairs (trm_tangent_bc_series_upload), [nt][Nh] doubles in the order of d_tan_bc, `tan_bcs_nt` their
+    // levels; null: none yet (trm_step_tangent allocates zeros).  Zeroed by trm_tangent_open, freed by trm_tangent_close.
+    double* d_tan_bcs[4] = {};
+    long tan_bcs_nt[4] = {};
     // reverse-mode gradients (trm_adjoint_*): the cotangent fields of U, T, liq in the same layout, and the tape of trm_step_record --
     // `tape_cap` slots of [Nh][Nzp] doubles, slot k the internal energy before taped step k, `tape_dt[k]` that step's dt.  `adj_stale`:
     // another call has changed the state or a boundary condition since the first taped step (state_changed / bc_changed below).
@@ -188,6 +196,12 @@ struct trm_ctx {
     double* d_adj_bc[4] = {};
     // the thermal-parameter accumulators (trm_adjoint_param_open): eight per-cell fields [Nh][Nzp] in the order of tan_param, and the
     // result of k_param_reduce, [TRM_THERMAL_PARAM_COUNT][Nh]; null: the sweep runs the instances without
+    // the node accumulators of the seriesed pairs (trm_adjoint_bc_series_download), [nt][Nh] doubles in the order of d_tan_bc, zeroed in
+    // front of every sweep; `tape_rows`: the SeriesRows trm_step_record uploaded, [taped step][series] -- the sweep uploads the slice a
+    // launch covers, so that it sees exactly the record's brackets and fractions
+    double* d_adj_bcs[4] = {};
+    long adj_bcs_nt[4] = {};
+    std::vector<trm::SeriesRow> tape_rows;
     double* d_adj_param[8] = {};
     double* d_adj_param_out = nullptr;
     double* d_tape = nullptr;
@@ -557,6 +571,7 @@ struct TangentLaunch {
     static int step(trm_ctx* c, double dt, int nsteps);
     static int step_bc(trm_ctx* c, double dt, int nsteps);   // with boundary seeds (trm_launch_column_tangent_bc.hip)
     static int step_param(trm_ctx* c, double dt, int nsteps);   // with boundary and parameter seeds (trm_launch_column_tangent_param.hip)
+    static int step_series(trm_ctx* c, double dt, int nsteps);   // with boundary series in the launch (trm_launch_column_tangent_series.hip)
     static int closure(trm_ctx* c);
     static int closure_param(trm_ctx* c);                    // with parameter seeds (trm_launch_column_tangent_param.hip)
 };
@@ -568,6 +583,9 @@ struct AdjointLaunch {
     // with boundary and parameter gradients, and k_param_reduce that ends a sweep on either tape (trm_launch_column_adjoint_param.hip)
     static int backward_param(trm_ctx* c, double dt, int nsteps, int slot, int fold);
     static int param_reduce(trm_ctx* c);
+    // with boundary series in the launch and node gradients (trm_launch_column_adjoint_series.hip)
+    static int record_series(trm_ctx* c, double dt, int nsteps, int slot);
+    static int backward_series(trm_ctx* c, double dt, int nsteps, int slot, int fold);
 };
 // the strided k_column_record / k_column_adjoint_ckpt (trm_launch_column_adjoint_ckpt.hip): the record stores before the steps `first`,
 // `first + every`, ... of the launch into the slots from `slot` on; the backward launch pulls lam through the segment of `nsteps`
@@ -577,6 +595,9 @@ struct CheckpointLaunch {
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
     static int backward_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // with boundary gradients (trm_launch_column_adjoint_ckpt_bc.hip)
     static int backward_param(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // ... and parameter gradients (trm_launch_column_adjoint_ckpt_param.hip)
+    // with boundary series in the launch (trm_launch_column_adjoint_series.hip, trm_launch_column_adjoint_ckpt_series.hip)
+    static int record_series(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
+    static int backward_series(trm_ctx* c, double dt, int nsteps, int slot, int fold);
 };
 // The chain rule between the ten thermal parameters (TRM_THERMAL_PARAM_*, the order of trm_params) and the eight numbers the kernels
 // differentiate (make_dev_params): w[q] = d(derived number) / d(parameter q), with sk_i = sqrt(k_i), s0 = sqrt(k_mineral) frac_mineral +

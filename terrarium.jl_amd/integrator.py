@@ -435,6 +435,17 @@ class DeviceState:
         a[...] = values
         self._check(self._lib.trm_tangent_bc_upload(self._ctx, _capi.BC_VAR[var], _capi.SIDE[side], a.ctypes.data), "trm_tangent_bc_upload")
 
+    def set_bc_series_tangent(self, var, side, values):
+        """Seeds the nodes of the time series that drives (`var`, `side`): [nt][Nh], or anything that broadcasts to it, nt the levels
+        of the series (trm_tangent_bc_series_upload; option `derivative_series`).  A step's seed is interpolated between the seeds of
+        its two bracketing nodes with the weights of the series' own interpolation."""
+        a = np.asarray(values, dtype=np.float64)
+        nt = a.shape[0] if a.ndim >= 1 else self.series_info((var, side))["levels"]
+        seeds = np.empty((nt, self.grid.Nh), dtype=np.float64)
+        seeds[...] = a.reshape(nt, 1) if a.ndim == 1 else a
+        self._check(self._lib.trm_tangent_bc_series_upload(self._ctx, _capi.BC_VAR[var], _capi.SIDE[side], nt, seeds.ctypes.data),
+                    "trm_tangent_bc_series_upload")
+
     def set_param_tangent(self, seeds):
         """Seeds thermal parameters: {name: d(parameter)} over `k_water, k_ice, k_air, k_mineral, k_organic, c_water, c_ice, c_air,
         c_mineral, c_organic` (the ones left out are 0), one number each for all columns (trm_tangent_param_set).  The seeds hold for
@@ -496,6 +507,15 @@ class DeviceState:
         Gradient condition) or `internal_energy` (a Flux).  Zeros where the pair's kind reads no value (trm_adjoint_bc_download)."""
         a = np.empty(self.grid.Nh, dtype=np.float64)
         self._check(self._lib.trm_adjoint_bc_download(self._ctx, _capi.BC_VAR[var], _capi.SIDE[side], a.ctypes.data), "trm_adjoint_bc_download")
+        return a
+
+    def bc_series_gradient(self, var, side) -> np.ndarray:
+        """dL/d(node value) of the time series that drives (`var`, `side`) as [nt][Nh], after adjoint_backward; exact zeros for the
+        nodes no taped step touched (trm_adjoint_bc_series_download; option `derivative_series`)."""
+        nt = self.series_info((var, side))["levels"]
+        a = np.empty((nt, self.grid.Nh), dtype=np.float64)
+        self._check(self._lib.trm_adjoint_bc_series_download(self._ctx, _capi.BC_VAR[var], _capi.SIDE[side], nt, a.ctypes.data),
+                    "trm_adjoint_bc_series_download")
         return a
 
     def open_param_gradient(self):
@@ -651,7 +671,9 @@ class DeviceState:
         """Which kernel instance the last step launch of this context selected (TRM_INFO_LAST_PROGRAM), decoded: the selection
         rules of the library are pure host logic on sizes, kinds and options -- a wrong rule costs speed, never correctness, so
         nothing but a look at this id would notice."""
-        return _capi.decode_program(self.get_option("info_last_program"))
+        out = _capi.decode_program(self.get_option("info_last_program"))
+        out["series"] = self.get_option("info_derivative_series")     # (time series the last derivative launch evaluated in the kernel)
+        return out
 
     def set_stream(self, hip_stream_handle):
         self._check(self._lib.trm_set_stream(self._ctx, C.c_void_p(hip_stream_handle)), "trm_set_stream")
@@ -925,14 +947,42 @@ class ModelIntegrator:
 _BOUNDARY_DERIVATIVE_KINDS = {"temperature": ("value", "gradient"), "internal_energy": ("flux",)}
 
 
+def _series_driven(integ, var, side):
+    """The boundary condition on (var, side) is a device-resident time series: a FieldTimeSeries or a time-indexed raster source."""
+    value = integ.boundary_conditions.get((var, side), (None, None))[1]
+    return isinstance(value, FieldTimeSeries) or (isinstance(value, RasterInputSource) and not value.static)
+
+
+class _derivative_series:
+    """Sets the option `derivative_series` for the duration of a jvp / vjp call where a boundary series drives the run."""
+
+    def __init__(self, integ):
+        self.st = integ.state
+        self.wanted = any(_series_driven(integ, var, side) for var, side in integ.boundary_conditions)
+
+    def __enter__(self):
+        self.before = self.st.get_option("derivative_series")
+        if self.wanted:
+            self.st.set_option("derivative_series", 1)
+        return self
+
+    def __exit__(self, *exc):
+        if self.wanted:
+            self.st.set_option("derivative_series", self.before)
+        return False
+
+
 def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, d_params=None) -> dict:
     """Forward-mode derivative of `run!(integ; steps)` with respect to the initial internal energy: the integrator is stepped `steps`
     times with its own dt, its state carrying the tangent seeded by `d_internal_energy` ([Nz][Nh], or anything that broadcasts to
     it).  Returns {"internal_energy", "temperature", "liquid_water_fraction"}: the tangents of those fields after the last step.
     `d_boundary` = {(var, side): values}: seeds d(value) of boundary conditions, [Nh] or a scalar each -- a Value or a Gradient on
     `temperature`, a Flux on `internal_energy` -- held over the run like the values themselves (trm_tangent_bc_upload).
+    For a pair driven by a `FieldTimeSeries` or a time-indexed raster source the seeds have the series' shape, [nt][Nh]: d(node value)
+    of every node of the record (trm_tangent_bc_series_upload); the option `derivative_series` is set for the duration of the call.
     `d_params` = {name: value}: seeds on the thermal parameters (`k_mineral`, `c_water`, ...: trm_tangent_param_set).
-    The heat-only SoilModel in fp64 with ForwardEuler and constant boundary conditions and inputs (trm_step_tangent)."""
+    The heat-only SoilModel in fp64 with ForwardEuler and boundary conditions that are constant over the run or whole-record time
+    series (trm_step_tangent); callables, state functions and windowed sources are refused."""
     if not isinstance(integ.timestepper, ForwardEuler):
         raise ValueError("jvp: ForwardEuler only")
     if integ._has_time_dependence() or integ._windowed():
@@ -942,13 +992,17 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, 
     if opened:
         st.open_tangent()
     try:
-        st.set_tangent("internal_energy", d_internal_energy)
-        for (var, side), values in (d_boundary or {}).items():
-            st.set_bc_tangent(var, side, values)
-        if d_params is not None:
-            st.set_param_tangent(d_params)
-        st.step_tangent(integ.timestepper.dt, int(steps))
-        return {name: st.tangent(name) for name in _capi.TANGENT}
+        with _derivative_series(integ):
+            st.set_tangent("internal_energy", d_internal_energy)
+            for (var, side), values in (d_boundary or {}).items():
+                if _series_driven(integ, var, side):
+                    st.set_bc_series_tangent(var, side, values)
+                else:
+                    st.set_bc_tangent(var, side, values)
+            if d_params is not None:
+                st.set_param_tangent(d_params)
+            st.step_tangent(integ.timestepper.dt, int(steps))
+            return {name: st.tangent(name) for name in _capi.TANGENT}
     finally:
         if opened:
             st.close_tangent()
@@ -963,7 +1017,9 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
     states in between formed again by the backward sweep -- the same gradient bit for bit.  The coverage and refusals of `jvp`.
     With `wrt_boundary` it returns (dL/dU_0, {(var, side): dL/d(value) as [Nh]}) for the boundary conditions of the integrator whose
     value the run reads -- a Value or a Gradient on `temperature`, a Flux on `internal_energy` -- from the same sweep
-    (trm_adjoint_bc_open).  With `wrt_params` it appends {name: dL/d(parameter) as [Nh]} for the ten thermal parameters, each column's
+    (trm_adjoint_bc_open); a pair driven by a `FieldTimeSeries` or a time-indexed raster source gets dL/d(node value) as [nt][Nh], the
+    shape of its record (trm_adjoint_bc_series_download; the option `derivative_series` is set for the duration of the call).
+    With `wrt_params` it appends {name: dL/d(parameter) as [Nh]} for the ten thermal parameters, each column's
     share (trm_adjoint_param_open): (dL/dU_0, params), or (dL/dU_0, boundary, params) with `wrt_boundary` as well."""
     if not isinstance(integ.timestepper, ForwardEuler):
         raise ValueError("vjp: ForwardEuler only")
@@ -981,24 +1037,26 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
         if opened or st.adjoint_checkpoints() != (K, 0, slots):
             st.open_adjoint(slots, K)
     try:
-        st.step_record(integ.timestepper.dt, steps)
-        for name, w in (("internal_energy", internal_energy), ("temperature", temperature), ("liquid_water_fraction", liquid_water_fraction)):
-            st.set_cotangent(name, 0.0 if w is None else w)
-        if wrt_boundary:
-            st.open_bc_gradient()
-        if wrt_params:
-            st.open_param_gradient()
-        st.adjoint_backward()
-        g = st.cotangent("internal_energy")
-        if not wrt_boundary and not wrt_params:
-            return g
-        out = [g]
-        if wrt_boundary:
-            pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
-            out.append({(var, side): st.bc_gradient(var, side) for var, side in pairs})
-        if wrt_params:
-            out.append({name: st.param_gradient(name) for name in _capi.THERMAL_PARAMS})
-        return tuple(out)
+        with _derivative_series(integ):
+            st.step_record(integ.timestepper.dt, steps)
+            for name, w in (("internal_energy", internal_energy), ("temperature", temperature), ("liquid_water_fraction", liquid_water_fraction)):
+                st.set_cotangent(name, 0.0 if w is None else w)
+            if wrt_boundary:
+                st.open_bc_gradient()
+            if wrt_params:
+                st.open_param_gradient()
+            st.adjoint_backward()
+            g = st.cotangent("internal_energy")
+            if not wrt_boundary and not wrt_params:
+                return g
+            out = [g]
+            if wrt_boundary:
+                pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
+                out.append({(var, side): st.bc_series_gradient(var, side) if _series_driven(integ, var, side) else st.bc_gradient(var, side)
+                            for var, side in pairs})
+            if wrt_params:
+                out.append({name: st.param_gradient(name) for name in _capi.THERMAL_PARAMS})
+            return tuple(out)
     finally:
         if opened:
             st.close_adjoint()
