@@ -287,6 +287,33 @@ template <class NF> const LaunchArgs<NF>& launch_args(trm_ctx* c) {
 template const LaunchArgs<double>& launch_args<double>(trm_ctx*);
 template const LaunchArgs<float>& launch_args<float>(trm_ctx*);
 
+// The derivative launchers: each ride's instantiation lives in a translation unit of its own (trm_host.hpp, trm_launch_derivative.inl)
+int TangentLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride) {
+    switch (ride) {
+        case RIDE_BC: return tangent_step<RIDE_BC>(c, dt, nsteps);
+        case RIDE_PARAM: return tangent_step<RIDE_PARAM>(c, dt, nsteps);
+        case RIDE_SERIES: return tangent_step<RIDE_SERIES>(c, dt, nsteps);
+        default: return tangent_step<RIDE_NONE>(c, dt, nsteps);
+    }
+}
+int TangentLaunch::closure(trm_ctx* c, Ride ride) { return ride == RIDE_PARAM ? tangent_closure<RIDE_PARAM>(c) : tangent_closure<RIDE_NONE>(c); }
+template <bool CKPT> static int backward_by_ride(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) {
+    switch (ride) {
+        case RIDE_BC: return adjoint_backward<CKPT, RIDE_BC>(c, dt, nsteps, slot, fold);
+        case RIDE_PARAM: return adjoint_backward<CKPT, RIDE_PARAM>(c, dt, nsteps, slot, fold);
+        case RIDE_SERIES: return adjoint_backward<CKPT, RIDE_SERIES>(c, dt, nsteps, slot, fold);
+        default: return adjoint_backward<CKPT, RIDE_NONE>(c, dt, nsteps, slot, fold);
+    }
+}
+int AdjointLaunch::record(trm_ctx* c, double dt, int nsteps, int slot, bool series) {
+    return series ? adjoint_record<false, true>(c, dt, nsteps, slot, 0, 1) : adjoint_record<false, false>(c, dt, nsteps, slot, 0, 1);
+}
+int AdjointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) { return backward_by_ride<false>(c, dt, nsteps, slot, fold, ride); }
+int CheckpointLaunch::record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every, bool series) {
+    return series ? adjoint_record<true, true>(c, dt, nsteps, slot, first, every) : adjoint_record<true, false>(c, dt, nsteps, slot, first, every);
+}
+int CheckpointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) { return backward_by_ride<true>(c, dt, nsteps, slot, fold, ride); }
+
 // Time interpolation indices of a series at time t -- Oceananigans' FieldTimeSeries indexing (Linear / Clamp /
 // Cyclical), restated; that package is not part of the reference tree (parity unpinned).
 // Returns 0-based nodes n1, n2 and the fraction f: value = v[n2] * f + v[n1] * (1 - f); n1 == n2 means "copy".
@@ -2493,6 +2520,20 @@ const char* derivative_step_unsupported(const trm_ctx* c) {
             return "no Value or Gradient condition on the liquid water fraction";
     return nullptr;
 }
+// what rides along with a tangent step / a backward sweep: series first, then the thermal parameters, then the boundary values
+Ride tangent_ride(const trm_ctx* c, int nser) { return nser ? RIDE_SERIES : c->tan_param_seeded ? RIDE_PARAM : c->tan_bc_seeded ? RIDE_BC : RIDE_NONE; }
+Ride backward_ride(const trm_ctx* c, int nser) { return nser ? RIDE_SERIES : c->d_adj_param_out ? RIDE_PARAM : c->d_adj_bc[0] ? RIDE_BC : RIDE_NONE; }
+// trm_step_tangent and trm_step_record issue the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to
+// TRM_OPT_STEPS_PER_LAUNCH steps each ...
+int derivative_steps_per_launch(trm_ctx* c) { return c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c); }
+// ... and leave what a finalizing step leaves
+int derivative_steps_done(trm_ctx* c) {
+    c->closure_consistent = true;
+    c->psi_consistent = false;
+    c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
+    c->top_valid = false;
+    return finish(c, TRM_OK);
+}
 int tangent_args_ok(trm_ctx* c, int which, const void* ptr, const char* who) {
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no tangent is open (trm_tangent_open)");
     if (which < 0 || which > TRM_TANGENT_LIQUID_WATER_FRACTION || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument");
@@ -2686,7 +2727,7 @@ int trm_tangent_closure(trm_ctx* c) {
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_closure: no tangent is open (trm_tangent_open)");
     if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_closure: ") + why);
     if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_closure") + kStaleTangent);
-    return finish(c, c->tan_param_seeded ? TangentLaunch::closure_param(c) : TangentLaunch::closure(c));
+    return finish(c, TangentLaunch::closure(c, tangent_ride(c, 0)));
 }
 int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     TRM_ENTER(c);
@@ -2704,26 +2745,17 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
         }
     }
     bc_changed(c);             // (a state-changing call for an open tape)
-    // the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to TRM_OPT_STEPS_PER_LAUNCH steps each
-    const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);
-    int n = 0;
-    while (n < nsteps) {
-        const int m = std::min(spl, nsteps - n);
+    const int spl = derivative_steps_per_launch(c);
+    const Ride ride = tangent_ride(c, nser);
+    for (int n = 0, m; n < nsteps; n += m) {
+        m = std::min(spl, nsteps - n);
         int rc = nser ? Ops<double>::upload_series_rows(c, dt, m) : Ops<double>::update_inputs(c, c->state, c->time);
-        if (!rc) rc = nser                  ? TangentLaunch::step_series(c, dt, m)
-                      : c->tan_param_seeded ? TangentLaunch::step_param(c, dt, m)
-                      : c->tan_bc_seeded    ? TangentLaunch::step_bc(c, dt, m)
-                                            : TangentLaunch::step(c, dt, m);
+        if (!rc) rc = TangentLaunch::step(c, dt, m, ride);
         if (rc) return rc;
         c->derivative_series = nser;
         tick(c, dt, m);
-        n += m;
     }
-    c->closure_consistent = true;
-    c->psi_consistent = false;
-    c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
-    c->top_valid = false;
-    return finish(c, TRM_OK);
+    return derivative_steps_done(c);
 }
 
 // ---- reverse-mode gradients of the heat-only run (trm_column_adjoint.hpp) -----------------------------------------------------
@@ -3048,18 +3080,15 @@ int trm_step_record(trm_ctx* c, double dt, int nsteps) {
     if (nser && c->d_adj_param_out) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + kSeriesWithParams);
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_step_record") + kStaleTape);
     if (nsteps > 0) c->tan_stale = true;       // (a state-changing call for an open tangent)
-    // the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to TRM_OPT_STEPS_PER_LAUNCH steps each
-    const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);
-    int n = 0;
-    while (n < nsteps) {
-        const int m = std::min(spl, nsteps - n);
+    const int spl = derivative_steps_per_launch(c);
+    for (int n = 0, m; n < nsteps; n += m) {
+        m = std::min(spl, nsteps - n);
         // (with series: the rows of the launch's steps stay with the tape, [taped step][series])
         const size_t rows_before = c->tape_rows.size();
         int rc = nser ? Ops<double>::upload_series_rows(c, dt, m, &c->tape_rows) : Ops<double>::update_inputs(c, c->state, c->time);
         // (checkpointed: the launch stores before its steps room, room + K, ... -- the starts of the segments it opens)
         const int room = K ? open_segment_room(c, dt) : 0;
-        if (!rc && nser) rc = K ? CheckpointLaunch::record_series(c, dt, m, (int)c->tape_segs.size(), room, K) : AdjointLaunch::record_series(c, dt, m, (int)c->tape_dt.size());
-        else if (!rc) rc = K ? CheckpointLaunch::record(c, dt, m, (int)c->tape_segs.size(), room, K) : AdjointLaunch::record(c, dt, m, (int)c->tape_dt.size());
+        if (!rc) rc = K ? CheckpointLaunch::record(c, dt, m, (int)c->tape_segs.size(), room, K, nser != 0) : AdjointLaunch::record(c, dt, m, (int)c->tape_dt.size(), nser != 0);
         if (rc) {
             c->tape_rows.resize(rows_before);
             c->adj_stale = taped_steps(c) > 0;
@@ -3082,13 +3111,8 @@ int trm_step_record(trm_ctx* c, double dt, int nsteps) {
             }
         } else c->tape_dt.insert(c->tape_dt.end(), (size_t)m, dt);
         tick(c, dt, m);
-        n += m;
     }
-    c->closure_consistent = true;
-    c->psi_consistent = false;
-    c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
-    c->top_valid = false;
-    return finish(c, TRM_OK);
+    return derivative_steps_done(c);
 }
 int trm_adjoint_backward(trm_ctx* c) {
     TRM_ENTER(c);
@@ -3111,50 +3135,41 @@ int trm_adjoint_backward(trm_ctx* c) {
     }
     // (the rows of taped steps [first, first + n), uploaded in front of the launch that walks them)
     auto kept_rows = [&](int first, int n) { return Ops<double>::upload_series_rows(c, 0.0, n, nullptr, c->tape_rows.data() + (size_t)first * (size_t)nser); };
+    const Ride ride = backward_ride(c, nser);
+    int rc = TRM_OK, fold = 1;
     if (c->ckpt_interval) {   // one launch per segment, newest first; the first launch folds (an empty tape: that launch alone, no step)
-        int fold = 1;
         size_t s = c->tape_segs.size();
         do {
             const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
-            int rc = nser ? kept_rows(seg.first, seg.len) : TRM_OK;
-            if (!rc) rc = nser                 ? CheckpointLaunch::backward_series(c, seg.dt, seg.len, seg.slot, fold)
-                          : c->d_adj_param_out ? CheckpointLaunch::backward_param(c, seg.dt, seg.len, seg.slot, fold)
-                          : c->d_adj_bc[0]     ? CheckpointLaunch::backward_bc(c, seg.dt, seg.len, seg.slot, fold)
-                                               : CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold);
-            if (rc) {
-                c->adj_stale = true;       // (lam is part way down the tape)
-                return rc;
-            }
+            rc = nser ? kept_rows(seg.first, seg.len) : TRM_OK;
+            if (!rc) rc = CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold, ride);
+            if (rc) break;
             c->derivative_series = nser;
             fold = 0;
             if (s > 0) --s;
         } while (s > 0);
-        c->tape_segs.clear();
-        c->tape_rows.clear();
-        c->adj_stale = false;
-        return finish(c, c->d_adj_param_out ? AdjointLaunch::param_reduce(c) : TRM_OK);
+    } else {
+        // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch
+        // folds the cotangents of T and liq in (an empty tape: that launch alone)
+        const int spl = derivative_steps_per_launch(c);
+        int end = (int)c->tape_dt.size();
+        do {
+            int begin = end;
+            while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
+            const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
+            rc = nser ? kept_rows(begin, end - begin) : TRM_OK;
+            if (!rc) rc = AdjointLaunch::backward(c, dt_block, end - begin, begin, fold, ride);
+            if (rc) break;
+            c->derivative_series = nser;
+            end = begin;
+            fold = 0;
+        } while (end > 0);
     }
-    // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch folds
-    // the cotangents of T and liq in (an empty tape: that launch alone)
-    const int spl = c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c);
-    int end = (int)c->tape_dt.size(), fold = 1;
-    do {
-        int begin = end;
-        while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
-        const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
-        int rc = nser ? kept_rows(begin, end - begin) : TRM_OK;
-        if (!rc) rc = nser                 ? AdjointLaunch::backward_series(c, dt_block, end - begin, begin, fold)
-                      : c->d_adj_param_out ? AdjointLaunch::backward_param(c, dt_block, end - begin, begin, fold)
-                      : c->d_adj_bc[0]     ? AdjointLaunch::backward_bc(c, dt_block, end - begin, begin, fold)
-                                           : AdjointLaunch::backward(c, dt_block, end - begin, begin, fold);
-        if (rc) {
-            c->adj_stale = true;       // (lam is part way down the tape)
-            return rc;
-        }
-        c->derivative_series = nser;
-        end = begin;
-        fold = 0;
-    } while (end > 0);
+    if (rc) {
+        c->adj_stale = true;       // (lam is part way down the tape)
+        return rc;
+    }
+    c->tape_segs.clear();
     c->tape_dt.clear();
     c->tape_rows.clear();
     c->adj_stale = false;

@@ -39,11 +39,7 @@
 // own transposes, and the slopes are formed by the tangent's expressions.  No operation has an additive constant, so scaling the
 // cotangents by a power of two scales the gradient bit for bit, and a zero cotangent gives a zero gradient.
 #pragma once
-// (trm_column_tangent.hpp defines the non-template kernel k_closure_tangent, which trm_launch_column_tangent.hip owns: this translation
-// unit takes the header for closure_tangent and conductivity_tangent and gives its copy of that kernel a name of its own)
-#define k_closure_tangent k_closure_tangent_in_adjoint_unit
 #include "trm_column_tangent.hpp"
-#undef k_closure_tangent
 
 namespace trm {
 

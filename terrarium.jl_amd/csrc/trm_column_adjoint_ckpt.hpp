@@ -12,10 +12,6 @@
 // record chain entered step c with for every c > 0 (the closure the step before ended with, or its stored result), and for the first
 // state of a tape under the contract of trm_step_record: the stored T and liq are the closure of the stored U.
 #pragma once
-// (as trm_column_adjoint.hpp: this translation unit's copy of the non-template kernel of trm_column_tangent.hpp gets a name of its own)
-#define k_closure_tangent k_closure_tangent_in_adjoint_ckpt_unit
-#include "trm_column_tangent.hpp"
-#undef k_closure_tangent
 #include "trm_column_adjoint.hpp"
 
 namespace trm {

@@ -277,23 +277,9 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
     if (viol && ln.act) atomicOr(v.status, viol);
 }
 
-// trm_tangent_closure: (dT, dliq) of the stored (U, sat) and dU, one thread per cell of the device layout
-__global__ void __launch_bounds__(256) k_closure_tangent(View<double> v, DevParams<double> p, TangentArgs ta) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (size_t)v.Nh * (size_t)v.Nzp || (int)(e % (size_t)v.Nzp) >= v.Nz) return;
-    const double U = v.U[e], sat = v.sat[e];
-    double liq, T;
-    uint32_t viol = 0;
-    energy_closure(p, U, sat, liq, T, viol);
-    Frac<double> f = fractions_unchecked(p, sat, liq);
-    double dliq, dT;
-    closure_tangent(p, U, sat, heat_capacity(p, f), ta.dU[e], dliq, dT);
-    ta.dT[e] = dT;
-    ta.dliq[e] = dliq;
-}
-// ... with parameter seeds (trm_tangent_param_set): and the heat-capacity term.  A template, so that only the translation unit that
-// launches it holds a copy.
-template <class Args> __global__ void __launch_bounds__(256) k_closure_tangent_param(View<double> v, DevParams<double> p, Args ta) {
+// trm_tangent_closure: (dT, dliq) of the stored (U, sat) and dU, one thread per cell of the device layout.  PSEED (Args = TangentParamArgs,
+// trm_tangent_param_set): and the heat-capacity term.  A template, so that only the translation unit that launches it holds a copy.
+template <class Args, bool PSEED = false> __global__ void __launch_bounds__(256) k_closure_tangent(View<double> v, DevParams<double> p, Args ta) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)v.Nh * (size_t)v.Nzp || (int)(e % (size_t)v.Nzp) >= v.Nz) return;
     const double U = v.U[e], sat = v.sat[e];
@@ -304,7 +290,8 @@ template <class Args> __global__ void __launch_bounds__(256) k_closure_tangent_p
     const double C = heat_capacity(p, f);
     double dliq, dT;
     closure_tangent(p, U, sat, C, ta.dU[e], dliq, dT);
-    ta.dT[e] = dT + closure_param_slope(T, C) * heat_capacity_seed(ta.s, f);
+    if constexpr (PSEED) dT = dT + closure_param_slope(T, C) * heat_capacity_seed(ta.s, f);
+    ta.dT[e] = dT;
     ta.dliq[e] = dliq;
 }
 

@@ -495,6 +495,12 @@ inline int bc_signature_of(const trm_ctx* c) {
 inline int program_id(int family, int hyd, int lpc, int derive, int staged, int scalar_in, int bcsig) {
     return family | (hyd << 8) | ((lpc / 32) << 10) | (derive << 12) | ((staged ? 1 : 0) << 15) | ((scalar_in ? 1 : 0) << 16) | ((bcsig + 1) << 17);
 }
+// ... and the family bits the derivative launches add (TRM_PROGRAM_COLUMN_TANGENT / _ADJOINT; bit 31 is TRM_PROGRAM_PARAMETERS)
+constexpr int PROGRAM_GENERIC_HALOS = 1 << 25;   // Gradient halos on temperature, where trm_step takes k_step_wave
+constexpr int PROGRAM_BC_SEEDS = 1 << 26;        // tangent: the boundary seeds ride along
+constexpr int PROGRAM_BACKWARD = 1 << 26;        // adjoint: the backward launch (the record has it clear)
+constexpr int PROGRAM_CHECKPOINTED = 1 << 27;    // adjoint: the checkpointed tape
+constexpr int PROGRAM_BC_GRADIENT = 1 << 30;     // adjoint: the boundary gradients ride along
 #define TRM_BY_HYD(c, CALL)                                   \
     switch (::trmh::Policy<NF>::hyd(c)) {                     \
         case HYD_BC_LINEAR: { constexpr int H = HYD_BC_LINEAR; CALL; } break; \
@@ -566,38 +572,34 @@ template <class NF> struct Veg {
 template <class NF, bool RICH, int PROG> struct ColumnLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps); };
 // the multi-step program with time averages accumulated in the launch (trm_launch_column_accum_*.hip)
 template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps, const AccumArgs& acc); };
-// k_column_tangent / k_closure_tangent (trm_launch_column_tangent.hip, fp64 NoFlow only)
+// ---- the derivative families of the heat-only fp64 run (trm_launch_derivative.inl) --------------------------------------------------
+// What rides along with a tangent step or a backward sweep: nothing; the seeds / gradients of the boundary values; those and the thermal
+// parameters'; or those with the boundary series evaluated in the launch and seeds / gradients per node of the series
+enum Ride { RIDE_NONE, RIDE_BC, RIDE_PARAM, RIDE_SERIES };
+// The launchers, one explicit instantiation per ride in trm_launch_column_{tangent,adjoint,adjoint_ckpt}{,_bc,_param,_series}.hip (the two
+// series records in trm_launch_column_adjoint_series.hip)
+template <Ride R> int tangent_step(trm_ctx* c, double dt, int nsteps);
+template <Ride R> int tangent_closure(trm_ctx* c);
+template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
+template <bool CKPT, Ride R> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+// k_column_tangent / k_closure_tangent (fp64 NoFlow only); the closure knows the parameter seeds alone.  These three choose the
+// instantiation of the ride (terrarium_hip.hip)
 struct TangentLaunch {
-    static int step(trm_ctx* c, double dt, int nsteps);
-    static int step_bc(trm_ctx* c, double dt, int nsteps);   // with boundary seeds (trm_launch_column_tangent_bc.hip)
-    static int step_param(trm_ctx* c, double dt, int nsteps);   // with boundary and parameter seeds (trm_launch_column_tangent_param.hip)
-    static int step_series(trm_ctx* c, double dt, int nsteps);   // with boundary series in the launch (trm_launch_column_tangent_series.hip)
-    static int closure(trm_ctx* c);
-    static int closure_param(trm_ctx* c);                    // with parameter seeds (trm_launch_column_tangent_param.hip)
+    static int step(trm_ctx* c, double dt, int nsteps, Ride ride);
+    static int closure(trm_ctx* c, Ride ride);
 };
-// k_column_record / k_column_adjoint (trm_launch_column_adjoint.hip, fp64 NoFlow only): `slot` is the tape slot of the launch's first step
+// k_column_record / k_column_adjoint (fp64 NoFlow only): `slot` is the tape slot of the launch's first step; k_param_reduce ends a
+// sweep with parameter gradients on either tape (trm_launch_column_adjoint_param.hip)
 struct AdjointLaunch {
-    static int record(trm_ctx* c, double dt, int nsteps, int slot);
-    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
-    static int backward_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // with boundary gradients (trm_launch_column_adjoint_bc.hip)
-    // with boundary and parameter gradients, and k_param_reduce that ends a sweep on either tape (trm_launch_column_adjoint_param.hip)
-    static int backward_param(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int record(trm_ctx* c, double dt, int nsteps, int slot, bool series);
+    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride);
     static int param_reduce(trm_ctx* c);
-    // with boundary series in the launch and node gradients (trm_launch_column_adjoint_series.hip)
-    static int record_series(trm_ctx* c, double dt, int nsteps, int slot);
-    static int backward_series(trm_ctx* c, double dt, int nsteps, int slot, int fold);
 };
-// the strided k_column_record / k_column_adjoint_ckpt (trm_launch_column_adjoint_ckpt.hip): the record stores before the steps `first`,
-// `first + every`, ... of the launch into the slots from `slot` on; the backward launch pulls lam through the segment of `nsteps`
-// steps whose checkpoint is in `slot`
+// the strided k_column_record / k_column_adjoint_ckpt: the record stores before the steps `first`, `first + every`, ... of the launch
+// into the slots from `slot` on; the backward launch pulls lam through the segment of `nsteps` steps whose checkpoint is in `slot`
 struct CheckpointLaunch {
-    static int record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
-    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
-    static int backward_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // with boundary gradients (trm_launch_column_adjoint_ckpt_bc.hip)
-    static int backward_param(trm_ctx* c, double dt, int nsteps, int slot, int fold);   // ... and parameter gradients (trm_launch_column_adjoint_ckpt_param.hip)
-    // with boundary series in the launch (trm_launch_column_adjoint_series.hip, trm_launch_column_adjoint_ckpt_series.hip)
-    static int record_series(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
-    static int backward_series(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every, bool series);
+    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride);
 };
 // The chain rule between the ten thermal parameters (TRM_THERMAL_PARAM_*, the order of trm_params) and the eight numbers the kernels
 // differentiate (make_dev_params): w[q] = d(derived number) / d(parameter q), with sk_i = sqrt(k_i), s0 = sqrt(k_mineral) frac_mineral +

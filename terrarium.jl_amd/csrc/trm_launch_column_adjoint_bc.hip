@@ -1,43 +1,7 @@
 // trm_launch_column_adjoint_bc.hip -- the launches of k_column_adjoint<HYD, LPC, true, AdjointBcArgs> (both lanes-per-column layouts;
 // trm_column_adjoint.hpp): the backward sweep of the per-step tape with the boundary gradients riding along (trm_adjoint_bc_open).
-#include "trm_host.hpp"
-// (this translation unit's copy of the non-template kernel of trm_column_tangent.hpp gets a name of its own)
-#define k_closure_tangent k_closure_tangent_in_adjoint_bc_unit
-#include "trm_column_tangent.hpp"
-#undef k_closure_tangent
-#include "trm_column_adjoint.hpp"
+#include "trm_launch_derivative.inl"
 
 namespace trmh {
-
-namespace {
-template <int H, int LPC> int launch_adjoint_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    const LaunchArgs<double>& la = launch_args<double>(c);
-    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
-    AdjointBcArgs aa;
-    aa.lU = c->d_adj[TRM_ADJOINT_INTERNAL_ENERGY];
-    aa.lT = c->d_adj[TRM_ADJOINT_TEMPERATURE];
-    aa.lliq = c->d_adj[TRM_ADJOINT_LIQUID_WATER_FRACTION];
-    aa.slot_elems = (long long)c->Nh * (long long)c->Nzp;
-    aa.tape = c->d_tape + (size_t)slot * (size_t)aa.slot_elems;
-    aa.generic = Policy<double>::generic_bcs(c) ? 1 : 0;
-    aa.fold = fold;
-    aa.g = BcGradPtrs{c->d_adj_bc[0], c->d_adj_bc[1], c->d_adj_bc[2], c->d_adj_bc[3]};
-    hipLaunchKernelGGL((k_column_adjoint<H, LPC, true, AdjointBcArgs>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
-    TRM_HIP(c, hipGetLastError());
-    c->last_program = program_id(TRM_PROGRAM_COLUMN_ADJOINT, H, LPC, DERIVE_NONE, 0, 0, -1) | (aa.generic ? 1 << 25 : 0) | 1 << 26 | 1 << 30;
-    return TRM_OK;
-}
-}  // namespace
-
-int AdjointLaunch::backward_bc(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    if (slot < 0 || nsteps < 0 || slot + nsteps > c->tape_cap) return fail(c, TRM_EINVAL, "k_column_adjoint (boundary gradients): the launch leaves the tape");
-    for (const double* q : c->d_adj_bc)
-        if (!q) return fail(c, TRM_EINVAL, "k_column_adjoint (boundary gradients): no accumulators");
-    int rc = TRM_OK;
-    using NF = double;
-    const bool deep = c->Nz > 32;
-    TRM_BY_HYD(c, rc = deep ? (launch_adjoint_bc<H, 64>(c, dt, nsteps, slot, fold)) : (launch_adjoint_bc<H, 32>(c, dt, nsteps, slot, fold)));
-    return rc;
-}
-
+template int adjoint_backward<false, RIDE_BC>(trm_ctx*, double, int, int, int);
 }  // namespace trmh

@@ -1,0 +1,230 @@
+// trm_launch_derivative.inl -- the launches of the two derivative families of the heat-only fp64 SoilModel run: k_column_tangent
+// (trm_column_tangent.hpp), k_column_record / k_column_adjoint (trm_column_adjoint.hpp) and k_column_adjoint_ckpt
+// (trm_column_adjoint_ckpt.hpp), each with what rides along (Ride, trm_host.hpp).  Included by the trm_launch_column_tangent*.hip and
+// trm_launch_column_adjoint*.hip files, each of which instantiates the launchers of one family and ride.
+#include "trm_host.hpp"
+#include "trm_column_adjoint_ckpt.hpp"
+
+namespace trmh {
+
+// ---- what a ride is called in a refusal, and the kernel arguments it selects ------------------------------------------------------
+inline std::string ride_name(const char* kernel, Ride r, bool tangent) {
+    const char* seeds[] = {"", " (boundary seeds)", " (parameter seeds)", " (series)"};
+    const char* grads[] = {"", " (boundary gradients)", " (parameter gradients)", " (series)"};
+    return std::string(kernel) + (tangent ? seeds : grads)[r];
+}
+template <Ride R, class None, class Bc, class Param, class Series>
+using RideArgs = std::conditional_t<R == RIDE_NONE, None, std::conditional_t<R == RIDE_BC, Bc, std::conditional_t<R == RIDE_PARAM, Param, Series>>>;
+
+// ---- the argument fillers ----------------------------------------------------------------------------------------------------------
+// the halo form trm_step would take; the series instances refuse the generic kinds (series_ok)
+inline int generic_halos(trm_ctx* c, bool series) { return !series && Policy<double>::generic_bcs(c) ? 1 : 0; }
+
+inline void fill_tangent(trm_ctx* c, TangentArgs& ta, bool series) {
+    ta.dU = c->d_tan[TRM_TANGENT_INTERNAL_ENERGY];
+    ta.dT = c->d_tan[TRM_TANGENT_TEMPERATURE];
+    ta.dliq = c->d_tan[TRM_TANGENT_LIQUID_WATER_FRACTION];
+    ta.generic = generic_halos(c, series);
+}
+// the seeds of the boundary values, and of the thermal parameters or the seriesed pairs behind them
+template <Ride R, class Args> void fill_tangent_seeds(const trm_ctx* c, Args& ta) {
+    if constexpr (R != RIDE_NONE) {
+        ta.sTb = c->d_tan_bc[0];
+        ta.sTt = c->d_tan_bc[1];
+        ta.sUb = c->d_tan_bc[2];
+        ta.sUt = c->d_tan_bc[3];
+    }
+    if constexpr (R == RIDE_PARAM) {
+        const double* s = c->tan_param;
+        ta.s = ParamSeeds{s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]};
+    }
+    if constexpr (R == RIDE_SERIES)
+        for (int s = 0; s < 4; ++s) ta.sn[s] = c->d_tan_bcs[s];
+}
+// the cotangent fields and the tape of AdjointArgs / CheckpointArgs (the same member names, no common base); `slot`: the tape slot of
+// the first step of the launch, or the segment's checkpoint
+template <class Args> void fill_cotangent(trm_ctx* c, Args& aa, int slot, int fold, bool series) {
+    aa.lU = c->d_adj[TRM_ADJOINT_INTERNAL_ENERGY];
+    aa.lT = c->d_adj[TRM_ADJOINT_TEMPERATURE];
+    aa.lliq = c->d_adj[TRM_ADJOINT_LIQUID_WATER_FRACTION];
+    aa.slot_elems = (long long)c->Nh * (long long)c->Nzp;
+    aa.tape = c->d_tape + (size_t)slot * (size_t)aa.slot_elems;
+    aa.generic = generic_halos(c, series);
+    aa.fold = fold;
+}
+inline BcGradPtrs bc_grad_ptrs(const trm_ctx* c) { return BcGradPtrs{c->d_adj_bc[0], c->d_adj_bc[1], c->d_adj_bc[2], c->d_adj_bc[3]}; }
+inline SeriesGradPtrs series_grad_ptrs(const trm_ctx* c) { return SeriesGradPtrs{{c->d_adj_bcs[0], c->d_adj_bcs[1], c->d_adj_bcs[2], c->d_adj_bcs[3]}}; }
+inline ParamGradPtrs param_grad_ptrs(const trm_ctx* c) {
+    ParamGradPtrs g;
+    for (int q = 0; q < 8; ++q) g.g[q] = c->d_adj_param[q];
+    return g;
+}
+// what rides along a backward launch on either tape
+template <Ride R, class Args> void fill_gradients(const trm_ctx* c, Args& aa) {
+    if constexpr (R != RIDE_NONE) aa.g = bc_grad_ptrs(c);
+    if constexpr (R == RIDE_PARAM) aa.pg = param_grad_ptrs(c);
+    if constexpr (R == RIDE_SERIES) aa.sg = series_grad_ptrs(c);
+}
+
+// ---- the preconditions -------------------------------------------------------------------------------------------------------------
+// the per-step tape: the launch's steps are the slots [slot, slot + nsteps)
+inline int tape_range_ok(trm_ctx* c, int nsteps, int slot, const std::string& who) {
+    if (slot < 0 || nsteps < 0 || slot + nsteps > c->tape_cap) return fail(c, TRM_EINVAL, who + ": the launch leaves the tape");
+    return TRM_OK;
+}
+// a segment of the checkpointed tape: its checkpoint is in `slot`
+inline int segment_range_ok(trm_ctx* c, int nsteps, int slot, const std::string& who) {
+    if (slot < 0 || nsteps < 0 || nsteps > TRM_ADJOINT_MAX_INTERVAL || slot >= c->tape_cap) return fail(c, TRM_EINVAL, who + ": the launch leaves the tape");
+    return TRM_OK;
+}
+// the strided record: its stores are the slots from `slot` on
+inline int strided_stores_ok(trm_ctx* c, int nsteps, int& slot, int first, int every, const std::string& who) {
+    if (slot < 0 || nsteps < 0 || first < 0 || every < 1) return fail(c, TRM_EINVAL, who + ": bad launch");
+    const int stores = first < nsteps ? (nsteps - first + every - 1) / every : 0;
+    if (slot + stores > c->tape_cap) return fail(c, TRM_EINVAL, who + ": the launch leaves the tape");
+    if (stores == 0) slot = 0;     // (no store: any address inside the tape)
+    return TRM_OK;
+}
+// accumulators / seed arrays present
+template <size_t N> int arrays_ok(trm_ctx* c, double* const (&arrays)[N], const std::string& who, const char* what) {
+    for (const double* q : arrays)
+        if (!q) return fail(c, TRM_EINVAL, who + ": no " + what);
+    return TRM_OK;
+}
+// what every series launch needs: the table, rows for its steps, the branch-free boundary kinds ...
+inline int series_rows_ok(trm_ctx* c, int nsteps, const std::string& who) {
+    if (!c->d_series_table || (nsteps > 0 && !c->d_series_rows) || Policy<double>::generic_bcs(c))
+        return fail(c, TRM_EINVAL, who + ": no series rows, or the generic boundary kinds");
+    return TRM_OK;
+}
+// ... and one that carries derivatives: node arrays (d_tan_bcs / d_adj_bcs, `nt` nodes each) of the shape of every series
+inline int series_nodes_ok(trm_ctx* c, double* const (&nodes)[4], const long (&nt)[4], const std::string& who, const char* what) {
+    for (const auto& sr : c->series) {
+        const int slot = Policy<double>::series_slot(c, sr);
+        if (slot < SLOT_T_BOT || slot > SLOT_FU_TOP || !nodes[slot] || nt[slot] != sr.cap) return fail(c, TRM_EINVAL, who + ": a series without " + what + " of its shape");
+    }
+    return TRM_OK;
+}
+// the accumulators a backward launch with ride R needs
+template <Ride R> int gradients_ok(trm_ctx* c, int nsteps, const std::string& who) {
+    if constexpr (R == RIDE_SERIES)
+        if (int rc = series_rows_ok(c, nsteps, who)) return rc;
+    if constexpr (R != RIDE_NONE)
+        if (int rc = arrays_ok(c, c->d_adj_bc, who, R == RIDE_PARAM ? "boundary accumulators" : "accumulators")) return rc;
+    if constexpr (R == RIDE_PARAM)
+        if (int rc = arrays_ok(c, c->d_adj_param, who, "accumulators")) return rc;
+    if constexpr (R == RIDE_SERIES)
+        if (int rc = series_nodes_ok(c, c->d_adj_bcs, c->adj_bcs_nt, who, "an accumulator")) return rc;
+    return TRM_OK;
+}
+
+// ---- the dispatch over (hydraulics instance, lanes per column): launch(H, LPC), both std::integral_constant -----------------------
+template <class F> int by_instance(trm_ctx* c, F&& launch) {
+    using NF = double;
+    using L32 = std::integral_constant<int, 32>;
+    using L64 = std::integral_constant<int, 64>;
+    int rc = TRM_OK;
+    const bool deep = c->Nz > 32;
+    TRM_BY_HYD(c, rc = deep ? launch(std::integral_constant<int, H>{}, L64{}) : launch(std::integral_constant<int, H>{}, L32{}));
+    return rc;
+}
+// TRM_INFO_LAST_PROGRAM of a derivative launch: the instance and the family bits (trm_host.hpp)
+inline int derivative_program_id(int family, int hyd, int lpc, int generic, int bits) {
+    return program_id(family, hyd, lpc, DERIVE_NONE, 0, 0, -1) | (generic ? PROGRAM_GENERIC_HALOS : 0) | bits;
+}
+
+// ---- one launch function per kernel template ----------------------------------------------------------------------------------------
+template <Ride R> int tangent_step(trm_ctx* c, double dt, int nsteps) {
+    using Args = RideArgs<R, TangentArgs, TangentBcArgs, TangentParamArgs, TangentSeriesArgs>;
+    const std::string who = ride_name("k_column_tangent", R, true);
+    if constexpr (R != RIDE_NONE)
+        if (int rc = arrays_ok(c, c->d_tan_bc, who, R == RIDE_PARAM ? "boundary seed arrays" : "seed arrays")) return rc;
+    if constexpr (R == RIDE_SERIES) {
+        if (int rc = series_rows_ok(c, nsteps, who)) return rc;
+        if (int rc = series_nodes_ok(c, c->d_tan_bcs, c->tan_bcs_nt, who, "seeds")) return rc;
+    }
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
+    Args ta;
+    fill_tangent(c, ta, R == RIDE_SERIES);
+    fill_tangent_seeds<R>(c, ta);
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        hipLaunchKernelGGL((k_column_tangent<H, LPC, R != RIDE_NONE, Args, R == RIDE_PARAM, R == RIDE_SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0,
+                           c->stream, la.state, la.p, a, ta);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_TANGENT, H, LPC, ta.generic,
+                                                (R != RIDE_NONE ? PROGRAM_BC_SEEDS : 0) | (R == RIDE_PARAM ? (int)TRM_PROGRAM_PARAMETERS : 0));
+        return (int)TRM_OK;
+    });
+}
+
+// trm_tangent_closure: with the heat-capacity term of the parameter seeds (RIDE_PARAM) or without (RIDE_NONE)
+template <Ride R> int tangent_closure(trm_ctx* c) {
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const size_t cells = (size_t)c->Nh * (size_t)c->Nzp;
+    RideArgs<R, TangentArgs, TangentBcArgs, TangentParamArgs, TangentSeriesArgs> ta;
+    fill_tangent(c, ta, false);
+    fill_tangent_seeds<R>(c, ta);
+    hipLaunchKernelGGL((k_closure_tangent<decltype(ta), R == RIDE_PARAM>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, la.state, la.p, ta);
+    TRM_HIP(c, hipGetLastError());
+    return TRM_OK;
+}
+
+// k_column_record on the per-step tape (`slot`: of the launch's first step) or STRIDED on the checkpointed one (the stores before the
+// steps first, first + every, ... go into the slots from `slot` on); SERIES: with the boundary series evaluated in the launch
+template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every) {
+    using Args = std::conditional_t<STRIDED, CheckpointArgs, AdjointArgs>;
+    const std::string who = std::string(STRIDED ? "k_column_record (strided)" : "k_column_record") + (SERIES ? " (series)" : "");
+    if (int rc = STRIDED ? strided_stores_ok(c, nsteps, slot, first, every, who) : tape_range_ok(c, nsteps, slot, who)) return rc;
+    if constexpr (SERIES)
+        if (int rc = series_rows_ok(c, nsteps, who)) return rc;
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
+    Args aa;
+    fill_cotangent(c, aa, slot, 0, SERIES);
+    if constexpr (STRIDED) {
+        aa.first = first;
+        aa.every = every;
+    }
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        hipLaunchKernelGGL((k_column_record<H, LPC, STRIDED, Args, SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT, H, LPC, aa.generic, STRIDED ? PROGRAM_CHECKPOINTED : 0);
+        return (int)TRM_OK;
+    });
+}
+
+// the backward launch of a block of the per-step tape (k_column_adjoint) or, CKPT, of one segment of the checkpointed tape
+// (k_column_adjoint_ckpt: the segment's states in dynamic LDS, 2 KiB per step and workgroup)
+template <bool CKPT, Ride R> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
+    using Args = std::conditional_t<CKPT, RideArgs<R, CheckpointArgs, CheckpointBcArgs, CheckpointParamArgs, CheckpointSeriesArgs>,
+                                    RideArgs<R, AdjointArgs, AdjointBcArgs, AdjointParamArgs, AdjointSeriesArgs>>;
+    const std::string who = ride_name(CKPT ? "k_column_adjoint_ckpt" : "k_column_adjoint", R, false);
+    if (int rc = CKPT ? segment_range_ok(c, nsteps, slot, who) : tape_range_ok(c, nsteps, slot, who)) return rc;
+    if (int rc = gradients_ok<R>(c, nsteps, who)) return rc;
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
+    Args aa;
+    fill_cotangent(c, aa, slot, fold, R == RIDE_SERIES);
+    fill_gradients<R>(c, aa);
+    if constexpr (CKPT) {
+        aa.first = 0;
+        aa.every = 1;
+    }
+    const int bits = PROGRAM_BACKWARD | (CKPT ? PROGRAM_CHECKPOINTED : 0) | (R != RIDE_NONE ? PROGRAM_BC_GRADIENT : 0) | (R == RIDE_PARAM ? (int)TRM_PROGRAM_PARAMETERS : 0);
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        constexpr bool BCGRAD = R != RIDE_NONE, PGRAD = R == RIDE_PARAM, SERIES = R == RIDE_SERIES;
+        if constexpr (CKPT)
+            hipLaunchKernelGGL((k_column_adjoint_ckpt<H, LPC, BCGRAD, Args, PGRAD, SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK),
+                               (size_t)nsteps * TRM_STEP_BLOCK * sizeof(double), c->stream, la.state, la.p, a, aa);
+        else hipLaunchKernelGGL((k_column_adjoint<H, LPC, BCGRAD, Args, PGRAD, SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT, H, LPC, aa.generic, bits);
+        return (int)TRM_OK;
+    });
+}
+
+}  // namespace trmh

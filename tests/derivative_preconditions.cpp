@@ -1,0 +1,57 @@
+// Exercises the host-side preconditions of the derivative launches (trm_launch_derivative.inl) on contexts built by hand: no GPU call.
+// Built with the host sanitizers and run by `make -C terrarium.jl_amd/csrc check-preconditions` (cross-compiles; runs without a GPU).
+#include "trm_launch_derivative.inl"
+#include <cassert>
+
+namespace trmh {
+static std::string last;
+int fail(trm_ctx*, int code, const std::string& msg) { last = msg; return code; }
+template <class NF> const LaunchArgs<NF>& launch_args(trm_ctx*) { static LaunchArgs<NF> a{}; return a; }
+}  // namespace trmh
+using namespace trmh;
+
+int main() {
+    trm_ctx c;
+    c.Nh = 3; c.Nz = 4; c.Nzp = 4;
+    c.tape_cap = 8;
+    // tape range: the per-step tape and a segment
+    assert(tape_range_ok(&c, 8, 0, "r") == TRM_OK && tape_range_ok(&c, 8, 1, "r") == TRM_EINVAL && tape_range_ok(&c, -1, 0, "r") == TRM_EINVAL);
+    assert(segment_range_ok(&c, TRM_ADJOINT_MAX_INTERVAL, 7, "s") == TRM_OK && segment_range_ok(&c, TRM_ADJOINT_MAX_INTERVAL + 1, 7, "s") == TRM_EINVAL);
+    assert(segment_range_ok(&c, 1, 8, "s") == TRM_EINVAL && last == "s: the launch leaves the tape");
+    // store count of the strided record
+    int slot = 6;
+    assert(strided_stores_ok(&c, 9, slot, 1, 4, "k") == TRM_OK && slot == 6);          // stores before steps 1 and 5: slots 6, 7
+    assert(strided_stores_ok(&c, 10, slot, 1, 4, "k") == TRM_EINVAL);                   // ... and 9: slot 8 is outside
+    slot = 8;                                                                        // (a full tape)
+    assert(strided_stores_ok(&c, 3, slot, 3, 4, "k") == TRM_OK && slot == 0);          // no store: any slot inside the tape
+    assert(strided_stores_ok(&c, 3, slot, 0, 0, "k") == TRM_EINVAL && last == "k: bad launch");
+    // missing accumulators
+    double x[4] = {};
+    assert(gradients_ok<RIDE_NONE>(&c, 1, "g") == TRM_OK);
+    assert(gradients_ok<RIDE_BC>(&c, 1, "g") == TRM_EINVAL && last == "g: no accumulators");
+    for (int q = 0; q < 3; ++q) c.d_adj_bc[q] = x;
+    assert(gradients_ok<RIDE_BC>(&c, 1, "g") == TRM_EINVAL);
+    c.d_adj_bc[3] = x;
+    assert(gradients_ok<RIDE_BC>(&c, 1, "g") == TRM_OK);
+    assert(gradients_ok<RIDE_PARAM>(&c, 1, "g") == TRM_EINVAL && last == "g: no accumulators");
+    for (auto& q : c.d_adj_param) q = x;
+    assert(gradients_ok<RIDE_PARAM>(&c, 1, "g") == TRM_OK);
+    // series: rows, and a node accumulator of the shape of every series
+    assert(gradients_ok<RIDE_SERIES>(&c, 1, "g") == TRM_EINVAL && last == "g: no series rows, or the generic boundary kinds");
+    c.d_series_table = x;
+    assert(series_rows_ok(&c, 0, "g") == TRM_OK && series_rows_ok(&c, 1, "g") == TRM_EINVAL);
+    c.d_series_rows = x;
+    c.bc_kind[TRM_BCV_TEMPERATURE][TRM_TOP] = TRM_BC_VALUE;
+    trm_ctx::Series sr;
+    sr.is_bc = true; sr.var = TRM_BCV_TEMPERATURE; sr.side = TRM_TOP; sr.cap = 5;
+    c.series.push_back(sr);
+    assert(gradients_ok<RIDE_SERIES>(&c, 1, "g") == TRM_EINVAL && last == "g: a series without an accumulator of its shape");
+    c.d_adj_bcs[SLOT_T_TOP] = x;
+    c.adj_bcs_nt[SLOT_T_TOP] = 4;
+    assert(gradients_ok<RIDE_SERIES>(&c, 1, "g") == TRM_EINVAL);
+    c.adj_bcs_nt[SLOT_T_TOP] = 5;
+    assert(gradients_ok<RIDE_SERIES>(&c, 1, "g") == TRM_OK);
+    assert(series_nodes_ok(&c, c.d_tan_bcs, c.tan_bcs_nt, "t", "seeds") == TRM_EINVAL && last == "t: a series without seeds of its shape");
+    std::puts("derivative preconditions ok");
+    return 0;
+}

@@ -20,6 +20,8 @@ def test_library_exports_the_tangent_entry_points():
     assert trm._capi.TANGENT == dict(internal_energy=enum["TRM_TANGENT_INTERNAL_ENERGY"], temperature=enum["TRM_TANGENT_TEMPERATURE"],
                                      liquid_water_fraction=enum["TRM_TANGENT_LIQUID_WATER_FRACTION"])
     assert enum["TRM_PROGRAM_COLUMN_TANGENT"] == 14 == trm._capi.PROGRAM.index("column_tangent")
+    # (k_closure_tangent is a template: no translation unit carries a renamed copy of it)
+    assert b"k_closure_tangent_in_" not in open(trm._capi.LIB_PATH, "rb").read()
 
 
 def test_no_context_is_refused_without_a_gpu():
