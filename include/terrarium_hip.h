@@ -232,6 +232,11 @@ enum {
                                     /* gradients of such a pair have the series' shape (trm_tangent_bc_series_upload,                            */
                                     /* trm_adjoint_bc_series_download).  0 (default): a context with a series attached is refused with          */
                                     /* TRM_EUNSUPPORTED by those three calls                                                                      */
+    ,TRM_OPT_DERIVATIVE_SERIES_PARAMS = 15 /* 1, together with TRM_OPT_DERIVATIVE_SERIES = 1: a context that carries such boundary series also   */
+                                    /* accepts trm_tangent_param_set and trm_adjoint_param_open, and the three stepping calls run with          */
+                                    /* parameter seeds or an open parameter gradient: one launch carries the node seeds / gradients of the      */
+                                    /* series and the thermal parameters' (TRM_INFO_LAST_PROGRAM: bits 26 / 30 and 31).  0 (default): the two   */
+                                    /* together are refused with TRM_EUNSUPPORTED.  Without TRM_OPT_DERIVATIVE_SERIES it changes nothing        */
 };
 /* DIAGNOSTIC, read-only (trm_get_option): which fast paths the NEXT step will take -- what the library tracks about its own
  * buffers.  Tests pin them (a wrong value costs speed, never correctness, so nothing else would notice). */
@@ -662,7 +667,9 @@ int trm_tangent_bc_upload(trm_ctx* ctx, int bc_var, int side, const void* host);
  *                                           seeds.  A pair without a series keeps its constant value and its trm_tangent_bc_upload seed.
  * Every operation is linear in the seeds: doubling them doubles the tangents bit for bit.  TRM_INFO_DERIVATIVE_SERIES reports the
  * series the last launch evaluated.  Refused with TRM_EUNSUPPORTED by trm_step_tangent: a series of kind Gradient, any series on the
- * generic boundary kinds, an input (forcing) series, a windowed or trimmed series, parameter seeds together with a series.
+ * generic boundary kinds, an input (forcing) series, a windowed or trimmed series, and parameter seeds together with a series unless
+ * TRM_OPT_DERIVATIVE_SERIES_PARAMS = 1: then trm_tangent_param_set is accepted on a context with series, and one launch carries the node
+ * seeds and the parameter seeds (bits 26 and 31), the parameter terms of every step formed at the boundary values the series gave it.
  * Errors: TRM_EINVAL without a context or an open tangent, for a pair without a series, an nt other than the series' levels or a NULL
  * pointer; trm_tangent_bc_upload on a seriesed pair (option set) returns TRM_EINVAL and names this call; TRM_ENOMEM. */
 int trm_tangent_bc_series_upload(trm_ctx* ctx, int bc_var, int side, int nt, const void* host);
@@ -786,7 +793,10 @@ int trm_adjoint_bc_device_ptr(trm_ctx* ctx, int bc_var, int side, void** dev);
  * trm_series_window and trm_series_trim_before make a tape that holds steps stale.
  * Errors: TRM_EINVAL without a context or an open adjoint, for a pair without a series, an nt other than the series' levels or a NULL
  * pointer; trm_adjoint_bc_download / _device_ptr on a seriesed pair (option set) return TRM_EINVAL and name these calls; TRM_EUNSUPPORTED
- * from trm_step_record / trm_adjoint_backward as for trm_step_tangent, and for an open parameter gradient together with a series. */
+ * from trm_step_record / trm_adjoint_backward as for trm_step_tangent, and for an open parameter gradient together with a series unless
+ * TRM_OPT_DERIVATIVE_SERIES_PARAMS = 1: then trm_adjoint_param_open is accepted on a context with series and one sweep delivers g, the
+ * node gradients, the per-column gradients of the pairs without a series and the ten parameter gradients (bits 30 and 31), on either
+ * tape; g and the node gradients are bit for bit those of the sweep without the parameter gradient. */
 int trm_adjoint_bc_series_download(trm_ctx* ctx, int bc_var, int side, int nt, void* host);
 int trm_adjoint_bc_series_device_ptr(trm_ctx* ctx, int bc_var, int side, void** dev, int* nt);
 /* Parameter gradients: dL/d(parameter) of the ten thermal parameters trm_tangent_param_set seeds (TRM_THERMAL_PARAM_*), per column, from

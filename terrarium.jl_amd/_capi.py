@@ -52,10 +52,12 @@ OPTION_LATER = dict(defer_closure_stores=12, info_closure_stored=106, info_mater
 OPTION_INTERIOR = dict(interior_steps=13, info_interior_launches=108)
 # ... and those of TRM_OPT_DERIVATIVE_SERIES (tests/test_series_derivative_host.py)
 OPTION_DERIVATIVE = dict(derivative_series=14, info_derivative_series=109)
+# ... and TRM_OPT_DERIVATIVE_SERIES_PARAMS (tests/test_param_series_host.py)
+OPTION_DERIVATIVE_PARAMS = dict(derivative_series_params=15)
 
 
 def option_id(name: str) -> int:
-    for table in (OPTION, OPTION_LATER, OPTION_INTERIOR, OPTION_DERIVATIVE):
+    for table in (OPTION, OPTION_LATER, OPTION_INTERIOR, OPTION_DERIVATIVE, OPTION_DERIVATIVE_PARAMS):
         if name in table:
             return table[name]
     raise KeyError(name)

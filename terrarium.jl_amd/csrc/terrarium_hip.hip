@@ -293,6 +293,7 @@ int TangentLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride) {
         case RIDE_BC: return tangent_step<RIDE_BC>(c, dt, nsteps);
         case RIDE_PARAM: return tangent_step<RIDE_PARAM>(c, dt, nsteps);
         case RIDE_SERIES: return tangent_step<RIDE_SERIES>(c, dt, nsteps);
+        case RIDE_PARAM_SERIES: return tangent_step<RIDE_PARAM_SERIES>(c, dt, nsteps);
         default: return tangent_step<RIDE_NONE>(c, dt, nsteps);
     }
 }
@@ -302,6 +303,7 @@ template <bool CKPT> static int backward_by_ride(trm_ctx* c, double dt, int nste
         case RIDE_BC: return adjoint_backward<CKPT, RIDE_BC>(c, dt, nsteps, slot, fold);
         case RIDE_PARAM: return adjoint_backward<CKPT, RIDE_PARAM>(c, dt, nsteps, slot, fold);
         case RIDE_SERIES: return adjoint_backward<CKPT, RIDE_SERIES>(c, dt, nsteps, slot, fold);
+        case RIDE_PARAM_SERIES: return adjoint_backward<CKPT, RIDE_PARAM_SERIES>(c, dt, nsteps, slot, fold);
         default: return adjoint_backward<CKPT, RIDE_NONE>(c, dt, nsteps, slot, fold);
     }
 }
@@ -2504,7 +2506,9 @@ const trm_ctx::Series* bc_series_of(const trm_ctx* c, int bc_var, int side) {
 }
 // series the derivative launches of this context evaluate in-kernel (0: none attached)
 int derivative_series_count(const trm_ctx* c) { return (int)c->series.size(); }
-const char* kSeriesWithParams = "no thermal-parameter seeds or gradients together with a time series (a follow-up: DESIGN 7 (8))";
+const char* kSeriesWithParams = "no thermal-parameter seeds or gradients together with a time series unless TRM_OPT_DERIVATIVE_SERIES_PARAMS is set";
+// parameters and series together are refused: a series the derivative kernels would evaluate, and the option that joins the two is off
+bool series_refuse_params(const trm_ctx* c) { return !c->series.empty() && !c->opt_derivative_series_params; }
 // ... and what a step needs besides: constant inputs, no accumulation, the temperature halos of the heat-only programs
 const char* derivative_step_unsupported(const trm_ctx* c) {
     if (const char* why = derivative_unsupported(c)) return why;
@@ -2520,9 +2524,16 @@ const char* derivative_step_unsupported(const trm_ctx* c) {
             return "no Value or Gradient condition on the liquid water fraction";
     return nullptr;
 }
-// what rides along with a tangent step / a backward sweep: series first, then the thermal parameters, then the boundary values
-Ride tangent_ride(const trm_ctx* c, int nser) { return nser ? RIDE_SERIES : c->tan_param_seeded ? RIDE_PARAM : c->tan_bc_seeded ? RIDE_BC : RIDE_NONE; }
-Ride backward_ride(const trm_ctx* c, int nser) { return nser ? RIDE_SERIES : c->d_adj_param_out ? RIDE_PARAM : c->d_adj_bc[0] ? RIDE_BC : RIDE_NONE; }
+// what rides along with a tangent step / a backward sweep: series first (with the thermal parameters where they are seeded / open:
+// TRM_OPT_DERIVATIVE_SERIES_PARAMS, the steps have refused them otherwise), then the thermal parameters, then the boundary values
+Ride tangent_ride(const trm_ctx* c, int nser) {
+    if (nser) return c->tan_param_seeded ? RIDE_PARAM_SERIES : RIDE_SERIES;
+    return c->tan_param_seeded ? RIDE_PARAM : c->tan_bc_seeded ? RIDE_BC : RIDE_NONE;
+}
+Ride backward_ride(const trm_ctx* c, int nser) {
+    if (nser) return c->d_adj_param_out ? RIDE_PARAM_SERIES : RIDE_SERIES;
+    return c->d_adj_param_out ? RIDE_PARAM : c->d_adj_bc[0] ? RIDE_BC : RIDE_NONE;
+}
 // trm_step_tangent and trm_step_record issue the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to
 // TRM_OPT_STEPS_PER_LAUNCH steps each ...
 int derivative_steps_per_launch(trm_ctx* c) { return c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c); }
@@ -2674,7 +2685,7 @@ int trm_tangent_param_set(trm_ctx* c, const double seed[TRM_THERMAL_PARAM_COUNT]
     if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_param_set: ") + why);
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_param_set: no tangent is open (trm_tangent_open)");
     if (!seed) return fail(c, TRM_EINVAL, "trm_tangent_param_set: bad argument");
-    if (c->opt_derivative_series && !c->series.empty()) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_param_set: ") + kSeriesWithParams);
+    if (c->opt_derivative_series && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_param_set: ") + kSeriesWithParams);
     if (const char* why = thermal_params_not_differentiable(c)) return fail(c, TRM_EINVAL, std::string("trm_tangent_param_set: ") + why);
     if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_param_set")) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -2735,7 +2746,7 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_tangent: nsteps < 0");
     if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + why);
     const int nser = derivative_series_count(c);
-    if (nser && c->tan_param_seeded) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + kSeriesWithParams);
+    if (nser && c->tan_param_seeded && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + kSeriesWithParams);
     if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_step_tangent") + kStaleTangent);
     if (nser) {   // series ride with the boundary-seeded instances: the per-column seeds, and zeros for a series nobody has seeded
         if (int rc = alloc_tangent_bc_seeds(c, "trm_step_tangent")) return rc;
@@ -2966,7 +2977,7 @@ int trm_adjoint_param_open(trm_ctx* c) {
     if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_param_open: ") + why);
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_param_open: no adjoint is open (trm_adjoint_open)");
     if (const char* why = thermal_params_not_differentiable(c)) return fail(c, TRM_EINVAL, std::string("trm_adjoint_param_open: ") + why);
-    if (c->opt_derivative_series && !c->series.empty()) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_param_open: ") + kSeriesWithParams);
+    if (c->opt_derivative_series && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_param_open: ") + kSeriesWithParams);
     if (int rc = trm_adjoint_bc_open(c)) return rc;   // (the accumulating instances carry both)
     const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double), out_bytes = (size_t)TRM_THERMAL_PARAM_COUNT * (size_t)c->Nh * sizeof(double);
     bool ok = true;
@@ -3077,7 +3088,7 @@ int trm_step_record(trm_ctx* c, double dt, int nsteps) {
     }
     if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + why);
     const int nser = derivative_series_count(c);
-    if (nser && c->d_adj_param_out) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + kSeriesWithParams);
+    if (nser && c->d_adj_param_out && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + kSeriesWithParams);
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_step_record") + kStaleTape);
     if (nsteps > 0) c->tan_stale = true;       // (a state-changing call for an open tangent)
     const int spl = derivative_steps_per_launch(c);
@@ -3119,7 +3130,7 @@ int trm_adjoint_backward(trm_ctx* c) {
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_backward: no adjoint is open (trm_adjoint_open)");
     if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + why);
     const int nser = derivative_series_count(c);
-    if (nser && c->d_adj_param_out) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + kSeriesWithParams);
+    if (nser && c->d_adj_param_out && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + kSeriesWithParams);
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_adjoint_backward") + kStaleTape);
     if (nser) {
         // series ride with the accumulating instances: the per-column accumulators if nobody has opened them, and the node accumulators,
@@ -3622,6 +3633,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
     c->heun_pending = false;
     // (an option that changes which program the next step takes: the arrays are made current here, not by whatever runs next)
     if (c->closure_deferred && option != TRM_OPT_ASYNC && option != TRM_OPT_WRITE_KF_EVERY_STEP && option != TRM_OPT_INTERIOR_STEPS && option != TRM_OPT_DERIVATIVE_SERIES &&
+        option != TRM_OPT_DERIVATIVE_SERIES_PARAMS &&
         !(option == TRM_OPT_DEFER_CLOSURE_STORES && value != 0)) {
         TRM_HIP(c, hipSetDevice(c->device));
         if (int rf = flush_closure(c)) return rf;
@@ -3663,6 +3675,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
             c->opt_interior = value;
             return TRM_OK;
         case TRM_OPT_DERIVATIVE_SERIES: c->opt_derivative_series = value != 0; return TRM_OK;
+        case TRM_OPT_DERIVATIVE_SERIES_PARAMS: c->opt_derivative_series_params = value != 0; return TRM_OK;
         default: break;
     }
     return fail(c, TRM_EINVAL, "trm_set_option: unknown option or value");
@@ -3688,6 +3701,7 @@ int trm_get_option(const trm_ctx* c, int option, int* value) {
         case TRM_OPT_INTERIOR_STEPS: *value = c->opt_interior; return TRM_OK;
         case TRM_INFO_INTERIOR_LAUNCHES: *value = (int)c->interior_launches; return TRM_OK;
         case TRM_OPT_DERIVATIVE_SERIES: *value = c->opt_derivative_series; return TRM_OK;
+        case TRM_OPT_DERIVATIVE_SERIES_PARAMS: *value = c->opt_derivative_series_params; return TRM_OK;
         case TRM_INFO_DERIVATIVE_SERIES: *value = c->derivative_series; return TRM_OK;
         case TRM_INFO_LAST_PROGRAM: *value = c->last_program; return TRM_OK;
         case TRM_INFO_GENERIC_BOUNDARY_KERNELS: *value = (c->precision == TRM_F64 ? trmh::Policy<double>::generic_bcs(c) : trmh::Policy<float>::generic_bcs(c)) ? 1 : 0; return TRM_OK;

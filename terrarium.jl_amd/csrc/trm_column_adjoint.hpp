@@ -33,6 +33,9 @@
 // ahead, with the next tape slot) and a seriesed pair's term goes w1 term onto node n1 and w2 term onto node n2 of a [nt][Nh]
 // accumulator instead of the per-column sum: the owning edge lane holds the two sums of the current bracket and stores / loads them
 // where a step's row names other nodes, and at the end of the launch.
+// PGRAD and SERIES (TRM_OPT_DERIVATIVE_SERIES_PARAMS): both; adjoint_step forms T_m, and with it the dry halo's pA and pA_t that feed the
+// sums of s0 and sk_air, from the temperature values the series gave the step, not from the constants loaded in front of the loop.  The
+// parameter sums do not feed lam: lam and the node sums are those of the SERIES sweep bit for bit.
 // Every coefficient is a function of the state U_k BEFORE step k: k_column_record is the multi-step primal that stores U_k into tape
 // slot k (the field layout [Nh][Nzp]) before every step; k_column_adjoint walks a block of slots backwards with lam in registers.
 // closure_tangent and conductivity_tangent are linear in their seed, one scalar slope per cell: applied to a cotangent they are their
@@ -122,6 +125,10 @@ struct ParamGradPtrs {
 };
 // ... of k_column_adjoint<HYD, LPC, true, AdjointParamArgs, true>
 struct AdjointParamArgs : AdjointBcArgs {
+    ParamGradPtrs pg;
+};
+// ... of k_column_adjoint<HYD, LPC, true, AdjointParamSeriesArgs, true, true>: the node accumulators and the per-cell parameter accumulators
+struct AdjointParamSeriesArgs : AdjointSeriesArgs {
     ParamGradPtrs pg;
 };
 // a lane's running sums for its own cell
@@ -398,6 +405,7 @@ TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, con
 // BCGRAD (Args = AdjointBcArgs): the boundary gradients ride along; the instances without are the code they were.
 // PGRAD (Args = AdjointParamArgs, with BCGRAD): and the per-cell parameter sums.
 // SERIES (Args = AdjointSeriesArgs, with BCGRAD): a.series_rows holds the rows of this launch's taped steps, oldest first.
+// PGRAD and SERIES (Args = AdjointParamSeriesArgs): both.
 template <int HYD, int LPC, bool BCGRAD = false, class Args = AdjointArgs, bool PGRAD = false, bool SERIES = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args aa) {
     using NF = double;

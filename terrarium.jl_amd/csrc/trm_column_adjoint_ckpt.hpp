@@ -37,6 +37,10 @@ struct CheckpointSeriesArgs : CheckpointBcArgs {
 struct CheckpointParamArgs : CheckpointBcArgs {
     ParamGradPtrs pg;
 };
+// ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointParamSeriesArgs, true, true>: both
+struct CheckpointParamSeriesArgs : CheckpointSeriesArgs {
+    ParamGradPtrs pg;
+};
 
 // lam pulled back through one segment: the checkpoint U_c at ca.tape and the a.nsteps - 1 states behind it under a.dt.
 // Dynamic LDS: a.nsteps * TRM_STEP_BLOCK doubles.
@@ -44,6 +48,7 @@ struct CheckpointParamArgs : CheckpointBcArgs {
 // PGRAD (Args = CheckpointParamArgs, with BCGRAD): and the per-cell parameter sums, likewise.
 // SERIES (Args = CheckpointSeriesArgs, with BCGRAD): a.series_rows holds the rows of the segment's steps, oldest first; the recompute
 // loop evaluates the series as the record did, the backward loop takes the temperature values again and sums onto the nodes.
+// PGRAD and SERIES (Args = CheckpointParamSeriesArgs): both, the parameter terms at each recomputed state's series temperatures.
 template <int HYD, int LPC, bool BCGRAD = false, class Args = CheckpointArgs, bool PGRAD = false, bool SERIES = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ca) {
     using NF = double;

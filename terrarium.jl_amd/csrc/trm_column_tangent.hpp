@@ -30,6 +30,9 @@
 // SERIES (TangentSeriesArgs, always together with BCSEED; trm_series_derivative.hpp): in front of every step the seriesed pairs among the four
 // take the value of their series (the primal: as column_program<.., SERIES>) and the seed s[n1] w1 + s[n2] w2 of seeds shaped like the
 // series, [nt][Nh]; a pair without a series keeps its constant value and its per-column seed.
+// PSEED and SERIES (TangentParamSeriesArgs, TRM_OPT_DERIVATIVE_SERIES_PARAMS): the parameter terms of a step are formed at the boundary
+// values the series gave that step -- the Value halos in (T - T_m) of dkappa's product, the dry halo's dkappa_halo -- and both families
+// of seeds enter one dgU; the closure terms read no boundary value.
 #pragma once
 #include "trm_column.hpp"
 #include "trm_series_derivative.hpp"
@@ -59,6 +62,10 @@ struct TangentParamArgs : TangentBcArgs {
 // (null: the pair has no series)
 struct TangentSeriesArgs : TangentBcArgs {
     const double* sn[4];
+};
+// ... of k_column_tangent<HYD, LPC, true, TangentParamSeriesArgs, true, true>: the seeds of the seriesed pairs and of the thermal numbers
+struct TangentParamSeriesArgs : TangentSeriesArgs {
+    ParamSeeds s;
 };
 
 // tangent of the energy closure at (U, sat) -- C is the heat capacity the primal closure formed
@@ -154,6 +161,7 @@ TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& 
 // BCSEED (Args = TangentBcArgs): the boundary seeds are loaded once in front of the step loop; the instances without are the code they were.
 // PSEED (Args = TangentParamArgs, with BCSEED): the parameter seeds are kernel arguments.
 // SERIES (Args = TangentSeriesArgs, with BCSEED): values and seeds of the seriesed pairs are formed in front of every step.
+// PSEED and SERIES (Args = TangentParamSeriesArgs): both; the parameter terms take the step's boundary values.
 template <int HYD, int LPC, bool BCSEED = false, class Args = TangentArgs, bool PSEED = false, bool SERIES = false>
 __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ta) {
     using NF = double;
@@ -242,7 +250,8 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
         const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
                                        : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
         NF dgU;
-        if constexpr (PSEED) dgU = tendency_tangent<LPC, BCSEED, true>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt, &ta.s);
+        if constexpr (PSEED && SERIES) dgU = tendency_tangent<LPC, BCSEED, true>(v, p, L, ln, ii, c, dT, dliq, bc.bTb, bc.bTt, generic, dbTb, dbTt, &ta.s);
+        else if constexpr (PSEED) dgU = tendency_tangent<LPC, BCSEED, true>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt, &ta.s);
         else if constexpr (SERIES) dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bc.bTb, bc.bTt, generic, dbTb, dbTt);
         else dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt);
         NF gU = t.gU, gS = t.gS, z0;

@@ -9,12 +9,13 @@ namespace trmh {
 
 // ---- what a ride is called in a refusal, and the kernel arguments it selects ------------------------------------------------------
 inline std::string ride_name(const char* kernel, Ride r, bool tangent) {
-    const char* seeds[] = {"", " (boundary seeds)", " (parameter seeds)", " (series)"};
-    const char* grads[] = {"", " (boundary gradients)", " (parameter gradients)", " (series)"};
+    const char* seeds[] = {"", " (boundary seeds)", " (parameter seeds)", " (series)", " (series, parameter seeds)"};
+    const char* grads[] = {"", " (boundary gradients)", " (parameter gradients)", " (series)", " (series, parameter gradients)"};
     return std::string(kernel) + (tangent ? seeds : grads)[r];
 }
-template <Ride R, class None, class Bc, class Param, class Series>
-using RideArgs = std::conditional_t<R == RIDE_NONE, None, std::conditional_t<R == RIDE_BC, Bc, std::conditional_t<R == RIDE_PARAM, Param, Series>>>;
+template <Ride R, class None, class Bc, class Param, class Series, class ParamSeries>
+using RideArgs = std::conditional_t<R == RIDE_NONE, None,
+                                    std::conditional_t<R == RIDE_BC, Bc, std::conditional_t<R == RIDE_PARAM, Param, std::conditional_t<R == RIDE_SERIES, Series, ParamSeries>>>>;
 
 // ---- the argument fillers ----------------------------------------------------------------------------------------------------------
 // the halo form trm_step would take; the series instances refuse the generic kinds (series_ok)
@@ -34,11 +35,11 @@ template <Ride R, class Args> void fill_tangent_seeds(const trm_ctx* c, Args& ta
         ta.sUb = c->d_tan_bc[2];
         ta.sUt = c->d_tan_bc[3];
     }
-    if constexpr (R == RIDE_PARAM) {
+    if constexpr (ride_has_params(R)) {
         const double* s = c->tan_param;
         ta.s = ParamSeeds{s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]};
     }
-    if constexpr (R == RIDE_SERIES)
+    if constexpr (ride_has_series(R))
         for (int s = 0; s < 4; ++s) ta.sn[s] = c->d_tan_bcs[s];
 }
 // the cotangent fields and the tape of AdjointArgs / CheckpointArgs (the same member names, no common base); `slot`: the tape slot of
@@ -62,8 +63,8 @@ inline ParamGradPtrs param_grad_ptrs(const trm_ctx* c) {
 // what rides along a backward launch on either tape
 template <Ride R, class Args> void fill_gradients(const trm_ctx* c, Args& aa) {
     if constexpr (R != RIDE_NONE) aa.g = bc_grad_ptrs(c);
-    if constexpr (R == RIDE_PARAM) aa.pg = param_grad_ptrs(c);
-    if constexpr (R == RIDE_SERIES) aa.sg = series_grad_ptrs(c);
+    if constexpr (ride_has_params(R)) aa.pg = param_grad_ptrs(c);
+    if constexpr (ride_has_series(R)) aa.sg = series_grad_ptrs(c);
 }
 
 // ---- the preconditions -------------------------------------------------------------------------------------------------------------
@@ -107,14 +108,24 @@ inline int series_nodes_ok(trm_ctx* c, double* const (&nodes)[4], const long (&n
 }
 // the accumulators a backward launch with ride R needs
 template <Ride R> int gradients_ok(trm_ctx* c, int nsteps, const std::string& who) {
-    if constexpr (R == RIDE_SERIES)
+    if constexpr (ride_has_series(R))
         if (int rc = series_rows_ok(c, nsteps, who)) return rc;
     if constexpr (R != RIDE_NONE)
-        if (int rc = arrays_ok(c, c->d_adj_bc, who, R == RIDE_PARAM ? "boundary accumulators" : "accumulators")) return rc;
-    if constexpr (R == RIDE_PARAM)
+        if (int rc = arrays_ok(c, c->d_adj_bc, who, ride_has_params(R) ? "boundary accumulators" : "accumulators")) return rc;
+    if constexpr (ride_has_params(R))
         if (int rc = arrays_ok(c, c->d_adj_param, who, "accumulators")) return rc;
-    if constexpr (R == RIDE_SERIES)
+    if constexpr (ride_has_series(R))
         if (int rc = series_nodes_ok(c, c->d_adj_bcs, c->adj_bcs_nt, who, "an accumulator")) return rc;
+    return TRM_OK;
+}
+// the seed arrays a tangent launch with ride R needs (the parameter seeds travel by value)
+template <Ride R> int tangent_seeds_ok(trm_ctx* c, int nsteps, const std::string& who) {
+    if constexpr (R != RIDE_NONE)
+        if (int rc = arrays_ok(c, c->d_tan_bc, who, ride_has_params(R) ? "boundary seed arrays" : "seed arrays")) return rc;
+    if constexpr (ride_has_series(R)) {
+        if (int rc = series_rows_ok(c, nsteps, who)) return rc;
+        if (int rc = series_nodes_ok(c, c->d_tan_bcs, c->tan_bcs_nt, who, "seeds")) return rc;
+    }
     return TRM_OK;
 }
 
@@ -135,26 +146,21 @@ inline int derivative_program_id(int family, int hyd, int lpc, int generic, int 
 
 // ---- one launch function per kernel template ----------------------------------------------------------------------------------------
 template <Ride R> int tangent_step(trm_ctx* c, double dt, int nsteps) {
-    using Args = RideArgs<R, TangentArgs, TangentBcArgs, TangentParamArgs, TangentSeriesArgs>;
+    using Args = RideArgs<R, TangentArgs, TangentBcArgs, TangentParamArgs, TangentSeriesArgs, TangentParamSeriesArgs>;
     const std::string who = ride_name("k_column_tangent", R, true);
-    if constexpr (R != RIDE_NONE)
-        if (int rc = arrays_ok(c, c->d_tan_bc, who, R == RIDE_PARAM ? "boundary seed arrays" : "seed arrays")) return rc;
-    if constexpr (R == RIDE_SERIES) {
-        if (int rc = series_rows_ok(c, nsteps, who)) return rc;
-        if (int rc = series_nodes_ok(c, c->d_tan_bcs, c->tan_bcs_nt, who, "seeds")) return rc;
-    }
+    if (int rc = tangent_seeds_ok<R>(c, nsteps, who)) return rc;
     const LaunchArgs<double>& la = launch_args<double>(c);
     const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
     Args ta;
-    fill_tangent(c, ta, R == RIDE_SERIES);
+    fill_tangent(c, ta, ride_has_series(R));
     fill_tangent_seeds<R>(c, ta);
     return by_instance(c, [&](auto h, auto lpc) {
         constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        hipLaunchKernelGGL((k_column_tangent<H, LPC, R != RIDE_NONE, Args, R == RIDE_PARAM, R == RIDE_SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0,
+        hipLaunchKernelGGL((k_column_tangent<H, LPC, R != RIDE_NONE, Args, ride_has_params(R), ride_has_series(R)>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0,
                            c->stream, la.state, la.p, a, ta);
         TRM_HIP(c, hipGetLastError());
         c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_TANGENT, H, LPC, ta.generic,
-                                                (R != RIDE_NONE ? PROGRAM_BC_SEEDS : 0) | (R == RIDE_PARAM ? (int)TRM_PROGRAM_PARAMETERS : 0));
+                                                (R != RIDE_NONE ? PROGRAM_BC_SEEDS : 0) | (ride_has_params(R) ? (int)TRM_PROGRAM_PARAMETERS : 0));
         return (int)TRM_OK;
     });
 }
@@ -163,7 +169,7 @@ template <Ride R> int tangent_step(trm_ctx* c, double dt, int nsteps) {
 template <Ride R> int tangent_closure(trm_ctx* c) {
     const LaunchArgs<double>& la = launch_args<double>(c);
     const size_t cells = (size_t)c->Nh * (size_t)c->Nzp;
-    RideArgs<R, TangentArgs, TangentBcArgs, TangentParamArgs, TangentSeriesArgs> ta;
+    RideArgs<R, TangentArgs, TangentBcArgs, TangentParamArgs, TangentSeriesArgs, TangentParamSeriesArgs> ta;
     fill_tangent(c, ta, false);
     fill_tangent_seeds<R>(c, ta);
     hipLaunchKernelGGL((k_closure_tangent<decltype(ta), R == RIDE_PARAM>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, la.state, la.p, ta);
@@ -199,24 +205,24 @@ template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, i
 // the backward launch of a block of the per-step tape (k_column_adjoint) or, CKPT, of one segment of the checkpointed tape
 // (k_column_adjoint_ckpt: the segment's states in dynamic LDS, 2 KiB per step and workgroup)
 template <bool CKPT, Ride R> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    using Args = std::conditional_t<CKPT, RideArgs<R, CheckpointArgs, CheckpointBcArgs, CheckpointParamArgs, CheckpointSeriesArgs>,
-                                    RideArgs<R, AdjointArgs, AdjointBcArgs, AdjointParamArgs, AdjointSeriesArgs>>;
+    using Args = std::conditional_t<CKPT, RideArgs<R, CheckpointArgs, CheckpointBcArgs, CheckpointParamArgs, CheckpointSeriesArgs, CheckpointParamSeriesArgs>,
+                                    RideArgs<R, AdjointArgs, AdjointBcArgs, AdjointParamArgs, AdjointSeriesArgs, AdjointParamSeriesArgs>>;
     const std::string who = ride_name(CKPT ? "k_column_adjoint_ckpt" : "k_column_adjoint", R, false);
     if (int rc = CKPT ? segment_range_ok(c, nsteps, slot, who) : tape_range_ok(c, nsteps, slot, who)) return rc;
     if (int rc = gradients_ok<R>(c, nsteps, who)) return rc;
     const LaunchArgs<double>& la = launch_args<double>(c);
     const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
     Args aa;
-    fill_cotangent(c, aa, slot, fold, R == RIDE_SERIES);
+    fill_cotangent(c, aa, slot, fold, ride_has_series(R));
     fill_gradients<R>(c, aa);
     if constexpr (CKPT) {
         aa.first = 0;
         aa.every = 1;
     }
-    const int bits = PROGRAM_BACKWARD | (CKPT ? PROGRAM_CHECKPOINTED : 0) | (R != RIDE_NONE ? PROGRAM_BC_GRADIENT : 0) | (R == RIDE_PARAM ? (int)TRM_PROGRAM_PARAMETERS : 0);
+    const int bits = PROGRAM_BACKWARD | (CKPT ? PROGRAM_CHECKPOINTED : 0) | (R != RIDE_NONE ? PROGRAM_BC_GRADIENT : 0) | (ride_has_params(R) ? (int)TRM_PROGRAM_PARAMETERS : 0);
     return by_instance(c, [&](auto h, auto lpc) {
         constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        constexpr bool BCGRAD = R != RIDE_NONE, PGRAD = R == RIDE_PARAM, SERIES = R == RIDE_SERIES;
+        constexpr bool BCGRAD = R != RIDE_NONE, PGRAD = ride_has_params(R), SERIES = ride_has_series(R);
         if constexpr (CKPT)
             hipLaunchKernelGGL((k_column_adjoint_ckpt<H, LPC, BCGRAD, Args, PGRAD, SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK),
                                (size_t)nsteps * TRM_STEP_BLOCK * sizeof(double), c->stream, la.state, la.p, a, aa);

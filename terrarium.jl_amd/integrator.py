@@ -954,19 +954,26 @@ def _series_driven(integ, var, side):
 
 
 class _derivative_series:
-    """Sets the option `derivative_series` for the duration of a jvp / vjp call where a boundary series drives the run."""
+    """Sets the option `derivative_series` for the duration of a jvp / vjp call where a boundary series drives the run, and
+    `derivative_series_params` with it where the call carries thermal-parameter seeds or asks for their gradient (`params`)."""
 
-    def __init__(self, integ):
+    def __init__(self, integ, params=False):
         self.st = integ.state
         self.wanted = any(_series_driven(integ, var, side) for var, side in integ.boundary_conditions)
+        self.params = self.wanted and bool(params)
 
     def __enter__(self):
         self.before = self.st.get_option("derivative_series")
+        self.before_params = self.st.get_option("derivative_series_params")
         if self.wanted:
             self.st.set_option("derivative_series", 1)
+        if self.params:
+            self.st.set_option("derivative_series_params", 1)
         return self
 
     def __exit__(self, *exc):
+        if self.params:
+            self.st.set_option("derivative_series_params", self.before_params)
         if self.wanted:
             self.st.set_option("derivative_series", self.before)
         return False
@@ -980,7 +987,9 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, 
     `temperature`, a Flux on `internal_energy` -- held over the run like the values themselves (trm_tangent_bc_upload).
     For a pair driven by a `FieldTimeSeries` or a time-indexed raster source the seeds have the series' shape, [nt][Nh]: d(node value)
     of every node of the record (trm_tangent_bc_series_upload); the option `derivative_series` is set for the duration of the call.
-    `d_params` = {name: value}: seeds on the thermal parameters (`k_mineral`, `c_water`, ...: trm_tangent_param_set).
+    `d_params` = {name: value}: seeds on the thermal parameters (`k_mineral`, `c_water`, ...: trm_tangent_param_set).  They go together
+    with a boundary series, and with seeds on its nodes, in one run: the option `derivative_series_params` is set for the duration of
+    the call as well.
     The heat-only SoilModel in fp64 with ForwardEuler and boundary conditions that are constant over the run or whole-record time
     series (trm_step_tangent); callables, state functions and windowed sources are refused."""
     if not isinstance(integ.timestepper, ForwardEuler):
@@ -992,7 +1001,7 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, 
     if opened:
         st.open_tangent()
     try:
-        with _derivative_series(integ):
+        with _derivative_series(integ, params=d_params is not None):
             st.set_tangent("internal_energy", d_internal_energy)
             for (var, side), values in (d_boundary or {}).items():
                 if _series_driven(integ, var, side):
@@ -1020,7 +1029,9 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
     (trm_adjoint_bc_open); a pair driven by a `FieldTimeSeries` or a time-indexed raster source gets dL/d(node value) as [nt][Nh], the
     shape of its record (trm_adjoint_bc_series_download; the option `derivative_series` is set for the duration of the call).
     With `wrt_params` it appends {name: dL/d(parameter) as [Nh]} for the ten thermal parameters, each column's
-    share (trm_adjoint_param_open): (dL/dU_0, params), or (dL/dU_0, boundary, params) with `wrt_boundary` as well."""
+    share (trm_adjoint_param_open): (dL/dU_0, params), or (dL/dU_0, boundary, params) with `wrt_boundary` as well.  On a run driven by
+    a boundary series too: one sweep gives dL/dU_0, the node gradients and the ten parameter gradients (the option
+    `derivative_series_params` is set for the duration of the call)."""
     if not isinstance(integ.timestepper, ForwardEuler):
         raise ValueError("vjp: ForwardEuler only")
     if integ._has_time_dependence() or integ._windowed():
@@ -1037,7 +1048,7 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
         if opened or st.adjoint_checkpoints() != (K, 0, slots):
             st.open_adjoint(slots, K)
     try:
-        with _derivative_series(integ):
+        with _derivative_series(integ, params=wrt_params):
             st.step_record(integ.timestepper.dt, steps)
             for name, w in (("internal_energy", internal_energy), ("temperature", temperature), ("liquid_water_fraction", liquid_water_fraction)):
                 st.set_cotangent(name, 0.0 if w is None else w)
