@@ -378,24 +378,8 @@ void series_time_indices(const std::vector<double>& times, int indexing, double 
 
 namespace {
 
-// (measured: profiles/r04/coupling_exchange.log)
-#ifndef TRM_SINGLE_STEP_PROGRAM_MAX_COLUMNS
-#define TRM_SINGLE_STEP_PROGRAM_MAX_COLUMNS 0
-#endif
-
 template <class NF> int upload_impl(trm_ctx* c, int field, const NF* host);
 
-// time averages: the fused path's slot of a field (trm_average.hpp), -1 for a field it does not carry, and back
-const int kAccumField[ACC_SLOTS] = {
-    TRM_FIELD_INTERNAL_ENERGY, TRM_FIELD_SATURATION_WATER_ICE, TRM_FIELD_TEMPERATURE, TRM_FIELD_LIQUID_WATER_FRACTION, TRM_FIELD_PRESSURE_HEAD,
-    TRM_FIELD_SURFACE_EXCESS_WATER, TRM_FIELD_WATER_TABLE, TRM_FIELD_SKIN_TEMPERATURE, TRM_FIELD_GROUND_HEAT_FLUX, TRM_FIELD_SURFACE_SHORTWAVE_UP,
-    TRM_FIELD_SURFACE_LONGWAVE_UP, TRM_FIELD_SURFACE_NET_RADIATION, TRM_FIELD_SENSIBLE_HEAT_FLUX, TRM_FIELD_LATENT_HEAT_FLUX,
-    TRM_FIELD_EVAPORATION_GROUND, TRM_FIELD_INFILTRATION, TRM_FIELD_SURFACE_RUNOFF};
-int accum_slot(int field) {
-    for (int s = 0; s < ACC_SLOTS; ++s) if (kAccumField[s] == field) return s;
-    return -1;
-}
-int accum_field(int slot) { return kAccumField[slot]; }
 // the fields trm_average_open takes: the soil state and its closures, surface excess water and water table, and the LandModel's
 // surface diagnostics on a context with the surface energy balance -- never on a standalone VegetationModel
 bool averageable(const trm_ctx* c, int field) {
@@ -442,10 +426,11 @@ enum HeunPath { HEUN_ONE_LAUNCH, HEUN_LEVELS, HEUN_COUPLED, HEUN_REFERENCE };
 
 // The step sequences of one precision.  The launches themselves are Unfused / Veg / ColumnLaunch / GenericLaunch / LevelsLaunch /
 // LandLaunch / PackedLaunch (trm_host.hpp); the C ABI reaches the policies and the Unfused / Veg launches through Ops too.
-template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
-    using P = Policy<NF>;
+template <class NF> struct Ops : StepPolicy<NF>, Unfused<NF>, Veg<NF> {
+    using P = StepPolicy<NF>;
     using U = Unfused<NF>;
     using V = Veg<NF>;
+    using P::tops_current; using P::averaging; using P::averages_in_launch; using P::program_applies; using P::single_step_program;
 
     // nsteps steps of the standalone VegetationModel; time series inputs are evaluated by the host between launches
     static int veg_step(trm_ctx* c, double dt, int nsteps, int finalize, bool heun) {
@@ -551,10 +536,6 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
         st.pending = true;
         return TRM_OK;
     }
-    // the top-cell arrays (LandModel: T, sat, liq of the top cell, [Nh] each) can describe the state: they exist and no device
-    // pointer to T / sat / liq has been handed out.  Every "the next surface evaluation may read the arrays" decision goes
-    // through here -- a launch with TOP_ARRAYS on a context without them would read through a null pointer.
-    static bool tops_current(const trm_ctx* c) { return c->d_top3 != nullptr && !c->top_escaped; }
     static int unfused_step(trm_ctx* c, double dt, int finalize) {
         c->last_program = TRM_PROGRAM_UNFUSED;
         int rc = U::update_state(c, c->state, true);
@@ -565,10 +546,6 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
         return rc;
     }
     // ---- time averages (trm_average_*, trm_average.hpp) ----------------------------------------------------------------------
-    static bool averaging(const trm_ctx* c) {
-        for (const auto& a : c->averages) if (a.field >= 0) return true;
-        return false;
-    }
     // One step's terms of every open accumulator from the fields as the step launch left them: one k_accumulate launch (per 32
     // accumulators), the windows advanced by dt.  Nothing while none is open.
     static int accumulate_after(trm_ctx* c, double dt) {
@@ -594,17 +571,6 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
         if (int rc = AverageLaunch<NF>::accumulate(c, b)) return rc;
         c->last_program |= TRM_PROGRAM_AVERAGES_AFTER_LAUNCH;
         return TRM_OK;
-    }
-    // The multi-step program accumulates in its own launch when it covers every open accumulator's field (the surface excess water
-    // and the water table only under Richards: the NoFlow program does not carry them) -- columns of <= 64 levels.
-    static bool averages_in_launch(const trm_ctx* c) {
-        if (c->Nz > 64 || c->part >= 0) return false;
-        for (const auto& a : c->averages) {
-            if (a.field < 0) continue;
-            const int s = accum_slot(a.field);
-            if (s < 0 || (!P::richards(c) && (s == ACC_S || s == ACC_WT))) return false;
-        }
-        return true;
     }
     // k_column_accum: `nsteps` steps, partials added to the accumulators (one open accumulator of a field: straight into it; more:
     // into a zeroed scratch buffer, then one k_accumulate adds the scratch to each)
@@ -669,13 +635,13 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     // (k_column_land / k_step_pk_land), 65 ... 256 levels (k_column_deep / k_column_wide), the packed fp32 step (k_step_pk), the generic
     // boundary kinds (k_step_wave) or k_column.  Heun: in the launch, levels, generic (k_heun_generic) or k_column.  The multi-step
     // program: the time averages accumulated in the launch (k_column_accum), levels or k_column.
-    template <int PROG> static int step_launch(trm_ctx* c, bool in_launch, bool accum, double dt, int fin, int nsteps) {
-        if (in_launch) return std::is_same<NF, float>::value ? PackedLaunch::step_land(c, dt, fin) : FrontLaunch::run(c, dt, fin, PROG == PROG_HEUN);
-        if (accum) return multi_program_accum(c, dt, fin, nsteps);
-        if (P::levels_per_lane(c) > 1) return levels_launch<NF>(c, PROG, P::generic_bcs(c), dt, fin, nsteps);
-        if (PROG == PROG_EULER && P::packed_path(c)) return PackedLaunch::step(c, dt, fin);
-        if (PROG != PROG_MULTI && P::generic_bcs(c)) return PROG == PROG_HEUN ? GenericLaunch<NF>::heun(c, dt, fin) : GenericLaunch<NF>::step(c, dt, fin);
-        return P::richards(c) ? ColumnLaunch<NF, true, PROG>::run(c, dt, fin, nsteps) : ColumnLaunch<NF, false, PROG>::run(c, dt, fin, nsteps);
+    template <int PROG> static int step_launch(trm_ctx* c, const StepPlan& plan, double dt, int fin, int nsteps) {      // (plan: StepPolicy::plan_step)
+        if (plan.route == ROUTE_SURFACE_IN_LAUNCH) return std::is_same<NF, float>::value ? PackedLaunch::step_land(c, dt, fin) : FrontLaunch::run(c, plan, dt, fin, PROG == PROG_HEUN);
+        if (plan.route == ROUTE_ACCUM_IN_LAUNCH) return multi_program_accum(c, dt, fin, nsteps);
+        if (plan.route == ROUTE_LEVELS) return levels_launch<NF>(c, PROG, P::generic_bcs(c), dt, fin, nsteps);
+        if (plan.route == ROUTE_PACKED) return PackedLaunch::step(c, dt, fin);
+        if (plan.route == ROUTE_GENERIC) return PROG == PROG_HEUN ? GenericLaunch<NF>::heun(c, dt, fin) : GenericLaunch<NF>::step(c, dt, fin);
+        return P::richards(c) ? ColumnLaunch<NF, true, PROG>::run(c, plan, dt, fin, nsteps) : ColumnLaunch<NF, false, PROG>::run(c, plan, dt, fin, nsteps);
     }
     // What a fused launch leaves (rc: the launch's): the stored T / liq are the closure of the state once it has succeeded; the open
     // time averages take the step's terms (`accumulate`: the launch has not added them itself); only the finalizing launch stores
@@ -697,78 +663,24 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
     // their own small launch in front of the column kernel (LandModel; + the 0-D prognostics' step of the coupled vegetation) unless
     // the launch carries them (surface_in_launch).  (The per-cell plant_available_water field is materialised with the other per-cell
     // auxiliaries: by the finalizing launch, or every step under TRM_OPT_WRITE_KF_EVERY_STEP.)
-    // The step launch of fused_launch<PROG_EULER> will be a deriving instance of k_column / k_column_land (as step_launch and the
-    // launchers select it): the only launches that read neither T nor liq from memory.
-    static bool derives_unread(trm_ctx* c, bool in_launch) {
-        if (P::levels_per_lane(c) != 1 || c->part >= 0) return false;
-        if (std::is_same<NF, float>::value && (in_launch || P::packed_path(c))) return false;
-        if (!in_launch && P::generic_bcs(c)) return false;
-        return (P::richards(c) ? P::template derive_now<true>(c) : P::template derive_now<false>(c)) == DERIVE_T_LIQ;
-    }
-    // ... and may leave T / liq unstored (ColumnArgs::store_closure = 0): nothing reads the arrays before the next flush_closure -- no
-    // open time average of either (accumulate_after reads them), no tangent state, and on a LandModel the top-cell arrays are what the
-    // surface processes read (fused_epilogue's included).
-    static bool defer_closure_now(trm_ctx* c, bool in_launch) {
-        if (!c->opt_defer_closure || c->d_tan[0] || !derives_unread(c, in_launch)) return false;
-        for (const auto& a : c->averages)
-            if (a.field == TRM_FIELD_TEMPERATURE || a.field == TRM_FIELD_LIQUID_WATER_FRACTION) return false;
-        return !c->params.seb || tops_current(c);
-    }
-    // TRM_OPT_INTERIOR_STEPS: the context's per-step launch is one of the instances k_column_psi stands in for -- fp64, Richards, no
-    // LandModel, one level per lane, every column, a compiled hydraulics and one of the non-LandModel signatures, T / liq derived --
-    // and nothing reads a field between the launches of a call: no open time average (accumulate_after reads the arrays every step), no
-    // tangent state, no device pointer handed out; and the stored pressure_head / water_table are a step launch's (psi_consistent).
-    static bool interior_capable(trm_ctx* c) {
-        if (!std::is_same<NF, double>::value || !c->opt_interior || !c->psi_consistent || c->closure_escaped) return false;
-        // 2, the library's rule: states within the Infinity Cache (the bound of Policy::scalar_inputs_now).  Beyond it the step gains more
-        // (EXPERIMENTS R10.1), but bench.py's HBM-resident companion then reports a roofline fraction above 1 on its fixed 2 080 B per
-        // column-step, which tests/test_gpu_full_size.py bounds: left to 1 until that yardstick is recalibrated
-        if (c->opt_interior == 2 && (size_t)6 * (size_t)c->Nh * (size_t)c->Nzp * sizeof(NF) > ((size_t)256 << 20)) return false;
-        if (!c->opt_write_kf) return false;      // (without TRM_OPT_WRITE_KF_EVERY_STEP the K array is the last finalizing launch's: left to the classic launches)
-        if (!P::richards(c) || c->params.seb || P::coupled(c) || c->veg_mode == TRM_VEGETATION_STANDALONE) return false;
-        if (c->opt_kernel != TRM_KERNEL_FUSED || P::levels_per_lane(c) != 1 || c->part >= 0 || P::generic_bcs(c)) return false;
-        if (!c->opt_bc_signature || P::hyd(c) == HYD_GENERIC || !column_psi_supported(bc_signature_of(c))) return false;
-        if (averaging(c) || c->d_tan[0]) return false;
-        return P::template derive_now<true>(c) == DERIVE_T_LIQ;
-    }
-    template <int PROG> static int fused_launch(trm_ctx* c, double dt, int fin, int nsteps = 1) {
+    // `not_last`, `*interior`: Ops::step's two facts (StepPolicy::plan_step); `*interior` arrives as "the launch before was interior" and leaves as "this one was"
+    template <int PROG> static int fused_launch(trm_ctx* c, double dt, int fin, int nsteps = 1, bool not_last = false, bool* interior = nullptr) {
         int rc = fused_prologue<PROG>(c, dt, nsteps);
-        const bool in_launch = !rc && PROG != PROG_MULTI && surface_in_launch(c, PROG == PROG_HEUN);
+        const StepPlan plan = P::plan_step(c, PROG, not_last, interior && *interior);
+        const bool in_launch = plan.route == ROUTE_SURFACE_IN_LAUNCH, accum = plan.route == ROUTE_ACCUM_IN_LAUNCH;
         // T / liq left unstored by earlier launches: materialised in front of everything that reads them from the 3-D arrays -- any
         // step launch but a deriving one, the vegetation launches (never deriving), a surface launch that gathers the top cell from
         // the fields
         const bool surface_reads_fields = c->params.seb && !in_launch && !(c->top_valid && c->d_top3);
-        if (!rc && c->closure_deferred && (PROG != PROG_EULER || surface_reads_fields || !derives_unread(c, in_launch))) rc = flush_closure(c);
-        c->defer_launch = !rc && PROG == PROG_EULER && defer_closure_now(c, in_launch);
-        c->launch_deferred = false;
-        // The form of this launch (PSI_STORED: today's instance).  Behind an interior launch the pressure head in memory is stale: the
-        // launch must derive it; it goes interior itself if it is not the call's last (Ops::step) and leaves T / liq unstored anyway.
-        c->psi_request = PSI_STORED;
-        c->psi_check_entry = c->prev_interior ? 1 : 0;
-        c->psi_launched = PSI_STORED;
-        c->launch_psi_step = false;
-        if (PROG == PROG_EULER && !rc && (c->prev_interior || c->interior_wanted)) {
-            const bool capable = !in_launch && interior_capable(c);
-            if (capable && c->interior_wanted && c->defer_launch) c->psi_request = PSI_INTERIOR;
-            else if (c->prev_interior) {
-                if (!capable) rc = fail(c, TRM_EINVAL, "trm_step: the launch behind an interior launch cannot derive the pressure head");
-                c->psi_request = PSI_LAST;
-            }
-        } else if (c->prev_interior && !rc) rc = fail(c, TRM_EINVAL, "trm_step: an interior launch must be followed by a ForwardEuler launch");
+        if (!rc && c->closure_deferred && (surface_reads_fields || !plan.derives_unread)) rc = flush_closure(c);
+        if (PROG != PROG_EULER && plan.check_entry && !rc) rc = fail(c, TRM_EINVAL, "trm_step: an interior launch must be followed by a ForwardEuler launch");
+        if (!rc && plan.refusal) rc = fail(c, TRM_EINVAL, plan.refusal);
         if (!rc && PROG != PROG_MULTI && P::coupled(c)) rc = V::surface_veg(c, c->state, true, true, dt, c->opt_write_kf != 0);
         else if (!rc && PROG != PROG_MULTI && c->params.seb && !in_launch) rc = U::surface(c, c->state, true);
-        const bool accum = PROG == PROG_MULTI && averaging(c) && averages_in_launch(c);
-        if (!rc) rc = step_launch<PROG>(c, in_launch, accum, dt, fin, nsteps);
-        const bool deferred = c->launch_deferred;
-        c->defer_launch = c->launch_deferred = false;
-        if (!rc && c->psi_launched != c->psi_request) rc = fail(c, TRM_EINVAL, "trm_step: the step launch did not take the requested form");
-        const bool went_interior = !rc && c->psi_launched == PSI_INTERIOR;
-        if (went_interior) c->interior_launches += 1;
-        if (!rc) c->prev_interior = went_interior;
-        const bool psi_step = PROG == PROG_EULER && c->launch_psi_step;
-        c->psi_request = c->psi_launched = PSI_STORED;
-        c->launch_psi_step = false;
-        return fused_epilogue(c, rc, dt, fin, !accum, deferred, psi_step);
+        if (!rc) rc = step_launch<PROG>(c, plan, dt, fin, nsteps);
+        if (!rc && plan.psi_form == PSI_INTERIOR) c->interior_launches += 1;
+        if (!rc && interior) *interior = plan.psi_form == PSI_INTERIOR;
+        return fused_epilogue(c, rc, dt, fin, !accum, !plan.store_closure, plan.psi_step);
     }
     // ---- LandModel, per-step path: the surface processes of one half of the columns UNDER the column program of the other ----
     // (k_land_euler / k_land_pk, trm_column.hpp: one stream, two launches per step as before, each covering the soil columns
@@ -805,48 +717,11 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
                 rc = LandLaunch<NF>::run(c, 1, 0, dt, 0, tops_current(c));   // (half A has just been stepped: its top arrays are current)
             } else {
                 PartScope scope(c, 1);
-                rc = step_launch<PROG_EULER>(c, false, false, dt, fin, 1);
+                rc = step_launch<PROG_EULER>(c, P::plan_step(c, PROG_EULER, false, false), dt, fin, 1);
             }
             tick(c, dt, 1);
         }
         return fused_epilogue(c, rc, dt, finalize);
-    }
-    // TRM_OPT_SURFACE_IN_LAUNCH: a per-step launch of this context can carry its own surface processes (k_column_land) -- a
-    // bare-ground LandModel in fp64 on the branch-free program with the LandModel's boundary wiring, one level per lane, every
-    // column in one launch, the top-cell arrays current (the surface workgroups read them).
-    static bool surface_in_launch(trm_ctx* c, bool heun = false) {
-        if (c->opt_front == 0 || (heun && std::is_same<NF, float>::value)) return false;
-        if (!c->params.seb || !P::richards(c) || P::coupled(c) || c->Nz > 64 || P::generic_bcs(c) || c->part >= 0) return false;
-        if (c->opt_kernel != TRM_KERNEL_FUSED || !c->opt_bc_signature || bc_signature_of(c) != BCSIG_LAND) return false;
-        if (P::hyd(c) != HYD_BC_LINEAR && P::hyd(c) != HYD_VG_N2) return false;
-        if (!c->top_valid || !tops_current(c)) return false;
-        const int d = heun ? DERIVE_NONE : P::template derive_now<true>(c);      // (the Heun program reads T / liq as stored)
-        if (std::is_same<NF, float>::value ? !(P::packed_path(c) && (d == DERIVE_NONE || d == DERIVE_LIQ))         // k_step_pk_land
-                                           : !(d == DERIVE_NONE || d == DERIVE_T_LIQ)) return false;             // k_column_land
-        if (c->opt_front == 1) return true;
-        // The library's rule (2).  What the single launch saves is the FIXED cost of the second launch (~3-4 us); the surface chain
-        // itself is still evaluated, and the column waves of the first generation wait for it.  Measured, same box, pair -> one launch
-        // (profiles/r05/exp3d_prio_sleep.log, exp4_packed_surface_in_launch.log, exp4b_in_launch_by_size.log): fp64 1 780 columns
-        // 9.8 -> 7.1 us, 7 119 (the shard of BASELINE config 4) 11.1 -> 8.6, C4-VG shard 12.3 -> 9.2, 28 476 19.7 -> 19.3, N145
-        // (56 951) 30.3 -> 29.6 ... 30.0; fp32 12 696 columns 15.2 -> 10.6, 50 782 29.5 -> 31.2, 203 125 108.6 -> 106.6, C5
-        // (812 500) 425.4 -> 426.7, C5-VG 437.1 -> 451.0: a clear win where the step is launch-bound, nothing beyond.
-        return c->Nh <= (std::is_same<NF, float>::value ? 32768 : 65536);
-    }
-    // TRM_OPT_SINGLE_STEP_PROGRAM: a bare-ground LandModel stepped ONE step per call (its inputs change every step: a coupled
-    // atmosphere) takes the resident column program with the surface processes inline -- one launch instead of the
-    // k_surface + k_column pair.  At N145 the pair wins by far (the inline surface balance runs on every lane of the column's
-    // half-wave: C4 103.9 vs 34.1 us); on a shard of a few thousand columns the step is bound by launch latency and
-    // the single launch wins.
-    static bool single_step_program(const trm_ctx* c) {
-        if (!c->params.seb || c->Nz > 64 || c->opt_single_step == 0) return false;
-        if (c->opt_single_step == 1) return true;
-        return c->Nh <= TRM_SINGLE_STEP_PROGRAM_MAX_COLUMNS;
-    }
-    // how many steps ONE launch of trm_step covers for this context: 1 unless the resident multi-step program applies
-    static bool program_applies(const trm_ctx* c) {
-        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && P::levels_per_lane(c) > 0;
-        return fused && !P::generic_bcs(c) && !P::coupled(c) && c->veg_mode != TRM_VEGETATION_STANDALONE &&
-               ((c->Nz <= 64 && P::series_fit_program(c)) || (P::levels_per_lane(c) == 2 && !c->params.seb && c->series.empty()));
     }
     static int steps_per_launch_now(trm_ctx* c) {
         return !program_applies(c) ? 1 : (c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : auto_steps_per_launch(c));
@@ -866,6 +741,7 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
         const bool avg = averaging(c), avg_in_launch = avg && program_ok && averages_in_launch(c);
         const int spl = (avg && !avg_in_launch) ? 1 : steps_per_launch_now(c);
         int n = 0, rc = TRM_OK;
+        bool behind_interior = false;      // (the launch before was interior: psi, K, the water-table-derived fields in memory are stale until the call's last launch)
         while (n < nsteps && !rc) {
             int m = std::min(spl, nsteps - n);
             const int fin = (finalize && n + m == nsteps) ? 1 : 0;
@@ -877,7 +753,7 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
                 if (!rc) c->closure_consistent = true;   // closure! has just run
                 c->psi_consistent = false;
             } else if (m > 1 || (program_ok && single_step_program(c))) {
-                rc = fused_launch<PROG_MULTI>(c, dt, fin, m);
+                rc = fused_launch<PROG_MULTI>(c, dt, fin, m, false, &behind_interior);
             } else if (interleave_now(c, nsteps - n)) {
                 // every remaining step of the call in one go (the clock is ticked inside)
                 m = nsteps - n;
@@ -886,19 +762,16 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
                 continue;
             } else {
                 // (interior launches: inside this call only, never its last launch, never finalizing)
-                c->interior_wanted = n + m < nsteps && !fin;
-                rc = fused_launch<PROG_EULER>(c, dt, fin);
-                c->interior_wanted = false;
+                rc = fused_launch<PROG_EULER>(c, dt, fin, 1, n + m < nsteps && !fin, &behind_interior);
             }
             if (rc) break;
             tick(c, dt, m);
             n += m;
         }
-        if (c->prev_interior) {
+        if (behind_interior) {
             // A launch failed behind interior launches (the loop cannot end otherwise: the call's last launch is never interior): pressure_head,
             // water-table and hydraulic_conductivity arrays are those of an earlier step.  Rebuilt here from the stored state with the
             // reference-order kernels, whatever they return -- the caller gets the error of the launch that failed.
-            c->prev_interior = false;
             c->psi_consistent = false;
             const std::string err = c->err;
             if (!flush_closure(c) && !U::closure_hydrology(c, c->state, true, false)) (void)U::hydraulics(c, c->state);
@@ -971,7 +844,7 @@ template <class NF> struct Ops : Policy<NF>, Unfused<NF>, Veg<NF> {
         a.store_paw = c->opt_write_kf != 0;
         a.st_w_can = vg.w_can; a.st_C_veg = vg.C_veg; a.st_nu = vg.nu; a.st_An = vg.An; a.st_Ts = sv.Ts;
         rc = V::surface_veg_launch(c, v0, vs, a);
-        if (!rc) rc = step_launch<PROG_HEUN>(c, false, false, dt, finalize, 1);
+        if (!rc) rc = step_launch<PROG_HEUN>(c, P::plan_step(c, PROG_HEUN, false, false), dt, finalize, 1);
         if (!rc) {
             SurfaceVegArgs<NF> b{};
             b.dt = (NF)dt;

@@ -96,22 +96,16 @@ struct trm_ctx {
     bool closure_consistent = false, closure_escaped = false, saved_closure_consistent = false;
     // TRM_OPT_DEFER_CLOSURE_STORES: a deriving per-step launch does not store T / liq (nothing reads them before the next step derives
     // them again).  `closure_deferred`: the T / liq arrays are stale and the stored (U, sat) define them -- every entry point that may
-    // read or write field memory materialises them first (flush_closure, k_materialize_closure).  `defer_launch`: the launch being
-    // issued may pass ColumnArgs::store_closure = 0 (set by Ops::fused_launch for its step launch only); `launch_deferred`: it has.
+    // read or write field memory materialises them first (flush_closure, k_materialize_closure).
     int opt_defer_closure = 1;
-    bool closure_deferred = false, defer_launch = false, launch_deferred = false;
+    bool closure_deferred = false;
     int64_t materializations = 0;   // TRM_INFO_MATERIALIZATIONS: k_materialize_closure launches so far
     // TRM_OPT_INTERIOR_STEPS: inside one trm_step call the fp64 Richards per-step launches but the last store U, sat, surface_excess_water
     // and the water table alone (k_column_psi<PSI_INTERIOR>), and the launch behind one derives the pressure head at entry.
     // `psi_consistent`: the stored pressure_head / water_table are what a k_column ForwardEuler launch left for the stored saturation
-    // (set by Ops::fused_epilogue after such a launch, cleared by everything else that sets closure_consistent).  The rest lives inside
-    // Ops::step's loop only: `interior_wanted` (the launch being issued is not the call's last), `prev_interior` (the one before it was
-    // an interior launch: psi, K and the water-table-derived fields in memory are stale until the call's last launch has run),
-    // `psi_request` / `psi_check_entry` (what Ops::fused_launch asks of the launcher), `psi_launched` (what the launcher did),
-    // `launch_psi_step` (the launcher issued a k_column / k_column_psi ForwardEuler launch of a Richards state).
-    int opt_interior = 2;           // 0 off, 1 whenever legal, 2 the library's rule (Ops::interior_capable)
-    bool psi_consistent = false, interior_wanted = false, prev_interior = false, launch_psi_step = false;
-    int psi_request = 0, psi_check_entry = 0, psi_launched = 0;
+    // (set by Ops::fused_epilogue after such a launch, cleared by everything else that sets closure_consistent).
+    int opt_interior = 2;           // 0 off, 1 whenever legal, 2 the library's rule (StepPolicy::interior_capable)
+    bool psi_consistent = false;
     int64_t interior_launches = 0;  // TRM_INFO_INTERIOR_LAUNCHES
     void* d_zero = nullptr;  // [Nh] zeros: stands in for the value array of every unset boundary condition
     double* d_reduce = nullptr;  // scratch for trm_reduce
@@ -350,7 +344,7 @@ template <class NF> struct Policy {
         // (3, 4: the packed fp32 step's modes -- the liquid fraction alone; that and the pressure head.  The fp64 column program had
         // instances for "liquid fraction alone" and "pressure head as well" (value 5) until round 5: both measured slower than
         // deriving T and liq, EXPERIMENTS.md; the values now select what the library offers there: both T and liq)
-        const bool packed = std::is_same<NF, float>::value && packed_path(const_cast<trm_ctx*>(c));
+        const bool packed = std::is_same<NF, float>::value && packed_path(c);
         if (c->opt_derive == 3) return packed ? DERIVE_LIQ : DERIVE_T_LIQ;
         if (c->opt_derive == 5) return DERIVE_T_LIQ;
         if (c->opt_derive == 4) return packed ? (RICH ? DERIVE_LIQ_PSI : DERIVE_LIQ) : DERIVE_T_LIQ;
@@ -359,7 +353,7 @@ template <class NF> struct Policy {
         const bool large = c->Nh >= 24576;
         // fp32 on the packed kernel, HBM-resident: the liquid fraction alone (r3, re-measured on the final kernels,
         // profiles/r03/exp21_derive_liq_fp32.log: C5 443.7 vs 457.9 us, C5-VG 472.5 vs 476.3; before the store ordering it lost)
-        if (std::is_same<NF, float>::value) return (beyond_cache && packed_path(const_cast<trm_ctx*>(c))) ? DERIVE_LIQ : DERIVE_NONE;
+        if (std::is_same<NF, float>::value) return (beyond_cache && packed_path(c)) ? DERIVE_LIQ : DERIVE_NONE;
         return (beyond_cache || large) ? DERIVE_T_LIQ : DERIVE_NONE;
     }
     // The per-column outputs of the column program through the workgroup's staging table (template parameter STAGED) or as direct 2-lane
@@ -395,7 +389,7 @@ template <class NF> struct Policy {
     }
     // fp32: two columns per lane with packed math (trm_packed_f32.hpp) -- the reference-default hydraulics, and van
     // Genuchten retention with Mualem conductivity
-    static bool packed_path(trm_ctx* c) {
+    static bool packed_path(const trm_ctx* c) {
         if (!std::is_same<NF, float>::value || !c->opt_packed || generic_bcs(c)) return false;
         if (hyd(c) == HYD_VG_N2) return true;
         return hyd(c) == HYD_BC_LINEAR;
@@ -526,7 +520,7 @@ template <class NF> ColumnArgs<NF> column_args(trm_ctx* c, double dt, int finali
     a.series = (const SeriesTable<NF>*)c->d_series_table;
     a.series_rows = (const SeriesRow*)c->d_series_rows;
     a.nseries = (int)c->series.size();
-    a.store_closure = 1;      // (0: take_deferral, by the launchers of the deriving per-step instances alone)
+    a.store_closure = 1;      // (0: StepPlan::store_closure, taken over by the launchers of the deriving per-step instances alone)
     if (prog == PROG_HEUN && Policy<NF>::coupled(c)) {
         a.stage_sat = (NF*)c->stage.f[TRM_FIELD_SATURATION_WATER_ICE];
         a.stage_liq = (NF*)c->stage.f[TRM_FIELD_LIQUID_WATER_FRACTION];
@@ -536,13 +530,18 @@ template <class NF> ColumnArgs<NF> column_args(trm_ctx* c, double dt, int finali
     return a;
 }
 
-// A launcher of a deriving (DERIVE_T_LIQ) per-step instance of k_column / k_column_land asks here whether this launch leaves
-// T / liq unstored: yes where Ops::fused_launch has allowed it for the launch being issued.  Records that it has.
-template <class NF> void take_deferral(trm_ctx* c, ColumnArgs<NF>& a) {
-    if (!c->defer_launch) return;
-    a.store_closure = 0;
-    c->launch_deferred = true;
-}
+// One fused step launch, decided once (StepPolicy::plan_step, below) and handed to the launcher: the route of Ops::step_launch, in the order it is
+// tried, and -- for ForwardEuler on k_column / k_column_land, which have an instance per value; the other launches keep the plain form below -- what is
+// derived, how the per-column values travel (after Policy::io_paths), the boundary signature (-1: kinds read at run time), whether T / liq are
+// stored, how the pressure head arrives and leaves (PSI_*; `check_entry`: the launch before was an interior launch).  `derives_unread`: a deriving
+// k_column / k_column_land launch of every column, which reads neither T nor liq from memory; `psi_step`: a k_column / k_column_psi launch of a Richards state.
+enum StepRoute { ROUTE_SURFACE_IN_LAUNCH, ROUTE_ACCUM_IN_LAUNCH, ROUTE_LEVELS, ROUTE_PACKED, ROUTE_GENERIC, ROUTE_COLUMN };
+struct StepPlan {
+    StepRoute route = ROUTE_COLUMN;
+    int derive = DERIVE_NONE, staged = 0, scalar_in = 1, sig = -1, store_closure = 1, psi_form = PSI_STORED, check_entry = 0;
+    bool derives_unread = false, psi_step = false;
+    const char* refusal = nullptr;      // the context cannot take the launch the call needs here (the caller fails with this text)
+};
 
 // ---- the launchers: declared here, defined and explicitly instantiated in the trm_launch_*.hip files ------------------------
 // reference-order kernels, the 0-D surface kernel, update_inputs! of the time series (trm_launch_unfused.hip)
@@ -571,7 +570,7 @@ template <class NF> struct Veg {
     static int heun_average_0d(trm_ctx* c, const VegView<NF>& vs, const VegView<NF>& vg, double dt);
 };
 // the register-resident column programs k_column (trm_launch_column*.hip: one file per precision x program)
-template <class NF, bool RICH, int PROG> struct ColumnLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps); };
+template <class NF, bool RICH, int PROG> struct ColumnLaunch { static int run(trm_ctx* c, const StepPlan& plan, double dt, int finalize, int nsteps); };
 // the multi-step program with time averages accumulated in the launch (trm_launch_column_accum_*.hip)
 template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps, const AccumArgs& acc); };
 // ---- the derivative families of the heat-only fp64 run (trm_launch_derivative.inl) --------------------------------------------------
@@ -695,8 +694,143 @@ struct PackedLaunch {
 int front_args(trm_ctx* c, const char* kernel, FrontArgs& fa);
 // the LandModel's per-step launch with the surface processes in its first workgroups: k_column_land (fp64; trm_launch_column_land_*.hip)
 struct FrontLaunch {
-    static int run(trm_ctx* c, double dt, int finalize, bool heun = false);
-    template <int H> static int run_hyd(trm_ctx* c, double dt, int finalize, bool heun);
+    static int run(trm_ctx* c, const StepPlan& plan, double dt, int finalize, bool heun = false);
+    template <int H> static int run_hyd(trm_ctx* c, const StepPlan& plan, double dt, int finalize, bool heun);
+};
+
+// (measured: profiles/r04/coupling_exchange.log)
+#ifndef TRM_SINGLE_STEP_PROGRAM_MAX_COLUMNS
+#define TRM_SINGLE_STEP_PROGRAM_MAX_COLUMNS 0
+#endif
+
+// time averages: the fused path's slot of a field (trm_average.hpp), -1 for a field it does not carry, and back
+constexpr int kAccumField[ACC_SLOTS] = {
+    TRM_FIELD_INTERNAL_ENERGY, TRM_FIELD_SATURATION_WATER_ICE, TRM_FIELD_TEMPERATURE, TRM_FIELD_LIQUID_WATER_FRACTION, TRM_FIELD_PRESSURE_HEAD,
+    TRM_FIELD_SURFACE_EXCESS_WATER, TRM_FIELD_WATER_TABLE, TRM_FIELD_SKIN_TEMPERATURE, TRM_FIELD_GROUND_HEAT_FLUX, TRM_FIELD_SURFACE_SHORTWAVE_UP,
+    TRM_FIELD_SURFACE_LONGWAVE_UP, TRM_FIELD_SURFACE_NET_RADIATION, TRM_FIELD_SENSIBLE_HEAT_FLUX, TRM_FIELD_LATENT_HEAT_FLUX,
+    TRM_FIELD_EVAPORATION_GROUND, TRM_FIELD_INFILTRATION, TRM_FIELD_SURFACE_RUNOFF};
+inline int accum_slot(int field) {
+    for (int s = 0; s < ACC_SLOTS; ++s) if (kAccumField[s] == field) return s;
+    return -1;
+}
+inline int accum_field(int slot) { return kAccumField[slot]; }
+
+// ---- the pure predicates of the step sequences (Ops, terrarium_hip.hip) and the StepPlan they give: no HIP call (tests/step_plan_preconditions.cpp)
+template <class NF> struct StepPolicy : Policy<NF> {
+    using P = Policy<NF>;
+    // the top-cell arrays (LandModel: T, sat, liq of the top cell, [Nh] each) can describe the state: they exist and no device
+    // pointer to T / sat / liq has been handed out.  Every "the next surface evaluation may read the arrays" decision goes
+    // through here -- a launch with TOP_ARRAYS on a context without them would read through a null pointer.
+    static bool tops_current(const trm_ctx* c) { return c->d_top3 != nullptr && !c->top_escaped; }
+    static bool averaging(const trm_ctx* c) {
+        for (const auto& a : c->averages) if (a.field >= 0) return true;
+        return false;
+    }
+    // The multi-step program accumulates in its own launch when it covers every open accumulator's field (the surface excess water
+    // and the water table only under Richards: the NoFlow program does not carry them) -- columns of <= 64 levels.
+    static bool averages_in_launch(const trm_ctx* c) {
+        if (c->Nz > 64 || c->part >= 0) return false;
+        for (const auto& a : c->averages) {
+            if (a.field < 0) continue;
+            const int s = accum_slot(a.field);
+            if (s < 0 || (!P::richards(c) && (s == ACC_S || s == ACC_WT))) return false;
+        }
+        return true;
+    }
+    // A launch that reads neither T nor liq (StepPlan::derives_unread) may leave them unstored (ColumnArgs::store_closure = 0): nothing reads the arrays before the next flush_closure -- no
+    // open time average of either (accumulate_after reads them), no tangent state, and on a LandModel the top-cell arrays are what the
+    // surface processes read (fused_epilogue's included).
+    static bool defer_closure_now(const trm_ctx* c, bool derives_unread) {
+        if (!c->opt_defer_closure || c->d_tan[0] || !derives_unread) return false;
+        for (const auto& a : c->averages)
+            if (a.field == TRM_FIELD_TEMPERATURE || a.field == TRM_FIELD_LIQUID_WATER_FRACTION) return false;
+        return !c->params.seb || tops_current(c);
+    }
+    // TRM_OPT_INTERIOR_STEPS: the context's per-step launch is one of the instances k_column_psi stands in for -- fp64, Richards, no
+    // LandModel, one level per lane, every column, a compiled hydraulics and one of the non-LandModel signatures, T / liq derived --
+    // and nothing reads a field between the launches of a call: no open time average (accumulate_after reads the arrays every step), no
+    // tangent state, no device pointer handed out; and the stored pressure_head / water_table are a step launch's (psi_consistent).
+    static bool interior_capable(const trm_ctx* c) {
+        if (!std::is_same<NF, double>::value || !c->opt_interior || !c->psi_consistent || c->closure_escaped) return false;
+        // 2, the library's rule: states within the Infinity Cache (the bound of Policy::scalar_inputs_now).  Beyond it the step gains more
+        // (EXPERIMENTS R10.1), but bench.py's HBM-resident companion then reports a roofline fraction above 1 on its fixed 2 080 B per
+        // column-step, which tests/test_gpu_full_size.py bounds: left to 1 until that yardstick is recalibrated
+        if (c->opt_interior == 2 && (size_t)6 * (size_t)c->Nh * (size_t)c->Nzp * sizeof(NF) > ((size_t)256 << 20)) return false;
+        if (!c->opt_write_kf) return false;      // (without TRM_OPT_WRITE_KF_EVERY_STEP the K array is the last finalizing launch's: left to the classic launches)
+        if (!P::richards(c) || c->params.seb || P::coupled(c) || c->veg_mode == TRM_VEGETATION_STANDALONE) return false;
+        if (c->opt_kernel != TRM_KERNEL_FUSED || P::levels_per_lane(c) != 1 || c->part >= 0 || P::generic_bcs(c)) return false;
+        if (!c->opt_bc_signature || P::hyd(c) == HYD_GENERIC || !column_psi_supported(bc_signature_of(c))) return false;
+        if (averaging(c) || c->d_tan[0]) return false;
+        return P::template derive_now<true>(c) == DERIVE_T_LIQ;
+    }
+    // TRM_OPT_SURFACE_IN_LAUNCH: a per-step launch of this context can carry its own surface processes (k_column_land) -- a
+    // bare-ground LandModel in fp64 on the branch-free program with the LandModel's boundary wiring, one level per lane, every
+    // column in one launch, the top-cell arrays current (the surface workgroups read them).
+    static bool surface_in_launch(const trm_ctx* c, bool heun = false) {
+        if (c->opt_front == 0 || (heun && std::is_same<NF, float>::value)) return false;
+        if (!c->params.seb || !P::richards(c) || P::coupled(c) || c->Nz > 64 || P::generic_bcs(c) || c->part >= 0) return false;
+        if (c->opt_kernel != TRM_KERNEL_FUSED || !c->opt_bc_signature || bc_signature_of(c) != BCSIG_LAND) return false;
+        if (P::hyd(c) != HYD_BC_LINEAR && P::hyd(c) != HYD_VG_N2) return false;
+        if (!c->top_valid || !tops_current(c)) return false;
+        const int d = heun ? DERIVE_NONE : P::template derive_now<true>(c);      // (the Heun program reads T / liq as stored)
+        if (std::is_same<NF, float>::value ? !(P::packed_path(c) && (d == DERIVE_NONE || d == DERIVE_LIQ))         // k_step_pk_land
+                                           : !(d == DERIVE_NONE || d == DERIVE_T_LIQ)) return false;             // k_column_land
+        if (c->opt_front == 1) return true;
+        // The library's rule (2).  What the single launch saves is the FIXED cost of the second launch (~3-4 us); the surface chain
+        // itself is still evaluated, and the column waves of the first generation wait for it.  Measured, same box, pair -> one launch
+        // (profiles/r05/exp3d_prio_sleep.log, exp4_packed_surface_in_launch.log, exp4b_in_launch_by_size.log): fp64 1 780 columns
+        // 9.8 -> 7.1 us, 7 119 (the shard of BASELINE config 4) 11.1 -> 8.6, C4-VG shard 12.3 -> 9.2, 28 476 19.7 -> 19.3, N145
+        // (56 951) 30.3 -> 29.6 ... 30.0; fp32 12 696 columns 15.2 -> 10.6, 50 782 29.5 -> 31.2, 203 125 108.6 -> 106.6, C5
+        // (812 500) 425.4 -> 426.7, C5-VG 437.1 -> 451.0: a clear win where the step is launch-bound, nothing beyond.
+        return c->Nh <= (std::is_same<NF, float>::value ? 32768 : 65536);
+    }
+    // TRM_OPT_SINGLE_STEP_PROGRAM: a bare-ground LandModel stepped ONE step per call (its inputs change every step: a coupled
+    // atmosphere) takes the resident column program with the surface processes inline -- one launch instead of the
+    // k_surface + k_column pair.  At N145 the pair wins by far (the inline surface balance runs on every lane of the column's
+    // half-wave: C4 103.9 vs 34.1 us); on a shard of a few thousand columns the step is bound by launch latency and
+    // the single launch wins.
+    static bool single_step_program(const trm_ctx* c) {
+        if (!c->params.seb || c->Nz > 64 || c->opt_single_step == 0) return false;
+        if (c->opt_single_step == 1) return true;
+        return c->Nh <= TRM_SINGLE_STEP_PROGRAM_MAX_COLUMNS;
+    }
+    // how many steps ONE launch of trm_step covers for this context: 1 unless the resident multi-step program applies
+    static bool program_applies(const trm_ctx* c) {
+        const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && P::levels_per_lane(c) > 0;
+        return fused && !P::generic_bcs(c) && !P::coupled(c) && c->veg_mode != TRM_VEGETATION_STANDALONE &&
+               ((c->Nz <= 64 && P::series_fit_program(c)) || (P::levels_per_lane(c) == 2 && !c->params.seb && c->series.empty()));
+    }
+    // The plan of ONE fused launch of program `prog` (PROG_*) over the columns currently addressed, from the context and the two facts only Ops::step
+    // knows: the launch is not its call's last (it may go interior); the one before it was interior (this one must derive psi at entry).
+    static StepPlan plan_step(const trm_ctx* c, int prog, bool not_last, bool behind_interior) {
+        StepPlan s;
+        const bool rich = P::richards(c), in_launch = prog != PROG_MULTI && surface_in_launch(c, prog == PROG_HEUN);
+        if (in_launch) s.route = ROUTE_SURFACE_IN_LAUNCH;
+        else if (prog == PROG_MULTI && averaging(c) && averages_in_launch(c)) s.route = ROUTE_ACCUM_IN_LAUNCH;
+        else if (P::levels_per_lane(c) > 1) s.route = ROUTE_LEVELS;
+        else if (prog == PROG_EULER && P::packed_path(c)) s.route = ROUTE_PACKED;
+        else if (prog != PROG_MULTI && P::generic_bcs(c)) s.route = ROUTE_GENERIC;
+        if (prog == PROG_EULER && (s.route == ROUTE_COLUMN || (in_launch && std::is_same<NF, double>::value))) {      // (the form: k_column / fp64 k_column_land)
+            s.derive = rich ? P::template derive_now<true>(c) : P::template derive_now<false>(c);
+            s.sig = (c->opt_bc_signature && P::hyd(c) != HYD_GENERIC) ? bc_signature_of(c) : -1;
+            if (s.derive == DERIVE_T_LIQ) s.staged = rich ? P::template staged_now<true>(c) : P::template staged_now<false>(c);
+            if (s.derive == DERIVE_T_LIQ) s.scalar_in = rich ? P::template scalar_inputs_now<true>(c) : P::template scalar_inputs_now<false>(c);
+            const bool has_instance = s.sig == 0 || s.sig == BCSIG_T_TOP || s.sig == (BCSIG_T_TOP | BCSIG_FU_BOT) || (rich && (s.sig == BCSIG_LAND || s.sig == (BCSIG_T_TOP | BCSIG_FS_TOP)));
+            P::io_paths(!has_instance || s.sig == BCSIG_LAND, s.staged, s.scalar_in);
+            s.derives_unread = s.derive == DERIVE_T_LIQ && c->part < 0;
+            s.store_closure = defer_closure_now(c, s.derives_unread) ? 0 : 1;
+            s.psi_step = !in_launch && rich;
+        }
+        // behind an interior launch the launch must derive the pressure head; it goes interior itself if it is not the call's last and defers
+        s.check_entry = behind_interior ? 1 : 0;
+        if (prog == PROG_EULER && (behind_interior || not_last)) {
+            const bool capable = !in_launch && interior_capable(c);
+            if (capable && not_last && !s.store_closure) s.psi_form = PSI_INTERIOR;
+            else if (behind_interior && capable) s.psi_form = PSI_LAST;
+            else if (behind_interior) s.refusal = "trm_step: the launch behind an interior launch cannot derive the pressure head";
+        }
+        return s;
+    }
 };
 
 }  // namespace trmh

@@ -4,14 +4,14 @@
 
 namespace trmh {
 
-template <class NF, bool RICH, int H, int LPC, int PROG> static int launch_column(trm_ctx* c, double dt, int finalize, int nsteps) {
+template <class NF, bool RICH, int H, int LPC, int PROG> static int launch_column(trm_ctx* c, const StepPlan& plan, double dt, int finalize, int nsteps) {
     using P = Policy<NF>;
     const View<NF>& v = state_view<NF>(c);
     const DevParams<NF>& p = launch_args<NF>(c).p;
     ColumnArgs<NF> a = column_args<NF>(c, dt, finalize, nsteps, PROG);
     const dim3 grid = column_grid(c, LPC), block(TRM_STEP_BLOCK);
-    const int derive = P::template derive_now<RICH>(c);     // (for this kernel: DERIVE_NONE or DERIVE_T_LIQ)
-    if (PROG == PROG_EULER && derive == DERIVE_T_LIQ) take_deferral(c, a);      // (every instance below that derives)
+    const int derive = PROG == PROG_EULER ? plan.derive : P::template derive_now<RICH>(c);     // (ForwardEuler: the plan's instance; for this kernel DERIVE_NONE or DERIVE_T_LIQ)
+    if (PROG == PROG_EULER) a.store_closure = plan.store_closure;      // (0: a deriving instance alone)
     if (derive != DERIVE_NONE && derive != DERIVE_T_LIQ) return fail(c, TRM_EINVAL, "k_column: no instance for this derivation mode");
     int pid = 0;    // TRM_INFO_LAST_PROGRAM of the instance that is launched below
     if constexpr (PROG == PROG_MULTI) {
@@ -23,25 +23,20 @@ template <class NF, bool RICH, int H, int LPC, int PROG> static int launch_colum
         else hipLaunchKernelGGL((k_column<NF, RICH, H, LPC, DERIVE_NONE, PROG_MULTI, false, false>), grid, block, 0, c->stream, v, p, a);
     } else if constexpr (PROG == PROG_EULER) {
         // the context's boundary kinds as a signature; the instantiated ones take the program with the kinds compiled in (fp64; with
-        // the derivation of T / liq or without it)
-        const int sig = (c->opt_bc_signature && H != HYD_GENERIC) ? bc_signature_of(c) : -1;
-        int staged = derive == DERIVE_T_LIQ ? P::template staged_now<RICH>(c) : 0, scalar_in = derive == DERIVE_T_LIQ ? P::template scalar_inputs_now<RICH>(c) : 1;
-        const bool has_instance = sig == 0 || sig == BCSIG_T_TOP || sig == (BCSIG_T_TOP | BCSIG_FU_BOT) || (RICH && (sig == BCSIG_LAND || sig == (BCSIG_T_TOP | BCSIG_FS_TOP)));
-        P::io_paths(!has_instance || sig == BCSIG_LAND, staged, scalar_in);
-        if (RICH) c->launch_psi_step = true;      // (every instance below stores pressure_head / water_table as column_closure forms them -- or is an interior launch)
-        if (c->psi_request != PSI_STORED) {
-            // TRM_OPT_INTERIOR_STEPS (Ops::fused_launch): the instance that derives the pressure head at entry stands in for the signature
-            // instance this launch would otherwise be, and reports that instance's id
+        // the derivation of T / liq or without it); every instance below stores pressure_head / water_table as column_closure forms them, or is interior
+        const int sig = plan.sig, staged = plan.staged, scalar_in = plan.scalar_in;
+        if (plan.psi_form != PSI_STORED) {
+            // TRM_OPT_INTERIOR_STEPS: the instance that derives the pressure head at entry stands in for the signature instance this
+            // launch would otherwise be, and reports that instance's id
             if constexpr (std::is_same<NF, double>::value && RICH && H != HYD_GENERIC) {
                 if (derive != DERIVE_T_LIQ || !column_psi_supported(sig) || staged == scalar_in) return fail(c, TRM_EINVAL, "k_column_psi: no instance for this launch");
-                a.check_entry = c->psi_check_entry;
+                a.check_entry = plan.check_entry;
                 switch (sig) {
-                    case 0: ColumnPsiLaunch<0>::run(c, v, p, a, grid, block, LPC, c->psi_request, staged, scalar_in); break;
-                    case BCSIG_T_TOP: ColumnPsiLaunch<BCSIG_T_TOP>::run(c, v, p, a, grid, block, LPC, c->psi_request, staged, scalar_in); break;
-                    case BCSIG_T_TOP | BCSIG_FU_BOT: ColumnPsiLaunch<BCSIG_T_TOP | BCSIG_FU_BOT>::run(c, v, p, a, grid, block, LPC, c->psi_request, staged, scalar_in); break;
-                    default: ColumnPsiLaunch<BCSIG_T_TOP | BCSIG_FS_TOP>::run(c, v, p, a, grid, block, LPC, c->psi_request, staged, scalar_in); break;
+                    case 0: ColumnPsiLaunch<0>::run(c, v, p, a, grid, block, LPC, plan.psi_form, staged, scalar_in); break;
+                    case BCSIG_T_TOP: ColumnPsiLaunch<BCSIG_T_TOP>::run(c, v, p, a, grid, block, LPC, plan.psi_form, staged, scalar_in); break;
+                    case BCSIG_T_TOP | BCSIG_FU_BOT: ColumnPsiLaunch<BCSIG_T_TOP | BCSIG_FU_BOT>::run(c, v, p, a, grid, block, LPC, plan.psi_form, staged, scalar_in); break;
+                    default: ColumnPsiLaunch<BCSIG_T_TOP | BCSIG_FS_TOP>::run(c, v, p, a, grid, block, LPC, plan.psi_form, staged, scalar_in); break;
                 }
-                c->psi_launched = c->psi_request;
                 pid = program_id(TRM_PROGRAM_COLUMN_EULER, H, LPC, DERIVE_T_LIQ, staged, scalar_in, sig);
             } else return fail(c, TRM_EINVAL, "k_column_psi: no instance for this launch");
         }
@@ -74,10 +69,10 @@ template <class NF, bool RICH, int H, int LPC, int PROG> static int launch_colum
     return TRM_OK;
 }
 
-template <class NF, bool RICH, int PROG> int ColumnLaunch<NF, RICH, PROG>::run(trm_ctx* c, double dt, int finalize, int nsteps) {
+template <class NF, bool RICH, int PROG> int ColumnLaunch<NF, RICH, PROG>::run(trm_ctx* c, const StepPlan& plan, double dt, int finalize, int nsteps) {
     int rc = TRM_OK;
     const bool deep = c->Nz > 32;
-    TRM_BY_HYD(c, rc = deep ? (launch_column<NF, RICH, H, 64, PROG>(c, dt, finalize, nsteps)) : (launch_column<NF, RICH, H, 32, PROG>(c, dt, finalize, nsteps)));
+    TRM_BY_HYD(c, rc = deep ? (launch_column<NF, RICH, H, 64, PROG>(c, plan, dt, finalize, nsteps)) : (launch_column<NF, RICH, H, 32, PROG>(c, plan, dt, finalize, nsteps)));
     return rc;
 }
 

@@ -5,9 +5,8 @@
 
 namespace trmh {
 
-template <int H, int LPC> static int launch_column_land(trm_ctx* c, double dt, int finalize, bool heun) {
+template <int H, int LPC> static int launch_column_land(trm_ctx* c, const StepPlan& plan, double dt, int finalize, bool heun) {
     using NF = double;
-    using P = Policy<NF>;
     const LaunchArgs<NF>& la = launch_args<NF>(c);
     const View<NF>& v = la.state;
     FrontArgs fa;
@@ -22,10 +21,8 @@ template <int H, int LPC> static int launch_column_land(trm_ctx* c, double dt, i
         c->last_program = program_id(TRM_PROGRAM_COLUMN_LAND, H, LPC, DERIVE_NONE, 0, 1, BCSIG_LAND) | (PROG_HEUN << 25);
         return TRM_OK;
     }
-    const int derive = P::derive_now<true>(c);
-    if (derive == DERIVE_T_LIQ) take_deferral(c, a);
-    int staged = derive == DERIVE_T_LIQ ? P::staged_now<true>(c) : 0, scalar_in = derive == DERIVE_T_LIQ ? P::scalar_inputs_now<true>(c) : 1;
-    P::io_paths(true, staged, scalar_in);
+    const int derive = plan.derive, staged = plan.staged, scalar_in = plan.scalar_in;      // (StepPolicy::plan_step)
+    a.store_closure = plan.store_closure;      // (0: a deriving instance alone)
 #define TRM_LAND1(D, ST, SC) hipLaunchKernelGGL((k_column_land<NF, true, H, LPC, D, ST, SC>), grid, block, 0, c->stream, v, la.p, a, fa)
     if (derive == DERIVE_NONE) TRM_LAND1(DERIVE_NONE, false, true);
     else if (derive != DERIVE_T_LIQ) return fail(c, TRM_EINVAL, "k_column_land: no instance for this derivation mode");
@@ -38,8 +35,8 @@ template <int H, int LPC> static int launch_column_land(trm_ctx* c, double dt, i
     return TRM_OK;
 }
 
-template <int H> int FrontLaunch::run_hyd(trm_ctx* c, double dt, int finalize, bool heun) {
-    return c->Nz > 32 ? launch_column_land<H, 64>(c, dt, finalize, heun) : launch_column_land<H, 32>(c, dt, finalize, heun);
+template <int H> int FrontLaunch::run_hyd(trm_ctx* c, const StepPlan& plan, double dt, int finalize, bool heun) {
+    return c->Nz > 32 ? launch_column_land<H, 64>(c, plan, dt, finalize, heun) : launch_column_land<H, 32>(c, plan, dt, finalize, heun);
 }
 
 }  // namespace trmh
