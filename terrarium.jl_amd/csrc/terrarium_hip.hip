@@ -1,7 +1,8 @@
 // terrarium_hip.hip -- context management, the step sequences and the C ABI of libterrarium_hip.so
-// (include/terrarium_hip.h).  gfx950 only; no CPU fallback.  The kernel instantiations live in the trm_launch_*.hip files
-// (trm_host.hpp declares their launchers); this file launches only the small data-movement kernels (transposition, ring
-// scatter / gather, reductions).
+// (include/terrarium_hip.h) but its derivative entry points, which trm_derivative_api.hip holds.  gfx950 only; no CPU fallback.  The
+// kernel instantiations live in the trm_launch_*.hip files (trm_host.hpp declares their launchers); this file launches only the small
+// data-movement kernels (transposition, ring scatter / gather, reductions), and defines the host pieces both files use (finish, tick,
+// bc_changed / state_changed, flush_closure, io_buffer, upload_3d / download_3d).
 #include "trm_host.hpp"
 
 #include <dlfcn.h>
@@ -287,35 +288,6 @@ template <class NF> const LaunchArgs<NF>& launch_args(trm_ctx* c) {
 template const LaunchArgs<double>& launch_args<double>(trm_ctx*);
 template const LaunchArgs<float>& launch_args<float>(trm_ctx*);
 
-// The derivative launchers: each ride's instantiation lives in a translation unit of its own (trm_host.hpp, trm_launch_derivative.inl)
-int TangentLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride) {
-    switch (ride) {
-        case RIDE_BC: return tangent_step<RIDE_BC>(c, dt, nsteps);
-        case RIDE_PARAM: return tangent_step<RIDE_PARAM>(c, dt, nsteps);
-        case RIDE_SERIES: return tangent_step<RIDE_SERIES>(c, dt, nsteps);
-        case RIDE_PARAM_SERIES: return tangent_step<RIDE_PARAM_SERIES>(c, dt, nsteps);
-        default: return tangent_step<RIDE_NONE>(c, dt, nsteps);
-    }
-}
-int TangentLaunch::closure(trm_ctx* c, Ride ride) { return ride == RIDE_PARAM ? tangent_closure<RIDE_PARAM>(c) : tangent_closure<RIDE_NONE>(c); }
-template <bool CKPT> static int backward_by_ride(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) {
-    switch (ride) {
-        case RIDE_BC: return adjoint_backward<CKPT, RIDE_BC>(c, dt, nsteps, slot, fold);
-        case RIDE_PARAM: return adjoint_backward<CKPT, RIDE_PARAM>(c, dt, nsteps, slot, fold);
-        case RIDE_SERIES: return adjoint_backward<CKPT, RIDE_SERIES>(c, dt, nsteps, slot, fold);
-        case RIDE_PARAM_SERIES: return adjoint_backward<CKPT, RIDE_PARAM_SERIES>(c, dt, nsteps, slot, fold);
-        default: return adjoint_backward<CKPT, RIDE_NONE>(c, dt, nsteps, slot, fold);
-    }
-}
-int AdjointLaunch::record(trm_ctx* c, double dt, int nsteps, int slot, bool series) {
-    return series ? adjoint_record<false, true>(c, dt, nsteps, slot, 0, 1) : adjoint_record<false, false>(c, dt, nsteps, slot, 0, 1);
-}
-int AdjointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) { return backward_by_ride<false>(c, dt, nsteps, slot, fold, ride); }
-int CheckpointLaunch::record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every, bool series) {
-    return series ? adjoint_record<true, true>(c, dt, nsteps, slot, first, every) : adjoint_record<true, false>(c, dt, nsteps, slot, first, every);
-}
-int CheckpointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) { return backward_by_ride<true>(c, dt, nsteps, slot, fold, ride); }
-
 // Time interpolation indices of a series at time t -- Oceananigans' FieldTimeSeries indexing (Linear / Clamp /
 // Cyclical), restated; that package is not part of the reference tree (parity unpinned).
 // Returns 0-based nodes n1, n2 and the fraction f: value = v[n2] * f + v[n1] * (1 - f); n1 == n2 means "copy".
@@ -374,6 +346,47 @@ void series_time_indices(const std::vector<double>& times, int indexing, double 
         else if (t <= times[0]) { n1 = n2 = 0; f = 0.0; }
     }
 }
+
+// ---- shared with trm_derivative_api.hip (declared in trm_host.hpp) ------------------------------------------------------------------
+// The state has changed behind the derivatives' backs: an open tangent needs a new seed, a tape that holds steps no longer leads to the
+// stored state.  bc_changed: a boundary condition has (the backward sweep reads the values the context holds when it runs).
+void bc_changed(trm_ctx* c) {
+    if (!c->tape_dt.empty() || !c->tape_segs.empty()) c->adj_stale = true;
+}
+void state_changed(trm_ctx* c) {
+    c->tan_stale = true;
+    bc_changed(c);
+}
+// tick! per step: the same sequence of sums as per-step calls (restarts compare the clock bit for bit)
+void tick(trm_ctx* c, double dt, int nsteps) {
+    for (int j = 0; j < nsteps; ++j) c->time += dt;
+    c->iteration += nsteps;
+}
+// TRM_OPT_DEFER_CLOSURE_STORES: temperature and liquid_water_fraction of the state into their arrays (one small launch on the
+// context stream) if the last step launches left them unstored; nothing otherwise.  Every reader and writer of field memory other than
+// a deriving per-step launch comes through here first: the ABI entries (TRM_ENTER / TRM_ENTER_HEUN) and Ops::fused_launch.
+int flush_closure(trm_ctx* c) {
+    if (!c->closure_deferred) return TRM_OK;
+    if (int rc = c->precision == TRM_F64 ? MaterializeLaunch<double>::run(c) : MaterializeLaunch<float>::run(c)) return rc;
+    c->closure_deferred = false;
+    c->materializations += 1;
+    return TRM_OK;
+}
+int finish(trm_ctx* c, int rc) {
+    if (rc) return rc;
+    if (!c->opt_async) TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int io_buffer(trm_ctx* c, size_t bytes) {
+    if (bytes > c->io_cap) {
+        if (c->d_io) TRM_HIP(c, hipFree(c->d_io));
+        c->d_io = nullptr;
+        c->io_cap = 0;
+        TRM_HIP(c, hipMalloc(&c->d_io, bytes));
+        c->io_cap = bytes;
+    }
+    return TRM_OK;
+}
 }  // namespace trmh
 
 namespace {
@@ -387,33 +400,6 @@ bool averageable(const trm_ctx* c, int field) {
     const int s = accum_slot(field);
     if (s < 0) return false;
     return s < ACC_TS || c->params.seb != 0;
-}
-
-// tick! per step: the same sequence of sums as per-step calls (restarts compare the clock bit for bit)
-// The state has changed behind the derivatives' backs: an open tangent needs a new seed, a tape that holds steps no longer leads to the
-// stored state.  bc_changed: a boundary condition has (the backward sweep reads the values the context holds when it runs).
-void bc_changed(trm_ctx* c) {
-    if (!c->tape_dt.empty() || !c->tape_segs.empty()) c->adj_stale = true;
-}
-void state_changed(trm_ctx* c) {
-    c->tan_stale = true;
-    bc_changed(c);
-}
-
-void tick(trm_ctx* c, double dt, int nsteps) {
-    for (int j = 0; j < nsteps; ++j) c->time += dt;
-    c->iteration += nsteps;
-}
-
-// TRM_OPT_DEFER_CLOSURE_STORES: temperature and liquid_water_fraction of the state into their arrays (one small launch on the
-// context stream) if the last step launches left them unstored; nothing otherwise.  Every reader and writer of field memory other than
-// a deriving per-step launch comes through here first: the ABI entries (TRM_ENTER / TRM_ENTER_HEUN) and Ops::fused_launch.
-int flush_closure(trm_ctx* c) {
-    if (!c->closure_deferred) return TRM_OK;
-    if (int rc = c->precision == TRM_F64 ? MaterializeLaunch<double>::run(c) : MaterializeLaunch<float>::run(c)) return rc;
-    c->closure_deferred = false;
-    c->materializations += 1;
-    return TRM_OK;
 }
 
 // Heun's path (Ops::heun_path).  One launch with both stages on the column in registers (Ops::fused_launch<PROG_HEUN>), by
@@ -466,75 +452,6 @@ template <class NF> struct Ops : StepPolicy<NF>, Unfused<NF>, Veg<NF> {
         for (int k = 0; k < c->Nz; ++k)
             for (long i = 0; i < c->Nh; ++i) host[(size_t)k * c->Nh + i] = R[k] / total;
         return upload_impl<NF>(c, TRM_FIELD_ROOT_FRACTION, host.data());
-    }
-    // slot table + [nsteps][nseries] rows for a multi-step launch that starts at the context clock.  `keep`: the rows are appended there
-    // as well (trm_step_record's tape); `kept`: the rows are these, formed by an earlier call, and not the clock's (trm_adjoint_backward)
-    static int upload_series_rows(trm_ctx* c, double dt, int nsteps, std::vector<SeriesRow>* keep = nullptr, const SeriesRow* kept = nullptr) {
-        const int ns = (int)c->series.size();
-        const size_t nrows = (size_t)nsteps * ns, need = sizeof(SeriesTable<NF>) + nrows * sizeof(SeriesRow);
-        trm_ctx::RowStage& st = c->row_stage[c->row_stage_next];
-        c->row_stage_next = (c->row_stage_next + 1) % 4;
-        if (st.pending) {
-            TRM_HIP(c, hipEventSynchronize(st.done));
-            st.pending = false;
-        }
-        if (!st.done) TRM_HIP(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-        if (need > st.cap) {
-            if (st.h) TRM_HIP(c, hipHostFree(st.h));
-            st.h = nullptr;
-            st.cap = 0;
-            TRM_HIP(c, hipHostMalloc(&st.h, need, hipHostMallocDefault));
-            st.cap = need;
-        }
-        SeriesTable<NF>& tb = *(SeriesTable<NF>*)st.h;
-        SeriesRow* rows = (SeriesRow*)((char*)st.h + sizeof(SeriesTable<NF>));
-        std::memset(&tb, 0, sizeof(tb));
-        for (int j = 0; j < ns; ++j) {
-            auto& sr = c->series[j];
-            const int slot = P::series_slot(c, sr);
-            tb.base[slot] = (const NF*)sr.d_values;
-            tb.row_of[slot] = j;
-            tb.raster[slot] = sr.indexing == TRM_TIME_RASTER ? 1 : 0;
-            if (sr.is_bc) {
-                void*& dst = c->bc_value[sr.var][sr.side];
-                if (!dst) {
-                    TRM_HIP(c, hipMalloc(&dst, (size_t)c->Nh * sizeof(NF)));
-                    c->args_valid = false;
-                }
-                tb.dst[slot] = (NF*)dst;
-            } else {
-                tb.dst[slot] = (NF*)c->state.f[sr.field];
-            }
-            if (kept) continue;
-            double t = c->time;
-            if (sr.trimmed && t < sr.trimmed_before)
-                return fail(c, TRM_EINVAL, "a windowed time series was asked for a time before the levels it still holds (trm_series_trim_before released them)");
-            for (int s = 0; s < nsteps; ++s) {
-                int n1, n2;
-                double f, g;
-                series_time_indices(sr.times, sr.indexing, t, n1, n2, f, g);
-                if (int rw = U::await_levels(c, sr, std::max(n1, n2))) return rw;
-                rows[(size_t)s * ns + j] = SeriesRow{(long long)(sr.slot(n1) * (size_t)c->Nh), (long long)(sr.slot(n2) * (size_t)c->Nh), f, g};
-                t += dt;
-            }
-        }
-        if (kept && nrows > 0) std::memcpy(rows, kept, nrows * sizeof(SeriesRow));
-        if (keep) keep->insert(keep->end(), rows, rows + nrows);
-        if (!c->d_series_table) TRM_HIP(c, hipMalloc(&c->d_series_table, sizeof(SeriesTable<double>)));
-        if (nrows * sizeof(SeriesRow) > c->series_rows_cap) {
-            if (c->d_series_rows) TRM_HIP(c, hipFree(c->d_series_rows));   // (waits for the launches that read it)
-            c->d_series_rows = nullptr;
-            c->series_rows_cap = 0;
-            TRM_HIP(c, hipMalloc(&c->d_series_rows, nrows * sizeof(SeriesRow)));
-            c->series_rows_cap = nrows * sizeof(SeriesRow);
-        }
-        // in stream order behind the previous launch (which reads the device copies) and in front of the next one; the host
-        // does not wait
-        TRM_HIP(c, hipMemcpyAsync(c->d_series_table, &tb, sizeof(tb), hipMemcpyHostToDevice, c->stream));
-        if (nrows > 0) TRM_HIP(c, hipMemcpyAsync(c->d_series_rows, rows, nrows * sizeof(SeriesRow), hipMemcpyHostToDevice, c->stream));
-        TRM_HIP(c, hipEventRecord(st.done, c->stream));
-        st.pending = true;
-        return TRM_OK;
     }
     static int unfused_step(trm_ctx* c, double dt, int finalize) {
         c->last_program = TRM_PROGRAM_UNFUSED;
@@ -616,17 +533,11 @@ template <class NF> struct Ops : StepPolicy<NF>, Unfused<NF>, Veg<NF> {
         }
         return TRM_OK;
     }
-    // TRM_OPT_STEPS_PER_LAUNCH = 0: run!'s loop (model_integrator.jl:72-88) is exactly trm_step(ctx, dt, nsteps, 0), so the
-    // resident-column program is what a plain call gets whenever it is legal.  Measured: 2.0-4.6 us per step
-    // against 6.8-12 on N72 / 7 119-column shards, 12.3 against 24-26 at N145 -- and for fp32 contexts whose per-step path is
-    // the packed kernel as well: C5 371 against 447-451 us, C5-VG 479 against 489, a 12 696-column fp32 shard 7.3 against 13.3
-    // (r3: the rule used to keep the packed kernel there).
-    static int auto_steps_per_launch(trm_ctx*) { return 50; }
     // ---- the fused step of the state: one sequence for every program -------------------------------------------------------
     // update_inputs! of the state; Heun: of the stage as well, at its clock t + dt (heun.jl:52); the multi-step program with time
     // series: the rows it interpolates itself instead
     template <int PROG> static int fused_prologue(trm_ctx* c, double dt, int nsteps) {
-        if (PROG == PROG_MULTI && !c->series.empty()) return upload_series_rows(c, dt, nsteps);
+        if (PROG == PROG_MULTI && !c->series.empty()) return U::upload_series_rows(c, dt, nsteps);
         int rc = U::update_inputs(c, c->state, c->time);
         if (!rc && PROG == PROG_HEUN) rc = U::update_inputs(c, c->stage, c->time + dt);
         return rc;
@@ -724,7 +635,7 @@ template <class NF> struct Ops : StepPolicy<NF>, Unfused<NF>, Veg<NF> {
         return fused_epilogue(c, rc, dt, finalize);
     }
     static int steps_per_launch_now(trm_ctx* c) {
-        return !program_applies(c) ? 1 : (c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : auto_steps_per_launch(c));
+        return !program_applies(c) ? 1 : (c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : P::auto_steps_per_launch(c));
     }
     static int step(trm_ctx* c, double dt, int nsteps, int finalize) {
         if (c->veg_mode == TRM_VEGETATION_STANDALONE) return veg_step(c, dt, nsteps, finalize, false);
@@ -927,12 +838,6 @@ template <class NF> struct Ops : StepPolicy<NF>, Unfused<NF>, Veg<NF> {
 };
 
 #define DISPATCH(c, expr) ((c)->precision == TRM_F64 ? Ops<double>::expr : Ops<float>::expr)
-
-int finish(trm_ctx* c, int rc) {
-    if (rc) return rc;
-    if (!c->opt_async) TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
 
 // The zero fills run on the CONTEXT stream and are waited for.  A plain hipMemset goes to the null stream, which the context's
 // non-blocking stream does not synchronise with: under load (two processes time-slicing one device) a fill could land AFTER a
@@ -1200,53 +1105,57 @@ template <class NF> __global__ void k_gather_ring(const NF* __restrict__ full, N
     const size_t r = blockIdx.y;
     rows[r * (size_t)Nh + i] = full[r * (size_t)P + idx[i]];
 }
-int io_buffer(trm_ctx* c, size_t bytes) {
-    if (bytes > c->io_cap) {
-        if (c->d_io) TRM_HIP(c, hipFree(c->d_io));
-        c->d_io = nullptr;
-        c->io_cap = 0;
-        TRM_HIP(c, hipMalloc(&c->d_io, bytes));
-        c->io_cap = bytes;
-    }
+}  // namespace
+
+namespace trmh {
+// Host data [Nz][Nh] to / from a 3-D device buffer [Nh][Nzp] through d_io, synchronised.  `top`: the [Nh] buffer of a Face field's top
+// face, which travels as row Nz of the host array (null: Nz rows).
+template <class NF> int upload_3d(trm_ctx* c, const NF* host, NF* dev, NF* top) {
+    const long Nh = c->Nh;
+    const size_t bytes = (size_t)(c->Nz + (top ? 1 : 0)) * Nh * sizeof(NF);
+    if (int rc = io_buffer(c, bytes)) return rc;
+    TRM_HIP(c, hipMemcpyAsync(c->d_io, host, bytes, hipMemcpyHostToDevice, c->stream));
+    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
+    hipLaunchKernelGGL((k_transpose<NF, true>), grid, dim3(256), 0, c->stream, (const NF*)c->d_io, dev, Nh, c->Nz, c->Nzp);
+    TRM_HIP(c, hipGetLastError());
+    if (top) TRM_HIP(c, hipMemcpyAsync(top, (const NF*)c->d_io + (size_t)c->Nz * Nh, (size_t)Nh * sizeof(NF), hipMemcpyDeviceToDevice, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
 }
-template <class NF> int upload_impl(trm_ctx* c, int field, const NF* host) {
-    const long Nh = c->Nh, rows = field_rows(c, field);
-    if (!is_3d(field)) {
-        TRM_HIP(c, hipMemcpyAsync(c->state.f[field], host, (size_t)Nh * sizeof(NF), hipMemcpyHostToDevice, c->stream));
-        TRM_HIP(c, hipStreamSynchronize(c->stream));
-        return TRM_OK;
-    }
-    int rc = io_buffer(c, (size_t)rows * Nh * sizeof(NF));
-    if (rc) return rc;
-    TRM_HIP(c, hipMemcpyAsync(c->d_io, host, (size_t)rows * Nh * sizeof(NF), hipMemcpyHostToDevice, c->stream));
+template <class NF> int download_3d(trm_ctx* c, const NF* dev, NF* host, const NF* top) {
+    const long Nh = c->Nh;
+    const size_t bytes = (size_t)(c->Nz + (top ? 1 : 0)) * Nh * sizeof(NF);
+    if (int rc = io_buffer(c, bytes)) return rc;
     dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
-    hipLaunchKernelGGL((k_transpose<NF, true>), grid, dim3(256), 0, c->stream, (const NF*)c->d_io, (NF*)c->state.f[field], Nh, c->Nz, c->Nzp);
+    hipLaunchKernelGGL((k_transpose<NF, false>), grid, dim3(256), 0, c->stream, dev, (NF*)c->d_io, Nh, c->Nz, c->Nzp);
     TRM_HIP(c, hipGetLastError());
-    if (rows == c->Nz + 1)  // Face field: the top face lives in its own [Nh] buffer
-        TRM_HIP(c, hipMemcpyAsync(c->state.kf_top, (const NF*)c->d_io + (size_t)c->Nz * Nh, (size_t)Nh * sizeof(NF), hipMemcpyDeviceToDevice, c->stream));
+    if (top) TRM_HIP(c, hipMemcpyAsync((NF*)c->d_io + (size_t)c->Nz * Nh, top, (size_t)Nh * sizeof(NF), hipMemcpyDeviceToDevice, c->stream));
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_io, bytes, hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+template int upload_3d<double>(trm_ctx*, const double*, double*, double*);
+template int upload_3d<float>(trm_ctx*, const float*, float*, float*);
+template int download_3d<double>(trm_ctx*, const double*, double*, const double*);
+template int download_3d<float>(trm_ctx*, const float*, float*, const float*);
+}  // namespace trmh
+
+namespace {
+
+template <class NF> int upload_impl(trm_ctx* c, int field, const NF* host) {
+    if (is_3d(field))   // (Face field: the top face lives in its own [Nh] buffer)
+        return upload_3d<NF>(c, host, (NF*)c->state.f[field], field_rows(c, field) == c->Nz + 1 ? (NF*)c->state.kf_top : nullptr);
+    TRM_HIP(c, hipMemcpyAsync(c->state.f[field], host, (size_t)c->Nh * sizeof(NF), hipMemcpyHostToDevice, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
 }
 template <class NF> int download_impl(trm_ctx* c, int field, NF* host) {
-    const long Nh = c->Nh, rows = field_rows(c, field);
-    if (!is_3d(field)) {
-        TRM_HIP(c, hipMemcpyAsync(host, c->state.f[field], (size_t)Nh * sizeof(NF), hipMemcpyDeviceToHost, c->stream));
-        TRM_HIP(c, hipStreamSynchronize(c->stream));
-        return TRM_OK;
-    }
-    int rc = io_buffer(c, (size_t)rows * Nh * sizeof(NF));
-    if (rc) return rc;
-    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
-    hipLaunchKernelGGL((k_transpose<NF, false>), grid, dim3(256), 0, c->stream, (const NF*)c->state.f[field], (NF*)c->d_io, Nh, c->Nz, c->Nzp);
-    TRM_HIP(c, hipGetLastError());
-    if (rows == c->Nz + 1)
-        TRM_HIP(c, hipMemcpyAsync((NF*)c->d_io + (size_t)c->Nz * Nh, c->state.kf_top, (size_t)Nh * sizeof(NF), hipMemcpyDeviceToDevice, c->stream));
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_io, (size_t)rows * Nh * sizeof(NF), hipMemcpyDeviceToHost, c->stream));
+    if (is_3d(field))
+        return download_3d<NF>(c, (const NF*)c->state.f[field], host, field_rows(c, field) == c->Nz + 1 ? (const NF*)c->state.kf_top : nullptr);
+    TRM_HIP(c, hipMemcpyAsync(host, c->state.f[field], (size_t)c->Nh * sizeof(NF), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
 }
-
 
 // rows [row0, row0 + nrows) of a field into the staging buffer d_io as [nrows][Nh] (on the context stream, not synchronised)
 template <class NF> int stage_rows(trm_ctx* c, int field, int row0, int nrows) {
@@ -1390,24 +1299,6 @@ int comm_allreduce(trm_ctx* c, double* host, int n, ncclRedOp_t op) {
 // ======================================================================================================
 extern "C" {
 
-// TRM_ENTER: any entry point but the three of the two-call Heun step and the read-only ones.  A stage predicted by
-// trm_heun_predict belongs to the state and clock it was predicted from: whatever else runs in between drops it, and a later
-// trm_heun_correct fails ("call trm_heun_predict first") instead of averaging tendencies of a stage that describes another state.
-// Both materialise T / liq first if the last step launches left them unstored (flush_closure, TRM_OPT_DEFER_CLOSURE_STORES): whatever
-// the entry point reads or writes, it finds the arrays an eagerly storing context has.  TRM_ENTER_KEEP: the entry points that neither
-// read nor write field memory, or order the accesses themselves -- trm_step / trm_step_timed (Ops::fused_launch), trm_restore_state
-// (overwrites the fields), trm_synchronize, trm_status; the getters that take no macro at all belong here too.
-#define TRM_ENTER_KEEP(c)                                    \
-    if (!(c)) return TRM_EINVAL;                             \
-    TRM_HIP(c, hipSetDevice((c)->device));
-#define TRM_ENTER_HEUN(c)                                    \
-    TRM_ENTER_KEEP(c)                                        \
-    if ((c)->closure_deferred)                               \
-        if (int rc_flush__ = flush_closure(c)) return rc_flush__;
-#define TRM_ENTER(c)                                         \
-    TRM_ENTER_HEUN(c)                                        \
-    (c)->heun_pending = false;
-
 int trm_abi_version(void) { return TRM_ABI_VERSION; }
 
 int trm_default_params(trm_params* p) {
@@ -1548,22 +1439,8 @@ int trm_destroy(trm_ctx* c) {
         if (a.d_sum) (void)hipFree(a.d_sum);
     for (double* q : c->d_acc_partial)
         if (q) (void)hipFree(q);
-    for (double* q : c->d_tan)
-        if (q) (void)hipFree(q);
-    for (double* q : c->d_adj)
-        if (q) (void)hipFree(q);
-    for (double* q : c->d_tan_bc)
-        if (q) (void)hipFree(q);
-    for (double* q : c->d_adj_bc)
-        if (q) (void)hipFree(q);
-    for (double* q : c->d_tan_bcs)
-        if (q) (void)hipFree(q);
-    for (double* q : c->d_adj_bcs)
-        if (q) (void)hipFree(q);
-    for (double* q : c->d_adj_param)
-        if (q) (void)hipFree(q);
-    if (c->d_adj_param_out) (void)hipFree(c->d_adj_param_out);
-    if (c->d_tape) (void)hipFree(c->d_tape);
+    release_tangent(c);
+    release_adjoint(c);
 
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->args && c->args_free) c->args_free(c->args);
@@ -2344,720 +2221,6 @@ int trm_average_close(trm_ctx* c, int handle) {
     TRM_HIP(c, hipFree(a->d_sum));
     *a = trm_ctx::Average{};
     return TRM_OK;
-}
-
-// ---- forward-mode tangents of the heat-only step (trm_column_tangent.hpp) ---------------------------------------------------
-namespace {
-// what the tangent and adjoint programs cover: the heat-only fp64 SoilModel in columns of one level per lane
-const char* derivative_unsupported(const trm_ctx* c) {
-    if (c->precision != TRM_F64) return "fp64 contexts only";
-    if (c->params.flow == TRM_FLOW_RICHARDS) return "the heat-only SoilModel (NoFlow) only";
-    if (c->params.seb || c->veg_mode != TRM_VEGETATION_OFF) return "not the LandModel or vegetation";
-    if (c->Nz > 64) return "columns of at most 64 levels";
-    return nullptr;
-}
-// TRM_OPT_DERIVATIVE_SERIES: the series the derivative kernels evaluate themselves -- boundary series of kind Value on temperature or
-// Flux on internal energy, whole records, on the branch-free boundary kinds
-const char* derivative_series_unsupported(const trm_ctx* c) {
-    if (Policy<double>::generic_bcs(c))
-        return "no time series with the generic boundary kinds (a Gradient condition on temperature off the branch-free kinds: that step reads its boundary values from memory)";
-    for (const auto& sr : c->series) {
-        if (!sr.is_bc) return "no input (forcing) time series: boundary series only";
-        const int slot = Policy<double>::series_slot(c, sr);
-        if (slot < SLOT_T_BOT || slot > SLOT_FU_TOP)
-            return "a boundary series of kind Value on temperature or Flux on internal energy only (not of kind Gradient, not on another variable)";
-        if (sr.windowed || sr.trimmed || sr.head != 0 || (long)sr.times.size() != sr.cap)
-            return "no windowed or trimmed time series: the sweep needs every level the tape spans";
-    }
-    return nullptr;
-}
-// the series of a (boundary variable, side) pair, or null
-const trm_ctx::Series* bc_series_of(const trm_ctx* c, int bc_var, int side) {
-    for (const auto& sr : c->series)
-        if (sr.is_bc && sr.var == bc_var && sr.side == side) return &sr;
-    return nullptr;
-}
-// series the derivative launches of this context evaluate in-kernel (0: none attached)
-int derivative_series_count(const trm_ctx* c) { return (int)c->series.size(); }
-const char* kSeriesWithParams = "no thermal-parameter seeds or gradients together with a time series unless TRM_OPT_DERIVATIVE_SERIES_PARAMS is set";
-// parameters and series together are refused: a series the derivative kernels would evaluate, and the option that joins the two is off
-bool series_refuse_params(const trm_ctx* c) { return !c->series.empty() && !c->opt_derivative_series_params; }
-// ... and what a step needs besides: constant inputs, no accumulation, the temperature halos of the heat-only programs
-const char* derivative_step_unsupported(const trm_ctx* c) {
-    if (const char* why = derivative_unsupported(c)) return why;
-    if (!c->series.empty()) {
-        if (!c->opt_derivative_series) return "no time series may be attached";
-        if (const char* why = derivative_series_unsupported(c)) return why;
-    }
-    for (const auto& a : c->averages)
-        if (a.field >= 0) return "no time average may be open";
-    if (c->opt_vwc_field) return "no per-cell vwc_forcing field";
-    for (int side = 0; side < 2; ++side)
-        if (c->bc_kind[TRM_BCV_LIQUID_WATER_FRACTION][side] == TRM_BC_VALUE || c->bc_kind[TRM_BCV_LIQUID_WATER_FRACTION][side] == TRM_BC_GRADIENT)
-            return "no Value or Gradient condition on the liquid water fraction";
-    return nullptr;
-}
-// what rides along with a tangent step / a backward sweep: series first (with the thermal parameters where they are seeded / open:
-// TRM_OPT_DERIVATIVE_SERIES_PARAMS, the steps have refused them otherwise), then the thermal parameters, then the boundary values
-Ride tangent_ride(const trm_ctx* c, int nser) {
-    if (nser) return c->tan_param_seeded ? RIDE_PARAM_SERIES : RIDE_SERIES;
-    return c->tan_param_seeded ? RIDE_PARAM : c->tan_bc_seeded ? RIDE_BC : RIDE_NONE;
-}
-Ride backward_ride(const trm_ctx* c, int nser) {
-    if (nser) return c->d_adj_param_out ? RIDE_PARAM_SERIES : RIDE_SERIES;
-    return c->d_adj_param_out ? RIDE_PARAM : c->d_adj_bc[0] ? RIDE_BC : RIDE_NONE;
-}
-// trm_step_tangent and trm_step_record issue the launches of trm_step(ctx, dt, nsteps, 1) on the multi-step program: up to
-// TRM_OPT_STEPS_PER_LAUNCH steps each ...
-int derivative_steps_per_launch(trm_ctx* c) { return c->opt_steps_per_launch > 0 ? c->opt_steps_per_launch : Ops<double>::auto_steps_per_launch(c); }
-// ... and leave what a finalizing step leaves
-int derivative_steps_done(trm_ctx* c) {
-    c->closure_consistent = true;
-    c->psi_consistent = false;
-    c->tend_valid = true;      // (every launch stores the tendency of its last step, as a finalizing launch)
-    c->top_valid = false;
-    return finish(c, TRM_OK);
-}
-int tangent_args_ok(trm_ctx* c, int which, const void* ptr, const char* who) {
-    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no tangent is open (trm_tangent_open)");
-    if (which < 0 || which > TRM_TANGENT_LIQUID_WATER_FRACTION || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument");
-    return TRM_OK;
-}
-// the slot of a (boundary variable, side) pair in d_tan_bc / d_adj_bc, -1 for a pair the heat-only step reads no value of
-int bc_pair_index(int bc_var, int side) {
-    if (side != TRM_BOTTOM && side != TRM_TOP) return -1;
-    if (bc_var == TRM_BCV_TEMPERATURE) return side == TRM_TOP ? 1 : 0;
-    if (bc_var == TRM_BCV_INTERNAL_ENERGY) return side == TRM_TOP ? 3 : 2;
-    return -1;
-}
-// the square roots of the five conductivities have no derivative at 0
-const char* thermal_params_not_differentiable(const trm_ctx* c) {
-    const trm_params& q = c->params;
-    if (!(q.k_water > 0.0 && q.k_ice > 0.0 && q.k_air > 0.0 && q.k_mineral > 0.0 && q.k_organic > 0.0))
-        return "every thermal conductivity must be > 0 (sqrt has no derivative at 0)";
-    return nullptr;
-}
-const char* kStaleTangent = ": the state has changed since the tangent was seeded: trm_tangent_upload a new dU first";
-}  // namespace
-
-int trm_tangent_open(trm_ctx* c) {
-    TRM_ENTER_HEUN(c);
-    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_open: ") + why);
-    const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double);
-    for (double*& q : c->d_tan) {
-        if (!q) TRM_HIP(c, hipMalloc((void**)&q, bytes));
-        TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
-    }
-    for (double* q : c->d_tan_bc)
-        if (q) TRM_HIP(c, hipMemsetAsync(q, 0, (size_t)c->Nh * sizeof(double), c->stream));
-    for (int s = 0; s < 4; ++s)
-        if (c->d_tan_bcs[s]) TRM_HIP(c, hipMemsetAsync(c->d_tan_bcs[s], 0, (size_t)c->tan_bcs_nt[s] * (size_t)c->Nh * sizeof(double), c->stream));
-    c->tan_bc_seeded = false;
-    std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
-    c->tan_param_seeded = false;
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    c->tan_stale = false;      // (a zero seed: zero tangents)
-    return TRM_OK;
-}
-int trm_tangent_close(trm_ctx* c) {
-    TRM_ENTER_HEUN(c);
-    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_close: no tangent is open");
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    for (double*& q : c->d_tan) {
-        TRM_HIP(c, hipFree(q));
-        q = nullptr;
-    }
-    for (double*& q : c->d_tan_bc) {
-        if (q) TRM_HIP(c, hipFree(q));
-        q = nullptr;
-    }
-    for (double*& q : c->d_tan_bcs) {
-        if (q) TRM_HIP(c, hipFree(q));
-        q = nullptr;
-    }
-    std::fill(std::begin(c->tan_bcs_nt), std::end(c->tan_bcs_nt), 0L);
-    c->tan_bc_seeded = false;
-    std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
-    c->tan_param_seeded = false;
-    c->tan_stale = false;
-    return TRM_OK;
-}
-namespace {
-// the four boundary seed arrays, zeroed where this call allocates them
-int alloc_tangent_bc_seeds(trm_ctx* c, const char* who) {
-    const size_t bytes = (size_t)c->Nh * sizeof(double);
-    for (double*& q : c->d_tan_bc)
-        if (!q) {
-            if (hipMalloc((void**)&q, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                q = nullptr;
-                return fail(c, TRM_ENOMEM, std::string(who) + ": the seed arrays do not fit");
-            }
-            TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
-        }
-    return TRM_OK;
-}
-// a [nt][Nh] array shaped like the series of pair `slot`, zeroed where this call allocates it (a series of another length replaces it)
-int alloc_series_shaped(trm_ctx* c, double*& q, long& have_nt, long nt, const char* who) {
-    if (q && have_nt == nt) return TRM_OK;
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    if (q) (void)hipFree(q);
-    q = nullptr;
-    have_nt = 0;
-    const size_t bytes = (size_t)nt * (size_t)c->Nh * sizeof(double);
-    if (hipMalloc((void**)&q, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        q = nullptr;
-        return fail(c, TRM_ENOMEM, std::string(who) + ": an array of the series' shape does not fit");
-    }
-    have_nt = nt;
-    TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
-    return TRM_OK;
-}
-// the arguments of the three per-node calls: the pair's slot and its series
-int bc_series_args(trm_ctx* c, int bc_var, int side, const char* who, int& slot, const trm_ctx::Series*& sr) {
-    slot = bc_pair_index(bc_var, side);
-    if (slot < 0) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument (internal energy or temperature, bottom or top)");
-    sr = bc_series_of(c, bc_var, side);
-    if (!sr) return fail(c, TRM_EINVAL, std::string(who) + ": the pair has no time series (trm_set_bc_series)");
-    return TRM_OK;
-}
-}  // namespace
-int trm_tangent_bc_series_upload(trm_ctx* c, int bc_var, int side, int nt, const void* host) {
-    TRM_ENTER_HEUN(c);
-    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_bc_series_upload: no tangent is open (trm_tangent_open)");
-    int slot = -1;
-    const trm_ctx::Series* sr = nullptr;
-    if (int rc = bc_series_args(c, bc_var, side, "trm_tangent_bc_series_upload", slot, sr)) return rc;
-    if (!host) return fail(c, TRM_EINVAL, "trm_tangent_bc_series_upload: bad argument");
-    if ((long)nt != sr->cap || (long)sr->times.size() != sr->cap)
-        return fail(c, TRM_EINVAL, "trm_tangent_bc_series_upload: nt must be the levels of the pair's series (" + std::to_string(sr->times.size()) + ")");
-    if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_bc_series_upload")) return rc;
-    if (int rc = alloc_series_shaped(c, c->d_tan_bcs[slot], c->tan_bcs_nt[slot], nt, "trm_tangent_bc_series_upload")) return rc;
-    TRM_HIP(c, hipMemcpyAsync(c->d_tan_bcs[slot], host, (size_t)nt * (size_t)c->Nh * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;             // (seeds are not state: tan_stale stays as it is)
-}
-int trm_tangent_bc_upload(trm_ctx* c, int bc_var, int side, const void* host) {
-    TRM_ENTER_HEUN(c);
-    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: no tangent is open (trm_tangent_open)");
-    const int slot = bc_pair_index(bc_var, side);
-    if (slot < 0 || !host) return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: bad argument (internal energy or temperature, bottom or top)");
-    if (c->opt_derivative_series && bc_series_of(c, bc_var, side))
-        return fail(c, TRM_EINVAL, "trm_tangent_bc_upload: the pair is driven by a time series: its seeds have the series' shape (trm_tangent_bc_series_upload)");
-    const size_t bytes = (size_t)c->Nh * sizeof(double);
-    if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_bc_upload")) return rc;
-    TRM_HIP(c, hipMemcpyAsync(c->d_tan_bc[slot], host, bytes, hipMemcpyHostToDevice, c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    c->tan_bc_seeded = true;   // (seeds are not state: tan_stale stays as it is)
-    return TRM_OK;
-}
-int trm_tangent_param_set(trm_ctx* c, const double seed[TRM_THERMAL_PARAM_COUNT]) {
-    TRM_ENTER_HEUN(c);
-    // (a context the tangent does not cover has none open: it is told why, not to open one)
-    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_param_set: ") + why);
-    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_param_set: no tangent is open (trm_tangent_open)");
-    if (!seed) return fail(c, TRM_EINVAL, "trm_tangent_param_set: bad argument");
-    if (c->opt_derivative_series && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_param_set: ") + kSeriesWithParams);
-    if (const char* why = thermal_params_not_differentiable(c)) return fail(c, TRM_EINVAL, std::string("trm_tangent_param_set: ") + why);
-    if (int rc = alloc_tangent_bc_seeds(c, "trm_tangent_param_set")) return rc;
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    // the chain rule to the eight numbers the kernels hold (thermal_param_chain): a sum per derived number, in the order of trm_params
-    double w[TRM_THERMAL_PARAM_COUNT];
-    thermal_param_chain(c->params, launch_args<double>(c).p, w);
-    std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
-    for (int q = 0; q < TRM_THERMAL_PARAM_COUNT; ++q) c->tan_param[thermal_param_target(q)] += w[q] * seed[q];
-    c->tan_param_seeded = true;   // (seeds are not state: tan_stale stays as it is)
-    return TRM_OK;
-}
-int trm_tangent_upload(trm_ctx* c, int which, const void* host) {
-    TRM_ENTER_HEUN(c);
-    if (int rc = tangent_args_ok(c, which, host, "trm_tangent_upload")) return rc;
-    const long Nh = c->Nh;
-    const size_t bytes = (size_t)c->Nz * Nh * sizeof(double);
-    if (int rc = io_buffer(c, bytes)) return rc;
-    TRM_HIP(c, hipMemcpyAsync(c->d_io, host, bytes, hipMemcpyHostToDevice, c->stream));
-    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
-    hipLaunchKernelGGL((k_transpose<double, true>), grid, dim3(256), 0, c->stream, (const double*)c->d_io, c->d_tan[which], Nh, c->Nz, c->Nzp);
-    TRM_HIP(c, hipGetLastError());
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    if (which == TRM_TANGENT_INTERNAL_ENERGY) c->tan_stale = false;
-    return TRM_OK;
-}
-int trm_tangent_download(trm_ctx* c, int which, void* host) {
-    TRM_ENTER_HEUN(c);
-    if (int rc = tangent_args_ok(c, which, host, "trm_tangent_download")) return rc;
-    if (which != TRM_TANGENT_INTERNAL_ENERGY && c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_download") + kStaleTangent);
-    const long Nh = c->Nh;
-    const size_t bytes = (size_t)c->Nz * Nh * sizeof(double);
-    if (int rc = io_buffer(c, bytes)) return rc;
-    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
-    hipLaunchKernelGGL((k_transpose<double, false>), grid, dim3(256), 0, c->stream, (const double*)c->d_tan[which], (double*)c->d_io, Nh, c->Nz, c->Nzp);
-    TRM_HIP(c, hipGetLastError());
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_io, bytes, hipMemcpyDeviceToHost, c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
-int trm_tangent_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_elems) {
-    TRM_ENTER_HEUN(c);
-    if (int rc = tangent_args_ok(c, which, dev, "trm_tangent_device_ptr")) return rc;
-    if (!pitch_elems) return fail(c, TRM_EINVAL, "trm_tangent_device_ptr: bad argument");
-    *dev = c->d_tan[which];
-    *pitch_elems = c->Nzp;
-    return TRM_OK;
-}
-int trm_tangent_closure(trm_ctx* c) {
-    TRM_ENTER_HEUN(c);
-    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_tangent_closure: no tangent is open (trm_tangent_open)");
-    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_tangent_closure: ") + why);
-    if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_closure") + kStaleTangent);
-    return finish(c, TangentLaunch::closure(c, tangent_ride(c, 0)));
-}
-int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
-    TRM_ENTER(c);
-    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, "trm_step_tangent: no tangent is open (trm_tangent_open)");
-    if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_tangent: nsteps < 0");
-    if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + why);
-    const int nser = derivative_series_count(c);
-    if (nser && c->tan_param_seeded && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_tangent: ") + kSeriesWithParams);
-    if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_step_tangent") + kStaleTangent);
-    if (nser) {   // series ride with the boundary-seeded instances: the per-column seeds, and zeros for a series nobody has seeded
-        if (int rc = alloc_tangent_bc_seeds(c, "trm_step_tangent")) return rc;
-        for (const auto& sr : c->series) {
-            const int slot = bc_pair_index(sr.var, sr.side);
-            if (int rc = alloc_series_shaped(c, c->d_tan_bcs[slot], c->tan_bcs_nt[slot], sr.cap, "trm_step_tangent")) return rc;
-        }
-    }
-    bc_changed(c);             // (a state-changing call for an open tape)
-    const int spl = derivative_steps_per_launch(c);
-    const Ride ride = tangent_ride(c, nser);
-    for (int n = 0, m; n < nsteps; n += m) {
-        m = std::min(spl, nsteps - n);
-        int rc = nser ? Ops<double>::upload_series_rows(c, dt, m) : Ops<double>::update_inputs(c, c->state, c->time);
-        if (!rc) rc = TangentLaunch::step(c, dt, m, ride);
-        if (rc) return rc;
-        c->derivative_series = nser;
-        tick(c, dt, m);
-    }
-    return derivative_steps_done(c);
-}
-
-// ---- reverse-mode gradients of the heat-only run (trm_column_adjoint.hpp) -----------------------------------------------------
-namespace {
-int adjoint_args_ok(trm_ctx* c, int which, const void* ptr, const char* who) {
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no adjoint is open (trm_adjoint_open)");
-    if (which < 0 || which > TRM_ADJOINT_LIQUID_WATER_FRACTION || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument");
-    return TRM_OK;
-}
-const char* kStaleTape = ": the state or a boundary condition has changed since the first taped step: trm_adjoint_open starts a new tape";
-void free_tape(trm_ctx* c) {
-    if (c->d_tape) (void)hipFree(c->d_tape);
-    c->d_tape = nullptr;
-    c->tape_cap = 0;
-    c->ckpt_interval = 0;
-    c->tape_dt.clear();
-    c->tape_segs.clear();
-    c->tape_rows.clear();
-    c->adj_stale = false;
-}
-void free_adjoint_params(trm_ctx* c) {
-    for (double*& q : c->d_adj_param) {
-        if (q) (void)hipFree(q);
-        q = nullptr;
-    }
-    if (c->d_adj_param_out) (void)hipFree(c->d_adj_param_out);
-    c->d_adj_param_out = nullptr;
-}
-void free_adjoint(trm_ctx* c) {
-    for (double*& q : c->d_adj) {
-        if (q) (void)hipFree(q);
-        q = nullptr;
-    }
-    for (double*& q : c->d_adj_bc) {
-        if (q) (void)hipFree(q);
-        q = nullptr;
-    }
-    for (double*& q : c->d_adj_bcs) {
-        if (q) (void)hipFree(q);
-        q = nullptr;
-    }
-    std::fill(std::begin(c->adj_bcs_nt), std::end(c->adj_bcs_nt), 0L);
-    free_adjoint_params(c);
-    free_tape(c);
-}
-// steps on the tape, per-step or checkpointed
-int taped_steps(const trm_ctx* c) {
-    if (c->ckpt_interval == 0) return (int)c->tape_dt.size();
-    return c->tape_segs.empty() ? 0 : c->tape_segs.back().first + c->tape_segs.back().len;
-}
-// trm_adjoint_open (`interval` 0: `capacity` slots, one per step) and trm_adjoint_open_checkpointed (`capacity` checkpoint slots)
-int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who) {
-    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, who + ": " + why);
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double);
-    if (capacity != c->tape_cap || interval != c->ckpt_interval) {
-        free_tape(c);
-        if (hipMalloc((void**)&c->d_tape, (size_t)capacity * bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            c->d_tape = nullptr;
-            const bool was_open = c->d_adj[0] != nullptr;
-            free_adjoint(c);
-            return fail(c, TRM_ENOMEM, who + ": a tape of " + std::to_string(capacity) + (interval ? " checkpoints x " : " steps x ") + std::to_string(bytes) +
-                                           " bytes does not fit" + (was_open ? " (the adjoint that was open is closed)" : ""));
-        }
-        c->tape_cap = capacity;
-        c->ckpt_interval = interval;
-    }
-    for (double*& q : c->d_adj) {
-        if (!q && hipMalloc((void**)&q, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            q = nullptr;
-            free_adjoint(c);
-            return fail(c, TRM_ENOMEM, who + ": the cotangent fields do not fit");
-        }
-        TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
-    }
-    for (double* q : c->d_adj_bc)   // (opening again keeps open boundary gradients, zero)
-        if (q) TRM_HIP(c, hipMemsetAsync(q, 0, (size_t)c->Nh * sizeof(double), c->stream));
-    for (int s = 0; s < 4; ++s)     // (... and node gradients)
-        if (c->d_adj_bcs[s]) TRM_HIP(c, hipMemsetAsync(c->d_adj_bcs[s], 0, (size_t)c->adj_bcs_nt[s] * (size_t)c->Nh * sizeof(double), c->stream));
-    for (double* q : c->d_adj_param)   // (... and open parameter gradients)
-        if (q) TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
-    if (c->d_adj_param_out) TRM_HIP(c, hipMemsetAsync(c->d_adj_param_out, 0, (size_t)TRM_THERMAL_PARAM_COUNT * (size_t)c->Nh * sizeof(double), c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    c->tape_dt.clear();        // (a fresh tape)
-    c->tape_segs.clear();
-    c->tape_rows.clear();
-    c->adj_stale = false;
-    return TRM_OK;
-}
-}  // namespace
-
-int trm_adjoint_open(trm_ctx* c, int capacity_steps) {
-    TRM_ENTER_HEUN(c);
-    if (capacity_steps < 1) return fail(c, TRM_EINVAL, "trm_adjoint_open: capacity_steps < 1");
-    return open_adjoint(c, capacity_steps, 0, "trm_adjoint_open");
-}
-int trm_adjoint_open_checkpointed(trm_ctx* c, int capacity_slots, int interval) {
-    TRM_ENTER_HEUN(c);
-    if (capacity_slots < 1) return fail(c, TRM_EINVAL, "trm_adjoint_open_checkpointed: capacity_slots < 1");
-    if (interval < 1 || interval > TRM_ADJOINT_MAX_INTERVAL)
-        return fail(c, TRM_EINVAL, "trm_adjoint_open_checkpointed: the interval is 1 ... " + std::to_string(TRM_ADJOINT_MAX_INTERVAL));
-    return open_adjoint(c, capacity_slots, interval, "trm_adjoint_open_checkpointed");
-}
-int trm_adjoint_checkpoints(const trm_ctx* c, int* interval, int* slots_used, int* slots_capacity) {
-    if (!c) return TRM_EINVAL;
-    if (!c->d_adj[0]) return fail(const_cast<trm_ctx*>(c), TRM_EINVAL, "trm_adjoint_checkpoints: no adjoint is open (trm_adjoint_open)");
-    if (interval) *interval = c->ckpt_interval;
-    if (slots_used) *slots_used = c->ckpt_interval ? (int)c->tape_segs.size() : (int)c->tape_dt.size();
-    if (slots_capacity) *slots_capacity = c->tape_cap;
-    return TRM_OK;
-}
-int trm_adjoint_close(trm_ctx* c) {
-    TRM_ENTER_HEUN(c);
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_close: no adjoint is open");
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    free_adjoint(c);
-    return TRM_OK;
-}
-namespace {
-// the four per-column accumulators, zeroed: all of them (trm_adjoint_bc_open) or the ones this call allocates (`only_new`: a sweep with
-// series, which rides with the accumulating instances, opens them if nobody has)
-int open_adjoint_bc(trm_ctx* c, bool only_new, const char* who) {
-    const size_t bytes = (size_t)c->Nh * sizeof(double);
-    for (double*& q : c->d_adj_bc) {
-        const bool fresh = !q;
-        if (!q && hipMalloc((void**)&q, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            q = nullptr;
-            for (double*& r : c->d_adj_bc) {
-                if (r) (void)hipFree(r);
-                r = nullptr;
-            }
-            return fail(c, TRM_ENOMEM, std::string(who) + ": the accumulators do not fit");
-        }
-        if (fresh || !only_new) TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
-    }
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
-}  // namespace
-int trm_adjoint_bc_open(trm_ctx* c) {
-    TRM_ENTER_HEUN(c);
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_bc_open: no adjoint is open (trm_adjoint_open)");
-    return open_adjoint_bc(c, false, "trm_adjoint_bc_open");
-}
-namespace {
-int adjoint_bc_args(trm_ctx* c, int bc_var, int side, const void* ptr, const char* who, int& slot) {
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no adjoint is open (trm_adjoint_open)");
-    if (!c->d_adj_bc[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no boundary gradients are open (trm_adjoint_bc_open)");
-    slot = bc_pair_index(bc_var, side);
-    if (slot < 0 || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument (internal energy or temperature, bottom or top)");
-    if (c->opt_derivative_series && bc_series_of(c, bc_var, side))
-        return fail(c, TRM_EINVAL, std::string(who) + ": the pair is driven by a time series: its gradient has the series' shape (trm_adjoint_bc_series_download)");
-    return TRM_OK;
-}
-// the node accumulator of a seriesed pair (zeros until a sweep has run)
-int adjoint_bc_series_args(trm_ctx* c, int bc_var, int side, const void* ptr, const char* who, int& slot, long& nt) {
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no adjoint is open (trm_adjoint_open)");
-    const trm_ctx::Series* sr = nullptr;
-    if (int rc = bc_series_args(c, bc_var, side, who, slot, sr)) return rc;
-    if (!ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument");
-    nt = sr->cap;
-    if (int rc = alloc_series_shaped(c, c->d_adj_bcs[slot], c->adj_bcs_nt[slot], nt, who)) return rc;
-    return TRM_OK;
-}
-}  // namespace
-int trm_adjoint_bc_series_download(trm_ctx* c, int bc_var, int side, int nt, void* host) {
-    TRM_ENTER_HEUN(c);
-    int slot = -1;
-    long have = 0;
-    if (int rc = adjoint_bc_series_args(c, bc_var, side, host, "trm_adjoint_bc_series_download", slot, have)) return rc;
-    if ((long)nt != have) return fail(c, TRM_EINVAL, "trm_adjoint_bc_series_download: nt must be the levels of the pair's series (" + std::to_string(have) + ")");
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_adj_bcs[slot], (size_t)nt * (size_t)c->Nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
-int trm_adjoint_bc_series_device_ptr(trm_ctx* c, int bc_var, int side, void** dev, int* nt) {
-    TRM_ENTER_HEUN(c);
-    int slot = -1;
-    long have = 0;
-    if (!nt) return fail(c, TRM_EINVAL, "trm_adjoint_bc_series_device_ptr: bad argument");
-    if (int rc = adjoint_bc_series_args(c, bc_var, side, dev, "trm_adjoint_bc_series_device_ptr", slot, have)) return rc;
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    *dev = c->d_adj_bcs[slot];
-    *nt = (int)have;
-    return TRM_OK;
-}
-int trm_adjoint_bc_download(trm_ctx* c, int bc_var, int side, void* host) {
-    TRM_ENTER_HEUN(c);
-    int slot = -1;
-    if (int rc = adjoint_bc_args(c, bc_var, side, host, "trm_adjoint_bc_download", slot)) return rc;
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_adj_bc[slot], (size_t)c->Nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
-int trm_adjoint_bc_device_ptr(trm_ctx* c, int bc_var, int side, void** dev) {
-    TRM_ENTER_HEUN(c);
-    int slot = -1;
-    if (int rc = adjoint_bc_args(c, bc_var, side, dev, "trm_adjoint_bc_device_ptr", slot)) return rc;
-    *dev = c->d_adj_bc[slot];
-    return TRM_OK;
-}
-int trm_adjoint_param_open(trm_ctx* c) {
-    TRM_ENTER_HEUN(c);
-    // (a context the adjoint does not cover has none open: it is told why, not to open one)
-    if (const char* why = derivative_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_param_open: ") + why);
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_param_open: no adjoint is open (trm_adjoint_open)");
-    if (const char* why = thermal_params_not_differentiable(c)) return fail(c, TRM_EINVAL, std::string("trm_adjoint_param_open: ") + why);
-    if (c->opt_derivative_series && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_param_open: ") + kSeriesWithParams);
-    if (int rc = trm_adjoint_bc_open(c)) return rc;   // (the accumulating instances carry both)
-    const size_t bytes = (size_t)c->Nh * (size_t)c->Nzp * sizeof(double), out_bytes = (size_t)TRM_THERMAL_PARAM_COUNT * (size_t)c->Nh * sizeof(double);
-    bool ok = true;
-    for (double*& q : c->d_adj_param)
-        if (ok && !q && hipMalloc((void**)&q, bytes) != hipSuccess) {
-            q = nullptr;
-            ok = false;
-        }
-    if (ok && !c->d_adj_param_out && hipMalloc((void**)&c->d_adj_param_out, out_bytes) != hipSuccess) {
-        c->d_adj_param_out = nullptr;
-        ok = false;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        free_adjoint_params(c);
-        return fail(c, TRM_ENOMEM, "trm_adjoint_param_open: the accumulators do not fit");
-    }
-    for (double* q : c->d_adj_param) TRM_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
-    TRM_HIP(c, hipMemsetAsync(c->d_adj_param_out, 0, out_bytes, c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
-namespace {
-int adjoint_param_args(trm_ctx* c, int which, const void* ptr, const char* who) {
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, std::string(who) + ": no adjoint is open (trm_adjoint_open)");
-    if (!c->d_adj_param_out) return fail(c, TRM_EINVAL, std::string(who) + ": no parameter gradients are open (trm_adjoint_param_open)");
-    if (which < 0 || which >= TRM_THERMAL_PARAM_COUNT || !ptr) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument (TRM_THERMAL_PARAM_*)");
-    return TRM_OK;
-}
-}  // namespace
-int trm_adjoint_param_download(trm_ctx* c, int which, void* host) {
-    TRM_ENTER_HEUN(c);
-    if (int rc = adjoint_param_args(c, which, host, "trm_adjoint_param_download")) return rc;
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_adj_param_out + (size_t)which * (size_t)c->Nh, (size_t)c->Nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
-int trm_adjoint_param_device_ptr(trm_ctx* c, int which, void** dev) {
-    TRM_ENTER_HEUN(c);
-    if (int rc = adjoint_param_args(c, which, dev, "trm_adjoint_param_device_ptr")) return rc;
-    *dev = c->d_adj_param_out + (size_t)which * (size_t)c->Nh;
-    return TRM_OK;
-}
-int trm_adjoint_upload(trm_ctx* c, int which, const void* host) {
-    TRM_ENTER_HEUN(c);
-    if (int rc = adjoint_args_ok(c, which, host, "trm_adjoint_upload")) return rc;
-    const long Nh = c->Nh;
-    const size_t bytes = (size_t)c->Nz * Nh * sizeof(double);
-    if (int rc = io_buffer(c, bytes)) return rc;
-    TRM_HIP(c, hipMemcpyAsync(c->d_io, host, bytes, hipMemcpyHostToDevice, c->stream));
-    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
-    hipLaunchKernelGGL((k_transpose<double, true>), grid, dim3(256), 0, c->stream, (const double*)c->d_io, c->d_adj[which], Nh, c->Nz, c->Nzp);
-    TRM_HIP(c, hipGetLastError());
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
-int trm_adjoint_download(trm_ctx* c, int which, void* host) {
-    TRM_ENTER_HEUN(c);
-    if (int rc = adjoint_args_ok(c, which, host, "trm_adjoint_download")) return rc;
-    const long Nh = c->Nh;
-    const size_t bytes = (size_t)c->Nz * Nh * sizeof(double);
-    if (int rc = io_buffer(c, bytes)) return rc;
-    dim3 grid((unsigned)((Nh + 31) / 32), (unsigned)((c->Nzp + 31) / 32));
-    hipLaunchKernelGGL((k_transpose<double, false>), grid, dim3(256), 0, c->stream, (const double*)c->d_adj[which], (double*)c->d_io, Nh, c->Nz, c->Nzp);
-    TRM_HIP(c, hipGetLastError());
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_io, bytes, hipMemcpyDeviceToHost, c->stream));
-    TRM_HIP(c, hipStreamSynchronize(c->stream));
-    return TRM_OK;
-}
-int trm_adjoint_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_elems) {
-    TRM_ENTER_HEUN(c);
-    if (int rc = adjoint_args_ok(c, which, dev, "trm_adjoint_device_ptr")) return rc;
-    if (!pitch_elems) return fail(c, TRM_EINVAL, "trm_adjoint_device_ptr: bad argument");
-    *dev = c->d_adj[which];
-    *pitch_elems = c->Nzp;
-    return TRM_OK;
-}
-int trm_adjoint_tape(const trm_ctx* c, int* recorded, int* capacity) {
-    if (!c) return TRM_EINVAL;
-    if (!c->d_adj[0]) return fail(const_cast<trm_ctx*>(c), TRM_EINVAL, "trm_adjoint_tape: no adjoint is open (trm_adjoint_open)");
-    if (recorded) *recorded = taped_steps(c);
-    if (capacity) *capacity = (int)std::min<long long>((long long)c->tape_cap * std::max(c->ckpt_interval, 1), std::numeric_limits<int>::max());
-    return TRM_OK;
-}
-namespace {
-// the steps the open segment of a checkpointed tape still takes under `dt` (0: the next step opens a segment)
-int open_segment_room(const trm_ctx* c, double dt) {
-    if (c->tape_segs.empty() || c->tape_segs.back().dt != dt) return 0;
-    return c->ckpt_interval - c->tape_segs.back().len;
-}
-}  // namespace
-int trm_step_record(trm_ctx* c, double dt, int nsteps) {
-    TRM_ENTER(c);
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_step_record: no adjoint is open (trm_adjoint_open)");
-    if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_record: nsteps < 0");
-    const int K = c->ckpt_interval;
-    if (K == 0) {
-        const int recorded = (int)c->tape_dt.size();
-        if (nsteps > c->tape_cap - recorded)
-            return fail(c, TRM_EINVAL, "trm_step_record: " + std::to_string(nsteps) + " steps do not fit the tape (" + std::to_string(recorded) + " of " +
-                                           std::to_string(c->tape_cap) + " slots taken)");
-    } else {   // the checkpoints this call takes: the steps the open segment has no room for, K to a slot
-        const long long room = open_segment_room(c, dt), used = (long long)c->tape_segs.size();
-        const long long need = nsteps > room ? (nsteps - room + K - 1) / K : 0;
-        if (need > c->tape_cap - used)
-            return fail(c, TRM_EINVAL, "trm_step_record: " + std::to_string(nsteps) + " steps need " + std::to_string(need) + " checkpoints (" +
-                                           std::to_string(used) + " of " + std::to_string(c->tape_cap) + " slots taken)");
-    }
-    if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + why);
-    const int nser = derivative_series_count(c);
-    if (nser && c->d_adj_param_out && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_step_record: ") + kSeriesWithParams);
-    if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_step_record") + kStaleTape);
-    if (nsteps > 0) c->tan_stale = true;       // (a state-changing call for an open tangent)
-    const int spl = derivative_steps_per_launch(c);
-    for (int n = 0, m; n < nsteps; n += m) {
-        m = std::min(spl, nsteps - n);
-        // (with series: the rows of the launch's steps stay with the tape, [taped step][series])
-        const size_t rows_before = c->tape_rows.size();
-        int rc = nser ? Ops<double>::upload_series_rows(c, dt, m, &c->tape_rows) : Ops<double>::update_inputs(c, c->state, c->time);
-        // (checkpointed: the launch stores before its steps room, room + K, ... -- the starts of the segments it opens)
-        const int room = K ? open_segment_room(c, dt) : 0;
-        if (!rc) rc = K ? CheckpointLaunch::record(c, dt, m, (int)c->tape_segs.size(), room, K, nser != 0) : AdjointLaunch::record(c, dt, m, (int)c->tape_dt.size(), nser != 0);
-        if (rc) {
-            c->tape_rows.resize(rows_before);
-            c->adj_stale = taped_steps(c) > 0;
-            return rc;
-        }
-        c->derivative_series = nser;
-        if (K) {
-            int left = m, at = taped_steps(c);
-            if (room > 0 && left > 0) {
-                const int take = std::min(room, left);
-                c->tape_segs.back().len += take;
-                left -= take;
-                at += take;
-            }
-            while (left > 0) {
-                const int take = std::min(K, left);
-                c->tape_segs.push_back({at, take, dt, (int)c->tape_segs.size()});
-                left -= take;
-                at += take;
-            }
-        } else c->tape_dt.insert(c->tape_dt.end(), (size_t)m, dt);
-        tick(c, dt, m);
-    }
-    return derivative_steps_done(c);
-}
-int trm_adjoint_backward(trm_ctx* c) {
-    TRM_ENTER(c);
-    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, "trm_adjoint_backward: no adjoint is open (trm_adjoint_open)");
-    if (const char* why = derivative_step_unsupported(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + why);
-    const int nser = derivative_series_count(c);
-    if (nser && c->d_adj_param_out && series_refuse_params(c)) return fail(c, TRM_EUNSUPPORTED, std::string("trm_adjoint_backward: ") + kSeriesWithParams);
-    if (c->adj_stale) return fail(c, TRM_ESTALE, std::string("trm_adjoint_backward") + kStaleTape);
-    if (nser) {
-        // series ride with the accumulating instances: the per-column accumulators if nobody has opened them, and the node accumulators,
-        // zero in front of the sweep's first launch; every launch gets the rows the record kept for its steps
-        if (c->tape_rows.size() != (size_t)taped_steps(c) * (size_t)nser)
-            return fail(c, TRM_ESTALE, "trm_adjoint_backward: the tape was recorded without the series the context holds now: trm_adjoint_open starts a new tape");
-        if (int rc = open_adjoint_bc(c, true, "trm_adjoint_backward")) return rc;
-        for (const auto& sr : c->series) {
-            const int slot = bc_pair_index(sr.var, sr.side);
-            if (int rc = alloc_series_shaped(c, c->d_adj_bcs[slot], c->adj_bcs_nt[slot], sr.cap, "trm_adjoint_backward")) return rc;
-            TRM_HIP(c, hipMemsetAsync(c->d_adj_bcs[slot], 0, (size_t)sr.cap * (size_t)c->Nh * sizeof(double), c->stream));
-        }
-    }
-    // (the rows of taped steps [first, first + n), uploaded in front of the launch that walks them)
-    auto kept_rows = [&](int first, int n) { return Ops<double>::upload_series_rows(c, 0.0, n, nullptr, c->tape_rows.data() + (size_t)first * (size_t)nser); };
-    const Ride ride = backward_ride(c, nser);
-    int rc = TRM_OK, fold = 1;
-    if (c->ckpt_interval) {   // one launch per segment, newest first; the first launch folds (an empty tape: that launch alone, no step)
-        size_t s = c->tape_segs.size();
-        do {
-            const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
-            rc = nser ? kept_rows(seg.first, seg.len) : TRM_OK;
-            if (!rc) rc = CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold, ride);
-            if (rc) break;
-            c->derivative_series = nser;
-            fold = 0;
-            if (s > 0) --s;
-        } while (s > 0);
-    } else {
-        // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch
-        // folds the cotangents of T and liq in (an empty tape: that launch alone)
-        const int spl = derivative_steps_per_launch(c);
-        int end = (int)c->tape_dt.size();
-        do {
-            int begin = end;
-            while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
-            const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
-            rc = nser ? kept_rows(begin, end - begin) : TRM_OK;
-            if (!rc) rc = AdjointLaunch::backward(c, dt_block, end - begin, begin, fold, ride);
-            if (rc) break;
-            c->derivative_series = nser;
-            end = begin;
-            fold = 0;
-        } while (end > 0);
-    }
-    if (rc) {
-        c->adj_stale = true;       // (lam is part way down the tape)
-        return rc;
-    }
-    c->tape_segs.clear();
-    c->tape_dt.clear();
-    c->tape_rows.clear();
-    c->adj_stale = false;
-    return finish(c, c->d_adj_param_out ? AdjointLaunch::param_reduce(c) : TRM_OK);
 }
 
 int trm_clock(const trm_ctx* c, double* time, int64_t* iteration) {

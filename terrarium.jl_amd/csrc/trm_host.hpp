@@ -1,7 +1,8 @@
 // trm_host.hpp -- host side shared by the translation units of libterrarium_hip.so: the context, the launch arguments and
 // the launch policies (which kernel instance a context takes).  The kernel instantiations are spread over the trm_launch_*.hip
 // files (one family per file, compiled in parallel); terrarium_hip.hip holds the context management, the step sequences and the
-// C ABI.  Nothing here is part of the ABI.
+// C ABI but its derivative entry points (trm_tangent_*, trm_adjoint_*, trm_step_tangent, trm_step_record), which trm_derivative_api.hip
+// holds; what the two share is declared here.  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/terrarium_hip.h"
 #include "trm_kernels.hpp"
@@ -232,6 +233,41 @@ int fail(trm_ctx* ctx, int code, const std::string& msg);
         if (e__ != hipSuccess)                                                                           \
             return ::trmh::fail(ctx, TRM_EHIP, std::string(#call) + ": " + hipGetErrorString(e__));     \
     } while (0)
+
+// ---- shared by the entry points of terrarium_hip.hip and trm_derivative_api.hip (defined, and described, in terrarium_hip.hip) ----
+int finish(trm_ctx* c, int rc);                 // the end of a launching entry point: waits for the stream unless TRM_OPT_ASYNC
+void tick(trm_ctx* c, double dt, int nsteps);   // tick! per step
+void bc_changed(trm_ctx* c);                    // a boundary condition has changed under an open tape
+void state_changed(trm_ctx* c);                 // ... the state has, under an open tangent or tape
+int flush_closure(trm_ctx* c);                  // T / liq into their arrays if the last step launches left them unstored
+int io_buffer(trm_ctx* c, size_t bytes);        // the staging buffer d_io, grown to `bytes`
+// Host data [Nz][Nh] to / from a 3-D device buffer [Nh][Nzp] through d_io, synchronised (instantiated for double and float).  `top`: the
+// [Nh] buffer of a Face field's top face, which travels as row Nz of the host array (null: Nz rows)
+template <class NF> int upload_3d(trm_ctx* c, const NF* host, NF* dev, NF* top = nullptr);
+template <class NF> int download_3d(trm_ctx* c, const NF* dev, NF* host, const NF* top = nullptr);
+// the derivative buffers of the context (d_tan*, d_adj*, d_tape) are freed here and nowhere else: the close calls, an open that fails,
+// trm_destroy (trm_derivative_api.hip)
+void release_tangent(trm_ctx* c);
+void release_adjoint(trm_ctx* c);
+
+// TRM_ENTER: any entry point but the three of the two-call Heun step and the read-only ones.  A stage predicted by
+// trm_heun_predict belongs to the state and clock it was predicted from: whatever else runs in between drops it, and a later
+// trm_heun_correct fails ("call trm_heun_predict first") instead of averaging tendencies of a stage that describes another state.
+// Both materialise T / liq first if the last step launches left them unstored (flush_closure, TRM_OPT_DEFER_CLOSURE_STORES): whatever
+// the entry point reads or writes, it finds the arrays an eagerly storing context has.  TRM_ENTER_KEEP: the entry points that neither
+// read nor write field memory, or order the accesses themselves -- trm_step / trm_step_timed (Ops::fused_launch), trm_restore_state
+// (overwrites the fields), trm_synchronize, trm_status; the getters that take no macro at all belong here too.
+#define TRM_ENTER_KEEP(c)                                    \
+    if (!(c)) return TRM_EINVAL;                             \
+    TRM_HIP(c, hipSetDevice((c)->device));
+#define TRM_ENTER_HEUN(c)                                    \
+    TRM_ENTER_KEEP(c)                                        \
+    if ((c)->closure_deferred)                               \
+        if (int rc_flush__ = ::trmh::flush_closure(c)) return rc_flush__;
+#define TRM_ENTER(c)                                         \
+    TRM_ENTER_HEUN(c)                                        \
+    (c)->heun_pending = false;
+
 
 inline long field_rows(const trm_ctx* c, int field) {
     if (field == TRM_FIELD_HYDRAULIC_CONDUCTIVITY) return c->Nz + 1;
@@ -548,6 +584,8 @@ struct StepPlan {
 template <class NF> struct Unfused {
     static int await_levels(trm_ctx* c, trm_ctx::Series& sr, int last_level);
     static int update_inputs(trm_ctx* c, const FieldSet& s, double time);
+    // the slot table and the rows of a multi-step launch with time series; `keep` / `kept`: the tape of trm_step_record
+    static int upload_series_rows(trm_ctx* c, double dt, int nsteps, std::vector<SeriesRow>* keep = nullptr, const SeriesRow* kept = nullptr);
     static int hydraulics(trm_ctx* c, const FieldSet& s);
     static int surface(trm_ctx* c, const FieldSet& s, bool from_state = false);
     static int compute_auxiliary(trm_ctx* c, const FieldSet& s);
@@ -587,7 +625,7 @@ template <Ride R> int tangent_closure(trm_ctx* c);
 template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
 template <bool CKPT, Ride R> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
 // k_column_tangent / k_closure_tangent (fp64 NoFlow only); the closure knows the parameter seeds alone.  These three choose the
-// instantiation of the ride (terrarium_hip.hip)
+// instantiation of the ride (trm_derivative_api.hip)
 struct TangentLaunch {
     static int step(trm_ctx* c, double dt, int nsteps, Ride ride);
     static int closure(trm_ctx* c, Ride ride);
@@ -605,6 +643,38 @@ struct CheckpointLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every, bool series);
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride);
 };
+// The tape of trm_step_record as the host keeps it (trm_ctx::tape_dt, or tape_segs when checkpointed): bookkeeping alone, no HIP call
+// (tests/derivative_preconditions.cpp).  Steps on the tape:
+inline int taped_steps(const trm_ctx* c) {
+    if (c->ckpt_interval == 0) return (int)c->tape_dt.size();
+    return c->tape_segs.empty() ? 0 : c->tape_segs.back().first + c->tape_segs.back().len;
+}
+// the steps the open segment of a checkpointed tape still takes under `dt` (0: the next step opens a segment)
+inline int open_segment_room(const trm_ctx* c, double dt) {
+    if (c->tape_segs.empty() || c->tape_segs.back().dt != dt) return 0;
+    return c->ckpt_interval - c->tape_segs.back().len;
+}
+// slots taken, and the slots `nsteps` more steps under `dt` take: one each on the per-step tape; checkpointed, the steps the open segment
+// has no room for, K to a slot
+inline long long tape_slots_used(const trm_ctx* c) { return c->ckpt_interval ? (long long)c->tape_segs.size() : (long long)c->tape_dt.size(); }
+inline long long tape_slots_needed(const trm_ctx* c, double dt, int nsteps) {
+    const long long K = c->ckpt_interval, room = open_segment_room(c, dt);
+    if (K == 0) return nsteps;
+    return nsteps > room ? (nsteps - room + K - 1) / K : 0;
+}
+// `m` recorded steps under `dt` join the tape: they fill the open segment, then open segments of up to K steps in the next slots
+inline void tape_append(trm_ctx* c, double dt, int m) {
+    const int K = c->ckpt_interval;
+    if (K == 0) {
+        c->tape_dt.insert(c->tape_dt.end(), (size_t)m, dt);
+        return;
+    }
+    int at = taped_steps(c);
+    const int fill = std::min(open_segment_room(c, dt), m);
+    if (fill > 0) c->tape_segs.back().len += fill;
+    for (m -= fill, at += fill; m > 0; m -= std::min(K, m), at += K)
+        c->tape_segs.push_back({at, std::min(K, m), dt, (int)c->tape_segs.size()});
+}
 // The chain rule between the ten thermal parameters (TRM_THERMAL_PARAM_*, the order of trm_params) and the eight numbers the kernels
 // differentiate (make_dev_params): w[q] = d(derived number) / d(parameter q), with sk_i = sqrt(k_i), s0 = sqrt(k_mineral) frac_mineral +
 // sqrt(k_organic) frac_organic, C0 = c_mineral frac_mineral + c_organic frac_organic.  Parameter q feeds derived number
@@ -794,6 +864,12 @@ template <class NF> struct StepPolicy : Policy<NF> {
         if (c->opt_single_step == 1) return true;
         return c->Nh <= TRM_SINGLE_STEP_PROGRAM_MAX_COLUMNS;
     }
+    // TRM_OPT_STEPS_PER_LAUNCH = 0: run!'s loop (model_integrator.jl:72-88) is exactly trm_step(ctx, dt, nsteps, 0), so the
+    // resident-column program is what a plain call gets whenever it is legal.  Measured: 2.0-4.6 us per step
+    // against 6.8-12 on N72 / 7 119-column shards, 12.3 against 24-26 at N145 -- and for fp32 contexts whose per-step path is
+    // the packed kernel as well: C5 371 against 447-451 us, C5-VG 479 against 489, a 12 696-column fp32 shard 7.3 against 13.3
+    // (r3: the rule used to keep the packed kernel there).
+    static int auto_steps_per_launch(const trm_ctx*) { return 50; }
     // how many steps ONE launch of trm_step covers for this context: 1 unless the resident multi-step program applies
     static bool program_applies(const trm_ctx* c) {
         const bool fused = c->opt_kernel == TRM_KERNEL_FUSED && P::levels_per_lane(c) > 0;

@@ -54,6 +54,75 @@ template <class NF> int Unfused<NF>::update_inputs(trm_ctx* c, const FieldSet& s
     }
     return flush();
 }
+// slot table + [nsteps][nseries] rows for a multi-step launch that starts at the context clock.  `keep`: the rows are appended there
+// as well (trm_step_record's tape); `kept`: the rows are these, formed by an earlier call, and not the clock's (trm_adjoint_backward)
+template <class NF> int Unfused<NF>::upload_series_rows(trm_ctx* c, double dt, int nsteps, std::vector<SeriesRow>* keep, const SeriesRow* kept) {
+    const int ns = (int)c->series.size();
+    const size_t nrows = (size_t)nsteps * ns, need = sizeof(SeriesTable<NF>) + nrows * sizeof(SeriesRow);
+    trm_ctx::RowStage& st = c->row_stage[c->row_stage_next];
+    c->row_stage_next = (c->row_stage_next + 1) % 4;
+    if (st.pending) {
+        TRM_HIP(c, hipEventSynchronize(st.done));
+        st.pending = false;
+    }
+    if (!st.done) TRM_HIP(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    if (need > st.cap) {
+        if (st.h) TRM_HIP(c, hipHostFree(st.h));
+        st.h = nullptr;
+        st.cap = 0;
+        TRM_HIP(c, hipHostMalloc(&st.h, need, hipHostMallocDefault));
+        st.cap = need;
+    }
+    SeriesTable<NF>& tb = *(SeriesTable<NF>*)st.h;
+    SeriesRow* rows = (SeriesRow*)((char*)st.h + sizeof(SeriesTable<NF>));
+    std::memset(&tb, 0, sizeof(tb));
+    for (int j = 0; j < ns; ++j) {
+        auto& sr = c->series[j];
+        const int slot = Policy<NF>::series_slot(c, sr);
+        tb.base[slot] = (const NF*)sr.d_values;
+        tb.row_of[slot] = j;
+        tb.raster[slot] = sr.indexing == TRM_TIME_RASTER ? 1 : 0;
+        if (sr.is_bc) {
+            void*& dst = c->bc_value[sr.var][sr.side];
+            if (!dst) {
+                TRM_HIP(c, hipMalloc(&dst, (size_t)c->Nh * sizeof(NF)));
+                c->args_valid = false;
+            }
+            tb.dst[slot] = (NF*)dst;
+        } else {
+            tb.dst[slot] = (NF*)c->state.f[sr.field];
+        }
+        if (kept) continue;
+        double t = c->time;
+        if (sr.trimmed && t < sr.trimmed_before)
+            return fail(c, TRM_EINVAL, "a windowed time series was asked for a time before the levels it still holds (trm_series_trim_before released them)");
+        for (int s = 0; s < nsteps; ++s) {
+            int n1, n2;
+            double f, g;
+            series_time_indices(sr.times, sr.indexing, t, n1, n2, f, g);
+            if (int rw = await_levels(c, sr, std::max(n1, n2))) return rw;
+            rows[(size_t)s * ns + j] = SeriesRow{(long long)(sr.slot(n1) * (size_t)c->Nh), (long long)(sr.slot(n2) * (size_t)c->Nh), f, g};
+            t += dt;
+        }
+    }
+    if (kept && nrows > 0) std::memcpy(rows, kept, nrows * sizeof(SeriesRow));
+    if (keep) keep->insert(keep->end(), rows, rows + nrows);
+    if (!c->d_series_table) TRM_HIP(c, hipMalloc(&c->d_series_table, sizeof(SeriesTable<double>)));
+    if (nrows * sizeof(SeriesRow) > c->series_rows_cap) {
+        if (c->d_series_rows) TRM_HIP(c, hipFree(c->d_series_rows));   // (waits for the launches that read it)
+        c->d_series_rows = nullptr;
+        c->series_rows_cap = 0;
+        TRM_HIP(c, hipMalloc(&c->d_series_rows, nrows * sizeof(SeriesRow)));
+        c->series_rows_cap = nrows * sizeof(SeriesRow);
+    }
+    // in stream order behind the previous launch (which reads the device copies) and in front of the next one; the host
+    // does not wait
+    TRM_HIP(c, hipMemcpyAsync(c->d_series_table, &tb, sizeof(tb), hipMemcpyHostToDevice, c->stream));
+    if (nrows > 0) TRM_HIP(c, hipMemcpyAsync(c->d_series_rows, rows, nrows * sizeof(SeriesRow), hipMemcpyHostToDevice, c->stream));
+    TRM_HIP(c, hipEventRecord(st.done, c->stream));
+    st.pending = true;
+    return TRM_OK;
+}
 template <class NF> int Unfused<NF>::hydraulics(trm_ctx* c, const FieldSet& s) {
     const View<NF>& v = cached_view<NF>(c, s);
     const DevParams<NF>& p = launch_args<NF>(c).p;

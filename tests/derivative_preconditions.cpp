@@ -52,6 +52,44 @@ int main() {
     c.adj_bcs_nt[SLOT_T_TOP] = 5;
     assert(gradients_ok<RIDE_SERIES>(&c, 1, "g") == TRM_OK);
     assert(series_nodes_ok(&c, c.d_tan_bcs, c.tan_bcs_nt, "t", "seeds") == TRM_EINVAL && last == "t: a series without seeds of its shape");
+    // the tape's bookkeeping (trm_host.hpp): checkpointed, K = 4 steps to a slot, 3 slots
+    trm_ctx t;
+    t.ckpt_interval = 4;
+    t.tape_cap = 3;
+    auto seg = [&](size_t s, int first, int len, double dt, int slot) {
+        const trm_ctx::TapeSegment& g = t.tape_segs[s];
+        return g.first == first && g.len == len && g.dt == dt && g.slot == slot;
+    };
+    assert(taped_steps(&t) == 0 && open_segment_room(&t, 1.0) == 0 && tape_slots_used(&t) == 0);                  // an empty tape
+    assert(tape_slots_needed(&t, 1.0, 0) == 0 && tape_slots_needed(&t, 1.0, 1) == 1 && tape_slots_needed(&t, 1.0, 4) == 1 && tape_slots_needed(&t, 1.0, 5) == 2);
+    assert(tape_slots_needed(&t, 1.0, 12) == 3 && tape_slots_needed(&t, 1.0, 13) == 4);                            // exactly the capacity, one over
+    tape_append(&t, 1.0, 1);
+    assert(t.tape_segs.size() == 1 && seg(0, 0, 1, 1.0, 0) && taped_steps(&t) == 1);
+    assert(open_segment_room(&t, 1.0) == 3 && open_segment_room(&t, 2.0) == 0);                                    // room under the same dt, none under another
+    assert(tape_slots_needed(&t, 1.0, 3) == 0 && tape_slots_needed(&t, 1.0, 4) == 1 && tape_slots_needed(&t, 2.0, 1) == 1);
+    assert(tape_slots_needed(&t, 1.0, 3 + 8) == 2 && tape_slots_needed(&t, 1.0, 3 + 9) == 3);                      // 2 free slots: the capacity, one over
+    tape_append(&t, 1.0, 2);                                                                                       // m < room + K, within the room
+    assert(t.tape_segs.size() == 1 && seg(0, 0, 3, 1.0, 0) && open_segment_room(&t, 1.0) == 1);
+    tape_append(&t, 1.0, 1 + 4);                                                                                   // m == room + K: fills, opens one full segment
+    assert(t.tape_segs.size() == 2 && seg(0, 0, 4, 1.0, 0) && seg(1, 4, 4, 1.0, 1) && taped_steps(&t) == 8 && open_segment_room(&t, 1.0) == 0);
+    tape_append(&t, 2.0, 3);                                                                                       // another dt: a new segment at once
+    assert(t.tape_segs.size() == 3 && seg(2, 8, 3, 2.0, 2) && taped_steps(&t) == 11 && tape_slots_used(&t) == 3);
+    assert(tape_slots_needed(&t, 2.0, 1) == 0 && tape_slots_needed(&t, 2.0, 2) == 1 && tape_slots_needed(&t, 1.0, 1) == 1);
+    t.tape_segs.clear();
+    t.tape_cap = 4;
+    tape_append(&t, 1.0, 2);
+    tape_append(&t, 1.0, 2 + 4 + 3);                                                                               // m > room + K: fills, a full segment, a part
+    assert(t.tape_segs.size() == 3 && seg(0, 0, 4, 1.0, 0) && seg(1, 4, 4, 1.0, 1) && seg(2, 8, 3, 1.0, 2) && taped_steps(&t) == 11);
+    tape_append(&t, 1.0, 0);
+    assert(t.tape_segs.size() == 3 && taped_steps(&t) == 11);
+    // ... and per step (K = 0): a slot per step, no segments
+    trm_ctx p;
+    p.tape_cap = 5;
+    assert(taped_steps(&p) == 0 && open_segment_room(&p, 1.0) == 0 && tape_slots_needed(&p, 1.0, 5) == 5 && tape_slots_needed(&p, 1.0, 6) == 6);
+    tape_append(&p, 1.0, 2);
+    tape_append(&p, 2.0, 1);
+    assert(p.tape_segs.empty() && p.tape_dt == std::vector<double>({1.0, 1.0, 2.0}) && taped_steps(&p) == 3 && tape_slots_used(&p) == 3);
+    assert(tape_slots_needed(&p, 2.0, 2) == 2 && open_segment_room(&p, 2.0) == 0);
     std::puts("derivative preconditions ok");
     return 0;
 }
