@@ -523,7 +523,8 @@ template <class NF> struct Ops : StepPolicy<NF>, Unfused<NF>, Veg<NF> {
                 e.src_double = 1;
             }
         }
-        int rc = P::richards(c) ? ColumnAccumLaunch<NF, true>::run(c, dt, finalize, nsteps, aa) : ColumnAccumLaunch<NF, false>::run(c, dt, finalize, nsteps, aa);
+        int rc = TRM_OK;
+        by_bool(P::richards(c), [&](auto RICH) { rc = ColumnAccumLaunch<NF, RICH()>::run(c, dt, finalize, nsteps, aa); });
         if (!rc) rc = AverageLaunch<NF>::accumulate(c, b);
         if (rc) return rc;
         for (auto& a : c->averages) {
@@ -552,7 +553,9 @@ template <class NF> struct Ops : StepPolicy<NF>, Unfused<NF>, Veg<NF> {
         if (plan.route == ROUTE_LEVELS) return levels_launch<NF>(c, PROG, P::generic_bcs(c), dt, fin, nsteps);
         if (plan.route == ROUTE_PACKED) return PackedLaunch::step(c, dt, fin);
         if (plan.route == ROUTE_GENERIC) return PROG == PROG_HEUN ? GenericLaunch<NF>::heun(c, dt, fin) : GenericLaunch<NF>::step(c, dt, fin);
-        return P::richards(c) ? ColumnLaunch<NF, true, PROG>::run(c, plan, dt, fin, nsteps) : ColumnLaunch<NF, false, PROG>::run(c, plan, dt, fin, nsteps);
+        int rc = TRM_OK;
+        by_bool(P::richards(c), [&](auto RICH) { rc = ColumnLaunch<NF, RICH(), PROG>::run(c, plan, dt, fin, nsteps); });
+        return rc;
     }
     // What a fused launch leaves (rc: the launch's): the stored T / liq are the closure of the state once it has succeeded; the open
     // time averages take the step's terms (`accumulate`: the launch has not added them itself); only the finalizing launch stores

@@ -8,6 +8,7 @@
 #include "trm_kernels.hpp"
 #include "trm_column.hpp"
 #include "trm_vegetation.hpp"
+#include "trm_dispatch.hpp"
 
 #include <rccl/rccl.h>   // types only: the library is opened lazily by trm_comm_init (no link-time dependency)
 
@@ -533,12 +534,16 @@ constexpr int PROGRAM_BC_SEEDS = 1 << 26;        // tangent: the boundary seeds 
 constexpr int PROGRAM_BACKWARD = 1 << 26;        // adjoint: the backward launch (the record has it clear)
 constexpr int PROGRAM_CHECKPOINTED = 1 << 27;    // adjoint: the checkpointed tape
 constexpr int PROGRAM_BC_GRADIENT = 1 << 30;     // adjoint: the boundary gradients ride along
-#define TRM_BY_HYD(c, CALL)                                   \
-    switch (::trmh::Policy<NF>::hyd(c)) {                     \
-        case HYD_BC_LINEAR: { constexpr int H = HYD_BC_LINEAR; CALL; } break; \
-        case HYD_VG_N2: { constexpr int H = HYD_VG_N2; CALL; } break;         \
-        default: { constexpr int H = HYD_GENERIC; CALL; } break;             \
-    }
+// One kernel launch on the context's stream, checked: like TRM_HIP it RETURNS from the enclosing function with the error.
+// tests/launch_dispatch.cpp defines the macro before this header, to count launches instead of making them (no kernel is instantiated
+// there); a replacement must stay a single statement and may only return an error code from the enclosing function.
+#ifndef TRM_LAUNCH
+#define TRM_LAUNCH(c, K, grid, block, ...)                                     \
+    do {                                                                       \
+        hipLaunchKernelGGL(K, grid, block, 0, (c)->stream, __VA_ARGS__);       \
+        TRM_HIP(c, hipGetLastError());                                         \
+    } while (0)
+#endif
 // whether a step launch stores the hydraulic conductivity: the finalizing one, or every one under TRM_OPT_WRITE_KF_EVERY_STEP
 inline int write_kf(const trm_ctx* c, int finalize) { return (c->opt_write_kf || finalize) ? 1 : 0; }
 // The arguments of a column program launch: `nsteps` steps of program `prog` (PROG_*), the stage's temperature boundary values
@@ -697,46 +702,54 @@ inline void thermal_param_chain(const trm_params& q, const trm::DevParams<double
 template <class NF> struct MaterializeLaunch { static int run(trm_ctx* c); };
 // k_accumulate (trm_launch_average.hip)
 template <class NF> struct AverageLaunch { static int accumulate(trm_ctx* c, const AccumBatch& b); };
-constexpr int TRM_PROGRAM_BIT_AVERAGES_IN_LAUNCH = TRM_PROGRAM_AVERAGES_IN_LAUNCH;
-// the ForwardEuler program with the derivation of T / liq and the boundary-condition signature compiled in (BCSIG, trm_kernels.hpp):
-// one explicit instantiation per signature in the trm_launch_column_sig_*.hip files; `supported` lists them.
+// What a launcher's return code starts as: the callbacks of its dispatch (trm_dispatch.hpp) assign it the launch's; where none ran, no
+// instance takes the values and the launcher refuses
+constexpr int NO_INSTANCE = -1;
+inline int launched(trm_ctx* c, int rc, const char* refusal) { return rc == NO_INSTANCE ? fail(c, TRM_EINVAL, refusal) : rc; }
+// ---- one launch function per kernel template of the column program: it launches the instance and records TRM_INFO_LAST_PROGRAM from the
+// instance's own template arguments, so the id cannot disagree with what ran
+template <class NF, bool RICH, int H, int LPC, int DERIVE, int PROG, bool SEB = false, bool SERIES = false, bool STAGED = false, bool SCALAR_IN = true, int BCSIG = BCSIG_RUNTIME>
+int run_column(trm_ctx* c, dim3 grid, dim3 block, const View<NF>& v, const DevParams<NF>& p, const ColumnArgs<NF>& a) {
+    TRM_LAUNCH(c, (k_column<NF, RICH, H, LPC, DERIVE, PROG, SEB, SERIES, STAGED, SCALAR_IN, BCSIG>), grid, block, v, p, a);
+    constexpr int family = PROG == PROG_EULER ? TRM_PROGRAM_COLUMN_EULER : PROG == PROG_HEUN ? TRM_PROGRAM_COLUMN_HEUN : TRM_PROGRAM_COLUMN_MULTI;
+    c->last_program = program_id(family, H, LPC, DERIVE, STAGED, SCALAR_IN, BCSIG) | (SEB ? 1 << 25 : 0) | (SERIES ? 1 << 26 : 0);
+    return TRM_OK;
+}
+// (the one exception: k_column_psi reports the id of the k_column signature instance it stands in for)
+template <int H, int LPC, bool STAGED, bool SCALAR_IN, int BCSIG, int PSI>
+int run_column_psi(trm_ctx* c, dim3 grid, dim3 block, const View<double>& v, const DevParams<double>& p, const ColumnArgs<double>& a) {
+    TRM_LAUNCH(c, (k_column_psi<H, LPC, STAGED, SCALAR_IN, BCSIG, PSI>), grid, block, v, p, a);
+    c->last_program = program_id(TRM_PROGRAM_COLUMN_EULER, H, LPC, DERIVE_T_LIQ, STAGED, SCALAR_IN, BCSIG);
+    return TRM_OK;
+}
+// (the id of the PROG_MULTI instance of k_column with the same arguments + the bit of the accumulation in the launch)
+template <class NF, bool RICH, int H, int LPC, bool SEB, bool SERIES>
+int run_column_accum(trm_ctx* c, dim3 grid, dim3 block, const View<NF>& v, const DevParams<NF>& p, const ColumnArgs<NF>& a, const AccumArgs& acc) {
+    TRM_LAUNCH(c, (k_column_accum<NF, RICH, H, LPC, SEB, SERIES>), grid, block, v, p, a, acc);
+    c->last_program = program_id(TRM_PROGRAM_COLUMN_MULTI, H, LPC, DERIVE_NONE, 0, 1, BCSIG_RUNTIME) | (SEB ? 1 << 25 : 0) | (SERIES ? 1 << 26 : 0) | TRM_PROGRAM_AVERAGES_IN_LAUNCH;
+    return TRM_OK;
+}
+template <int H, int LPC, int DERIVE, bool STAGED, bool SCALAR_IN, int PROG>
+int run_column_land(trm_ctx* c, dim3 grid, dim3 block, const View<double>& v, const DevParams<double>& p, const ColumnArgs<double>& a, const FrontArgs& fa) {
+    TRM_LAUNCH(c, (k_column_land<double, true, H, LPC, DERIVE, STAGED, SCALAR_IN, PROG>), grid, block, v, p, a, fa);
+    c->last_program = program_id(TRM_PROGRAM_COLUMN_LAND, H, LPC, DERIVE, STAGED, SCALAR_IN, BCSIG_LAND) | (PROG << 25);
+    return TRM_OK;
+}
+// The k_column instances with the boundary-condition signature compiled in (BCSIG, trm_kernels.hpp; fp64, the two compiled hydraulics), one
+// explicit instantiation per signature of kSignatures (trm_dispatch.hpp).  Each run returns TRM_EINVAL where the values name no instance.
+// ForwardEuler, with the derivation of T / liq or without it (trm_launch_column_sig_*.hip):
 template <class NF, bool RICH, int SIG> struct ColumnSigLaunch {
-    static void run(trm_ctx* c, const View<NF>& v, const DevParams<NF>& p, const ColumnArgs<NF>& a, dim3 grid, dim3 block, int lpc, int derive, int staged, int scalar_in);
+    static int run(trm_ctx* c, dim3 grid, dim3 block, const View<NF>& v, const DevParams<NF>& p, const ColumnArgs<NF>& a, int derive, int staged, int scalar_in);
 };
 // the fp64 Richards instances that derive the pressure head at entry (k_column_psi<..., PSI_LAST | PSI_INTERIOR>, trm_launch_column_psi_f64_*.hip):
-// `form` is PSI_LAST or PSI_INTERIOR, (staged, scalar_in) one of (0, 1), (1, 0); `supported`: the signatures that have instances
+// `form` is PSI_LAST or PSI_INTERIOR, (staged, scalar_in) one of (0, 1), (1, 0)
 template <int SIG> struct ColumnPsiLaunch {
-    static void run(trm_ctx* c, const View<double>& v, const DevParams<double>& p, const ColumnArgs<double>& a, dim3 grid, dim3 block, int lpc, int form, int staged, int scalar_in);
+    static int run(trm_ctx* c, dim3 grid, dim3 block, const View<double>& v, const DevParams<double>& p, const ColumnArgs<double>& a, int form, int staged, int scalar_in);
 };
-inline bool column_psi_supported(int sig) { return sig == 0 || sig == BCSIG_T_TOP || sig == (BCSIG_T_TOP | BCSIG_FU_BOT) || sig == (BCSIG_T_TOP | BCSIG_FS_TOP); }
-// the same for the one-launch Heun program (trm_launch_column_sig_heun_*.hip)
+// the one-launch Heun program (trm_launch_column_sig_heun_*.hip)
 template <class NF, bool RICH, int SIG> struct ColumnSigHeunLaunch {
-    static void run(trm_ctx* c, const View<NF>& v, const DevParams<NF>& p, const ColumnArgs<NF>& a, dim3 grid, dim3 block, int lpc);
+    static int run(trm_ctx* c, dim3 grid, dim3 block, const View<NF>& v, const DevParams<NF>& p, const ColumnArgs<NF>& a);
 };
-// the signatures that have instances: launches L<NF, RICH, sig>::run(args...) and returns true, or returns false (the caller then takes
-// the program that reads the kinds at run time)
-template <template <class, bool, int> class L, class NF, bool RICH, class... A> bool launch_by_signature(int sig, A&&... args) {
-    if constexpr (!std::is_same<NF, double>::value) return false;
-    else switch (sig) {
-        case 0: L<NF, RICH, 0>::run(args...); return true;
-        case BCSIG_T_TOP: L<NF, RICH, BCSIG_T_TOP>::run(args...); return true;
-        case BCSIG_T_TOP | BCSIG_FU_BOT: L<NF, RICH, BCSIG_T_TOP | BCSIG_FU_BOT>::run(args...); return true;
-        case BCSIG_LAND:
-            if constexpr (RICH) { L<NF, RICH, BCSIG_LAND>::run(args...); return true; }
-            return false;
-        case BCSIG_T_TOP | BCSIG_FS_TOP:      // prescribed surface temperature + InfiltrationFlux (soil_model_bcs.jl:28)
-            if constexpr (RICH) { L<NF, RICH, BCSIG_T_TOP | BCSIG_FS_TOP>::run(args...); return true; }
-            return false;
-        default: return false;
-    }
-}
-// the signature instances exist for the two compiled hydraulics (the reference default; van Genuchten n = 2): a context with
-// run-time exponents takes the program that reads the kinds at run time too
-#define TRM_BY_COMPILED_HYD(c, CALL)                          \
-    switch (::trmh::Policy<NF>::hyd(c)) {                     \
-        case HYD_BC_LINEAR: { constexpr int H = HYD_BC_LINEAR; CALL; } break; \
-        default: { constexpr int H = HYD_VG_N2; CALL; } break;               \
-    }
 // generic boundary kinds: k_step_wave (Euler) and k_heun_generic (trm_launch_generic*.hip)
 template <class NF> struct GenericLaunch {
     static int step(trm_ctx* c, double dt, int finalize);
@@ -891,7 +904,7 @@ template <class NF> struct StepPolicy : Policy<NF> {
             s.sig = (c->opt_bc_signature && P::hyd(c) != HYD_GENERIC) ? bc_signature_of(c) : -1;
             if (s.derive == DERIVE_T_LIQ) s.staged = rich ? P::template staged_now<true>(c) : P::template staged_now<false>(c);
             if (s.derive == DERIVE_T_LIQ) s.scalar_in = rich ? P::template scalar_inputs_now<true>(c) : P::template scalar_inputs_now<false>(c);
-            const bool has_instance = s.sig == 0 || s.sig == BCSIG_T_TOP || s.sig == (BCSIG_T_TOP | BCSIG_FU_BOT) || (rich && (s.sig == BCSIG_LAND || s.sig == (BCSIG_T_TOP | BCSIG_FS_TOP)));
+            const bool has_instance = signature_has_instance(s.sig, rich);
             P::io_paths(!has_instance || s.sig == BCSIG_LAND, s.staged, s.scalar_in);
             s.derives_unread = s.derive == DERIVE_T_LIQ && c->part < 0;
             s.store_closure = defer_closure_now(c, s.derives_unread) ? 0 : 1;

@@ -4,10 +4,8 @@ namespace trmh {
 extern template int FrontLaunch::run_hyd<HYD_VG_N2>(trm_ctx*, const StepPlan&, double, int, bool);     // (trm_launch_column_land_vg.hip)
 template int FrontLaunch::run_hyd<HYD_BC_LINEAR>(trm_ctx*, const StepPlan&, double, int, bool);
 int FrontLaunch::run(trm_ctx* c, const StepPlan& plan, double dt, int finalize, bool heun) {
-    switch (Policy<double>::hyd(c)) {
-        case HYD_BC_LINEAR: return run_hyd<HYD_BC_LINEAR>(c, plan, dt, finalize, heun);
-        case HYD_VG_N2: return run_hyd<HYD_VG_N2>(c, plan, dt, finalize, heun);
-        default: return fail(c, TRM_EINVAL, "k_column_land: no instance for the generic hydraulics");
-    }
+    int rc = NO_INSTANCE;
+    by_compiled_hyd(Policy<double>::hyd(c), [&](auto H) { rc = run_hyd<H()>(c, plan, dt, finalize, heun); });
+    return launched(c, rc, "k_column_land: no instance for the generic hydraulics");
 }
 }  // namespace trmh

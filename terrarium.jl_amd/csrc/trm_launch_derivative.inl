@@ -131,12 +131,8 @@ template <Ride R> int tangent_seeds_ok(trm_ctx* c, int nsteps, const std::string
 
 // ---- the dispatch over (hydraulics instance, lanes per column): launch(H, LPC), both std::integral_constant -----------------------
 template <class F> int by_instance(trm_ctx* c, F&& launch) {
-    using NF = double;
-    using L32 = std::integral_constant<int, 32>;
-    using L64 = std::integral_constant<int, 64>;
     int rc = TRM_OK;
-    const bool deep = c->Nz > 32;
-    TRM_BY_HYD(c, rc = deep ? launch(std::integral_constant<int, H>{}, L64{}) : launch(std::integral_constant<int, H>{}, L32{}));
+    by_hyd(Policy<double>::hyd(c), [&](auto H) { by_lanes(c->Nz, [&](auto LPC) { rc = launch(H, LPC); }); });
     return rc;
 }
 // TRM_INFO_LAST_PROGRAM of a derivative launch: the instance and the family bits (trm_host.hpp)

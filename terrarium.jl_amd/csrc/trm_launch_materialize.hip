@@ -10,11 +10,9 @@ template <class NF> int MaterializeLaunch<NF>::run(trm_ctx* c) {
     const LaunchArgs<NF>& la = launch_args<NF>(c);
     const int part = c->part;
     c->part = -1;
-    const int lpc = c->Nz > 32 ? 64 : 32;
-    const dim3 grid = column_grid(c, lpc), block(TRM_STEP_BLOCK);
+    const dim3 grid = column_grid(c, lanes_per_column(c->Nz)), block(TRM_STEP_BLOCK);
     c->part = part;
-    if (lpc == 64) hipLaunchKernelGGL((k_materialize_closure<NF, 64>), grid, block, 0, c->stream, la.state, la.p);
-    else hipLaunchKernelGGL((k_materialize_closure<NF, 32>), grid, block, 0, c->stream, la.state, la.p);
+    by_lanes(c->Nz, [&](auto LPC) { hipLaunchKernelGGL((k_materialize_closure<NF, LPC()>), grid, block, 0, c->stream, la.state, la.p); });
     TRM_HIP(c, hipGetLastError());
     return TRM_OK;
 }

@@ -5,93 +5,71 @@
 
 namespace trmh {
 
-template <bool RICH, int LPC> static int launch_packed(trm_ctx* c, double dt, int finalize) {
-    using NF = float;
-    using P = Policy<float>;
-    const LaunchArgs<NF>& la = launch_args<NF>(c);
-    const int wkf = write_kf(c, finalize);
-    const long pairs = (ncols(c) + 1) / 2;
-    const View<NF>& sv = state_view<NF>(c);
+// the workgroups that step `n` columns, two per lane
+template <int LPC> static unsigned packed_blocks(long n) {
+    const long pairs = (n + 1) / 2;
     const long waves = (pairs + (64 / LPC) - 1) / (64 / LPC);
-    dim3 pg((unsigned)((waves * 64 + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK));
-    const int derive = P::derive_now<RICH>(c);
-    const int staged = P::staged_now<RICH>(c, true);
-    const dim3 blk(TRM_STEP_BLOCK);
-    // (the boundary kinds compiled in for the signatures that have an instance: TRM_OPT_BC_SIGNATURE, trm_kernels.hpp BCSIG)
-    const int sig = c->opt_bc_signature ? bc_signature_of(c) : -1;
-#define TRM_LAUNCH_PK(HYDV)                                                                                                                        \
-    do {                                                                                                                                           \
-        if (derive == DERIVE_T_LIQ) hipLaunchKernelGGL((k_step_pk<RICH, LPC, HYDV, DERIVE_T_LIQ>), pg, blk, 0, c->stream, sv, la.p, (float)dt, finalize, wkf, staged); \
-        else if (derive == DERIVE_LIQ && RICH && sig == BCSIG_LAND) hipLaunchKernelGGL((k_step_pk<RICH, LPC, HYDV, DERIVE_LIQ, RICH ? BCSIG_LAND : BCSIG_RUNTIME>), pg, blk, 0, c->stream, sv, la.p, (float)dt, finalize, wkf, staged); \
-        else if (derive == DERIVE_LIQ && RICH && sig == BCSIG_T_TOP) hipLaunchKernelGGL((k_step_pk<RICH, LPC, HYDV, DERIVE_LIQ, RICH ? BCSIG_T_TOP : BCSIG_RUNTIME>), pg, blk, 0, c->stream, sv, la.p, (float)dt, finalize, wkf, staged); \
-        else if (derive == DERIVE_LIQ) hipLaunchKernelGGL((k_step_pk<RICH, LPC, HYDV, DERIVE_LIQ>), pg, blk, 0, c->stream, sv, la.p, (float)dt, finalize, wkf, staged); \
-        else if (derive == DERIVE_LIQ_PSI) hipLaunchKernelGGL((k_step_pk<RICH, LPC, HYDV, DERIVE_LIQ_PSI>), pg, blk, 0, c->stream, sv, la.p, (float)dt, finalize, wkf, staged); \
-        else hipLaunchKernelGGL((k_step_pk<RICH, LPC, HYDV, DERIVE_NONE>), pg, blk, 0, c->stream, sv, la.p, (float)dt, finalize, wkf, staged);     \
-    } while (0)
-    if (P::hyd(c) == HYD_VG_N2) TRM_LAUNCH_PK(HYD_VG_N2);
-    else TRM_LAUNCH_PK(HYD_BC_LINEAR);
-#undef TRM_LAUNCH_PK
-    TRM_HIP(c, hipGetLastError());
-    {
-        const bool sig_instance = derive == DERIVE_LIQ && RICH && (sig == BCSIG_LAND || sig == BCSIG_T_TOP);
-        c->last_program = program_id(TRM_PROGRAM_PACKED_F32, P::hyd(c) == HYD_VG_N2 ? HYD_VG_N2 : HYD_BC_LINEAR, LPC, derive, staged, 1, sig_instance ? sig : -1);
-    }
+    return (unsigned)((waves * 64 + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK);
+}
+// (the id reports the run-time `staged` argument; BCSIG: the boundary kinds compiled in, for the signatures that have an instance)
+template <bool RICH, int LPC, int H, int DERIVE, int BCSIG = BCSIG_RUNTIME> static int run_packed(trm_ctx* c, double dt, int finalize, int staged) {
+    const LaunchArgs<float>& la = launch_args<float>(c);
+    TRM_LAUNCH(c, (k_step_pk<RICH, LPC, H, DERIVE, BCSIG>), dim3(packed_blocks<LPC>(ncols(c))), dim3(TRM_STEP_BLOCK), state_view<float>(c), la.p, (float)dt, finalize, write_kf(c, finalize), staged);
+    c->last_program = program_id(TRM_PROGRAM_PACKED_F32, H, LPC, DERIVE, staged, 1, BCSIG);
     return TRM_OK;
 }
-// k_step_pk_land: the packed LandModel step with the surface processes in the first workgroups of the launch
-template <int LPC> static int launch_packed_land(trm_ctx* c, double dt, int finalize) {
+int PackedLaunch::step(trm_ctx* c, double dt, int finalize) {
     using P = Policy<float>;
+    int rc = NO_INSTANCE;
+    by_bool(P::richards(c), [&](auto RICH) { by_lanes(c->Nz, [&](auto LPC) { by_compiled_hyd(P::hyd(c), [&](auto H) {
+        const int derive = P::derive_now<RICH()>(c);
+        const int staged = P::staged_now<RICH()>(c, true);
+        // (TRM_OPT_BC_SIGNATURE: the liquid fraction alone under Richards has the signature instances)
+        if constexpr (RICH()) {
+            if (derive == DERIVE_LIQ && c->opt_bc_signature)
+                by_packed_signature(bc_signature_of(c), [&](auto SIG) { rc = run_packed<true, LPC(), H(), DERIVE_LIQ, SIG()>(c, dt, finalize, staged); });
+        }
+        if (rc == NO_INSTANCE)
+            by_value<DERIVE_NONE, DERIVE_T_LIQ, DERIVE_LIQ, DERIVE_LIQ_PSI>(derive, [&](auto D) { rc = run_packed<RICH(), LPC(), H(), D()>(c, dt, finalize, staged); });
+    }); }); });
+    return launched(c, rc, "k_step_pk: no instance for this launch");
+}
+
+// k_step_pk_land: the packed LandModel step with the surface processes in the first workgroups of the launch
+template <int LPC, int H, int DERIVE> static int run_packed_land(trm_ctx* c, const FrontArgs& fa, double dt, int finalize, int staged) {
     const LaunchArgs<float>& la = launch_args<float>(c);
-    const View<float>& sv = la.state;
-    FrontArgs fa;
-    if (int rc = front_args(c, "k_step_pk_land", fa)) return rc;
-    const int wkf = write_kf(c, finalize);
-    const long pairs = (c->Nh + 1) / 2;
-    const long waves = (pairs + (64 / LPC) - 1) / (64 / LPC);
-    const dim3 pg((unsigned)fa.chain_blocks + (unsigned)((waves * 64 + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK)), blk(TRM_STEP_BLOCK);
-    const int derive = P::derive_now<true>(c);
-    const int staged = P::staged_now<true>(c, true);
-    const bool vg = P::hyd(c) == HYD_VG_N2;
-#define TRM_PK_LAND(HYDV, D) hipLaunchKernelGGL((k_step_pk_land<LPC, HYDV, D>), pg, blk, 0, c->stream, sv, la.p, (float)dt, finalize, wkf, staged, fa)
-    if (derive == DERIVE_LIQ) { if (vg) TRM_PK_LAND(HYD_VG_N2, DERIVE_LIQ); else TRM_PK_LAND(HYD_BC_LINEAR, DERIVE_LIQ); }
-    else if (derive == DERIVE_NONE) { if (vg) TRM_PK_LAND(HYD_VG_N2, DERIVE_NONE); else TRM_PK_LAND(HYD_BC_LINEAR, DERIVE_NONE); }
-    else return fail(c, TRM_EINVAL, "k_step_pk_land: no instance for this derivation mode");
-#undef TRM_PK_LAND
-    TRM_HIP(c, hipGetLastError());
-    c->last_program = program_id(TRM_PROGRAM_PACKED_LAND, vg ? HYD_VG_N2 : HYD_BC_LINEAR, LPC, derive, staged, 1, BCSIG_LAND);
+    TRM_LAUNCH(c, (k_step_pk_land<LPC, H, DERIVE>), dim3((unsigned)fa.chain_blocks + packed_blocks<LPC>(c->Nh)), dim3(TRM_STEP_BLOCK), la.state, la.p, (float)dt, finalize, write_kf(c, finalize), staged, fa);
+    c->last_program = program_id(TRM_PROGRAM_PACKED_LAND, H, LPC, DERIVE, staged, 1, BCSIG_LAND);
     return TRM_OK;
 }
 int PackedLaunch::step_land(trm_ctx* c, double dt, int finalize) {
-    return c->Nz > 32 ? launch_packed_land<64>(c, dt, finalize) : launch_packed_land<32>(c, dt, finalize);
-}
-
-int PackedLaunch::step(trm_ctx* c, double dt, int finalize) {
-    const bool deep = c->Nz > 32;
-    if (Policy<float>::richards(c)) return deep ? launch_packed<true, 64>(c, dt, finalize) : launch_packed<true, 32>(c, dt, finalize);
-    return deep ? launch_packed<false, 64>(c, dt, finalize) : launch_packed<false, 32>(c, dt, finalize);
+    using P = Policy<float>;
+    FrontArgs fa;
+    if (int rc = front_args(c, "k_step_pk_land", fa)) return rc;
+    const int derive = P::derive_now<true>(c), staged = P::staged_now<true>(c, true);
+    if (derive != DERIVE_NONE && derive != DERIVE_LIQ) return fail(c, TRM_EINVAL, "k_step_pk_land: no instance for this derivation mode");
+    int rc = NO_INSTANCE;
+    by_lanes(c->Nz, [&](auto LPC) { by_compiled_hyd(P::hyd(c), [&](auto H) { by_value<DERIVE_NONE, DERIVE_LIQ>(derive, [&](auto D) {
+        rc = run_packed_land<LPC(), H(), D()>(c, fa, dt, finalize, staged);
+    }); }); });
+    return launched(c, rc, "k_step_pk_land: no instance for the generic hydraulics");
 }
 
 // columns of part `qcol` step; the surface processes of part `qsurf` run beside them for ITS next column step (k_land_pk)
-template <int H, int LPC> static int launch_land_pk(trm_ctx* c, int qcol, int qsurf, double dt, int finalize, bool top_arrays) {
+template <int H, int LPC, bool TOP_ARRAYS> static int run_land_pk(trm_ctx* c, int qcol, int qsurf, double dt, int finalize) {
     const LaunchArgs<float>& la = launch_args<float>(c);
-    const View<float>&vc = la.part[qcol], &vs = la.part[qsurf];
-    if (top_arrays && !vs.top_T) return fail(c, TRM_EINVAL, "LandModel launch: the top-cell arrays were requested on a context that has none");
-    const int wkf = write_kf(c, finalize);
     const unsigned sblocks = (unsigned)((c->part_n[qsurf] + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK);
-    const dim3 block(TRM_STEP_BLOCK);
-    const long pairs = (c->part_n[qcol] + 1) / 2;
-    const long waves = (pairs + (64 / LPC) - 1) / (64 / LPC);
-    const dim3 grid(sblocks + (unsigned)((waves * 64 + TRM_STEP_BLOCK - 1) / TRM_STEP_BLOCK));
-    if (top_arrays) hipLaunchKernelGGL((k_land_pk<true, LPC, H, true>), grid, block, 0, c->stream, vc, la.p, (float)dt, finalize, wkf, vs, (int)sblocks);
-    else hipLaunchKernelGGL((k_land_pk<true, LPC, H, false>), grid, block, 0, c->stream, vc, la.p, (float)dt, finalize, wkf, vs, (int)sblocks);
-    TRM_HIP(c, hipGetLastError());
+    TRM_LAUNCH(c, (k_land_pk<true, LPC, H, TOP_ARRAYS>), dim3(sblocks + packed_blocks<LPC>(c->part_n[qcol])), dim3(TRM_STEP_BLOCK), la.part[qcol], la.p, (float)dt, finalize, write_kf(c, finalize), la.part[qsurf], (int)sblocks);
     c->last_program = program_id(TRM_PROGRAM_LAND_INTERLEAVED, H, LPC, DERIVE_NONE, 0, 1, -1);
     return TRM_OK;
 }
 template <> int LandLaunch<float>::run(trm_ctx* c, int qcol, int qsurf, double dt, int finalize, bool top_arrays) {
-    const bool deep = c->Nz > 32;
-    if (Policy<float>::hyd(c) == HYD_VG_N2) return deep ? launch_land_pk<HYD_VG_N2, 64>(c, qcol, qsurf, dt, finalize, top_arrays) : launch_land_pk<HYD_VG_N2, 32>(c, qcol, qsurf, dt, finalize, top_arrays);
-    return deep ? launch_land_pk<HYD_BC_LINEAR, 64>(c, qcol, qsurf, dt, finalize, top_arrays) : launch_land_pk<HYD_BC_LINEAR, 32>(c, qcol, qsurf, dt, finalize, top_arrays);
+    if (top_arrays && !launch_args<float>(c).part[qsurf].top_T) return fail(c, TRM_EINVAL, "LandModel launch: the top-cell arrays were requested on a context that has none");
+    int rc = NO_INSTANCE;
+    by_compiled_hyd(Policy<float>::hyd(c), [&](auto H) { by_lanes(c->Nz, [&](auto LPC) { by_bool(top_arrays, [&](auto TOPS) {
+        rc = run_land_pk<H(), LPC(), TOPS()>(c, qcol, qsurf, dt, finalize);
+    }); }); });
+    return launched(c, rc, "k_land_pk: no instance for the generic hydraulics");
 }
 
 }  // namespace trmh

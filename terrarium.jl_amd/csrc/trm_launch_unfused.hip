@@ -126,7 +126,7 @@ template <class NF> int Unfused<NF>::upload_series_rows(trm_ctx* c, double dt, i
 template <class NF> int Unfused<NF>::hydraulics(trm_ctx* c, const FieldSet& s) {
     const View<NF>& v = cached_view<NF>(c, s);
     const DevParams<NF>& p = launch_args<NF>(c).p;
-    TRM_BY_HYD(c, hipLaunchKernelGGL((k_hydraulics<NF, H>), cell_grid(c, c->Nz), dim3(256), 0, c->stream, v, p));
+    by_hyd(Policy<NF>::hyd(c), [&](auto H) { hipLaunchKernelGGL((k_hydraulics<NF, H()>), cell_grid(c, c->Nz), dim3(256), 0, c->stream, v, p); });
     TRM_HIP(c, hipGetLastError());
     return TRM_OK;
 }
@@ -134,11 +134,9 @@ template <class NF> int Unfused<NF>::surface(trm_ctx* c, const FieldSet& s, bool
     const View<NF>& v = cached_view<NF>(c, s);
     const DevParams<NF>& p = launch_args<NF>(c).p;
     if (from_state && c->top_valid && c->d_top3 && &s == &c->state) {   // (the top-cell arrays: only where they exist)
-        if (Policy<NF>::richards(c)) { TRM_BY_HYD(c, hipLaunchKernelGGL((k_surface<NF, true, H, true, true>), col_grid(c), dim3(256), 0, c->stream, v, p)); }
-        else { TRM_BY_HYD(c, hipLaunchKernelGGL((k_surface<NF, false, H, true, true>), col_grid(c), dim3(256), 0, c->stream, v, p)); }
+        by_bool(Policy<NF>::richards(c), [&](auto RICH) { by_hyd(Policy<NF>::hyd(c), [&](auto H) { hipLaunchKernelGGL((k_surface<NF, RICH(), H(), true, true>), col_grid(c), dim3(256), 0, c->stream, v, p); }); });
     } else if (from_state) {
-        if (Policy<NF>::richards(c)) { TRM_BY_HYD(c, hipLaunchKernelGGL((k_surface<NF, true, H, true, false>), col_grid(c), dim3(256), 0, c->stream, v, p)); }
-        else { TRM_BY_HYD(c, hipLaunchKernelGGL((k_surface<NF, false, H, true, false>), col_grid(c), dim3(256), 0, c->stream, v, p)); }
+        by_bool(Policy<NF>::richards(c), [&](auto RICH) { by_hyd(Policy<NF>::hyd(c), [&](auto H) { hipLaunchKernelGGL((k_surface<NF, RICH(), H(), true, false>), col_grid(c), dim3(256), 0, c->stream, v, p); }); });
     } else {
         if (Policy<NF>::richards(c)) hipLaunchKernelGGL((k_surface<NF, true, HYD_GENERIC, false, false>), col_grid(c), dim3(256), 0, c->stream, v, p);
         else hipLaunchKernelGGL((k_surface<NF, false, HYD_GENERIC, false, false>), col_grid(c), dim3(256), 0, c->stream, v, p);
@@ -197,7 +195,7 @@ template <class NF> int Unfused<NF>::closure_hydrology(trm_ctx* c, const FieldSe
     const View<NF>& v = cached_view<NF>(c, s);
     const DevParams<NF>& p = launch_args<NF>(c).p;
     if (with_psi) {
-        TRM_BY_HYD(c, (launch_closure_hydrology<NF, true, true, H>(c, v, p)));
+        by_hyd(Policy<NF>::hyd(c), [&](auto H) { launch_closure_hydrology<NF, true, true, H()>(c, v, p); });
     } else if (with_adjust) {
         launch_closure_hydrology<NF, false, true, HYD_GENERIC>(c, v, p);
     } else {

@@ -22,8 +22,7 @@ template <class NF> int Veg<NF>::surface_veg_launch(trm_ctx* c, const View<NF>& 
     const VegDev<NF> vp = Policy<NF>::veg_dev(c);
     const dim3 blocks((unsigned)((ncols(c) + 63) / 64));   // 64 columns per 256-thread workgroup
     // (the kernel is bound by cold instruction fetch: the hydraulics of the top-face conductivity are compiled in)
-    if (c->Nzp == 32) { TRM_BY_HYD(c, hipLaunchKernelGGL((k_surface_veg<NF, 32, H>), blocks, dim3(256), 0, c->stream, v, p, vv, vp, a)); }
-    else if (c->Nzp == 64) { TRM_BY_HYD(c, hipLaunchKernelGGL((k_surface_veg<NF, 64, H>), blocks, dim3(256), 0, c->stream, v, p, vv, vp, a)); }
+    if (c->Nzp == 32 || c->Nzp == 64) by_hyd(Policy<NF>::hyd(c), [&](auto H) { by_value<32, 64>(c->Nzp, [&](auto NZP) { hipLaunchKernelGGL((k_surface_veg<NF, NZP(), H()>), blocks, dim3(256), 0, c->stream, v, p, vv, vp, a); }); });
     else hipLaunchKernelGGL((k_surface_veg<NF, 0, HYD_GENERIC>), col_grid(c), dim3(256), 0, c->stream, v, p, vv, vp, a);
     TRM_HIP(c, hipGetLastError());
     return TRM_OK;
