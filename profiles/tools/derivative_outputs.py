@@ -1,6 +1,6 @@
 """sha256 of the tangents / gradients and TRM_INFO_LAST_PROGRAM of every (ride, tape, layout) of the derivative launches: what a
-host-side change of the launch layer must leave bit for bit.  Rides: none, boundary values, thermal parameters, boundary series; the
-tangent, and the adjoint on the per-step tape and on a checkpointed tape of K = 4; Nz = 24 (32 lanes per column) and 40 (64).
+host-side change of the launch layer must leave bit for bit.  Rides: none, boundary values, thermal parameters, boundary series, and
+thermal parameters with a boundary series (derivative_series_params); the tangent, and the adjoint on the per-step tape and on a checkpointed tape of K = 4; Nz = 24 (32 lanes per column) and 40 (64).
     python profiles/tools/derivative_outputs.py OUTFILE      (library: TRM_LIBRARY, or the tree's)
 Run once per library and compare the two files (profiles/r13/derivative_outputs_sha256.txt)."""
 import hashlib
@@ -31,17 +31,19 @@ def fresh(Nz, ride):
     w = W.make_workload("heat", lat[sel], lon[sel], Nz)
     d = W.setup_device(w, steps_per_launch=SPL)
     d.closure()
-    if ride == "series":
+    if ride in ("series", "param_series"):
         kind, value = w["bcs"][TOP]
         times = np.linspace(0.0, STEPS * w["dt"], NODES)
         vals = np.asarray(value, dtype=np.float64)[None, :] + np.linspace(-2.0, 3.0, NODES)[:, None]
         d.set_bc_series(*TOP, kind, times, vals.copy())
         d.set_option("derivative_series", 1)
+        if ride == "param_series":
+            d.set_option("derivative_series_params", 1)
     return w, d
 
 
 for Nz in (24, 40):
-    for ride in ("none", "bc", "param", "series"):
+    for ride in ("none", "bc", "param", "series", "param_series"):
         rng = np.random.default_rng(7)
         w, d = fresh(Nz, ride)
         Nh = w["Nh"]
@@ -50,9 +52,9 @@ for Nz in (24, 40):
         d.set_tangent("internal_energy", rng.standard_normal((Nz, Nh)))
         if ride in ("bc", "param"):
             d.set_bc_tangent(*TOP, rng.standard_normal(Nh))
-        if ride == "param":
+        if ride in ("param", "param_series"):
             d.set_param_tangent({"k_water": 1.0, "k_mineral": -0.5, "c_ice": 2.0e3, "c_organic": 1.0e3})
-        if ride == "series":
+        if ride in ("series", "param_series"):
             d.set_bc_series_tangent(*TOP, rng.standard_normal((NODES, Nh)))
         d.tangent_closure()
         for name in ("temperature", "liquid_water_fraction"):
@@ -70,7 +72,7 @@ for Nz in (24, 40):
             d.open_adjoint(STEPS if K == 0 else -(-STEPS // K), checkpoint_every=K or None)
             if ride == "bc":
                 d.open_bc_gradient()
-            if ride == "param":
+            if ride in ("param", "param_series"):
                 d.open_param_gradient()
             d.step_record(w["dt"], STEPS)
             prog(combo, "record", d)
@@ -82,10 +84,10 @@ for Nz in (24, 40):
             put(combo, "internal_energy", d.cotangent("internal_energy"))
             if ride in ("bc", "param"):
                 put(combo, "bc_temperature_top", d.bc_gradient(*TOP))
-            if ride == "param":
+            if ride in ("param", "param_series"):
                 for name in ("k_water", "k_mineral", "c_ice", "c_organic"):
                     put(combo, "param_" + name, d.param_gradient(name))
-            if ride == "series":
+            if ride in ("series", "param_series"):
                 put(combo, "series_temperature_top", d.bc_series_gradient(*TOP))
             assert d.status() == 0
 

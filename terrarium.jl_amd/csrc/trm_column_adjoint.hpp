@@ -11,7 +11,14 @@
 // The boundary faces use the transposed halo rules: a Value halo extrapolates through a constant (dT - dT_halo = +-dT dzf / (dzf / 2)),
 // a Gradient halo copies the edge cell (no term), the mirror policy's halo conductivity is the edge cell's (its A counts twice), the dry
 // halo cell of the reference-zero policy has dkappa = 0.  Flux boundary terms are constants.
-// BCGRAD (trm_adjoint_bc_open): the sweep also forms dL/d(boundary value) of the four pairs (temperature, internal-energy flux) x (bottom,
+// The sweeps take what rides along as one template parameter, Ride R (trm_kernels.hpp); SweepArgs<CKPT, R> holds exactly its parts:
+//   R                  BCGRAD  SERIES  PGRAD   SweepArgs<CKPT, R> = TapeArgs<CKPT> +
+//   RIDE_NONE            -       -       -     nothing
+//   RIDE_BC              x       -       -     BcGradPtrs g
+//   RIDE_PARAM           x       -       x     BcGradPtrs g, ParamGradPtrs pg
+//   RIDE_SERIES          x       x       -     BcGradPtrs g, SeriesGradPtrs sg
+//   RIDE_PARAM_SERIES    x       x       x     BcGradPtrs g, SeriesGradPtrs sg, ParamGradPtrs pg
+// BCGRAD (ride_has_bc, trm_adjoint_bc_open): the sweep also forms dL/d(boundary value) of the four pairs (temperature, internal-energy flux) x (bottom,
 // top), the transposes of the seed terms of k_column_tangent<.., BCSEED>: with pB / pB_t the cotangents of the boundary-face differences
 //   Value     top  += div_const(pB_t, dzf / 2) dzf,   bottom += -(div_const(pB, dzf / 2) dzf)
 //   Gradient  top  += pB_t dzf,                      bottom += pB dzf
@@ -19,7 +26,7 @@
 // summed in registers of the edge lanes over the taped steps, newest first: the launch that folds starts from 0, every other launch from
 // what the launch before stored, and the owning edge lane stores once at the end -- one strictly sequential sum per column and pair,
 // whatever the split into launches or segments.  No atomics.  lam is formed by the operations it was.
-// PGRAD (trm_adjoint_param_open, always with BCGRAD): the sweep also forms the cotangents of the eight thermal numbers of DevParams, the
+// PGRAD (ride_has_params, trm_adjoint_param_open, always with BCGRAD): the sweep also forms the cotangents of the eight thermal numbers of DevParams, the
 // transposes of the seed terms of k_column_tangent<.., PSEED>, per cell: with T~ and kappa~ of the cell as above, m = -(T / C) and s of
 // kappa = s^2,
 //   C~ = m T~        onto c_water (x water), c_ice (x ice), c_air (x air), C0          (the fold: m wT of the stored state)
@@ -28,7 +35,7 @@
 // Each lane sums its own cell's eight values in registers over the taped steps, newest first, carried from launch to launch in eight
 // fields [Nh][Nzp] like the boundary sums: strictly sequential per cell.  k_param_reduce sums a column's cells in ascending order and
 // applies the host's chain rule to the ten parameters.
-// SERIES (TRM_OPT_DERIVATIVE_SERIES, always with BCGRAD; trm_series_derivative.hpp): the record evaluates the boundary series in front of
+// SERIES (ride_has_series, TRM_OPT_DERIVATIVE_SERIES, always with BCGRAD; trm_series_derivative.hpp): the record evaluates the boundary series in front of
 // every step as column_program<.., SERIES> does; the sweep takes each step's temperature values from the series again (fetched a step
 // ahead, with the next tape slot) and a seriesed pair's term goes w1 term onto node n1 and w2 term onto node n2 of a [nt][Nh]
 // accumulator instead of the per-column sum: the owning edge lane holds the two sums of the current bracket and stores / loads them
@@ -46,25 +53,23 @@
 
 namespace trm {
 
-// Fourth kernel argument of k_column_record / k_column_adjoint
-struct AdjointArgs {
+// Fourth kernel argument of k_column_record (TapeArgs<STRIDED>) and of the sweeps (SweepArgs<CKPT, R>, below).  Either tape:
+struct TapeFields {
     double *lU, *lT, *lliq;   // the cotangent fields ([Nh][Nzp] like the state); lU carries lam between launches
     double* tape;             // the slot of the first step of this launch; slot s of the launch at tape + s * slot_elems
     long long slot_elems;     // Nh * Nzp
     int generic;              // 1: Gradient on temperature off the branch-free kinds (k_step_wave's halos, column_tendencies_generic)
     int fold;                 // backward: 1 in the first launch of a sweep: lam_n = wU + a_n wT + b_n wliq of the stored state, wT = wliq = 0 after
 };
+// ... and, STRIDED (the checkpointed tape, trm_column_adjoint_ckpt.hpp: `tape` is the slot of the record's first store, or the segment's
+// checkpoint): the step of the launch that stores first (>= nsteps: none does), and the interval K
+template <bool STRIDED> struct TapeArgs : TapeFields {};
+template <> struct TapeArgs<true> : TapeFields {
+    int first, every;
+};
 // the boundary-gradient accumulators of a BCGRAD sweep, [Nh] each: dL/d(temperature value) and dL/d(internal-energy flux), bottom / top
 struct BcGradPtrs {
     double *gTb, *gTt, *gUb, *gUt;
-};
-// ... of k_column_adjoint<HYD, LPC, true, AdjointBcArgs>
-struct AdjointBcArgs : AdjointArgs {
-    BcGradPtrs g;
-};
-// ... of k_column_adjoint<HYD, LPC, true, AdjointSeriesArgs, false, true>: and the node accumulators of the seriesed pairs
-struct AdjointSeriesArgs : AdjointBcArgs {
-    SeriesGradPtrs sg;
 };
 // a lane's running sums (the bottom lane owns Tb and Ub, the top lane Tt and Ut; the other lanes carry zeros)
 struct BcGrad {
@@ -123,14 +128,18 @@ TRM_DEV void series_grad_store(const ColumnArgs<double>& a, const SeriesGradPtrs
 struct ParamGradPtrs {
     double* g[8];
 };
-// ... of k_column_adjoint<HYD, LPC, true, AdjointParamArgs, true>
-struct AdjointParamArgs : AdjointBcArgs {
+// Fourth kernel argument of k_column_adjoint (CKPT = false) / k_column_adjoint_ckpt (true): the tape, then what the ride carries
+struct BcGradPart {
+    BcGradPtrs g;
+};
+struct SeriesGradPart {
+    SeriesGradPtrs sg;
+};
+struct ParamGradPart {
     ParamGradPtrs pg;
 };
-// ... of k_column_adjoint<HYD, LPC, true, AdjointParamSeriesArgs, true, true>: the node accumulators and the per-cell parameter accumulators
-struct AdjointParamSeriesArgs : AdjointSeriesArgs {
-    ParamGradPtrs pg;
-};
+template <bool CKPT, Ride R>
+struct SweepArgs : TapeArgs<CKPT>, PartIf<ride_has_bc(R), BcGradPart>, PartIf<ride_has_series(R), SeriesGradPart>, PartIf<ride_has_params(R), ParamGradPart> {};
 // a lane's running sums for its own cell
 struct ParamGrad {
     double sk_water = 0.0, sk_ice = 0.0, sk_air = 0.0, s0 = 0.0;
@@ -213,14 +222,14 @@ TRM_DEV void record_flux_U(const View<double>& v, const LaneInfo& ln, int ii, bo
 }
 
 // `a.nsteps` ForwardEuler steps of the state, U_k stored into tape slot k before step k; the outputs are those of a finalizing trm_step.
-// STRIDED (Args = CheckpointArgs, trm_column_adjoint_ckpt.hpp: the record of a checkpointed tape): U_k is stored before the steps
+// STRIDED (trm_column_adjoint_ckpt.hpp: the record of a checkpointed tape): U_k is stored before the steps
 // aa.first, aa.first + aa.every, ... of the launch alone, into the slots from aa.tape on -- a wave-uniform branch, everything else the
 // same.  (One kernel template and not a device function under two kernels: behind a call the existing instances came out of the
 // register allocator with other registers and three more instructions; as a defaulted template parameter they compile to the code
 // they had.)
 // SERIES: the seriesed boundary values are formed in front of every step (series_boundary_step), the last step writes them back.
-template <int HYD, int LPC, bool STRIDED = false, class Args = AdjointArgs, bool SERIES = false>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args aa) {
+template <int HYD, int LPC, bool STRIDED, bool SERIES>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, TapeArgs<STRIDED> aa) {
     using NF = double;
     int ii;
     size_t e;
@@ -402,12 +411,11 @@ TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, con
 }
 
 // The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
-// BCGRAD (Args = AdjointBcArgs): the boundary gradients ride along; the instances without are the code they were.
-// PGRAD (Args = AdjointParamArgs, with BCGRAD): and the per-cell parameter sums.
-// SERIES (Args = AdjointSeriesArgs, with BCGRAD): a.series_rows holds the rows of this launch's taped steps, oldest first.
-// PGRAD and SERIES (Args = AdjointParamSeriesArgs): both.
-template <int HYD, int LPC, bool BCGRAD = false, class Args = AdjointArgs, bool PGRAD = false, bool SERIES = false>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args aa) {
+// BCGRAD: the boundary gradients ride along.  PGRAD: and the per-cell parameter sums.  SERIES: a.series_rows holds the rows of this
+// launch's taped steps, oldest first.
+template <int HYD, int LPC, Ride R>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, SweepArgs<false, R> aa) {
+    constexpr bool BCGRAD = ride_has_bc(R), PGRAD = ride_has_params(R), SERIES = ride_has_series(R);
     using NF = double;
     int ii;
     size_t e;

@@ -16,41 +16,16 @@
 
 namespace trm {
 
-// Fourth kernel argument of k_column_record<HYD, LPC, true, CheckpointArgs> (the strided record) / k_column_adjoint_ckpt
-struct CheckpointArgs {
-    double *lU, *lT, *lliq;   // the cotangent fields; lU carries lam between launches
-    double* tape;             // record: the slot of the launch's first store; backward: the segment's checkpoint slot
-    long long slot_elems;     // Nh * Nzp
-    int generic;              // as AdjointArgs
-    int fold;                 // backward: 1 in the first launch of a sweep
-    int first, every;         // record: the step of the launch that stores first (>= nsteps: none does), and the interval K
-};
-// ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointBcArgs>: and the boundary-gradient accumulators (trm_column_adjoint.hpp)
-struct CheckpointBcArgs : CheckpointArgs {
-    BcGradPtrs g;
-};
-// ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointSeriesArgs, false, true>: and the node accumulators of the seriesed pairs
-struct CheckpointSeriesArgs : CheckpointBcArgs {
-    SeriesGradPtrs sg;
-};
-// ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointParamArgs, true>: and the per-cell parameter accumulators
-struct CheckpointParamArgs : CheckpointBcArgs {
-    ParamGradPtrs pg;
-};
-// ... of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointParamSeriesArgs, true, true>: both
-struct CheckpointParamSeriesArgs : CheckpointSeriesArgs {
-    ParamGradPtrs pg;
-};
-
 // lam pulled back through one segment: the checkpoint U_c at ca.tape and the a.nsteps - 1 states behind it under a.dt.
 // Dynamic LDS: a.nsteps * TRM_STEP_BLOCK doubles.
-// BCGRAD (Args = CheckpointBcArgs): the boundary gradients as in k_column_adjoint, added in the same order -- the per-step tape's sums.
-// PGRAD (Args = CheckpointParamArgs, with BCGRAD): and the per-cell parameter sums, likewise.
-// SERIES (Args = CheckpointSeriesArgs, with BCGRAD): a.series_rows holds the rows of the segment's steps, oldest first; the recompute
+// The ride R and its flags are k_column_adjoint's (the table of trm_column_adjoint.hpp); the fourth argument is SweepArgs<true, R>.
+// BCGRAD, PGRAD: the boundary gradients and the per-cell parameter sums as in k_column_adjoint, added in the same order.
+// SERIES: a.series_rows holds the rows of the segment's steps, oldest first; the recompute
 // loop evaluates the series as the record did, the backward loop takes the temperature values again and sums onto the nodes.
-// PGRAD and SERIES (Args = CheckpointParamSeriesArgs): both, the parameter terms at each recomputed state's series temperatures.
-template <int HYD, int LPC, bool BCGRAD = false, class Args = CheckpointArgs, bool PGRAD = false, bool SERIES = false>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ca) {
+// PGRAD and SERIES: both, the parameter terms at each recomputed state's series temperatures.
+template <int HYD, int LPC, Ride R>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<double> v, DevParams<double> p, ColumnArgs<double> a, SweepArgs<true, R> ca) {
+    constexpr bool BCGRAD = ride_has_bc(R), PGRAD = ride_has_params(R), SERIES = ride_has_series(R);
     using NF = double;
     extern __shared__ double seg[];
     int ii;

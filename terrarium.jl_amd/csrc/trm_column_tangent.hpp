@@ -12,13 +12,20 @@
 //                dwater = sat por dliq = -dice (NoFlow: sat is constant); the dry halo cell of the reference-zero policy has dkappa = 0
 //   face flux    qT = -(kappa + kappa_m) / 2 * (T - T_m) * rdz: the product rule, halo values formed as the primal forms them
 //   step         dU' = dU + dgU * dt (boundary values are constants: their tangent is 0 -- unless BCSEED, below)
-// BCSEED (TangentBcArgs: trm_tangent_bc_upload has seeded a boundary value): the per-column seeds dbTb, dbTt of the temperature values
+// The kernels take what rides along as one template parameter, Ride R (trm_kernels.hpp), and TangentArgs<R> holds exactly that ride's parts:
+//   R                  BCSEED  SERIES  PSEED   TangentArgs<R> = TangentFields +
+//   RIDE_NONE            -       -       -     nothing
+//   RIDE_BC              x       -       -     BcSeeds
+//   RIDE_PARAM           x       -       x     BcSeeds, ParamSeeds s
+//   RIDE_SERIES          x       x       -     BcSeeds, SeriesSeeds
+//   RIDE_PARAM_SERIES    x       x       x     BcSeeds, SeriesSeeds, ParamSeeds s
+// BCSEED (ride_has_bc: trm_tangent_bc_upload has seeded a boundary value): the per-column seeds dbTb, dbTt of the temperature values
 // and dF_b, dF_t of the internal-energy fluxes enter where the primal reads the value,
 //   Value     dT_t = dT + div_const(dbTt - dT, dzf / 2) dzf,   dT_b = dT + div_const(dT - dbTb, dzf / 2) (-dzf)
 //   Gradient  dT_t = dT + dbTt dzf,   dT_b = dT + dbTb (-dzf)   (also where the primal knows a zero Gradient at the bottom and skips it)
 //   Flux      dU' = dU + (dgU + dflux_U) dt,  dflux_U = flux_term_bottom(dF_b) on the bottom lane, -flux_term_top(dF_t) on the top lane
 // and a pair whose kind reads no value has none.  The primal half is the same code.
-// PSEED (TangentParamArgs: trm_tangent_param_set has seeded a thermal parameter; always together with BCSEED): the seeds of the eight
+// PSEED (ride_has_params: trm_tangent_param_set has seeded a thermal parameter; always together with BCSEED): the seeds of the eight
 // numbers DevParams holds -- dsk_i of the square roots sk_i, ds0 of s0 = kterm_mineral + kterm_organic, dc_i, dC0 of C0 = cterm_mineral +
 // cterm_organic -- ride in scalar registers and enter where the primal reads the parameter,
 //   closure      thawed / frozen: T = N / C with N free of the parameters: dT += m dC_p, m = -(T / C), dC_p = dc_w water + dc_i ice +
@@ -27,10 +34,10 @@
 //   dry halo     of the reference-zero policy: s_halo = sk_air por + s0, dkappa_halo = 2 s_halo (dsk_a por + ds0)
 // Every tangent operation is linear in (dU, dT, dliq) and the seeds with no additive constant, so scaling the seeds by a power of two
 // scales every tangent bit for bit.
-// SERIES (TangentSeriesArgs, always together with BCSEED; trm_series_derivative.hpp): in front of every step the seriesed pairs among the four
+// SERIES (ride_has_series, always together with BCSEED; trm_series_derivative.hpp): in front of every step the seriesed pairs among the four
 // take the value of their series (the primal: as column_program<.., SERIES>) and the seed s[n1] w1 + s[n2] w2 of seeds shaped like the
 // series, [nt][Nh]; a pair without a series keeps its constant value and its per-column seed.
-// PSEED and SERIES (TangentParamSeriesArgs, TRM_OPT_DERIVATIVE_SERIES_PARAMS): the parameter terms of a step are formed at the boundary
+// PSEED and SERIES (RIDE_PARAM_SERIES, TRM_OPT_DERIVATIVE_SERIES_PARAMS): the parameter terms of a step are formed at the boundary
 // values the series gave that step -- the Value halos in (T - T_m) of dkappa's product, the dry halo's dkappa_halo -- and both families
 // of seeds enter one dgU; the closure terms read no boundary value.
 #pragma once
@@ -39,34 +46,34 @@
 
 namespace trm {
 
-// Fourth kernel argument of k_column_tangent: the tangent fields ([Nh][Nzp] like the state) and which halo form trm_step would take
-struct TangentArgs {
+// A part of a kernel-argument struct that a ride may not carry: the part, or an empty base of a type of its own (it takes no room)
+template <class Part> struct Absent {};
+template <bool HAS, class Part> using PartIf = std::conditional_t<HAS, Part, Absent<Part>>;
+
+// Fourth kernel argument of k_column_tangent, TangentArgs<R>: the tangent fields ([Nh][Nzp] like the state) and trm_step's halo form,
+struct TangentFields {
     double *dU, *dT, *dliq;
     int generic;      // 1: Gradient on temperature off the branch-free kinds (k_step_wave's halos, column_tendencies_generic)
 };
-// ... of k_column_tangent<HYD, LPC, true, TangentBcArgs>: and the seeds of the boundary values, [Nh] each
-struct TangentBcArgs : TangentArgs {
+// ride_has_bc: and the seeds of the boundary values, [Nh] each,
+struct BcSeeds {
     const double *sTb, *sTt;   // d(temperature value) at the bottom / top: of a Value or a Gradient condition
     const double *sUb, *sUt;   // d(internal-energy flux) at the bottom / top
 };
-// the seeds of the eight thermal numbers of DevParams (the host's chain rule has taken the ten parameters there): wave-uniform, by value
+// ride_has_series: and the seeds of the seriesed pairs, [nt][Nh] each, by slot (null: the pair has no series)
+struct SeriesSeeds {
+    const double* sn[4];
+};
+// ride_has_params: and the seeds of the eight thermal numbers of DevParams (the host's chain rule took the ten parameters there), by value
 struct ParamSeeds {
     double dsk_water, dsk_ice, dsk_air, ds0;
     double dc_water, dc_ice, dc_air, dC0;
 };
-// ... of k_column_tangent<HYD, LPC, true, TangentParamArgs, true>
-struct TangentParamArgs : TangentBcArgs {
+struct ParamSeedsPart {
     ParamSeeds s;
 };
-// ... of k_column_tangent<HYD, LPC, true, TangentSeriesArgs, false, true>: and the seeds of the seriesed pairs, [nt][Nh] each, by slot
-// (null: the pair has no series)
-struct TangentSeriesArgs : TangentBcArgs {
-    const double* sn[4];
-};
-// ... of k_column_tangent<HYD, LPC, true, TangentParamSeriesArgs, true, true>: the seeds of the seriesed pairs and of the thermal numbers
-struct TangentParamSeriesArgs : TangentSeriesArgs {
-    ParamSeeds s;
-};
+template <Ride R>   // (the order a kernel reads by offset: fields, bc, series, params)
+struct TangentArgs : TangentFields, PartIf<ride_has_bc(R), BcSeeds>, PartIf<ride_has_series(R), SeriesSeeds>, PartIf<ride_has_params(R), ParamSeedsPart> {};
 
 // tangent of the energy closure at (U, sat) -- C is the heat capacity the primal closure formed
 TRM_DEV void closure_tangent(const DevParams<double>& p, double U, double sat, double C, double dU, double& dliq, double& dT) {
@@ -158,12 +165,11 @@ TRM_DEV double tendency_tangent(const View<double>& v, const DevParams<double>& 
 
 // `a.nsteps` ForwardEuler steps of the state and its tangent; the outputs are those of a finalizing trm_step (the tendency of the
 // last step, hydraulic_conductivity of the new state) and the three tangents.
-// BCSEED (Args = TangentBcArgs): the boundary seeds are loaded once in front of the step loop; the instances without are the code they were.
-// PSEED (Args = TangentParamArgs, with BCSEED): the parameter seeds are kernel arguments.
-// SERIES (Args = TangentSeriesArgs, with BCSEED): values and seeds of the seriesed pairs are formed in front of every step.
-// PSEED and SERIES (Args = TangentParamSeriesArgs): both; the parameter terms take the step's boundary values.
-template <int HYD, int LPC, bool BCSEED = false, class Args = TangentArgs, bool PSEED = false, bool SERIES = false>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> v, DevParams<double> p, ColumnArgs<double> a, Args ta) {
+// BCSEED: the boundary seeds are loaded once in front of the step loop.  PSEED: the parameter seeds are kernel arguments.  SERIES: values
+// and seeds of the seriesed pairs are formed in front of every step; with PSEED the parameter terms take the step's boundary values.
+template <int HYD, int LPC, Ride R>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> v, DevParams<double> p, ColumnArgs<double> a, TangentArgs<R> ta) {
+    constexpr bool BCSEED = ride_has_bc(R), PSEED = ride_has_params(R), SERIES = ride_has_series(R);
     using NF = double;
     constexpr int CPW = 64 / LPC;
     LaneInfo ln;
@@ -240,6 +246,8 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
         dflux_U = ln.is_bot ? dU_b : top_term;
     }
 
+    const ParamSeeds* ps = nullptr;
+    if constexpr (PSEED) ps = &ta.s;
     Cell<NF> n = c;
     Frac<NF> f_new{};
     NF gU_out = 0.0;
@@ -249,11 +257,8 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
         const Frac<NF>* pre = step > 0 ? &f_new : nullptr;
         const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
                                        : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
-        NF dgU;
-        if constexpr (PSEED && SERIES) dgU = tendency_tangent<LPC, BCSEED, true>(v, p, L, ln, ii, c, dT, dliq, bc.bTb, bc.bTt, generic, dbTb, dbTt, &ta.s);
-        else if constexpr (PSEED) dgU = tendency_tangent<LPC, BCSEED, true>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt, &ta.s);
-        else if constexpr (SERIES) dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bc.bTb, bc.bTt, generic, dbTb, dbTt);
-        else dgU = tendency_tangent<LPC, BCSEED>(v, p, L, ln, ii, c, dT, dliq, bTb, bTt, generic, dbTb, dbTt);
+        // (the temperature values: the series' of this step, or the launch's constants)
+        const NF dgU = tendency_tangent<LPC, BCSEED, PSEED>(v, p, L, ln, ii, c, dT, dliq, SERIES ? bc.bTb : bTb, SERIES ? bc.bTt : bTt, generic, dbTb, dbTt, ps);
         NF gU = t.gU, gS = t.gS, z0;
         column_advance<NF, false, LPC>(v, L, ln, Nz, bc, c.U, c.sat, gU, gS, a.dt, n, z0, bad);
         f_new = column_closure<NF, false, HYD>(p, L, z0, n, viol);
@@ -286,9 +291,10 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_tangent(View<double> 
     if (viol && ln.act) atomicOr(v.status, viol);
 }
 
-// trm_tangent_closure: (dT, dliq) of the stored (U, sat) and dU, one thread per cell of the device layout.  PSEED (Args = TangentParamArgs,
-// trm_tangent_param_set): and the heat-capacity term.  A template, so that only the translation unit that launches it holds a copy.
-template <class Args, bool PSEED = false> __global__ void __launch_bounds__(256) k_closure_tangent(View<double> v, DevParams<double> p, Args ta) {
+// trm_tangent_closure: (dT, dliq) of the stored (U, sat) and dU, one thread per cell of the device layout.  PSEED (trm_tangent_param_set):
+// and the heat-capacity term.  A template, so that only the translation unit that launches it holds a copy.
+template <Ride R> __global__ void __launch_bounds__(256) k_closure_tangent(View<double> v, DevParams<double> p, TangentArgs<R> ta) {
+    constexpr bool PSEED = ride_has_params(R);
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)v.Nh * (size_t)v.Nzp || (int)(e % (size_t)v.Nzp) >= v.Nz) return;
     const double U = v.U[e], sat = v.sat[e];

@@ -10,23 +10,22 @@ using namespace trmh;
 namespace trmh {
 // The derivative launchers: each ride's instantiation lives in a translation unit of its own (trm_host.hpp, trm_launch_derivative.inl)
 int TangentLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride) {
-    switch (ride) {
-        case RIDE_BC: return tangent_step<RIDE_BC>(c, dt, nsteps);
-        case RIDE_PARAM: return tangent_step<RIDE_PARAM>(c, dt, nsteps);
-        case RIDE_SERIES: return tangent_step<RIDE_SERIES>(c, dt, nsteps);
-        case RIDE_PARAM_SERIES: return tangent_step<RIDE_PARAM_SERIES>(c, dt, nsteps);
-        default: return tangent_step<RIDE_NONE>(c, dt, nsteps);
-    }
+    int rc = NO_INSTANCE;
+    by_ride(ride, [&](auto r) { rc = tangent_step<decltype(r)::value>(c, dt, nsteps); });
+    return launched(c, rc, "k_column_tangent: a ride without an instance");
 }
-int TangentLaunch::closure(trm_ctx* c, Ride ride) { return ride == RIDE_PARAM ? tangent_closure<RIDE_PARAM>(c) : tangent_closure<RIDE_NONE>(c); }
+// k_closure_tangent reads no boundary value: it has the instances RIDE_NONE and RIDE_PARAM (trm_launch_column_tangent{,_param}.hip), and
+// every other ride takes RIDE_NONE's
+constexpr Ride closure_ride(Ride r) { return r == RIDE_PARAM ? RIDE_PARAM : RIDE_NONE; }
+int TangentLaunch::closure(trm_ctx* c, Ride ride) {
+    int rc = NO_INSTANCE;
+    by_ride(ride, [&](auto r) { rc = tangent_closure<closure_ride(decltype(r)::value)>(c); });
+    return launched(c, rc, "k_closure_tangent: a ride without an instance");
+}
 template <bool CKPT> static int backward_by_ride(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) {
-    switch (ride) {
-        case RIDE_BC: return adjoint_backward<CKPT, RIDE_BC>(c, dt, nsteps, slot, fold);
-        case RIDE_PARAM: return adjoint_backward<CKPT, RIDE_PARAM>(c, dt, nsteps, slot, fold);
-        case RIDE_SERIES: return adjoint_backward<CKPT, RIDE_SERIES>(c, dt, nsteps, slot, fold);
-        case RIDE_PARAM_SERIES: return adjoint_backward<CKPT, RIDE_PARAM_SERIES>(c, dt, nsteps, slot, fold);
-        default: return adjoint_backward<CKPT, RIDE_NONE>(c, dt, nsteps, slot, fold);
-    }
+    int rc = NO_INSTANCE;
+    by_ride(ride, [&](auto r) { rc = adjoint_backward<CKPT, decltype(r)::value>(c, dt, nsteps, slot, fold); });
+    return launched(c, rc, "k_column_adjoint: a ride without an instance");
 }
 int AdjointLaunch::record(trm_ctx* c, double dt, int nsteps, int slot, bool series) {
     return series ? adjoint_record<false, true>(c, dt, nsteps, slot, 0, 1) : adjoint_record<false, false>(c, dt, nsteps, slot, 0, 1);

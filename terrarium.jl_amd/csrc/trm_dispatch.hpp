@@ -29,6 +29,11 @@ template <class F> bool by_bool(bool b, F&& f) {
     else f(std::false_type{});
     return true;
 }
+// what rides along with a derivative launch (Ride, trm_kernels.hpp): f(std::integral_constant<Ride, R>{}) for the ride that equals r
+template <Ride... Rs, class F> bool by_ride_value(int r, F&& f) {
+    return ((r == Rs && (f(std::integral_constant<Ride, Rs>{}), true)) || ...);
+}
+template <class F> bool by_ride(int r, F&& f) { return by_ride_value<RIDE_NONE, RIDE_BC, RIDE_PARAM, RIDE_SERIES, RIDE_PARAM_SERIES>(r, f); }
 // (STAGED, SCALAR_IN) as Policy::io_paths leaves them: f(ST, SC) for (0, 1), (1, 0), (1, 1).  (0, 0) -- direct 2-lane stores AND vector
 // loads of one address -- has no instance anywhere
 template <class F> bool by_io(int staged, int scalar_in, F&& f) {

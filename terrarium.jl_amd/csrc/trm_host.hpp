@@ -617,14 +617,8 @@ template <class NF, bool RICH, int PROG> struct ColumnLaunch { static int run(tr
 // the multi-step program with time averages accumulated in the launch (trm_launch_column_accum_*.hip)
 template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps, const AccumArgs& acc); };
 // ---- the derivative families of the heat-only fp64 run (trm_launch_derivative.inl) --------------------------------------------------
-// What rides along with a tangent step or a backward sweep: nothing; the seeds / gradients of the boundary values; those and the thermal
-// parameters'; or those with the boundary series evaluated in the launch and seeds / gradients per node of the series; or the series and
-// the thermal parameters' together (TRM_OPT_DERIVATIVE_SERIES_PARAMS)
-enum Ride { RIDE_NONE, RIDE_BC, RIDE_PARAM, RIDE_SERIES, RIDE_PARAM_SERIES };
-constexpr bool ride_has_params(Ride r) { return r == RIDE_PARAM || r == RIDE_PARAM_SERIES; }
-constexpr bool ride_has_series(Ride r) { return r == RIDE_SERIES || r == RIDE_PARAM_SERIES; }
-// The launchers, one explicit instantiation per ride in trm_launch_column_{tangent,adjoint,adjoint_ckpt}{,_bc,_param,_series,_param_series}.hip
-// (the two series records in trm_launch_column_adjoint_series.hip: the record carries no derivative, so both series rides share it)
+// What rides along with a tangent step or a backward sweep is a Ride (trm_kernels.hpp).  The launchers, one explicit instantiation per
+// ride in trm_launch_column_{tangent,adjoint,adjoint_ckpt}{,_bc,_param,_series,_param_series}.hip (the two series records in trm_launch_column_adjoint_series.hip: the record carries no derivative, so both series rides share it)
 template <Ride R> int tangent_step(trm_ctx* c, double dt, int nsteps);
 template <Ride R> int tangent_closure(trm_ctx* c);
 template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);

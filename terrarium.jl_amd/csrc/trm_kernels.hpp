@@ -74,6 +74,15 @@ enum { BCSIG_RUNTIME = -1,
 enum { DERIVE_NONE = 0, DERIVE_T_LIQ = 1, DERIVE_LIQ = 2,
        DERIVE_LIQ_PSI = 3,     // (packed fp32 step only) the liquid fraction AND the pressure head: psi = psi(sat, water table), two reads less
        DERIVE_ALL = 4 };       // (fp64 column program, Richards) T, liq AND psi: the step reads U and sat alone
+// What rides along with a launch of the derivative families of the heat-only fp64 run (trm_column_tangent.hpp, trm_column_adjoint.hpp;
+// the one template parameter of their kernels and of the host's launchers): nothing; the seeds / gradients of the boundary values; those
+// and the thermal parameters'; those with the boundary series evaluated in the launch and seeds / gradients per node of the series; or
+// the series and the thermal parameters' together (TRM_OPT_DERIVATIVE_SERIES_PARAMS).  A new ride is a new value here, in by_ride
+// (trm_dispatch.hpp) and in the predicates below.
+enum Ride { RIDE_NONE, RIDE_BC, RIDE_PARAM, RIDE_SERIES, RIDE_PARAM_SERIES };
+constexpr bool ride_has_bc(Ride r) { return r != RIDE_NONE; }
+constexpr bool ride_has_params(Ride r) { return r == RIDE_PARAM || r == RIDE_PARAM_SERIES; }
+constexpr bool ride_has_series(Ride r) { return r == RIDE_SERIES || r == RIDE_PARAM_SERIES; }
 enum { SMALL_KF_TOP = 0, SMALL_S, SMALL_WT, SMALL_G_S, SMALL_TOP_T, SMALL_TOP_SAT, SMALL_TOP_LIQ, SMALL_TS, SMALL_COUNT };
 template <class NF> inline void fill_small_table(View<NF>& v) {
     v.small[SMALL_KF_TOP] = v.Kf_top; v.small[SMALL_S] = v.S; v.small[SMALL_WT] = v.wt; v.small[SMALL_G_S] = v.G_S;

@@ -1,4 +1,4 @@
-// trm_launch_column_adjoint_ckpt.hip -- the launches of the strided k_column_record<HYD, LPC, true, CheckpointArgs> and k_column_adjoint_ckpt<HYD, LPC>
+// trm_launch_column_adjoint_ckpt.hip -- the launches of the strided k_column_record<HYD, LPC, true, false> and k_column_adjoint_ckpt<HYD, LPC, RIDE_NONE>
 // (both lanes-per-column layouts; trm_column_adjoint_ckpt.hpp): the checkpointed tape of the reverse-mode gradients.
 #include "trm_launch_derivative.inl"
 

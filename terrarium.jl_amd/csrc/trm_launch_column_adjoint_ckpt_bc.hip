@@ -1,4 +1,4 @@
-// trm_launch_column_adjoint_ckpt_bc.hip -- the launches of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointBcArgs> (both lanes-per-column
+// trm_launch_column_adjoint_ckpt_bc.hip -- the launches of k_column_adjoint_ckpt<HYD, LPC, RIDE_BC> (both lanes-per-column
 // layouts; trm_column_adjoint_ckpt.hpp): the backward sweep of the checkpointed tape with the boundary gradients riding along.
 #include "trm_launch_derivative.inl"
 

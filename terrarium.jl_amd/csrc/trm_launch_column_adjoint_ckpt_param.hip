@@ -1,4 +1,4 @@
-// trm_launch_column_adjoint_ckpt_param.hip -- the launches of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointParamArgs, true> (both
+// trm_launch_column_adjoint_ckpt_param.hip -- the launches of k_column_adjoint_ckpt<HYD, LPC, RIDE_PARAM> (both
 // lanes-per-column layouts; trm_column_adjoint_ckpt.hpp): the backward sweep of the checkpointed tape with the boundary and the thermal
 // parameter gradients riding along.
 #include "trm_launch_derivative.inl"

@@ -1,4 +1,4 @@
-// trm_launch_column_adjoint_ckpt_series.hip -- the launches of k_column_adjoint_ckpt<HYD, LPC, true, CheckpointSeriesArgs, false, true>
+// trm_launch_column_adjoint_ckpt_series.hip -- the launches of k_column_adjoint_ckpt<HYD, LPC, RIDE_SERIES>
 // (both lanes-per-column layouts; trm_column_adjoint_ckpt.hpp, trm_series_derivative.hpp): the backward sweep of the checkpointed tape
 // with boundary time series evaluated in the launch and the gradients delivered per node of the series.
 #include "trm_launch_derivative.inl"

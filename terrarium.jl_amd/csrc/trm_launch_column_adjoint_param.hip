@@ -1,4 +1,4 @@
-// trm_launch_column_adjoint_param.hip -- the launches of k_column_adjoint<HYD, LPC, true, AdjointParamArgs, true> (both lanes-per-column
+// trm_launch_column_adjoint_param.hip -- the launches of k_column_adjoint<HYD, LPC, RIDE_PARAM> (both lanes-per-column
 // layouts) and k_param_reduce (trm_column_adjoint.hpp): the backward sweep of the per-step tape with the boundary and the thermal
 // parameter gradients riding along (trm_adjoint_param_open), and the reduction that ends a sweep on either tape.
 #include "trm_launch_derivative.inl"

@@ -1,35 +1,32 @@
 // trm_launch_derivative.inl -- the launches of the two derivative families of the heat-only fp64 SoilModel run: k_column_tangent
 // (trm_column_tangent.hpp), k_column_record / k_column_adjoint (trm_column_adjoint.hpp) and k_column_adjoint_ckpt
-// (trm_column_adjoint_ckpt.hpp), each with what rides along (Ride, trm_host.hpp).  Included by the trm_launch_column_tangent*.hip and
+// (trm_column_adjoint_ckpt.hpp), each with what rides along (Ride, trm_kernels.hpp).  Included by the trm_launch_column_tangent*.hip and
 // trm_launch_column_adjoint*.hip files, each of which instantiates the launchers of one family and ride.
 #include "trm_host.hpp"
 #include "trm_column_adjoint_ckpt.hpp"
 
 namespace trmh {
 
-// ---- what a ride is called in a refusal, and the kernel arguments it selects ------------------------------------------------------
+// ---- what a ride is called in a refusal ----------------------------------------------------------------------------------------------
 inline std::string ride_name(const char* kernel, Ride r, bool tangent) {
     const char* seeds[] = {"", " (boundary seeds)", " (parameter seeds)", " (series)", " (series, parameter seeds)"};
     const char* grads[] = {"", " (boundary gradients)", " (parameter gradients)", " (series)", " (series, parameter gradients)"};
     return std::string(kernel) + (tangent ? seeds : grads)[r];
 }
-template <Ride R, class None, class Bc, class Param, class Series, class ParamSeries>
-using RideArgs = std::conditional_t<R == RIDE_NONE, None,
-                                    std::conditional_t<R == RIDE_BC, Bc, std::conditional_t<R == RIDE_PARAM, Param, std::conditional_t<R == RIDE_SERIES, Series, ParamSeries>>>>;
 
 // ---- the argument fillers ----------------------------------------------------------------------------------------------------------
 // the halo form trm_step would take; the series instances refuse the generic kinds (series_ok)
 inline int generic_halos(trm_ctx* c, bool series) { return !series && Policy<double>::generic_bcs(c) ? 1 : 0; }
 
-inline void fill_tangent(trm_ctx* c, TangentArgs& ta, bool series) {
+inline void fill_tangent(trm_ctx* c, TangentFields& ta, bool series) {
     ta.dU = c->d_tan[TRM_TANGENT_INTERNAL_ENERGY];
     ta.dT = c->d_tan[TRM_TANGENT_TEMPERATURE];
     ta.dliq = c->d_tan[TRM_TANGENT_LIQUID_WATER_FRACTION];
     ta.generic = generic_halos(c, series);
 }
 // the seeds of the boundary values, and of the thermal parameters or the seriesed pairs behind them
-template <Ride R, class Args> void fill_tangent_seeds(const trm_ctx* c, Args& ta) {
-    if constexpr (R != RIDE_NONE) {
+template <Ride R> void fill_tangent_seeds(const trm_ctx* c, TangentArgs<R>& ta) {
+    if constexpr (ride_has_bc(R)) {
         ta.sTb = c->d_tan_bc[0];
         ta.sTt = c->d_tan_bc[1];
         ta.sUb = c->d_tan_bc[2];
@@ -42,9 +39,8 @@ template <Ride R, class Args> void fill_tangent_seeds(const trm_ctx* c, Args& ta
     if constexpr (ride_has_series(R))
         for (int s = 0; s < 4; ++s) ta.sn[s] = c->d_tan_bcs[s];
 }
-// the cotangent fields and the tape of AdjointArgs / CheckpointArgs (the same member names, no common base); `slot`: the tape slot of
-// the first step of the launch, or the segment's checkpoint
-template <class Args> void fill_cotangent(trm_ctx* c, Args& aa, int slot, int fold, bool series) {
+// the cotangent fields and the tape; `slot`: the tape slot of the first step of the launch, or the segment's checkpoint
+inline void fill_cotangent(trm_ctx* c, TapeFields& aa, int slot, int fold, bool series) {
     aa.lU = c->d_adj[TRM_ADJOINT_INTERNAL_ENERGY];
     aa.lT = c->d_adj[TRM_ADJOINT_TEMPERATURE];
     aa.lliq = c->d_adj[TRM_ADJOINT_LIQUID_WATER_FRACTION];
@@ -61,8 +57,8 @@ inline ParamGradPtrs param_grad_ptrs(const trm_ctx* c) {
     return g;
 }
 // what rides along a backward launch on either tape
-template <Ride R, class Args> void fill_gradients(const trm_ctx* c, Args& aa) {
-    if constexpr (R != RIDE_NONE) aa.g = bc_grad_ptrs(c);
+template <bool CKPT, Ride R> void fill_gradients(const trm_ctx* c, SweepArgs<CKPT, R>& aa) {
+    if constexpr (ride_has_bc(R)) aa.g = bc_grad_ptrs(c);
     if constexpr (ride_has_params(R)) aa.pg = param_grad_ptrs(c);
     if constexpr (ride_has_series(R)) aa.sg = series_grad_ptrs(c);
 }
@@ -110,7 +106,7 @@ inline int series_nodes_ok(trm_ctx* c, double* const (&nodes)[4], const long (&n
 template <Ride R> int gradients_ok(trm_ctx* c, int nsteps, const std::string& who) {
     if constexpr (ride_has_series(R))
         if (int rc = series_rows_ok(c, nsteps, who)) return rc;
-    if constexpr (R != RIDE_NONE)
+    if constexpr (ride_has_bc(R))
         if (int rc = arrays_ok(c, c->d_adj_bc, who, ride_has_params(R) ? "boundary accumulators" : "accumulators")) return rc;
     if constexpr (ride_has_params(R))
         if (int rc = arrays_ok(c, c->d_adj_param, who, "accumulators")) return rc;
@@ -120,7 +116,7 @@ template <Ride R> int gradients_ok(trm_ctx* c, int nsteps, const std::string& wh
 }
 // the seed arrays a tangent launch with ride R needs (the parameter seeds travel by value)
 template <Ride R> int tangent_seeds_ok(trm_ctx* c, int nsteps, const std::string& who) {
-    if constexpr (R != RIDE_NONE)
+    if constexpr (ride_has_bc(R))
         if (int rc = arrays_ok(c, c->d_tan_bc, who, ride_has_params(R) ? "boundary seed arrays" : "seed arrays")) return rc;
     if constexpr (ride_has_series(R)) {
         if (int rc = series_rows_ok(c, nsteps, who)) return rc;
@@ -142,33 +138,33 @@ inline int derivative_program_id(int family, int hyd, int lpc, int generic, int 
 
 // ---- one launch function per kernel template ----------------------------------------------------------------------------------------
 template <Ride R> int tangent_step(trm_ctx* c, double dt, int nsteps) {
-    using Args = RideArgs<R, TangentArgs, TangentBcArgs, TangentParamArgs, TangentSeriesArgs, TangentParamSeriesArgs>;
     const std::string who = ride_name("k_column_tangent", R, true);
     if (int rc = tangent_seeds_ok<R>(c, nsteps, who)) return rc;
     const LaunchArgs<double>& la = launch_args<double>(c);
     const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
-    Args ta;
+    TangentArgs<R> ta;
     fill_tangent(c, ta, ride_has_series(R));
-    fill_tangent_seeds<R>(c, ta);
+    fill_tangent_seeds(c, ta);
     return by_instance(c, [&](auto h, auto lpc) {
         constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        hipLaunchKernelGGL((k_column_tangent<H, LPC, R != RIDE_NONE, Args, ride_has_params(R), ride_has_series(R)>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0,
-                           c->stream, la.state, la.p, a, ta);
+        hipLaunchKernelGGL((k_column_tangent<H, LPC, R>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, ta);
         TRM_HIP(c, hipGetLastError());
         c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_TANGENT, H, LPC, ta.generic,
-                                                (R != RIDE_NONE ? PROGRAM_BC_SEEDS : 0) | (ride_has_params(R) ? (int)TRM_PROGRAM_PARAMETERS : 0));
+                                                (ride_has_bc(R) ? PROGRAM_BC_SEEDS : 0) | (ride_has_params(R) ? (int)TRM_PROGRAM_PARAMETERS : 0));
         return (int)TRM_OK;
     });
 }
 
-// trm_tangent_closure: with the heat-capacity term of the parameter seeds (RIDE_PARAM) or without (RIDE_NONE)
+// trm_tangent_closure: with the heat-capacity term of the parameter seeds (RIDE_PARAM) or without (RIDE_NONE); the closure reads no
+// boundary value, so these two are the only instances and every other ride takes RIDE_NONE's (closure_ride, trm_derivative_api.hip)
 template <Ride R> int tangent_closure(trm_ctx* c) {
+    static_assert(R == RIDE_NONE || R == RIDE_PARAM, "k_closure_tangent has these two instances");
     const LaunchArgs<double>& la = launch_args<double>(c);
     const size_t cells = (size_t)c->Nh * (size_t)c->Nzp;
-    RideArgs<R, TangentArgs, TangentBcArgs, TangentParamArgs, TangentSeriesArgs, TangentParamSeriesArgs> ta;
+    TangentArgs<R> ta;
     fill_tangent(c, ta, false);
-    fill_tangent_seeds<R>(c, ta);
-    hipLaunchKernelGGL((k_closure_tangent<decltype(ta), R == RIDE_PARAM>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, la.state, la.p, ta);
+    fill_tangent_seeds(c, ta);
+    hipLaunchKernelGGL((k_closure_tangent<R>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, la.state, la.p, ta);
     TRM_HIP(c, hipGetLastError());
     return TRM_OK;
 }
@@ -176,14 +172,13 @@ template <Ride R> int tangent_closure(trm_ctx* c) {
 // k_column_record on the per-step tape (`slot`: of the launch's first step) or STRIDED on the checkpointed one (the stores before the
 // steps first, first + every, ... go into the slots from `slot` on); SERIES: with the boundary series evaluated in the launch
 template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every) {
-    using Args = std::conditional_t<STRIDED, CheckpointArgs, AdjointArgs>;
     const std::string who = std::string(STRIDED ? "k_column_record (strided)" : "k_column_record") + (SERIES ? " (series)" : "");
     if (int rc = STRIDED ? strided_stores_ok(c, nsteps, slot, first, every, who) : tape_range_ok(c, nsteps, slot, who)) return rc;
     if constexpr (SERIES)
         if (int rc = series_rows_ok(c, nsteps, who)) return rc;
     const LaunchArgs<double>& la = launch_args<double>(c);
     const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
-    Args aa;
+    TapeArgs<STRIDED> aa;
     fill_cotangent(c, aa, slot, 0, SERIES);
     if constexpr (STRIDED) {
         aa.first = first;
@@ -191,7 +186,7 @@ template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, i
     }
     return by_instance(c, [&](auto h, auto lpc) {
         constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        hipLaunchKernelGGL((k_column_record<H, LPC, STRIDED, Args, SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
+        hipLaunchKernelGGL((k_column_record<H, LPC, STRIDED, SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
         TRM_HIP(c, hipGetLastError());
         c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT, H, LPC, aa.generic, STRIDED ? PROGRAM_CHECKPOINTED : 0);
         return (int)TRM_OK;
@@ -201,28 +196,25 @@ template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, i
 // the backward launch of a block of the per-step tape (k_column_adjoint) or, CKPT, of one segment of the checkpointed tape
 // (k_column_adjoint_ckpt: the segment's states in dynamic LDS, 2 KiB per step and workgroup)
 template <bool CKPT, Ride R> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    using Args = std::conditional_t<CKPT, RideArgs<R, CheckpointArgs, CheckpointBcArgs, CheckpointParamArgs, CheckpointSeriesArgs, CheckpointParamSeriesArgs>,
-                                    RideArgs<R, AdjointArgs, AdjointBcArgs, AdjointParamArgs, AdjointSeriesArgs, AdjointParamSeriesArgs>>;
     const std::string who = ride_name(CKPT ? "k_column_adjoint_ckpt" : "k_column_adjoint", R, false);
     if (int rc = CKPT ? segment_range_ok(c, nsteps, slot, who) : tape_range_ok(c, nsteps, slot, who)) return rc;
     if (int rc = gradients_ok<R>(c, nsteps, who)) return rc;
     const LaunchArgs<double>& la = launch_args<double>(c);
     const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
-    Args aa;
+    SweepArgs<CKPT, R> aa;
     fill_cotangent(c, aa, slot, fold, ride_has_series(R));
-    fill_gradients<R>(c, aa);
+    fill_gradients(c, aa);
     if constexpr (CKPT) {
         aa.first = 0;
         aa.every = 1;
     }
-    const int bits = PROGRAM_BACKWARD | (CKPT ? PROGRAM_CHECKPOINTED : 0) | (R != RIDE_NONE ? PROGRAM_BC_GRADIENT : 0) | (ride_has_params(R) ? (int)TRM_PROGRAM_PARAMETERS : 0);
+    const int bits = PROGRAM_BACKWARD | (CKPT ? PROGRAM_CHECKPOINTED : 0) | (ride_has_bc(R) ? PROGRAM_BC_GRADIENT : 0) | (ride_has_params(R) ? (int)TRM_PROGRAM_PARAMETERS : 0);
     return by_instance(c, [&](auto h, auto lpc) {
         constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        constexpr bool BCGRAD = R != RIDE_NONE, PGRAD = ride_has_params(R), SERIES = ride_has_series(R);
         if constexpr (CKPT)
-            hipLaunchKernelGGL((k_column_adjoint_ckpt<H, LPC, BCGRAD, Args, PGRAD, SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK),
-                               (size_t)nsteps * TRM_STEP_BLOCK * sizeof(double), c->stream, la.state, la.p, a, aa);
-        else hipLaunchKernelGGL((k_column_adjoint<H, LPC, BCGRAD, Args, PGRAD, SERIES>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
+            hipLaunchKernelGGL((k_column_adjoint_ckpt<H, LPC, R>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), (size_t)nsteps * TRM_STEP_BLOCK * sizeof(double),
+                               c->stream, la.state, la.p, a, aa);
+        else hipLaunchKernelGGL((k_column_adjoint<H, LPC, R>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
         TRM_HIP(c, hipGetLastError());
         c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT, H, LPC, aa.generic, bits);
         return (int)TRM_OK;

@@ -11,11 +11,73 @@ template <class NF> const LaunchArgs<NF>& launch_args(trm_ctx*) { static LaunchA
 }  // namespace trmh
 using namespace trmh;
 
+// The kernel arguments of the derivative families are composed from parts by the ride (TangentArgs<R>, TapeArgs<STRIDED>, SweepArgs<CKPT, R>:
+// trm_column_tangent.hpp, trm_column_adjoint.hpp).  A ride's struct holds exactly its parts ...
+#define HAS_MEMBER(m)                                                     \
+    template <class T, class = void> struct has_##m : std::false_type {}; \
+    template <class T> struct has_##m<T, std::void_t<decltype(std::declval<T&>().m)>> : std::true_type {}
+HAS_MEMBER(g); HAS_MEMBER(sg); HAS_MEMBER(pg); HAS_MEMBER(sTb); HAS_MEMBER(sn); HAS_MEMBER(s);
+template <class T> constexpr int parts_of_sweep() { return has_g<T>::value | has_sg<T>::value << 1 | has_pg<T>::value << 2; }
+template <class T> constexpr int parts_of_tangent() { return has_sTb<T>::value | has_sn<T>::value << 1 | has_s<T>::value << 2; }
+// ... and every instance lies byte for byte as the hand-written struct it replaces lay: the sizes and offsets below were printed from
+// the fifteen structs TangentArgs ... CheckpointParamSeriesArgs of the commit before the composition (a kernel reads its arguments by
+// offset: fields, then bc, then series, then params)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+template <Ride R, size_t SIZE, size_t BC, size_t SERIES, size_t PARAMS> void check_tangent_layout() {
+    using T = TangentArgs<R>;
+    static_assert(offsetof(T, dU) == 0 && offsetof(T, dT) == 8 && offsetof(T, dliq) == 16 && offsetof(T, generic) == 24, "the fields");
+    static_assert(parts_of_tangent<T>() == (ride_has_bc(R) | ride_has_series(R) << 1 | ride_has_params(R) << 2), "exactly the ride's parts");
+    static_assert(std::is_trivially_copyable<T>::value, "a kernel argument");
+    static_assert(sizeof(T) == SIZE, "the size the hand-written struct had");
+    if constexpr (ride_has_bc(R)) static_assert(offsetof(T, sTb) == BC && offsetof(T, sTt) == BC + 8 && offsetof(T, sUb) == BC + 16 && offsetof(T, sUt) == BC + 24, "bc");
+    if constexpr (ride_has_series(R)) static_assert(offsetof(T, sn) == SERIES, "series");
+    if constexpr (ride_has_params(R)) static_assert(offsetof(T, s) == PARAMS, "params");
+}
+template <bool CKPT, Ride R, size_t SIZE, size_t BC, size_t SERIES, size_t PARAMS> void check_sweep_layout() {
+    using T = SweepArgs<CKPT, R>;
+    static_assert(offsetof(T, lU) == 0 && offsetof(T, lT) == 8 && offsetof(T, lliq) == 16 && offsetof(T, tape) == 24 && offsetof(T, slot_elems) == 32 &&
+                      offsetof(T, generic) == 40 && offsetof(T, fold) == 44, "the tape");
+    if constexpr (CKPT) static_assert(offsetof(T, first) == 48 && offsetof(T, every) == 52, "the strided tape");
+    static_assert(parts_of_sweep<T>() == (ride_has_bc(R) | ride_has_series(R) << 1 | ride_has_params(R) << 2), "exactly the ride's parts");
+    static_assert(std::is_trivially_copyable<T>::value, "a kernel argument");
+    static_assert(sizeof(T) == SIZE, "the size the hand-written struct had");
+    if constexpr (ride_has_bc(R)) static_assert(offsetof(T, g) == BC, "bc");
+    if constexpr (ride_has_series(R)) static_assert(offsetof(T, sg) == SERIES, "series");
+    if constexpr (ride_has_params(R)) static_assert(offsetof(T, pg) == PARAMS, "params");
+}
+static void check_argument_layouts() {
+    // what was pinned on RideArgs: the fifth ride has all three parts, the fourth has two and is smaller by the parameter part
+    static_assert(parts_of_sweep<SweepArgs<false, RIDE_PARAM_SERIES>>() == 7 && parts_of_sweep<SweepArgs<false, RIDE_SERIES>>() == 3, "g, sg, pg / g, sg");
+    static_assert(sizeof(SweepArgs<false, RIDE_PARAM_SERIES>) - sizeof(SweepArgs<false, RIDE_SERIES>) == sizeof(ParamGradPtrs), "");
+    static_assert(parts_of_tangent<TangentArgs<RIDE_PARAM_SERIES>>() == 7 && parts_of_tangent<TangentArgs<RIDE_SERIES>>() == 3, "sTb.., sn, s / sTb.., sn");
+    static_assert(sizeof(TangentArgs<RIDE_PARAM_SERIES>) - sizeof(TangentArgs<RIDE_SERIES>) == sizeof(ParamSeeds), "");
+    static_assert(sizeof(ParamSeeds) == 64 && sizeof(BcGradPtrs) == 32 && sizeof(SeriesGradPtrs) == 32 && sizeof(ParamGradPtrs) == 64, "the parts");
+    // (size, offset of the bc part, of the series part, of the parameter part; 0: the ride has none)
+    check_tangent_layout<RIDE_NONE, 32, 0, 0, 0>();
+    check_tangent_layout<RIDE_BC, 64, 32, 0, 0>();
+    check_tangent_layout<RIDE_PARAM, 128, 32, 0, 64>();
+    check_tangent_layout<RIDE_SERIES, 96, 32, 64, 0>();
+    check_tangent_layout<RIDE_PARAM_SERIES, 160, 32, 64, 96>();
+    static_assert(sizeof(TapeArgs<false>) == 48 && sizeof(TapeArgs<true>) == 56 && offsetof(TapeArgs<true>, first) == 48 && offsetof(TapeArgs<true>, every) == 52, "the records'");
+    static_assert(offsetof(TapeArgs<false>, fold) == 44 && offsetof(TapeArgs<true>, fold) == 44, "");
+    check_sweep_layout<false, RIDE_NONE, 48, 0, 0, 0>();
+    check_sweep_layout<false, RIDE_BC, 80, 48, 0, 0>();
+    check_sweep_layout<false, RIDE_PARAM, 144, 48, 0, 80>();
+    check_sweep_layout<false, RIDE_SERIES, 112, 48, 80, 0>();
+    check_sweep_layout<false, RIDE_PARAM_SERIES, 176, 48, 80, 112>();
+    check_sweep_layout<true, RIDE_NONE, 56, 0, 0, 0>();
+    check_sweep_layout<true, RIDE_BC, 88, 56, 0, 0>();
+    check_sweep_layout<true, RIDE_PARAM, 152, 56, 0, 88>();
+    check_sweep_layout<true, RIDE_SERIES, 120, 56, 88, 0>();
+    check_sweep_layout<true, RIDE_PARAM_SERIES, 184, 56, 88, 120>();
+}
+#pragma clang diagnostic pop
+
 int main() {
     static_assert(ride_has_params(RIDE_PARAM_SERIES) && ride_has_series(RIDE_PARAM_SERIES), "the union of both rides");
     static_assert(ride_has_params(RIDE_PARAM) && !ride_has_series(RIDE_PARAM) && !ride_has_params(RIDE_SERIES) && ride_has_series(RIDE_SERIES), "the rides as they were");
-    static_assert(std::is_same<RideArgs<RIDE_PARAM_SERIES, int, int, int, int, AdjointParamSeriesArgs>, AdjointParamSeriesArgs>::value, "RideArgs selects the fifth");
-    static_assert(std::is_same<RideArgs<RIDE_SERIES, int, int, int, AdjointSeriesArgs, char>, AdjointSeriesArgs>::value, "... and the fourth as before");
+    check_argument_layouts();
     trm_ctx c;
     c.Nh = 3; c.Nz = 4; c.Nzp = 4;
     c.tape_cap = 8;

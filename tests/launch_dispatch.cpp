@@ -63,6 +63,15 @@ static void check_helpers() {
     one([&](auto f) { return by_hyd(7, f); }, false);
     for (int nz : {1, 30, 32, 33, 40, 64}) assert(one([&](auto f) { return by_lanes(nz, f); }, true).a == (nz > 32 ? 64 : 32));
     for (bool b : {false, true}) assert(one([&](auto f) { return by_bool(b, f); }, true).a == (b ? 1 : 0));
+    // what rides along with a derivative launch: each of the five rides reaches its constant once; a value off the list reaches none
+    int ride_calls[5] = {};
+    for (int r = -1; r <= 5; ++r) {
+        const bool listed = r >= RIDE_NONE && r <= RIDE_PARAM_SERIES;
+        const Seen s = one([&](auto f) { return by_ride(r, f); }, listed);
+        if (listed) { assert(s.a == r); ++ride_calls[s.a]; }
+    }
+    for (int n : ride_calls) assert(n == 1);
+    by_ride(RIDE_PARAM_SERIES, [](auto k) { static_assert(std::is_same<typename decltype(k)::value_type, Ride>::value, "the constant is a Ride"); });
     for (int st : {0, 1, 2})
         for (int sc : {0, 1, 3}) {
             Seen s;
