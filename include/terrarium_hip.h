@@ -820,6 +820,51 @@ int trm_adjoint_bc_series_device_ptr(trm_ctx* ctx, int bc_var, int side, void** 
 int trm_adjoint_param_open(trm_ctx* ctx);
 int trm_adjoint_param_download(trm_ctx* ctx, int which, void* host);
 int trm_adjoint_param_device_ptr(trm_ctx* ctx, int which, void** dev);
+/* Adjoint observations: losses that read the run at taped positions and not at its end alone -- a borehole record, temperatures at a
+ * few depths at many times (the reference differentiates such a loss by pulling a seed back through run! once per observation time;
+ * here the cotangents enter one sweep).  An observation belongs to the taped position p at which it is registered, the number of steps
+ * on the tape, 0 <= p <= n: it is registered between trm_step_record calls and refers to the state the context holds then, U_p and its
+ * closure.  `levels`: nlevels rows of the host layout of trm_download (row 0 = bottom layer), strictly increasing.
+ *   trm_adjoint_observe(ctx, which, nlevels, levels, host)
+ *                                           linear: host[nlevels][num_columns] doubles, the cotangent w of U, T or liq (which:
+ *                                           TRM_ADJOINT_*) on those levels; adds <w, X_p[levels]> to L.  Stands in for one more seed
+ *                                           and sweep of the reference.
+ *   trm_adjoint_observe_misfit(ctx, nlevels, levels, observed, weight)
+ *                                           misfit: observed[nlevels][num_columns] temperatures T_obs and weights w >= 0 of the same
+ *                                           shape (NULL: 1); adds 1/2 w (T_p - T_obs)^2 per cell to the column's loss at once (one small
+ *                                           launch) and w (T_p - T_obs) to the cotangent of T_p in the sweep.  A NaN in `observed` is a
+ *                                           gap in the logger's record: it contributes nothing, exactly as a weight 0.  Stands in for
+ *                                           the loss function a calibration differentiates with Enzyme.
+ *   trm_adjoint_misfit_download(ctx, host)  host[num_columns] doubles: each column's share of the misfit so far (zeros without one)
+ *   trm_adjoint_misfit_device_ptr(ctx, &dev) the same on the device, num_columns contiguous doubles
+ *   trm_adjoint_observations(ctx, &count, &bytes)
+ *                                           observations registered and the device memory they hold: an observation keeps what the
+ *                                           caller gave, nlevels x num_columns x 8 bytes per array plus 4 bytes per level, never a field
+ * trm_adjoint_backward pulls the final cotangents of trm_adjoint_upload back as before and, when it has pulled back every step >= p,
+ * adds wU + a_p wT + b_p wliq on the observed cells to lam, a_p and b_p the closure slopes at U_p; with a parameter gradient open wT
+ * also goes through the heat capacity of that closure onto the parameter sums.  U_p is tape slot p; on the checkpointed tape an
+ * observation closes the open segment, so that the next taped step opens one -- and takes a slot, which trm_step_record counts before
+ * it launches anything -- and U_p is its checkpoint; for p = n it is the state itself.  The sweep splits at observed positions: on the
+ * per-step tape a block also ends there.  Order of every sum, whatever the split:
+ *   lam of a cell         ... the steps > p - 1, then the observations of p in registration order, then step p - 1 ...; those of p = n
+ *                         come first, in front of the fold of the final wT and wliq
+ *   parameter sums        the fold, the steps of the sweep's first launch, the observations of p = n (the launch that folds starts its
+ *                         sums from 0, so they follow it), then as lam: the observations of p in front of step p - 1, those of p = 0 last
+ *   boundary, node sums   accumulated from lam alone: nothing new
+ *   misfit of a column    the observations in registration order, the levels of each in list order
+ * One lane owns a cell in every one of them: no atomics.  Scaling every cotangent and weight by a power of two scales every gradient bit
+ * for bit; with every cotangent zero the sweep gives the values of the sweep without observations; dL/dU_0 of the checkpointed tape is
+ * the per-step tape's.  With no observation registered every call issues the launches it issued before and gives the same bits.
+ * trm_adjoint_open*, trm_adjoint_close and a trm_adjoint_backward that succeeded drop all observations and zero the misfit; a sweep that
+ * failed leaves the tape stale.  Observations do not touch the state, the clock or the status word, make no tangent stale, and their
+ * launches do not write TRM_INFO_LAST_PROGRAM: after a sweep it is that of the sweep's last launch.
+ * Errors: TRM_EINVAL without a context or an open adjoint, for a bad `which`, nlevels < 1, a level outside 0 ... Nz-1 or out of order,
+ * a NULL levels / host / observed, a negative or NaN weight; TRM_ESTALE on a stale tape; TRM_ENOMEM. */
+int trm_adjoint_observe(trm_ctx* ctx, int which, int nlevels, const int32_t* levels, const void* host);
+int trm_adjoint_observe_misfit(trm_ctx* ctx, int nlevels, const int32_t* levels, const void* observed, const void* weight);
+int trm_adjoint_misfit_download(trm_ctx* ctx, void* host);
+int trm_adjoint_misfit_device_ptr(trm_ctx* ctx, void** dev);
+int trm_adjoint_observations(const trm_ctx* ctx, int* count, int64_t* bytes);
 
 int trm_clock(const trm_ctx* ctx, double* time, int64_t* iteration);
 int trm_set_clock(trm_ctx* ctx, double time, int64_t iteration);

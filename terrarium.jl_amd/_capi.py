@@ -115,7 +115,8 @@ EXPORTS = (
     "trm_step_record trm_adjoint_backward trm_adjoint_open_checkpointed trm_adjoint_checkpoints "
     "trm_tangent_bc_upload trm_adjoint_bc_open trm_adjoint_bc_download trm_adjoint_bc_device_ptr "
     "trm_tangent_param_set trm_adjoint_param_open trm_adjoint_param_download trm_adjoint_param_device_ptr "
-    "trm_tangent_bc_series_upload trm_adjoint_bc_series_download trm_adjoint_bc_series_device_ptr").split()
+    "trm_tangent_bc_series_upload trm_adjoint_bc_series_download trm_adjoint_bc_series_device_ptr "
+    "trm_adjoint_observe trm_adjoint_observe_misfit trm_adjoint_misfit_download trm_adjoint_misfit_device_ptr trm_adjoint_observations").split()
 # the thermal parameters the tangent and the adjoint differentiate (TRM_THERMAL_PARAM_*), in the order of trm_params
 THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
 # forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
@@ -297,6 +298,11 @@ def lib():
     L.trm_tangent_bc_series_upload.argtypes = [vp, i32, i32, i32, vp]
     L.trm_adjoint_bc_series_download.argtypes = [vp, i32, i32, i32, vp]
     L.trm_adjoint_bc_series_device_ptr.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(i32)]
+    L.trm_adjoint_observe.argtypes = [vp, i32, i32, vp, vp]
+    L.trm_adjoint_observe_misfit.argtypes = [vp, i32, vp, vp, vp]
+    L.trm_adjoint_misfit_download.argtypes = [vp, vp]
+    L.trm_adjoint_misfit_device_ptr.argtypes = [vp, C.POINTER(vp)]
+    L.trm_adjoint_observations.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

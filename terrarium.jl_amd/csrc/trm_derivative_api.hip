@@ -68,7 +68,14 @@ void release(double*& q) {
 template <size_t N> void release(double* (&a)[N]) {
     for (double*& q : a) release(q);
 }
+// every observation of the tape (trm_adjoint_observe*): a fresh tape has none
+void drop_observations(trm_ctx* c) {
+    for (auto& o : c->observations) release(o.d_data);
+    c->observations.clear();
+    c->tape_seg_closed = false;
+}
 void release_tape(trm_ctx* c) {
+    drop_observations(c);
     release(c->d_tape);
     c->tape_cap = 0;
     c->ckpt_interval = 0;
@@ -99,6 +106,7 @@ void release_adjoint(trm_ctx* c) {
     std::fill(std::begin(c->adj_bcs_nt), std::end(c->adj_bcs_nt), 0L);
     release(c->d_adj_param);
     release(c->d_adj_param_out);
+    release(c->d_misfit);
     release_tape(c);
 }
 }  // namespace trmh
@@ -280,8 +288,10 @@ int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who)
     for (int s = 0; s < 4; ++s) if (!rc) rc = zero(c, c->d_adj_bcs[s], rows_bytes(c, c->adj_bcs_nt[s]));
     for (double* q : c->d_adj_param) if (!rc) rc = zero(c, q, bytes);
     if (!rc) rc = zero(c, c->d_adj_param_out, rows_bytes(c, TRM_THERMAL_PARAM_COUNT));
+    if (!rc) rc = zero(c, c->d_misfit, rows_bytes(c));
     if (rc) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
+    drop_observations(c);
     c->tape_dt.clear();        // (a fresh tape)
     c->tape_segs.clear();
     c->tape_rows.clear();
@@ -309,6 +319,65 @@ int adjoint_param_args(trm_ctx* c, int which, const void* ptr, const char* who) 
     if (int rc = adjoint_open(c, who)) return rc;
     if (int rc = require_open(c, c->d_adj_param_out, who, "parameter gradients are", "trm_adjoint_param_open")) return rc;
     return which_ok(c, which, TRM_THERMAL_PARAM_COUNT, ptr, who, " (TRM_THERMAL_PARAM_*)");
+}
+// ---- adjoint observations ------------------------------------------------------------------------------------------------------------
+// the level list of an observation: rows of the host layout, strictly increasing
+int observed_levels_ok(trm_ctx* c, int nlevels, const int32_t* levels, const char* who) {
+    if (nlevels < 1 || !levels) return fail(c, TRM_EINVAL, std::string(who) + ": bad argument (nlevels >= 1 levels)");
+    for (int j = 0; j < nlevels; ++j)
+        if (levels[j] < 0 || levels[j] >= c->Nz || (j > 0 && levels[j] <= levels[j - 1]))
+            return fail(c, TRM_EINVAL, std::string(who) + ": the levels are rows 0 ... " + std::to_string(c->Nz - 1) + " of the host layout, strictly increasing");
+    return TRM_OK;
+}
+// An observation of the state the context holds now joins the tape at position taped_steps: its arrays ([nlevels][Nh] doubles each; a
+// null one is left out) and the level list go to the device in one allocation.  Checkpointed: it closes the open segment.
+int register_observation(trm_ctx* c, int kind, int nlevels, const int32_t* levels, const void* first, const void* second, const char* who) {
+    trm_ctx::Observation o{taped_steps(c), kind, nlevels, second ? 2 : 1, nullptr};
+    const size_t array_bytes = rows_bytes(c, nlevels);
+    if (alloc_if_null(o.d_data, (size_t)o.bytes(c->Nh)) != hipSuccess) return fail(c, TRM_ENOMEM, std::string(who) + ": the observation does not fit");
+    const void* src[2] = {first, second};
+    hipError_t e = hipSuccess;
+    for (int a = 0; a < o.arrays && e == hipSuccess; ++a)
+        e = hipMemcpyAsync(o.d_data + (size_t)a * (size_t)nlevels * (size_t)c->Nh, src[a], array_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((void*)o.levels(c->Nh), levels, (size_t)nlevels * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        release(o.d_data);
+        return fail(c, TRM_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    c->observations.push_back(o);
+    if (c->ckpt_interval && !c->tape_segs.empty()) c->tape_seg_closed = true;
+    return TRM_OK;
+}
+// what both registrations check first
+int observe_args(trm_ctx* c, int nlevels, const int32_t* levels, const void* host, const char* who) {
+    if (int rc = adjoint_open(c, who)) return rc;
+    if (int rc = observed_levels_ok(c, nlevels, levels, who)) return rc;
+    if (int rc = which_ok(c, 0, 1, host, who)) return rc;
+    if (c->adj_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTape);
+    return TRM_OK;
+}
+bool observed(const trm_ctx* c, int position) {
+    for (const auto& o : c->observations)
+        if (o.position == position) return true;
+    return false;
+}
+// The observations of taped position p, in registration order (trm_adjoint_backward: in front of the launch whose newest step is p - 1,
+// behind the last launch for p = 0).  U_p: tape slot p, the checkpoint of the segment that starts at p, the context's U for p = n.
+int inject_observations(trm_ctx* c, int p, bool lam, bool params) {
+    if (c->observations.empty()) return TRM_OK;
+    const double* U_p = nullptr;
+    if (p != taped_steps(c)) {
+        const size_t slot_elems = (size_t)c->Nh * (size_t)c->Nzp;
+        if (!c->ckpt_interval) U_p = c->d_tape + (size_t)p * slot_elems;
+        for (const auto& seg : c->tape_segs)
+            if (seg.first == p) U_p = c->d_tape + (size_t)seg.slot * slot_elems;
+        if (!U_p && observed(c, p)) return fail(c, TRM_EINVAL, "trm_adjoint_backward: an observed position is no checkpoint");
+    }
+    for (const auto& o : c->observations)
+        if (o.position == p)
+            if (int rc = ObserveLaunch::inject(c, o, U_p, lam, params)) return rc;
+    return TRM_OK;
 }
 }  // namespace
 
@@ -640,13 +709,19 @@ int trm_adjoint_backward(trm_ctx* c) {
     // (the rows of taped steps [first, first + n), uploaded in front of the launch that walks them)
     auto kept_rows = [&](int first, int n) { return Unfused<double>::upload_series_rows(c, 0.0, n, nullptr, c->tape_rows.data() + (size_t)first * (size_t)nser); };
     const Ride ride = backward_ride(c, nser);
+    // Observations (trm_adjoint_observe*): those of position p enter in front of the launch whose newest step is p - 1.  The launch that
+    // folds starts its boundary and parameter sums from 0, so the observations of p = n give lam their share in front of it and the
+    // parameter sums theirs behind it; those of p = 0 < n follow the last launch.
+    const int n = taped_steps(c);
     int rc = TRM_OK, fold = 1;
     if (c->ckpt_interval) {   // one launch per segment, newest first; the first launch folds (an empty tape: that launch alone, no step)
         size_t s = c->tape_segs.size();
         do {
             const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
-            rc = nser ? kept_rows(seg.first, seg.len) : TRM_OK;
+            rc = inject_observations(c, seg.first + seg.len, true, !fold);   // (a segment ends at every observed position)
+            if (!rc) rc = nser ? kept_rows(seg.first, seg.len) : TRM_OK;
             if (!rc) rc = CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold, ride);
+            if (!rc && fold) rc = inject_observations(c, n, false, true);
             if (rc) break;
             c->derivative_series = nser;
             fold = 0;
@@ -659,25 +734,90 @@ int trm_adjoint_backward(trm_ctx* c) {
         int end = (int)c->tape_dt.size();
         do {
             int begin = end;
-            while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
+            // (a block also ends at an observed position: its cotangent enters lam between two launches)
+            while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1] && !(begin < end && observed(c, begin))) --begin;
             const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
-            rc = nser ? kept_rows(begin, end - begin) : TRM_OK;
+            rc = inject_observations(c, end, true, !fold);
+            if (!rc) rc = nser ? kept_rows(begin, end - begin) : TRM_OK;
             if (!rc) rc = AdjointLaunch::backward(c, dt_block, end - begin, begin, fold, ride);
+            if (!rc && fold) rc = inject_observations(c, n, false, true);
             if (rc) break;
             c->derivative_series = nser;
             end = begin;
             fold = 0;
         } while (end > 0);
     }
+    if (!rc && n > 0) rc = inject_observations(c, 0, true, true);
     if (rc) {
         c->adj_stale = true;       // (lam is part way down the tape)
         return rc;
     }
+    if (!c->observations.empty()) {   // (the launches above read them)
+        TRM_HIP(c, hipStreamSynchronize(c->stream));
+        drop_observations(c);
+    }
+    if (int rc0 = zero(c, c->d_misfit, rows_bytes(c))) return rc0;
     c->tape_segs.clear();
     c->tape_dt.clear();
     c->tape_rows.clear();
     c->adj_stale = false;
     return finish(c, c->d_adj_param_out ? AdjointLaunch::param_reduce(c) : TRM_OK);
+}
+
+// ---- adjoint observations: cotangents at taped positions (trm_launch_observe.hip) ----------------------------------------------------
+int trm_adjoint_observe(trm_ctx* c, int which, int nlevels, const int32_t* levels, const void* host) {
+    TRM_ENTER_HEUN(c);
+    const char* who = "trm_adjoint_observe";
+    if (int rc = observe_args(c, nlevels, levels, host, who)) return rc;
+    if (int rc = which_ok(c, which, TRM_ADJOINT_LIQUID_WATER_FRACTION + 1, host, who, " (TRM_ADJOINT_*)")) return rc;
+    return register_observation(c, which, nlevels, levels, host, nullptr, who);
+}
+int trm_adjoint_observe_misfit(trm_ctx* c, int nlevels, const int32_t* levels, const void* observed, const void* weight) {
+    TRM_ENTER_HEUN(c);
+    const char* who = "trm_adjoint_observe_misfit";
+    if (int rc = observe_args(c, nlevels, levels, observed, who)) return rc;
+    if (weight) {
+        const double* w = (const double*)weight;
+        for (size_t q = 0, end = (size_t)nlevels * (size_t)c->Nh; q < end; ++q)
+            if (!(w[q] >= 0.0)) return fail(c, TRM_EINVAL, "trm_adjoint_observe_misfit: a weight is negative or NaN");
+    }
+    if (int rc = ensure(c, c->d_misfit, rows_bytes(c), false, who, "the misfit accumulator does not fit")) return rc;
+    if (int rc = register_observation(c, trm_ctx::OBSERVE_MISFIT, nlevels, levels, observed, weight, who)) return rc;
+    if (int rc = ObserveLaunch::misfit(c, c->observations.back())) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_misfit_download(trm_ctx* c, void* host) {
+    TRM_ENTER_HEUN(c);
+    const char* who = "trm_adjoint_misfit_download";
+    if (int rc = adjoint_open(c, who)) return rc;
+    if (int rc = which_ok(c, 0, 1, host, who)) return rc;
+    if (!c->d_misfit) {        // (no misfit observation yet)
+        std::fill((double*)host, (double*)host + c->Nh, 0.0);
+        return TRM_OK;
+    }
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_misfit, rows_bytes(c), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_misfit_device_ptr(trm_ctx* c, void** dev) {
+    TRM_ENTER_HEUN(c);
+    const char* who = "trm_adjoint_misfit_device_ptr";
+    if (int rc = adjoint_open(c, who)) return rc;
+    if (int rc = which_ok(c, 0, 1, dev, who)) return rc;
+    if (int rc = ensure(c, c->d_misfit, rows_bytes(c), false, who, "the misfit accumulator does not fit")) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    *dev = c->d_misfit;
+    return TRM_OK;
+}
+int trm_adjoint_observations(const trm_ctx* c, int* count, int64_t* bytes) {
+    if (!c) return TRM_EINVAL;
+    if (int rc = adjoint_open(const_cast<trm_ctx*>(c), "trm_adjoint_observations")) return rc;
+    int64_t sum = 0;
+    for (const auto& o : c->observations) sum += o.bytes(c->Nh);
+    if (count) *count = (int)c->observations.size();
+    if (bytes) *bytes = sum;
+    return TRM_OK;
 }
 
 }  // extern "C"

@@ -216,6 +216,25 @@ struct trm_ctx {
     };
     int ckpt_interval = 0;
     std::vector<TapeSegment> tape_segs;
+    // adjoint observations (trm_adjoint_observe, trm_adjoint_observe_misfit; trm_launch_observe.hip): cotangents that enter lam at a taped
+    // position, in registration order.  An observation keeps what the caller gave and nothing else: `arrays` arrays of [nlevels][Nh]
+    // doubles (linear: the cotangent; misfit: T_obs, then the weights if any were given) and behind them the nlevels int32 levels, in
+    // one allocation.  `d_misfit`: each column's share of the misfit so far, [Nh] doubles, null until the first misfit observation.
+    // `tape_seg_closed`: an observation has closed the open segment of the checkpointed tape (open_segment_room), so that the next
+    // taped step opens one and the observed state is a checkpoint.
+    struct Observation {
+        int position;   // steps on the tape when it was registered
+        int kind;       // TRM_ADJOINT_* (linear), OBSERVE_MISFIT
+        int nlevels, arrays;
+        double* d_data;
+        const double* array(int a, long Nh) const { return a < arrays ? d_data + (size_t)a * (size_t)nlevels * (size_t)Nh : nullptr; }
+        const int32_t* levels(long Nh) const { return (const int32_t*)(d_data + (size_t)arrays * (size_t)nlevels * (size_t)Nh); }
+        int64_t bytes(long Nh) const { return (int64_t)arrays * nlevels * (int64_t)Nh * 8 + (int64_t)nlevels * 4; }
+    };
+    static constexpr int OBSERVE_MISFIT = 3;
+    std::vector<Observation> observations;
+    double* d_misfit = nullptr;
+    bool tape_seg_closed = false;
     bool args_valid = false;
     void* args = nullptr;   // LaunchArgs<NF>*, owned
     void (*args_free)(void*) = nullptr;
@@ -650,7 +669,7 @@ inline int taped_steps(const trm_ctx* c) {
 }
 // the steps the open segment of a checkpointed tape still takes under `dt` (0: the next step opens a segment)
 inline int open_segment_room(const trm_ctx* c, double dt) {
-    if (c->tape_segs.empty() || c->tape_segs.back().dt != dt) return 0;
+    if (c->tape_segs.empty() || c->tape_segs.back().dt != dt || c->tape_seg_closed) return 0;   // (closed: by an observation at its end)
     return c->ckpt_interval - c->tape_segs.back().len;
 }
 // slots taken, and the slots `nsteps` more steps under `dt` take: one each on the per-step tape; checkpointed, the steps the open segment
@@ -671,9 +690,19 @@ inline void tape_append(trm_ctx* c, double dt, int m) {
     int at = taped_steps(c);
     const int fill = std::min(open_segment_room(c, dt), m);
     if (fill > 0) c->tape_segs.back().len += fill;
-    for (m -= fill, at += fill; m > 0; m -= std::min(K, m), at += K)
+    for (m -= fill, at += fill; m > 0; m -= std::min(K, m), at += K) {
         c->tape_segs.push_back({at, std::min(K, m), dt, (int)c->tape_segs.size()});
+        c->tape_seg_closed = false;    // (a new segment is open)
+    }
 }
+// Adjoint observations (trm_launch_observe.hip).  misfit: 1/2 w (T - T_obs)^2 of the stored temperature on the observed levels onto
+// d_misfit, at registration.  inject: the observation's cotangent through the closure at U_p (`U_p` null: the context's U) onto lU
+// (`lam`) and, with a parameter gradient open, through the heat capacity of that closure onto the per-cell parameter sums (`params`).
+// Neither writes TRM_INFO_LAST_PROGRAM.
+struct ObserveLaunch {
+    static int misfit(trm_ctx* c, const trm_ctx::Observation& o);
+    static int inject(trm_ctx* c, const trm_ctx::Observation& o, const double* U_p, bool lam, bool params);
+};
 // The chain rule between the ten thermal parameters (TRM_THERMAL_PARAM_*, the order of trm_params) and the eight numbers the kernels
 // differentiate (make_dev_params): w[q] = d(derived number) / d(parameter q), with sk_i = sqrt(k_i), s0 = sqrt(k_mineral) frac_mineral +
 // sqrt(k_organic) frac_organic, C0 = c_mineral frac_mineral + c_organic frac_organic.  Parameter q feeds derived number

@@ -538,6 +538,43 @@ class DeviceState:
         """Pulls the cotangents back through every taped step and empties the tape (trm_adjoint_backward)."""
         self._check(self._lib.trm_adjoint_backward(self._ctx), "trm_adjoint_backward")
 
+    # -- adjoint observations (trm_adjoint_observe*): cotangents at taped positions, registered between step_record calls ---------
+    def _observed(self, levels, value):
+        lv = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+        a = np.empty((lv.size, self.grid.Nh), dtype=np.float64)
+        a[...] = value
+        return lv, a
+
+    def observe(self, levels, temperature=None, internal_energy=None, liquid_water_fraction=None):
+        """Linear observations of the state held now, at the taped position reached: for each cotangent given
+        ([len(levels)][Nh], or anything that broadcasts to it) <w, X[levels]> joins the loss adjoint_backward differentiates
+        (trm_adjoint_observe).  `levels`: rows of the host layout (row 0 = bottom layer), strictly increasing."""
+        for name, w in (("internal_energy", internal_energy), ("temperature", temperature), ("liquid_water_fraction", liquid_water_fraction)):
+            if w is None:
+                continue
+            lv, a = self._observed(levels, w)
+            self._check(self._lib.trm_adjoint_observe(self._ctx, _capi.TANGENT[name], lv.size, lv.ctypes.data, a.ctypes.data), "trm_adjoint_observe")
+
+    def observe_misfit(self, levels, observed, weight=None):
+        """1/2 w (T - observed)^2 on `levels` of the temperature held now joins the loss, per column (trm_adjoint_observe_misfit):
+        `observed` and `weight` >= 0 (None: 1) are [len(levels)][Nh] or broadcast to it; a NaN in `observed` is a gap and adds nothing."""
+        lv, obs = self._observed(levels, observed)
+        w = None if weight is None else self._observed(levels, weight)[1]
+        self._check(self._lib.trm_adjoint_observe_misfit(self._ctx, lv.size, lv.ctypes.data, obs.ctypes.data, None if w is None else w.ctypes.data),
+                    "trm_adjoint_observe_misfit")
+
+    def misfit(self) -> np.ndarray:
+        """Each column's share of the misfit registered so far, [Nh] (trm_adjoint_misfit_download); adjoint_backward zeroes it."""
+        a = np.empty(self.grid.Nh, dtype=np.float64)
+        self._check(self._lib.trm_adjoint_misfit_download(self._ctx, a.ctypes.data), "trm_adjoint_misfit_download")
+        return a
+
+    def adjoint_observations(self):
+        """(observations registered, device bytes they hold) (trm_adjoint_observations)."""
+        n, b = C.c_int32(0), C.c_int64(0)
+        self._check(self._lib.trm_adjoint_observations(self._ctx, C.byref(n), C.byref(b)), "trm_adjoint_observations")
+        return int(n.value), int(b.value)
+
     def adjoint_checkpoints(self):
         """(interval, slots used, slot capacity) of the tape (trm_adjoint_checkpoints); interval 0: a per-step tape, its slots are steps."""
         k, n, cap = C.c_int32(0), C.c_int32(0), C.c_int32(0)
@@ -1061,6 +1098,82 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
             if not wrt_boundary and not wrt_params:
                 return g
             out = [g]
+            if wrt_boundary:
+                pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
+                out.append({(var, side): st.bc_series_gradient(var, side) if _series_driven(integ, var, side) else st.bc_gradient(var, side)
+                            for var, side in pairs})
+            if wrt_params:
+                out.append({name: st.param_gradient(name) for name in _capi.THERMAL_PARAMS})
+            return tuple(out)
+    finally:
+        if opened:
+            st.close_adjoint()
+
+
+class TemperatureRecord:
+    """A temperature record as a borehole logger leaves it: `values[nobs][nlevels][Nh]` at the step counts `steps` (non-decreasing,
+    0 = the initial state) on the rows `levels` of the host layout (row 0 = bottom layer, strictly increasing).  `weight` >= 0
+    broadcasts to the shape of `values` (None: 1); a NaN in `values` is a gap and counts for nothing."""
+
+    def __init__(self, steps, levels, values, weight=None):
+        self.steps = [int(s) for s in np.asarray(steps).reshape(-1)]
+        self.levels = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+        self.values = np.asarray(values, dtype=np.float64)
+        if self.values.ndim != 3 or self.values.shape[:2] != (len(self.steps), self.levels.size):
+            raise ValueError("TemperatureRecord: values must be [len(steps)][len(levels)][Nh]")
+        if any(s < 0 for s in self.steps) or any(b < a for a, b in zip(self.steps, self.steps[1:])):
+            raise ValueError("TemperatureRecord: steps must be >= 0 and non-decreasing")
+        self.weight = None if weight is None else np.broadcast_to(np.asarray(weight, dtype=np.float64), self.values.shape)
+
+
+def _tape_slots(positions, steps, K):
+    """Slots a run of `steps` taped steps observed at `positions` takes: one per step, or, checkpointed every K, ceil(stretch / K) over
+    the stretches between observed positions (an observation closes the open segment)."""
+    if K is None:
+        return max(steps, 1)
+    cuts = sorted({0, steps} | {p for p in positions if 0 < p < steps})
+    return max(sum(-(-(b - a) // K) for a, b in zip(cuts, cuts[1:])), 1)
+
+
+def misfit_gradient(integ: ModelIntegrator, record: TemperatureRecord, steps=None, checkpoint_every=None, wrt_boundary=False,
+                    wrt_params=False):
+    """The misfit L = sum_k sum_levels 1/2 w (T_{steps_k} - values_k)^2 of `run!(integ; steps)` to a temperature record, per column,
+    and its gradient from one forward run and one backward sweep: the integrator is stepped `steps` times (None: to the last
+    observation) with its own dt, the record's samples registered where the run reaches their step counts
+    (trm_adjoint_observe_misfit), then everything is pulled back at once.  Returns (L as [Nh], dL/dU_0 as [Nz][Nh]) and behind them
+    what `vjp` appends for `wrt_boundary` and `wrt_params`.  The tape is sized here: one slot per step, or with `checkpoint_every` = K
+    the sum of ceil(stretch / K) over the stretches between observed positions.  Coverage, refusals and option handling of `vjp`."""
+    if not isinstance(integ.timestepper, ForwardEuler):
+        raise ValueError("misfit_gradient: ForwardEuler only")
+    if integ._has_time_dependence() or integ._windowed():
+        raise ValueError("misfit_gradient: boundary conditions and inputs must be constant over the run")
+    st = integ.state
+    last = record.steps[-1] if record.steps else 0
+    steps = last if steps is None else int(steps)
+    if steps < last:
+        raise ValueError("misfit_gradient: the record has observations behind the last step")
+    K = None if checkpoint_every is None else int(checkpoint_every)
+    opened = not getattr(st, "_adjoint_open", False)
+    st.open_adjoint(_tape_slots(record.steps, steps, K), K)
+    try:
+        with _derivative_series(integ, params=wrt_params):
+            dt, at = integ.timestepper.dt, 0
+            for k, s in enumerate(record.steps):
+                if s > at:
+                    st.step_record(dt, s - at)
+                    at = s
+                st.observe_misfit(record.levels, record.values[k], None if record.weight is None else record.weight[k])
+            if steps > at:
+                st.step_record(dt, steps - at)
+            for name in ("internal_energy", "temperature", "liquid_water_fraction"):
+                st.set_cotangent(name, 0.0)
+            if wrt_boundary:
+                st.open_bc_gradient()
+            if wrt_params:
+                st.open_param_gradient()
+            out = [st.misfit()]
+            st.adjoint_backward()
+            out.append(st.cotangent("internal_energy"))
             if wrt_boundary:
                 pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
                 out.append({(var, side): st.bc_series_gradient(var, side) if _series_driven(integ, var, side) else st.bc_gradient(var, side)
