@@ -866,6 +866,48 @@ int trm_adjoint_misfit_download(trm_ctx* ctx, void* host);
 int trm_adjoint_misfit_device_ptr(trm_ctx* ctx, void** dev);
 int trm_adjoint_observations(const trm_ctx* ctx, int* count, int64_t* bytes);
 
+/* ---- Attached records: a temperature record read INSIDE the backward launches ---------------------------------------------------
+ * The calls above make every observed position a launch boundary (and, checkpointed, a slot), and a sweep drops them.  A record that
+ * is ATTACHED to the open adjoint is neither: it is given once, survives sweeps, and the backward kernels read it themselves.
+ *   positions[npos]                 taped-step counts, >= 0, strictly increasing: position p is the state after p taped steps of the
+ *                                   current tape (0: the state at the first trm_step_record)
+ *   levels[nlevels]                 rows of the host layout, strictly increasing (as trm_adjoint_observe_misfit)
+ *   observed[npos][nlevels][num_columns], weight of the same shape (NULL: 1)
+ * L = sum_k sum_j 1/2 w (T_{p_k}[level_j] - T_obs)^2 per column; a NaN in `observed` or a weight 0 contributes nothing.  With a record
+ * attached trm_adjoint_backward gives the gradient of L plus the final cotangents with respect to everything the open rides cover:
+ * position p < n is injected by the launch that pulls back step p, right behind that step (steps > p - 1, the observation of p, step
+ * p - 1); position n enters with the fold.  No position ends a launch, none takes a checkpoint slot: a checkpointed tape of n steps
+ * under one dt takes ceil(n / K) slots whatever the record.
+ *   trm_adjoint_observe_record(ctx, npos, positions, nlevels, levels, observed, weight)
+ *                                           host arrays, copied to the device once
+ *   trm_adjoint_observe_record_device(ctx, npos, positions, nlevels, levels, d_observed, d_weight)
+ *                                           device arrays of the context's device, kept by pointer: they stay the caller's and must
+ *                                           outlive the attachment.  The library cannot read them here, so the weights are NOT
+ *                                           validated: the kernels treat a weight that is not > 0 (negative, NaN) as 0.
+ *   trm_adjoint_record_detach(ctx)          drops the record
+ *   trm_adjoint_record_residual_download(ctx, host)   host[npos][nlevels][num_columns]: r = T_p - T_obs of the last sweep, +0 for a gap
+ *   trm_adjoint_record_residual_device_ptr(ctx, &dev) the same on the device
+ *   trm_adjoint_record_misfit_download(ctx, host)     host[num_columns]: sum of 1/2 w r^2 per column, positions ascending, levels in
+ *                                                     list order, one term at a time (not the buffer of trm_adjoint_misfit_download)
+ *   trm_adjoint_record_info(ctx, &npos, &nlevels, &bytes)  zeros without a record; bytes: the device memory the library holds for it
+ * Residuals and misfit stay readable until the next sweep, a detach or trm_adjoint_close.  The record is dropped by
+ * trm_adjoint_record_detach, trm_adjoint_open* (a new tape) and trm_adjoint_close; trm_adjoint_backward keeps it, successful or not, so a
+ * loop of "upload U_0, trm_step_record, trm_adjoint_backward" never sends it again.  Attaching with steps on the tape is allowed:
+ * positions count from the tape's start.  The two paths do not mix: while a record is attached trm_adjoint_observe* are refused, and
+ * attaching is refused while per-position observations are registered.  These calls touch neither state, clock nor status, make no
+ * tangent stale, and TRM_INFO_LAST_PROGRAM of a record-reading launch is that of the same launch without a record.
+ * Errors: TRM_EINVAL without a context or an open adjoint, npos < 1, nlevels < 1, NULL pointers, positions negative or not strictly
+ * increasing, a level outside 0 ... Nz-1 or out of order, a negative or NaN host weight, a second attach without a detach, the mixing
+ * rules, a download before a sweep has run with this record; trm_adjoint_backward: TRM_EINVAL, before anything is launched and with the
+ * tape left usable, for a record with a position behind the taped steps; TRM_ENOMEM. */
+int trm_adjoint_observe_record(trm_ctx* ctx, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* observed, const void* weight);
+int trm_adjoint_observe_record_device(trm_ctx* ctx, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* d_observed, const void* d_weight);
+int trm_adjoint_record_detach(trm_ctx* ctx);
+int trm_adjoint_record_residual_download(trm_ctx* ctx, void* host);
+int trm_adjoint_record_residual_device_ptr(trm_ctx* ctx, void** dev);
+int trm_adjoint_record_misfit_download(trm_ctx* ctx, void* host);
+int trm_adjoint_record_info(const trm_ctx* ctx, int* npos, int* nlevels, int64_t* bytes);
+
 int trm_clock(const trm_ctx* ctx, double* time, int64_t* iteration);
 int trm_set_clock(trm_ctx* ctx, double time, int64_t iteration);
 

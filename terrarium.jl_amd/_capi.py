@@ -116,7 +116,9 @@ EXPORTS = (
     "trm_tangent_bc_upload trm_adjoint_bc_open trm_adjoint_bc_download trm_adjoint_bc_device_ptr "
     "trm_tangent_param_set trm_adjoint_param_open trm_adjoint_param_download trm_adjoint_param_device_ptr "
     "trm_tangent_bc_series_upload trm_adjoint_bc_series_download trm_adjoint_bc_series_device_ptr "
-    "trm_adjoint_observe trm_adjoint_observe_misfit trm_adjoint_misfit_download trm_adjoint_misfit_device_ptr trm_adjoint_observations").split()
+    "trm_adjoint_observe trm_adjoint_observe_misfit trm_adjoint_misfit_download trm_adjoint_misfit_device_ptr trm_adjoint_observations "
+    "trm_adjoint_observe_record trm_adjoint_observe_record_device trm_adjoint_record_detach trm_adjoint_record_residual_download "
+    "trm_adjoint_record_residual_device_ptr trm_adjoint_record_misfit_download trm_adjoint_record_info").split()
 # the thermal parameters the tangent and the adjoint differentiate (TRM_THERMAL_PARAM_*), in the order of trm_params
 THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
 # forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
@@ -303,6 +305,13 @@ def lib():
     L.trm_adjoint_misfit_download.argtypes = [vp, vp]
     L.trm_adjoint_misfit_device_ptr.argtypes = [vp, C.POINTER(vp)]
     L.trm_adjoint_observations.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
+    L.trm_adjoint_observe_record.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.trm_adjoint_observe_record_device.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.trm_adjoint_record_detach.argtypes = [vp]
+    L.trm_adjoint_record_residual_download.argtypes = [vp, vp]
+    L.trm_adjoint_record_residual_device_ptr.argtypes = [vp, C.POINTER(vp)]
+    L.trm_adjoint_record_misfit_download.argtypes = [vp, vp]
+    L.trm_adjoint_record_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

@@ -303,16 +303,28 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v
     if (viol && ln.act) atomicOr(v.status, viol);
 }
 
-// the transposed step at the state U (the tape's U_k): lam' -> lam.  BCGRAD: and this step's terms onto `acc`; PGRAD: and onto `pacc`
-template <int LPC, bool BCGRAD = false, bool PGRAD = false>
+// the closure quantities a step forms at its state U_k: what an attached record's sample of position k is measured against
+struct StepClosure {
+    double T, C;
+    Frac<double> f;
+};
+// the transposed step at the state U (the tape's U_k): lam' -> lam.  BCGRAD: and this step's terms onto `acc`; PGRAD: and onto `pacc`;
+// KEEP: and T, C and the fractions of the cell into `*keep` (the record-reading sweeps; without it the pointer is not touched)
+template <int LPC, bool BCGRAD = false, bool PGRAD = false, bool KEEP = false>
 TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, const LevelGeom<double>& L, const LaneInfo& ln, int ii,
-                            double U, double sat, double lam, double dt, double bTb, double bTt, bool generic, BcGrad& acc, ParamGrad& pacc) {
+                            double U, double sat, double lam, double dt, double bTb, double bTt, bool generic, BcGrad& acc, ParamGrad& pacc,
+                            StepClosure* keep = nullptr) {
     // T, liq, C and kappa of the cell, as the tangent recomputes them
     uint32_t viol_in = 0;
     double liq, T;
     const Frac<double> f = energy_closure_wave<double, 0>(p, U, sat, liq, T, viol_in);
     const double C = heat_capacity(p, f);
     const double kap = conductivity(p, f);
+    if constexpr (KEEP) {
+        keep->T = T;
+        keep->C = C;
+        keep->f = f;
+    }
     const double T_sh = shfl_up1<double, LPC>(T), kap_sh = shfl_up1<double, LPC>(kap);
     // temperature halos as the primal forms them
     double T_b = T, T_t = T;
@@ -476,6 +488,164 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> 
     if (ln.act) aa.lU[e] = lam;
     if constexpr (BCGRAD) bc_grad_store(aa.g, ln, ii, acc);
     if constexpr (PGRAD) param_grad_store(aa.pg, ln, e, pacc);
+}
+
+// ---- attached records (trm_adjoint_observe_record; DESIGN 4.8 "Attached records") ----------------------------------------------------
+// A temperature record attached to the open adjoint is read inside the backward launches: the loss gains 1/2 w (T_p - T_obs)^2 on the
+// record's levels at its positions, and position p is injected by the launch that pulls back step p, right behind that step's
+// adjoint_step, from the T, C and fractions the step has formed at U_p (StepClosure): lam gets a_p wT through closure_tangent, a
+// parameter sweep closure_param_slope(T, C) wT through param_grad_add_C.  Position n enters with the fold (adjoint_fold's OBS).
+// The fifth kernel argument of the record-reading sweeps.  Lane = level: `row_of_level[Nz]` (-1: not observed) is read once per lane in
+// front of the loop; `row_of_position` points at the entry of the launch's first step in the table of the whole tape ([n + 1], -1: no
+// sample) and is indexed with the step of the launch, a wave-uniform index, so "is this step observed" is a scalar branch.  Arrays
+// [npos][nlevels][Nh]: `observed`, `weight` (null: 1; a weight that is not > 0 counts as 0), and `residual`, where the owning lane
+// writes T_p - T_obs (+0 for a gap).  One lane owns a cell and a position occurs once: nothing is atomic.
+struct RecordArgs {
+    const int32_t* row_of_level;
+    const int32_t* row_of_position;
+    const double* observed;
+    const double* weight;
+    double* residual;
+    int nlevels;
+};
+// a lane's sample of one position, fetched a step ahead of its use (with the next tape slot)
+struct RecordSample {
+    double obs = 0.0, w = 0.0;
+    size_t q = 0;
+    bool have = false;      // this lane owns a sample of the position
+    // w (T - T_obs), +0 for a gap (a NaN sample, a weight that is not > 0) and for a lane without a sample
+    TRM_DEV double operator()(double T) const { return (have && obs == obs && w > 0.0) ? w * (T - obs) : 0.0; }
+};
+// `row`: the position's row of the record (wave-uniform, -1: none); `j`: the lane's row of the level list (-1: none, and for lanes that own no cell)
+TRM_DEV RecordSample record_fetch(const RecordArgs& r, int row, int j, int ii, long long Nh) {
+    RecordSample s;
+    if (row >= 0) {
+        s.have = j >= 0;
+        if (s.have) {
+            s.q = ((size_t)row * (size_t)r.nlevels + (size_t)j) * (size_t)Nh + (size_t)ii;
+            s.obs = r.observed[s.q];
+            s.w = r.weight ? r.weight[s.q] : 1.0;
+        }
+    }
+    return s;
+}
+// the residual of the owning lane, and the sample's cotangent wT
+TRM_DEV double record_residual(const RecordArgs& r, const RecordSample& s, double T) {
+    const double wT = s(T);
+    if (s.have) r.residual[s.q] = (s.obs == s.obs && s.w > 0.0) ? T - s.obs : 0.0;
+    return wT;
+}
+// behind adjoint_step of the step at U_p: the sample of position p onto lam and, PGRAD, onto the heat-capacity sums
+template <bool PGRAD>
+TRM_DEV void record_inject(const DevParams<double>& p, const RecordArgs& r, const RecordSample& s, const StepClosure& cl, double U, double sat, double& lam,
+                           ParamGrad& pacc) {
+    const double wT = record_residual(r, s, cl.T);
+    double via_T, unused_liq;
+    closure_tangent(p, U, sat, cl.C, wT, unused_liq, via_T);
+    lam = wT != 0.0 ? lam + via_T : lam;      // (a gap adds nothing, not even the sign of a zero)
+    if constexpr (PGRAD) param_grad_add_C(pacc, cl.f, closure_param_slope(cl.T, cl.C) * wT);
+}
+// The fold of a record-reading sweep: adjoint_fold, with the cotangent of the record's sample of position n = the launch's last position
+// added to the final wT in front of the closure.  (A function of its own and not a parameter of adjoint_fold: with the parameter the
+// existing parameter sweeps came out of the compiler with the operands of two additions swapped.)
+template <bool PGRAD>
+TRM_DEV void record_fold(const View<double>& v, const DevParams<double>& p, const RecordArgs& r, const LaneInfo& ln, int ii, int j, int nsteps, size_t e, double sat,
+                         double& lam, double* lT, double* lliq, ParamGrad& pacc) {
+    using NF = double;
+    const RecordSample s = record_fetch(r, r.row_of_position[nsteps], j, ii, v.Nh);
+    const NF U = v.U[e], wT_final = lT[e], wliq = lliq[e];
+    uint32_t viol_in = 0;
+    NF liq, T, via_T, via_liq, unused_liq, unused_T;
+    const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
+    const NF C = heat_capacity(p, f);
+    const NF x = record_residual(r, s, T);
+    const NF wT = x != 0.0 ? wT_final + x : wT_final;          // (a gap adds nothing, not even the sign of a zero)
+    closure_tangent(p, U, sat, C, wT, unused_liq, via_T);
+    closure_tangent(p, U, sat, C, wliq, via_liq, unused_T);
+    lam = lam + via_T + via_liq;
+    if constexpr (PGRAD) param_grad_add_C(pacc, f, closure_param_slope(T, C) * wT);
+    if (ln.act) {
+        lT[e] = 0.0;
+        lliq[e] = 0.0;
+    }
+}
+
+// k_column_adjoint with an attached record: the same sweep, and behind every step's adjoint_step the sample of the step's position.
+// The sample of a step is fetched where the slot of that step is, a step ahead; the fold takes position `a.nsteps` of the launch (n).
+template <int HYD, int LPC, Ride R>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, SweepArgs<false, R> aa, RecordArgs r) {
+    constexpr bool BCGRAD = ride_has_bc(R), PGRAD = ride_has_params(R), SERIES = ride_has_series(R);
+    using NF = double;
+    int ii;
+    size_t e;
+    const LaneInfo ln = adjoint_lane<LPC>(v, ii, e);
+    const bool generic = aa.generic != 0;
+    const NF sat = v.sat[e];
+    NF lam = aa.lU[e];
+    const int j = ln.act ? r.row_of_level[ln.k] : -1;
+    const NF* slot = aa.tape + (size_t)(a.nsteps > 0 ? a.nsteps - 1 : 0) * (size_t)aa.slot_elems + e;
+    NF U_next = a.nsteps > 0 ? *slot : 0.0;
+    int row_next = a.nsteps > 0 ? r.row_of_position[a.nsteps - 1] : -1;
+    RecordSample s_next = record_fetch(r, row_next, j, ii, v.Nh);
+    const LevelGeom<NF> L = level_geom(v, ln.k);
+    const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
+    const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
+    ParamGrad pacc;
+    if constexpr (PGRAD) pacc = param_grad_load(aa.pg, e, aa.fold);
+    if (aa.fold) record_fold<PGRAD>(v, p, r, ln, ii, j, a.nsteps, e, sat, lam, aa.lT, aa.lliq, pacc);
+    BcGrad acc;
+    if constexpr (BCGRAD) acc = bc_grad_load(aa.g, ii, aa.fold);
+    // as in k_column_adjoint: what the head has loaded is used in front of the loop, so that inside it the next slot and the next sample
+    // are the only loads in flight
+    asm volatile("" ::"v"(sat), "v"(lam), "v"(j), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt), "v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub), "v"(acc.Ut));
+    if constexpr (PGRAD)
+        asm volatile("" ::"v"(pacc.sk_water), "v"(pacc.sk_ice), "v"(pacc.sk_air), "v"(pacc.s0), "v"(pacc.c_water), "v"(pacc.c_ice), "v"(pacc.c_air), "v"(pacc.C0));
+    SeriesGrad sg;
+    NF bTb_next = bTb, bTt_next = bTt;
+    if constexpr (SERIES)
+        if (a.nsteps > 0) series_temperatures(a, ii, a.nsteps - 1, bTb_next, bTt_next);
+    for (int step = a.nsteps - 1; step >= 0; --step) {
+        const NF U = U_next, sTb = bTb_next, sTt = bTt_next;
+        const RecordSample s = s_next;
+        const int row = row_next;
+        if (step > 0) {
+            slot -= aa.slot_elems;
+            U_next = *slot;
+            row_next = r.row_of_position[step - 1];
+            s_next = record_fetch(r, row_next, j, ii, v.Nh);
+            if constexpr (SERIES) series_temperatures(a, ii, step - 1, bTb_next, bTt_next);
+        }
+        StepClosure cl;
+        if constexpr (SERIES) {
+            BcGrad term;
+            lam = adjoint_step<LPC, BCGRAD, PGRAD, true>(v, p, L, ln, ii, U, sat, lam, a.dt, sTb, sTt, generic, term, pacc, &cl);
+            series_grad_step(a, aa.sg, ln, ii, step, term, acc, sg);
+        } else lam = adjoint_step<LPC, BCGRAD, PGRAD, true>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc, pacc, &cl);
+        if (row >= 0) record_inject<PGRAD>(p, r, s, cl, U, sat, lam, pacc);
+    }
+    if constexpr (SERIES) series_grad_store(a, aa.sg, ln, ii, sg);
+    if (ln.act) aa.lU[e] = lam;
+    if constexpr (BCGRAD) bc_grad_store(aa.g, ln, ii, acc);
+    if constexpr (PGRAD) param_grad_store(aa.pg, ln, e, pacc);
+}
+
+// the misfit of an attached record after a sweep: one thread per column sums 1/2 w r^2 over the residuals the sweep wrote, positions in
+// ascending order, levels in list order, one term at a time (a weight that is not > 0 counts as 0; a gap's residual is +0).  A template
+// like k_param_reduce, so that only the translation unit that launches it holds a copy.
+template <class NF> __global__ void __launch_bounds__(256) k_record_misfit(const NF* __restrict__ residual, const NF* __restrict__ weight, NF* __restrict__ out,
+                                                       long long Nh, int npos, int nlevels) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= Nh) return;
+    double s = 0.0;
+    for (int k = 0; k < npos; ++k)
+        for (int j = 0; j < nlevels; ++j) {
+            const size_t q = ((size_t)k * (size_t)nlevels + (size_t)j) * (size_t)Nh + (size_t)i;
+            const double r = residual[q];
+            double w = weight ? weight[q] : 1.0;
+            if (!(w > 0.0)) w = 0.0;
+            s = s + 0.5 * w * r * r;
+        }
+    out[i] = s;
 }
 
 // trm_adjoint_backward's last launch under PGRAD: one thread per column sums each of the eight fields over k = 0 ... Nz-1 in ascending

@@ -102,4 +102,96 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt(View<dou
     if constexpr (PGRAD) param_grad_store(ca.pg, ln, e, pacc);
 }
 
+// k_column_adjoint_ckpt with an attached record (RecordArgs, trm_column_adjoint.hpp): the same recompute and the same backward loop, and
+// behind the adjoint_step of state j -- U_p is mine[j * TRM_STEP_BLOCK] -- the sample of the segment's position j; the fold takes
+// position m of the segment (n).  The sample of a step is fetched a step ahead.  Nothing new goes to LDS.
+template <int HYD, int LPC, Ride R>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_ckpt_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, SweepArgs<true, R> ca, RecordArgs r) {
+    constexpr bool BCGRAD = ride_has_bc(R), PGRAD = ride_has_params(R), SERIES = ride_has_series(R);
+    using NF = double;
+    extern __shared__ double seg[];
+    int ii;
+    size_t e;
+    const LaneInfo ln = adjoint_lane<LPC>(v, ii, e);
+    const bool generic = ca.generic != 0;
+    const int Nz = v.Nz, m = a.nsteps;
+    const NF sat = v.sat[e];
+    NF lam = ca.lU[e];
+    const int jl = ln.act ? r.row_of_level[ln.k] : -1;
+    Cell<NF> c;
+    c.U = m > 0 ? ca.tape[e] : 0.0;
+    c.sat = sat;
+    c.T = 0.0;
+    c.liq = 0.0;
+    c.psi = 0.0;
+    const LevelGeom<NF> L = level_geom(v, ln.k);
+    const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
+    const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
+    ParamGrad pacc;
+    if constexpr (PGRAD) pacc = param_grad_load(ca.pg, e, ca.fold);
+    if (ca.fold) record_fold<PGRAD>(v, p, r, ln, ii, jl, m, e, sat, lam, ca.lT, ca.lliq, pacc);
+    BcGrad acc;
+    if constexpr (BCGRAD) acc = bc_grad_load(ca.g, ii, ca.fold);
+
+    // ---- recompute: as k_column_adjoint_ckpt
+    NF* mine = seg + threadIdx.x;
+    if (m > 1) {
+        ColumnBC<NF> bc;
+        bc.bTb = bTb;
+        bc.bTt = bTt;
+        bc.flux_S = 0.0;
+        bc.has_U = true;
+        bc.has_S = false;
+        record_flux_U(v, ln, ii, generic, bc);
+        uint32_t viol = 0;
+        bool bad = false;
+        Frac<NF> f = column_closure<NF, false, HYD>(p, L, 0.0, c, viol);
+        for (int j = 0; j < m - 1; ++j) {
+            mine[j * TRM_STEP_BLOCK] = c.U;
+            if constexpr (SERIES) {
+                NF unused_b = 0.0, unused_t = 0.0, unused_U = 0.0;
+                series_boundary_step<false, false>(v, a, ln, ii, j, bc, nullptr, unused_b, unused_t, unused_U);
+            }
+            const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
+                                           : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, &f);
+            NF gU = t.gU, gS = t.gS, z0;
+            Cell<NF> n = c;
+            column_advance<NF, false, LPC>(v, L, ln, Nz, bc, c.U, c.sat, gU, gS, a.dt, n, z0, bad);
+            f = column_closure<NF, false, HYD>(p, L, z0, n, viol);
+            c = n;
+        }
+    }
+    if (m > 0) mine[(m - 1) * TRM_STEP_BLOCK] = c.U;
+
+    // ---- backward: the transposed steps at U_{c+m-1} ... U_c, each followed by the sample of its position
+    SeriesGrad sg;
+    NF sTb = bTb, sTt = bTt;
+    if constexpr (SERIES)
+        if (m > 0) series_temperatures(a, ii, m - 1, sTb, sTt);
+    int row_next = m > 0 ? r.row_of_position[m - 1] : -1;
+    RecordSample s_next = record_fetch(r, row_next, jl, ii, v.Nh);
+    for (int j = m - 1; j >= 0; --j) {
+        const NF uTb = sTb, uTt = sTt;
+        const RecordSample s = s_next;
+        const int row = row_next;
+        if (j > 0) {
+            row_next = r.row_of_position[j - 1];
+            s_next = record_fetch(r, row_next, jl, ii, v.Nh);
+            if constexpr (SERIES) series_temperatures(a, ii, j - 1, sTb, sTt);
+        }
+        const NF U = mine[j * TRM_STEP_BLOCK];
+        StepClosure cl;
+        if constexpr (SERIES) {
+            BcGrad term;
+            lam = adjoint_step<LPC, BCGRAD, PGRAD, true>(v, p, L, ln, ii, U, sat, lam, a.dt, uTb, uTt, generic, term, pacc, &cl);
+            series_grad_step(a, ca.sg, ln, ii, j, term, acc, sg);
+        } else lam = adjoint_step<LPC, BCGRAD, PGRAD, true>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc, pacc, &cl);
+        if (row >= 0) record_inject<PGRAD>(p, r, s, cl, U, sat, lam, pacc);
+    }
+    if constexpr (SERIES) series_grad_store(a, ca.sg, ln, ii, sg);
+    if (ln.act) ca.lU[e] = lam;
+    if constexpr (BCGRAD) bc_grad_store(ca.g, ln, ii, acc);
+    if constexpr (PGRAD) param_grad_store(ca.pg, ln, e, pacc);
+}
+
 }  // namespace trm

@@ -74,8 +74,22 @@ void drop_observations(trm_ctx* c) {
     c->observations.clear();
     c->tape_seg_closed = false;
 }
+// the attached record (trm_adjoint_observe_record*): its tables, outputs and copies; the caller's device arrays are the caller's
+void drop_record(trm_ctx* c) {
+    release(c->d_rec_owned);
+    release(c->d_rec_out);
+    release(c->d_rec_tables);
+    c->d_rec_observed = c->d_rec_weight = nullptr;
+    c->rec_positions.clear();
+    c->rec_levels.clear();
+    c->rec_table_host.clear();
+    c->rec_npos = c->rec_nlevels = 0;
+    c->rec_table_n = -1;
+    c->rec_swept = false;
+}
 void release_tape(trm_ctx* c) {
     drop_observations(c);
+    drop_record(c);
     release(c->d_tape);
     c->tape_cap = 0;
     c->ckpt_interval = 0;
@@ -292,6 +306,7 @@ int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who)
     if (rc) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     drop_observations(c);
+    drop_record(c);
     c->tape_dt.clear();        // (a fresh tape)
     c->tape_segs.clear();
     c->tape_rows.clear();
@@ -352,6 +367,7 @@ int register_observation(trm_ctx* c, int kind, int nlevels, const int32_t* level
 // what both registrations check first
 int observe_args(trm_ctx* c, int nlevels, const int32_t* levels, const void* host, const char* who) {
     if (int rc = adjoint_open(c, who)) return rc;
+    if (int rc = record_excludes_observations(c, who)) return rc;
     if (int rc = observed_levels_ok(c, nlevels, levels, who)) return rc;
     if (int rc = which_ok(c, 0, 1, host, who)) return rc;
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTape);
@@ -377,6 +393,56 @@ int inject_observations(trm_ctx* c, int p, bool lam, bool params) {
     for (const auto& o : c->observations)
         if (o.position == p)
             if (int rc = ObserveLaunch::inject(c, o, U_p, lam, params)) return rc;
+    return TRM_OK;
+}
+// ---- attached records ------------------------------------------------------------------------------------------------------------------
+// The record joins the open adjoint: the level table, the residuals and the misfit are the library's; `observed` / `weight` are host arrays
+// the library copies once (`device` false) or device arrays it keeps by pointer
+int attach_record(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* observed, const void* weight, bool device, const char* who) {
+    if (int rc = record_attach_ok(c, npos, positions, nlevels, levels, observed, device ? nullptr : (const double*)weight, who)) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t cells = (size_t)npos * (size_t)nlevels * (size_t)c->Nh, cell_bytes = cells * sizeof(double);
+    const std::string w(who);
+    int rc = ensure(c, c->d_rec_out, cell_bytes + rows_bytes(c), true, w, "the residuals do not fit");
+    if (!rc && !device) rc = ensure(c, c->d_rec_owned, cell_bytes * (weight ? 2 : 1), false, w, "the record does not fit");
+    if (!rc) {
+        hipError_t e = hipSuccess;
+        if (!device) {
+            e = hipMemcpyAsync(c->d_rec_owned, observed, cell_bytes, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess && weight) e = hipMemcpyAsync(c->d_rec_owned + cells, weight, cell_bytes, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        }
+        if (e != hipSuccess) rc = fail(c, TRM_EHIP, w + ": " + hipGetErrorString(e));
+    }
+    if (rc) {
+        drop_record(c);
+        return rc;
+    }
+    c->d_rec_observed = device ? (const double*)observed : c->d_rec_owned;
+    c->d_rec_weight = !weight ? nullptr : device ? (const double*)weight : c->d_rec_owned + cells;
+    c->rec_positions.assign(positions, positions + npos);
+    c->rec_levels.assign(levels, levels + nlevels);
+    c->rec_npos = npos;
+    c->rec_nlevels = nlevels;
+    c->rec_table_n = -1;       // (the tables go up with the first sweep: they depend on the steps the tape holds then)
+    c->rec_swept = false;
+    return TRM_OK;
+}
+// row_of_level and row_of_position of a tape of n steps, in front of a sweep's first launch; a sweep over the count of the sweep before
+// finds them in place
+int record_tables(trm_ctx* c, int n, const char* who) {
+    if (c->rec_table_n == n && c->d_rec_tables) return TRM_OK;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    release(c->d_rec_tables);
+    c->rec_table_n = -1;
+    c->rec_table_host = record_level_table(c->Nz, c->rec_levels);
+    const std::vector<int32_t> rows = record_position_table(n, c->rec_positions);
+    c->rec_table_host.insert(c->rec_table_host.end(), rows.begin(), rows.end());
+    const size_t bytes = c->rec_table_host.size() * sizeof(int32_t);
+    if (alloc_if_null(c->d_rec_tables, (bytes + 7) / 8 * 8) != hipSuccess) return fail(c, TRM_ENOMEM, std::string(who) + ": the record's tables do not fit");
+    TRM_HIP(c, hipMemcpyAsync(c->d_rec_tables, c->rec_table_host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    c->rec_table_n = n;
     return TRM_OK;
 }
 }  // namespace
@@ -694,6 +760,12 @@ int trm_adjoint_backward(trm_ctx* c) {
     const int nser = derivative_series_count(c);
     if (int rc = params_with_series_ok(c, c->d_adj_param_out != nullptr, who)) return rc;
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTape);
+    // An attached record (trm_adjoint_observe_record) is read inside the launches: no position of it is a launch boundary.  A record
+    // longer than the tape is refused here, in front of everything the sweep does
+    const bool rec = c->rec_npos > 0;
+    if (int rc = record_fits_tape(c, taped_steps(c), who)) return rc;
+    if (rec)
+        if (int rc = record_tables(c, taped_steps(c), who)) return rc;
     if (nser) {
         // series ride with the accumulating instances: the per-column accumulators if nobody has opened them, and the node accumulators,
         // zero in front of the sweep's first launch; every launch gets the rows the record kept for its steps
@@ -720,7 +792,7 @@ int trm_adjoint_backward(trm_ctx* c) {
             const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
             rc = inject_observations(c, seg.first + seg.len, true, !fold);   // (a segment ends at every observed position)
             if (!rc) rc = nser ? kept_rows(seg.first, seg.len) : TRM_OK;
-            if (!rc) rc = CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold, ride);
+            if (!rc) rc = rec ? RecordLaunch::backward(c, true, seg.dt, seg.len, seg.slot, fold, ride, seg.first) : CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold, ride);
             if (!rc && fold) rc = inject_observations(c, n, false, true);
             if (rc) break;
             c->derivative_series = nser;
@@ -739,7 +811,7 @@ int trm_adjoint_backward(trm_ctx* c) {
             const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
             rc = inject_observations(c, end, true, !fold);
             if (!rc) rc = nser ? kept_rows(begin, end - begin) : TRM_OK;
-            if (!rc) rc = AdjointLaunch::backward(c, dt_block, end - begin, begin, fold, ride);
+            if (!rc) rc = rec ? RecordLaunch::backward(c, false, dt_block, end - begin, begin, fold, ride, begin) : AdjointLaunch::backward(c, dt_block, end - begin, begin, fold, ride);
             if (!rc && fold) rc = inject_observations(c, n, false, true);
             if (rc) break;
             c->derivative_series = nser;
@@ -748,6 +820,10 @@ int trm_adjoint_backward(trm_ctx* c) {
         } while (end > 0);
     }
     if (!rc && n > 0) rc = inject_observations(c, 0, true, true);
+    if (!rc && rec) {          // (the residuals the launches wrote, summed in front of k_param_reduce)
+        rc = RecordLaunch::misfit(c);
+        c->rec_swept = rc == TRM_OK;
+    }
     if (rc) {
         c->adj_stale = true;       // (lam is part way down the tape)
         return rc;
@@ -808,6 +884,53 @@ int trm_adjoint_misfit_device_ptr(trm_ctx* c, void** dev) {
     if (int rc = ensure(c, c->d_misfit, rows_bytes(c), false, who, "the misfit accumulator does not fit")) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     *dev = c->d_misfit;
+    return TRM_OK;
+}
+// ---- attached records: a temperature record read inside the backward launches (trm_launch_record.hip) -------------------------------
+int trm_adjoint_observe_record(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* observed, const void* weight) {
+    TRM_ENTER_HEUN(c);
+    return attach_record(c, npos, positions, nlevels, levels, observed, weight, false, "trm_adjoint_observe_record");
+}
+int trm_adjoint_observe_record_device(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* d_observed, const void* d_weight) {
+    TRM_ENTER_HEUN(c);
+    return attach_record(c, npos, positions, nlevels, levels, d_observed, d_weight, true, "trm_adjoint_observe_record_device");
+}
+int trm_adjoint_record_detach(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    const char* who = "trm_adjoint_record_detach";
+    if (int rc = adjoint_open(c, who)) return rc;
+    if (c->rec_npos == 0) return fail(c, TRM_EINVAL, std::string(who) + ": no record is attached (trm_adjoint_observe_record)");
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    drop_record(c);
+    return TRM_OK;
+}
+int trm_adjoint_record_residual_download(trm_ctx* c, void* host) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = record_results_ok(c, host, "trm_adjoint_record_residual_download")) return rc;
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out, rows_bytes(c, (long)c->rec_npos * c->rec_nlevels), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_record_residual_device_ptr(trm_ctx* c, void** dev) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = record_results_ok(c, dev, "trm_adjoint_record_residual_device_ptr")) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    *dev = c->d_rec_out;
+    return TRM_OK;
+}
+int trm_adjoint_record_misfit_download(trm_ctx* c, void* host) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = record_results_ok(c, host, "trm_adjoint_record_misfit_download")) return rc;
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out + (size_t)c->rec_npos * (size_t)c->rec_nlevels * (size_t)c->Nh, rows_bytes(c), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_adjoint_record_info(const trm_ctx* c, int* npos, int* nlevels, int64_t* bytes) {
+    if (!c) return TRM_EINVAL;
+    if (int rc = adjoint_open(const_cast<trm_ctx*>(c), "trm_adjoint_record_info")) return rc;
+    if (npos) *npos = c->rec_npos;
+    if (nlevels) *nlevels = c->rec_nlevels;
+    if (bytes) *bytes = record_bytes(c);
     return TRM_OK;
 }
 int trm_adjoint_observations(const trm_ctx* c, int* count, int64_t* bytes) {

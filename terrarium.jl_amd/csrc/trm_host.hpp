@@ -235,6 +235,22 @@ struct trm_ctx {
     std::vector<Observation> observations;
     double* d_misfit = nullptr;
     bool tape_seg_closed = false;
+    // An attached temperature record (trm_adjoint_observe_record*; DESIGN 4.8 "Attached records"): read inside the backward launches, kept
+    // across sweeps, dropped by a detach, a new tape or trm_adjoint_close.  `rec_positions` / `rec_levels`: what the caller gave (taped-step
+    // counts and rows of the host layout, both strictly increasing); rec_npos == 0: none attached.  `d_rec_observed` / `d_rec_weight`
+    // ([npos][nlevels][Nh]; the weights may be null): the library's copies in `d_rec_owned`, or the caller's device arrays (then
+    // d_rec_owned is null).  `d_rec_out`: the residuals [npos][nlevels][Nh] and behind them the misfit [Nh].  `d_rec_tables`: int32
+    // row_of_level[Nz], then row_of_position[rec_table_n + 1] as built for a tape of rec_table_n steps (-1: not built yet; a sweep over
+    // another count builds it again).  `rec_swept`: a sweep has run with this record, so the residuals and the misfit are its.
+    std::vector<int> rec_positions, rec_levels;
+    int rec_npos = 0, rec_nlevels = 0;
+    double* d_rec_owned = nullptr;
+    const double *d_rec_observed = nullptr, *d_rec_weight = nullptr;
+    double* d_rec_out = nullptr;
+    double* d_rec_tables = nullptr;
+    int rec_table_n = -1;
+    std::vector<int32_t> rec_table_host;   // (the staging copy of row_of_position: alive while its upload is in flight)
+    bool rec_swept = false;
     bool args_valid = false;
     void* args = nullptr;   // LaunchArgs<NF>*, owned
     void (*args_free)(void*) = nullptr;
@@ -702,6 +718,79 @@ inline void tape_append(trm_ctx* c, double dt, int m) {
 struct ObserveLaunch {
     static int misfit(trm_ctx* c, const trm_ctx::Observation& o);
     static int inject(trm_ctx* c, const trm_ctx::Observation& o, const double* U_p, bool lam, bool params);
+};
+// ---- attached records (trm_adjoint_observe_record*; trm_launch_record.hip) -- bookkeeping alone, no HIP call
+// (tests/record_preconditions.cpp) ----
+// row_of_level[Nz]: the row of the record's level list a level has, -1 for a level it does not observe
+inline std::vector<int32_t> record_level_table(int Nz, const std::vector<int>& levels) {
+    std::vector<int32_t> t((size_t)Nz, -1);
+    for (size_t j = 0; j < levels.size(); ++j) t[(size_t)levels[j]] = (int32_t)j;
+    return t;
+}
+// row_of_position[n + 1] of a tape of n steps: the row of the record a taped position has, -1 without a sample.  Positions behind n
+// have no entry (the sweep refuses them first, record_fits_tape)
+inline std::vector<int32_t> record_position_table(int n, const std::vector<int>& positions) {
+    std::vector<int32_t> t((size_t)n + 1, -1);
+    for (size_t k = 0; k < positions.size(); ++k)
+        if (positions[k] <= n) t[(size_t)positions[k]] = (int32_t)k;
+    return t;
+}
+// what the library holds for an attached record: the tables, the residuals and the misfit, and its copies of a host record
+inline int64_t record_bytes(const trm_ctx* c) {
+    if (c->rec_npos == 0) return 0;
+    const int64_t cells = (int64_t)c->rec_npos * c->rec_nlevels * (int64_t)c->Nh * 8;
+    const int64_t tables = ((int64_t)c->Nz + (c->rec_table_n >= 0 ? (int64_t)c->rec_table_n + 1 : 0)) * 4;
+    const int64_t owned = c->d_rec_owned ? cells * (c->d_rec_weight ? 2 : 1) : 0;
+    return owned + cells + (int64_t)c->Nh * 8 + tables;
+}
+// What an attach checks before it touches the device, in the words of the neighbouring calls.  `host_weight`: the weights of the host
+// form (null: none given, or the device form, whose weights the library cannot read)
+inline int record_attach_ok(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* observed, const double* host_weight,
+                            const char* who) {
+    const std::string w(who);
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, w + ": no adjoint is open (trm_adjoint_open)");
+    if (npos < 1 || nlevels < 1 || !positions || !levels || !observed) return fail(c, TRM_EINVAL, w + ": bad argument (npos >= 1 positions, nlevels >= 1 levels, the observed temperatures)");
+    for (int k = 0; k < npos; ++k)
+        if (positions[k] < 0 || (k > 0 && positions[k] <= positions[k - 1])) return fail(c, TRM_EINVAL, w + ": the positions are taped-step counts >= 0, strictly increasing");
+    for (int j = 0; j < nlevels; ++j)
+        if (levels[j] < 0 || levels[j] >= c->Nz || (j > 0 && levels[j] <= levels[j - 1]))
+            return fail(c, TRM_EINVAL, w + ": the levels are rows 0 ... " + std::to_string(c->Nz - 1) + " of the host layout, strictly increasing");
+    if (host_weight)
+        for (size_t q = 0, end = (size_t)npos * (size_t)nlevels * (size_t)c->Nh; q < end; ++q)
+            if (!(host_weight[q] >= 0.0)) return fail(c, TRM_EINVAL, w + ": a weight is negative or NaN");
+    if (c->rec_npos) return fail(c, TRM_EINVAL, w + ": a record is attached already (trm_adjoint_record_detach)");
+    if (!c->observations.empty())
+        return fail(c, TRM_EINVAL, w + ": per-position observations are registered (trm_adjoint_observe, trm_adjoint_observe_misfit): the two paths do not mix");
+    return TRM_OK;
+}
+// trm_adjoint_observe / trm_adjoint_observe_misfit while a record is attached
+inline int record_excludes_observations(trm_ctx* c, const char* who) {
+    if (c->rec_npos == 0) return TRM_OK;
+    return fail(c, TRM_EINVAL, std::string(who) + ": a temperature record is attached (trm_adjoint_observe_record): the two paths do not mix");
+}
+// a sweep over a tape of n steps: every position of the record is on it
+inline int record_fits_tape(trm_ctx* c, int n, const char* who) {
+    if (c->rec_npos == 0 || c->rec_positions.back() <= n) return TRM_OK;
+    return fail(c, TRM_EINVAL, std::string(who) + ": the attached record is longer than the tape: position " + std::to_string(c->rec_positions.back()) + " of " +
+                                   std::to_string(n) + " taped steps");
+}
+// the residuals and the misfit are those of a sweep with this record
+inline int record_results_ok(trm_ctx* c, const void* ptr, const char* who) {
+    const std::string w(who);
+    if (!c->d_adj[0]) return fail(c, TRM_EINVAL, w + ": no adjoint is open (trm_adjoint_open)");
+    if (!ptr) return fail(c, TRM_EINVAL, w + ": bad argument");
+    if (c->rec_npos == 0) return fail(c, TRM_EINVAL, w + ": no record is attached (trm_adjoint_observe_record)");
+    if (!c->rec_swept) return fail(c, TRM_EINVAL, w + ": no sweep has run with this record (trm_adjoint_backward)");
+    return TRM_OK;
+}
+// The record-reading sweeps: k_column_adjoint_record / k_column_adjoint_ckpt_record (one explicit instantiation per tape and ride in
+// trm_launch_column_adjoint{,_ckpt}_record{,_bc,_param,_series,_param_series}.hip) and k_record_misfit (trm_launch_record.hip, with the
+// dispatch over the ride).  `first`: the taped position of the launch's first step.  TRM_INFO_LAST_PROGRAM is that of the same launch
+// without a record.
+template <bool CKPT, Ride R> int adjoint_backward_record(trm_ctx* c, double dt, int nsteps, int slot, int fold, int first);
+struct RecordLaunch {
+    static int backward(trm_ctx* c, bool ckpt, double dt, int nsteps, int slot, int fold, Ride ride, int first);
+    static int misfit(trm_ctx* c);
 };
 // The chain rule between the ten thermal parameters (TRM_THERMAL_PARAM_*, the order of trm_params) and the eight numbers the kernels
 // differentiate (make_dev_params): w[q] = d(derived number) / d(parameter q), with sk_i = sqrt(k_i), s0 = sqrt(k_mineral) frac_mineral +

@@ -481,10 +481,12 @@ class DeviceState:
         else:
             self._check(self._lib.trm_adjoint_open_checkpointed(self._ctx, int(capacity), int(checkpoint_every)), "trm_adjoint_open_checkpointed")
         self._adjoint_open = True
+        self._record_arrays = None      # (a new tape drops an attached record)
 
     def close_adjoint(self):
         self._check(self._lib.trm_adjoint_close(self._ctx), "trm_adjoint_close")
         self._adjoint_open = False
+        self._record_arrays = None
 
     def set_cotangent(self, name, value):
         """The cotangent of a final field ([Nz][Nh], or anything that broadcasts to it)."""
@@ -574,6 +576,60 @@ class DeviceState:
         n, b = C.c_int32(0), C.c_int64(0)
         self._check(self._lib.trm_adjoint_observations(self._ctx, C.byref(n), C.byref(b)), "trm_adjoint_observations")
         return int(n.value), int(b.value)
+
+    # -- attached records (trm_adjoint_observe_record*): a temperature record read inside the backward launches, kept across sweeps ----
+    def attach_record(self, positions, levels, observed, weight=None):
+        """Attaches a temperature record to the open adjoint: 1/2 w (T_p - observed)^2 on `levels` at the taped positions `positions`
+        (step counts of the current tape, strictly increasing) joins the loss of every adjoint_backward until detach_record, a new
+        tape or close_adjoint.  `observed[npos][nlevels][Nh]` and `weight` (None: 1) are numpy arrays (or anything that broadcasts to the
+        shape), copied once (trm_adjoint_observe_record), or float64 torch tensors of that shape on the context's device, kept by
+        pointer without a copy (trm_adjoint_observe_record_device; their weights are not validated: one that is not > 0 counts as 0).
+        No position is a launch boundary and none takes a checkpoint slot."""
+        pos = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1)
+        lv = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+        shape = (pos.size, lv.size, self.grid.Nh)
+        if hasattr(observed, "data_ptr"):
+            tensors = [observed] + ([] if weight is None else [weight])
+            for t in tensors:
+                if not hasattr(t, "data_ptr") or not t.is_cuda or t.device.index != int(self.grid.device) or str(t.dtype) != "torch.float64" \
+                        or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"attach_record: device arrays must be contiguous float64 tensors of shape {shape} on device {int(self.grid.device)}")
+            self._check(self._lib.trm_adjoint_observe_record_device(self._ctx, pos.size, pos.ctypes.data, lv.size, lv.ctypes.data, C.c_void_p(observed.data_ptr()),
+                                                                    None if weight is None else C.c_void_p(weight.data_ptr())), "trm_adjoint_observe_record_device")
+            self._record_arrays = tensors       # (the library keeps the pointers: the tensors live as long as the attachment)
+            return
+        obs = np.empty(shape, dtype=np.float64)
+        obs[...] = observed
+        w = None
+        if weight is not None:
+            w = np.empty(shape, dtype=np.float64)
+            w[...] = weight
+        self._check(self._lib.trm_adjoint_observe_record(self._ctx, pos.size, pos.ctypes.data, lv.size, lv.ctypes.data, obs.ctypes.data, None if w is None else w.ctypes.data),
+                    "trm_adjoint_observe_record")
+
+    def detach_record(self):
+        """Drops the attached record (trm_adjoint_record_detach)."""
+        self._check(self._lib.trm_adjoint_record_detach(self._ctx), "trm_adjoint_record_detach")
+        self._record_arrays = None
+
+    def record_info(self):
+        """(positions, levels, device bytes the library holds) of the attached record, zeros without one (trm_adjoint_record_info)."""
+        n, m, b = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._check(self._lib.trm_adjoint_record_info(self._ctx, C.byref(n), C.byref(m), C.byref(b)), "trm_adjoint_record_info")
+        return int(n.value), int(m.value), int(b.value)
+
+    def record_residuals(self) -> np.ndarray:
+        """T_p - observed of the last sweep as [npos][nlevels][Nh], +0 for a gap (trm_adjoint_record_residual_download)."""
+        npos, nlevels, _ = self.record_info()
+        a = np.empty((npos, nlevels, self.grid.Nh), dtype=np.float64)
+        self._check(self._lib.trm_adjoint_record_residual_download(self._ctx, a.ctypes.data if a.size else None), "trm_adjoint_record_residual_download")
+        return a
+
+    def record_misfit(self) -> np.ndarray:
+        """Each column's misfit to the attached record as the last sweep found it, [Nh] (trm_adjoint_record_misfit_download)."""
+        a = np.empty(self.grid.Nh, dtype=np.float64)
+        self._check(self._lib.trm_adjoint_record_misfit_download(self._ctx, a.ctypes.data), "trm_adjoint_record_misfit_download")
+        return a
 
     def adjoint_checkpoints(self):
         """(interval, slots used, slot capacity) of the tape (trm_adjoint_checkpoints); interval 0: a per-step tape, its slots are steps."""
@@ -1184,6 +1240,52 @@ def misfit_gradient(integ: ModelIntegrator, record: TemperatureRecord, steps=Non
     finally:
         if opened:
             st.close_adjoint()
+
+
+def record_gradient(integ: ModelIntegrator, record: TemperatureRecord, steps=None, checkpoint_every=None, wrt_boundary=False,
+                    wrt_params=False):
+    """What `misfit_gradient` returns, from a record that is attached once and read inside the backward launches
+    (trm_adjoint_observe_record): one attach, one step_record(dt, steps) and one sweep.  No sample is a launch boundary or takes a
+    slot: the tape has `steps` slots, or ceil(steps / K) with `checkpoint_every` = K, however dense the record.  `record.steps` must
+    be strictly increasing (one sample per position), otherwise ValueError.  Coverage, refusals and option handling of `vjp`."""
+    if not isinstance(integ.timestepper, ForwardEuler):
+        raise ValueError("record_gradient: ForwardEuler only")
+    if integ._has_time_dependence() or integ._windowed():
+        raise ValueError("record_gradient: boundary conditions and inputs must be constant over the run")
+    if not record.steps or any(b <= a for a, b in zip(record.steps, record.steps[1:])):
+        raise ValueError("record_gradient: the record's steps must be strictly increasing, one sample per position")
+    st = integ.state
+    last = record.steps[-1]
+    steps = last if steps is None else int(steps)
+    if steps < last:
+        raise ValueError("record_gradient: the record has observations behind the last step")
+    K = None if checkpoint_every is None else int(checkpoint_every)
+    opened = not getattr(st, "_adjoint_open", False)
+    st.open_adjoint(_tape_slots([], steps, K), K)
+    try:
+        with _derivative_series(integ, params=wrt_params):
+            st.attach_record(record.steps, record.levels, record.values, record.weight)
+            st.step_record(integ.timestepper.dt, steps)
+            for name in ("internal_energy", "temperature", "liquid_water_fraction"):
+                st.set_cotangent(name, 0.0)
+            if wrt_boundary:
+                st.open_bc_gradient()
+            if wrt_params:
+                st.open_param_gradient()
+            st.adjoint_backward()
+            out = [st.record_misfit(), st.cotangent("internal_energy")]
+            if wrt_boundary:
+                pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
+                out.append({(var, side): st.bc_series_gradient(var, side) if _series_driven(integ, var, side) else st.bc_gradient(var, side)
+                            for var, side in pairs})
+            if wrt_params:
+                out.append({name: st.param_gradient(name) for name in _capi.THERMAL_PARAMS})
+            return tuple(out)
+    finally:
+        if opened:
+            st.close_adjoint()
+        else:
+            st.detach_record()
 
 
 def current_time(integrator: ModelIntegrator) -> float:
