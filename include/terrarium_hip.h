@@ -691,6 +691,33 @@ enum {
     TRM_THERMAL_PARAM_C_MINERAL = 8, TRM_THERMAL_PARAM_C_ORGANIC = 9, TRM_THERMAL_PARAM_COUNT = 10
 };
 int trm_tangent_param_set(trm_ctx* ctx, const double seed[TRM_THERMAL_PARAM_COUNT]);
+/* Tangent records: the temperature and its tangent sampled inside the launches of trm_step_tangent, at positions and levels given once --
+ * J v at the samples of a temperature record from one run, the forward twin of trm_adjoint_observe_record.
+ *   trm_tangent_record_attach(ctx, npos, positions, nlevels, levels)
+ *                                           positions[npos]: tangent-step counts since the attach or the last rewind, >= 0, strictly
+ *                                           increasing; levels[nlevels]: rows of the host layout, inside [0, Nz), strictly increasing.
+ *                                           Allocates the samples of T and of dT, [npos][nlevels][Nh] doubles each, fills both with NaN
+ *                                           and sets the position counter to 0.  One record at a time.
+ *   trm_tangent_record_rewind(ctx)          the counter back to 0, both arrays NaN: the next trm_step_tangent starts at position 0
+ *   trm_tangent_record_detach(ctx)          drops it; trm_tangent_open and trm_tangent_close drop it as well
+ *   trm_tangent_record_download(ctx, which, host) / trm_tangent_record_device_ptr(ctx, which, &dev)
+ *                                           which: TRM_TANGENT_RECORD_TEMPERATURE or TRM_TANGENT_RECORD_TANGENT
+ *   trm_tangent_record_info(ctx, &npos, &nlevels, &position, &bytes)
+ *                                           zeros without a record; position: the counter; bytes: the device memory held for it
+ * With a record attached, trm_step_tangent stores T and dT of the state after every step whose count the record lists, on the listed
+ * levels, and advances the counter by the steps it ran -- across calls and across changes of dt.  Position 0 is the state the first call
+ * after the attach or the rewind starts from: the T its closure forms at the stored U, and the dT of trm_tangent_closure.  A position no
+ * step has reached reads NaN.  Steps behind the last position sample nothing.  The state and the three tangents are those of the run
+ * without a record, bit for bit, and so is TRM_INFO_LAST_PROGRAM.  No fields other than temperature, no duplicate positions.
+ * Errors: TRM_EUNSUPPORTED where the tangent is; TRM_EINVAL without a context, an open tangent or (rewind, detach, download, device_ptr)
+ * an attached record, for NULL pointers, a bad list or `which`, and for a second attach; TRM_ENOMEM. */
+enum { TRM_TANGENT_RECORD_TEMPERATURE = 0, TRM_TANGENT_RECORD_TANGENT = 1 };
+int trm_tangent_record_attach(trm_ctx* ctx, int npos, const int32_t* positions, int nlevels, const int32_t* levels);
+int trm_tangent_record_rewind(trm_ctx* ctx);
+int trm_tangent_record_detach(trm_ctx* ctx);
+int trm_tangent_record_download(trm_ctx* ctx, int which, void* host);
+int trm_tangent_record_device_ptr(trm_ctx* ctx, int which, void** dev);
+int trm_tangent_record_info(const trm_ctx* ctx, int* npos, int* nlevels, int64_t* position, int64_t* bytes);
 
 /* ---- reverse-mode gradients of the heat-only run (the reference pulls a seed back through run! with Enzyme's Reverse mode) ---------
  * The gradient g = dL/dU_0 of L = <wU, U_n> + <wT, T_n> + <wliq, liq_n> with respect to the initial internal energy, for what the

@@ -118,11 +118,15 @@ EXPORTS = (
     "trm_tangent_bc_series_upload trm_adjoint_bc_series_download trm_adjoint_bc_series_device_ptr "
     "trm_adjoint_observe trm_adjoint_observe_misfit trm_adjoint_misfit_download trm_adjoint_misfit_device_ptr trm_adjoint_observations "
     "trm_adjoint_observe_record trm_adjoint_observe_record_device trm_adjoint_record_detach trm_adjoint_record_residual_download "
-    "trm_adjoint_record_residual_device_ptr trm_adjoint_record_misfit_download trm_adjoint_record_info").split()
+    "trm_adjoint_record_residual_device_ptr trm_adjoint_record_misfit_download trm_adjoint_record_info "
+    "trm_tangent_record_attach trm_tangent_record_rewind trm_tangent_record_detach trm_tangent_record_download "
+    "trm_tangent_record_device_ptr trm_tangent_record_info").split()
 # the thermal parameters the tangent and the adjoint differentiate (TRM_THERMAL_PARAM_*), in the order of trm_params
 THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
 # forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
 TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
+# what a tangent record samples (TRM_TANGENT_RECORD_*)
+TANGENT_RECORD = dict(temperature=0, tangent=1)
 # the checkpointed tape of the adjoint (trm_adjoint_open_checkpointed): TRM_ADJOINT_MAX_INTERVAL, TRM_ADJOINT_DEFAULT_INTERVAL
 ADJOINT_MAX_INTERVAL, ADJOINT_DEFAULT_INTERVAL = 32, 16
 TIME_INDEXING = dict(linear=0, clamp=1, cyclical=2, raster=3)
@@ -312,6 +316,12 @@ def lib():
     L.trm_adjoint_record_residual_device_ptr.argtypes = [vp, C.POINTER(vp)]
     L.trm_adjoint_record_misfit_download.argtypes = [vp, vp]
     L.trm_adjoint_record_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
+    L.trm_tangent_record_attach.argtypes = [vp, i32, vp, i32, vp]
+    L.trm_tangent_record_rewind.argtypes = [vp]
+    L.trm_tangent_record_detach.argtypes = [vp]
+    L.trm_tangent_record_download.argtypes = [vp, i32, vp]
+    L.trm_tangent_record_device_ptr.argtypes = [vp, i32, C.POINTER(vp)]
+    L.trm_tangent_record_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
     for name in EXPORTS:
         if name not in ("trm_last_error",):
             getattr(L, name).restype = i32

@@ -14,6 +14,12 @@ int TangentLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride) {
     by_ride(ride, [&](auto r) { rc = tangent_step<decltype(r)::value>(c, dt, nsteps); });
     return launched(c, rc, "k_column_tangent: a ride without an instance");
 }
+// ... with a tangent record attached (trm_launch_column_tangent_record*.hip)
+int TangentRecordLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride) {
+    int rc = NO_INSTANCE;
+    by_ride(ride, [&](auto r) { rc = tangent_record_step<decltype(r)::value>(c, dt, nsteps); });
+    return launched(c, rc, "k_column_tangent_record: a ride without an instance");
+}
 // k_closure_tangent reads no boundary value: it has the instances RIDE_NONE and RIDE_PARAM (trm_launch_column_tangent{,_param}.hip), and
 // every other ride takes RIDE_NONE's
 constexpr Ride closure_ride(Ride r) { return r == RIDE_PARAM ? RIDE_PARAM : RIDE_NONE; }
@@ -87,6 +93,16 @@ void drop_record(trm_ctx* c) {
     c->rec_table_n = -1;
     c->rec_swept = false;
 }
+// the tangent record (trm_tangent_record_attach): its samples and tables
+void drop_tangent_record(trm_ctx* c) {
+    release(c->d_trec);
+    release(c->d_trec_tables);
+    c->trec_positions.clear();
+    c->trec_levels.clear();
+    c->trec_table_host.clear();
+    c->trec_npos = c->trec_nlevels = 0;
+    c->trec_position = 0;
+}
 void release_tape(trm_ctx* c) {
     drop_observations(c);
     drop_record(c);
@@ -107,6 +123,7 @@ void release_tangent(trm_ctx* c) {
     release(c->d_tan);
     release(c->d_tan_bc);
     release(c->d_tan_bcs);
+    drop_tangent_record(c);
     std::fill(std::begin(c->tan_bcs_nt), std::end(c->tan_bcs_nt), 0L);
     c->tan_bc_seeded = false;
     std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
@@ -469,6 +486,7 @@ int trm_tangent_open(trm_ctx* c) {
     std::fill(std::begin(c->tan_param), std::end(c->tan_param), 0.0);
     c->tan_param_seeded = false;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
+    drop_tangent_record(c);    // (a new tangent has no record)
     c->tan_stale = false;      // (a zero seed: zero tangents)
     return TRM_OK;
 }
@@ -578,13 +596,94 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     const Ride ride = tangent_ride(c, nser);
     for (int n = 0, m; n < nsteps; n += m) {
         m = std::min(spl, nsteps - n);
+        // (a tangent record: the launch ends at its last position at the latest; the steps behind it sample nothing and are the
+        // record-free kernel's)
+        const int recorded = tangent_record_steps(c, m);
+        if (recorded) m = recorded;
         int rc = nser ? Unfused<double>::upload_series_rows(c, dt, m) : Unfused<double>::update_inputs(c, c->state, c->time);
-        if (!rc) rc = TangentLaunch::step(c, dt, m, ride);
+        if (!rc) rc = recorded ? TangentRecordLaunch::step(c, dt, m, ride) : TangentLaunch::step(c, dt, m, ride);
         if (rc) return rc;
         c->derivative_series = nser;
+        if (c->trec_npos) c->trec_position += m;
         tick(c, dt, m);
     }
     return derivative_steps_done(c);
+}
+
+// ---- tangent records: T and dT sampled inside the tangent launches (trm_column_tangent_record.hpp) ----------------------------------
+int trm_tangent_record_attach(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels) {
+    TRM_ENTER_HEUN(c);
+    const char* who = "trm_tangent_record_attach";
+    // (a context the tangent does not cover has none open: it is told why, not to open one)
+    if (const char* why = derivative_unsupported(c)) return refuse(c, who, why);
+    if (int rc = tangent_record_attach_ok(c, npos, positions, nlevels, levels, who)) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    const std::string w(who);
+    c->trec_positions.assign(positions, positions + npos);
+    c->trec_levels.assign(levels, levels + nlevels);
+    c->trec_table_host = tangent_record_tables(c->Nz, c->trec_levels, c->trec_positions);
+    const size_t cell_bytes = rows_bytes(c, (long)npos * nlevels), table_bytes = c->trec_table_host.size() * sizeof(int32_t);
+    int rc = TRM_OK;
+    for (double*& q : c->d_trec)
+        if (!rc && alloc_if_null(q, cell_bytes) != hipSuccess) rc = fail(c, TRM_ENOMEM, w + ": the samples do not fit");
+    if (!rc && alloc_if_null(c->d_trec_tables, (table_bytes + 7) / 8 * 8) != hipSuccess) rc = fail(c, TRM_ENOMEM, w + ": the record's tables do not fit");
+    if (!rc) {
+        hipError_t e = hipMemcpyAsync(c->d_trec_tables, c->trec_table_host.data(), table_bytes, hipMemcpyHostToDevice, c->stream);
+        for (double* q : c->d_trec)
+            if (e == hipSuccess) e = hipMemsetAsync(q, 0xFF, cell_bytes, c->stream);    // (every byte set: a NaN)
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(c, TRM_EHIP, w + ": " + hipGetErrorString(e));
+    }
+    if (rc) {
+        drop_tangent_record(c);
+        return rc;
+    }
+    c->trec_npos = npos;
+    c->trec_nlevels = nlevels;
+    c->trec_position = 0;
+    return TRM_OK;
+}
+int trm_tangent_record_rewind(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = tangent_record_attached(c, "trm_tangent_record_rewind")) return rc;
+    for (double* q : c->d_trec) TRM_HIP(c, hipMemsetAsync(q, 0xFF, rows_bytes(c, (long)c->trec_npos * c->trec_nlevels), c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    c->trec_position = 0;
+    return TRM_OK;
+}
+int trm_tangent_record_detach(trm_ctx* c) {
+    TRM_ENTER_HEUN(c);
+    if (int rc = tangent_record_attached(c, "trm_tangent_record_detach")) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    drop_tangent_record(c);
+    return TRM_OK;
+}
+int trm_tangent_record_download(trm_ctx* c, int which, void* host) {
+    TRM_ENTER_HEUN(c);
+    const char* who = "trm_tangent_record_download";
+    if (int rc = tangent_record_attached(c, who)) return rc;
+    if (int rc = which_ok(c, which, TRM_TANGENT_RECORD_TANGENT + 1, host, who, " (TRM_TANGENT_RECORD_*)")) return rc;
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_trec[which], rows_bytes(c, (long)c->trec_npos * c->trec_nlevels), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
+}
+int trm_tangent_record_device_ptr(trm_ctx* c, int which, void** dev) {
+    TRM_ENTER_HEUN(c);
+    const char* who = "trm_tangent_record_device_ptr";
+    if (int rc = tangent_record_attached(c, who)) return rc;
+    if (int rc = which_ok(c, which, TRM_TANGENT_RECORD_TANGENT + 1, dev, who, " (TRM_TANGENT_RECORD_*)")) return rc;
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    *dev = c->d_trec[which];
+    return TRM_OK;
+}
+int trm_tangent_record_info(const trm_ctx* c, int* npos, int* nlevels, int64_t* position, int64_t* bytes) {
+    if (!c) return TRM_EINVAL;
+    if (int rc = tangent_open(const_cast<trm_ctx*>(c), "trm_tangent_record_info")) return rc;
+    if (npos) *npos = c->trec_npos;
+    if (nlevels) *nlevels = c->trec_nlevels;
+    if (position) *position = c->trec_position;
+    if (bytes) *bytes = tangent_record_bytes(c);
+    return TRM_OK;
 }
 
 // ---- reverse-mode gradients of the heat-only run (trm_column_adjoint.hpp) -----------------------------------------------------

@@ -251,6 +251,17 @@ struct trm_ctx {
     int rec_table_n = -1;
     std::vector<int32_t> rec_table_host;   // (the staging copy of row_of_position: alive while its upload is in flight)
     bool rec_swept = false;
+    // A tangent record (trm_tangent_record_attach; DESIGN 4.7 "Tangent records"): T and dT sampled inside the tangent launches, kept until
+    // a detach, trm_tangent_open or trm_tangent_close.  `trec_positions` / `trec_levels`: what the caller gave (tangent-step counts since
+    // the attach or the last rewind, and rows of the host layout, both strictly increasing); trec_npos == 0: none attached.  `d_trec`: the
+    // samples of T and of dT, [npos][nlevels][Nh] each, NaN where no launch has stored.  `d_trec_tables`: int32 row_of_level[Nz], then
+    // row_of_position[last position + 1].  `trec_position`: tangent steps run since the attach or the last rewind.
+    std::vector<int> trec_positions, trec_levels;
+    int trec_npos = 0, trec_nlevels = 0;
+    double* d_trec[2] = {};
+    double* d_trec_tables = nullptr;
+    std::vector<int32_t> trec_table_host;   // (the staging copy of the tables: alive while its upload is in flight)
+    long long trec_position = 0;
     bool args_valid = false;
     void* args = nullptr;   // LaunchArgs<NF>*, owned
     void (*args_free)(void*) = nullptr;
@@ -791,6 +802,56 @@ template <bool CKPT, Ride R> int adjoint_backward_record(trm_ctx* c, double dt, 
 struct RecordLaunch {
     static int backward(trm_ctx* c, bool ckpt, double dt, int nsteps, int slot, int fold, Ride ride, int first);
     static int misfit(trm_ctx* c);
+};
+// ---- tangent records (trm_tangent_record_*; trm_launch_tangent_record.inl) -- bookkeeping alone, no HIP call
+// (tests/tangent_record_preconditions.cpp) ----
+// The last position a record launch may reach: the record's last position -- or 1 for a record of position 0 alone, whose sample is the
+// entry's of a launch that has a step to run
+inline int tangent_record_limit(const std::vector<int>& positions) { return std::max(positions.back(), 1); }
+// the tables of a tangent record: row_of_level[Nz], then row_of_position[last position + 1] ([2] for a record of position 0 alone)
+inline std::vector<int32_t> tangent_record_tables(int Nz, const std::vector<int>& levels, const std::vector<int>& positions) {
+    std::vector<int32_t> t = record_level_table(Nz, levels);
+    const std::vector<int32_t> rows = record_position_table(tangent_record_limit(positions), positions);
+    t.insert(t.end(), rows.begin(), rows.end());
+    return t;
+}
+// What an attach checks before it touches the device (the caller has checked that the derivatives cover the context)
+inline int tangent_record_attach_ok(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const char* who) {
+    const std::string w(who);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, w + ": no tangent is open (trm_tangent_open)");
+    if (npos < 1 || nlevels < 1 || !positions || !levels) return fail(c, TRM_EINVAL, w + ": bad argument (npos >= 1 positions, nlevels >= 1 levels)");
+    for (int k = 0; k < npos; ++k)
+        if (positions[k] < 0 || (k > 0 && positions[k] <= positions[k - 1])) return fail(c, TRM_EINVAL, w + ": the positions are tangent-step counts >= 0, strictly increasing");
+    for (int j = 0; j < nlevels; ++j)
+        if (levels[j] < 0 || levels[j] >= c->Nz || (j > 0 && levels[j] <= levels[j - 1]))
+            return fail(c, TRM_EINVAL, w + ": the levels are rows 0 ... " + std::to_string(c->Nz - 1) + " of the host layout, strictly increasing");
+    if (c->trec_npos) return fail(c, TRM_EINVAL, w + ": a record is attached already (trm_tangent_record_detach)");
+    return TRM_OK;
+}
+// the calls that need an attached record
+inline int tangent_record_attached(trm_ctx* c, const char* who) {
+    const std::string w(who);
+    if (!c->d_tan[0]) return fail(c, TRM_EINVAL, w + ": no tangent is open (trm_tangent_open)");
+    if (c->trec_npos == 0) return fail(c, TRM_EINVAL, w + ": no record is attached (trm_tangent_record_attach)");
+    return TRM_OK;
+}
+// Of the next `m` tangent steps, the ones a record launch runs: those up to the last position (0: the launch samples nothing and is the
+// record-free kernel's).  A launch never runs past the position table: the steps behind it are a launch of their own.
+inline int tangent_record_steps(const trm_ctx* c, int m) {
+    if (c->trec_npos == 0 || c->trec_position >= (long long)tangent_record_limit(c->trec_positions)) return 0;
+    return (int)std::min<long long>(m, (long long)tangent_record_limit(c->trec_positions) - c->trec_position);
+}
+// what the library holds for a tangent record: both sample arrays and the tables
+inline int64_t tangent_record_bytes(const trm_ctx* c) {
+    if (c->trec_npos == 0) return 0;
+    return 2 * (int64_t)c->trec_npos * c->trec_nlevels * (int64_t)c->Nh * 8 + ((int64_t)c->Nz + (int64_t)tangent_record_limit(c->trec_positions) + 1) * 4;
+}
+// k_column_tangent_record (one explicit instantiation per ride in trm_launch_column_tangent_record{,_bc,_param,_series,_param_series}.hip):
+// the launch of tangent_step<R> that stores T and dT at the record's positions.  TRM_INFO_LAST_PROGRAM is that of the same launch without
+// a record.  The dispatch over the ride is TangentRecordLaunch::step (trm_derivative_api.hip)
+template <Ride R> int tangent_record_step(trm_ctx* c, double dt, int nsteps);
+struct TangentRecordLaunch {
+    static int step(trm_ctx* c, double dt, int nsteps, Ride ride);
 };
 // The chain rule between the ten thermal parameters (TRM_THERMAL_PARAM_*, the order of trm_params) and the eight numbers the kernels
 // differentiate (make_dev_params): w[q] = d(derived number) / d(parameter q), with sk_i = sqrt(k_i), s0 = sqrt(k_mineral) frac_mineral +

@@ -470,6 +470,41 @@ class DeviceState:
         """`nsteps` ForwardEuler steps of the state and its tangent; the state ends as after step(dt, nsteps, finalize=True)."""
         self._check(self._lib.trm_step_tangent(self._ctx, float(dt), int(nsteps)), "trm_step_tangent")
 
+    # -- tangent records (trm_tangent_record_*): T and dT sampled inside the tangent launches ---------------------------------------
+    def attach_tangent_record(self, positions, levels):
+        """Attaches a record to the open tangent: every step_tangent stores the temperature and its tangent on `levels` (rows of the
+        host layout, strictly increasing) behind the steps whose count since the attach (or the last rewind) `positions` lists
+        (>= 0, strictly increasing; 0 is the state the first step_tangent starts from), until detach_tangent_record, open_tangent or
+        close_tangent (trm_tangent_record_attach).  Both sample arrays start as NaN."""
+        pos = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1)
+        lv = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+        self._check(self._lib.trm_tangent_record_attach(self._ctx, pos.size, pos.ctypes.data, lv.size, lv.ctypes.data), "trm_tangent_record_attach")
+
+    def rewind_tangent_record(self):
+        """The position counter back to 0 and both sample arrays NaN (trm_tangent_record_rewind)."""
+        self._check(self._lib.trm_tangent_record_rewind(self._ctx), "trm_tangent_record_rewind")
+
+    def detach_tangent_record(self):
+        """Drops the tangent record (trm_tangent_record_detach)."""
+        self._check(self._lib.trm_tangent_record_detach(self._ctx), "trm_tangent_record_detach")
+
+    def tangent_record_info(self):
+        """(positions, levels, steps run since the attach or the last rewind, device bytes held) of the tangent record, zeros without
+        one (trm_tangent_record_info)."""
+        n, m, at, b = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.trm_tangent_record_info(self._ctx, C.byref(n), C.byref(m), C.byref(at), C.byref(b)), "trm_tangent_record_info")
+        return int(n.value), int(m.value), int(at.value), int(b.value)
+
+    def tangent_record(self, which) -> np.ndarray:
+        """The samples of `temperature` or of its `tangent` as [npos][nlevels][Nh]; NaN at a position no step has reached
+        (trm_tangent_record_download)."""
+        if which not in _capi.TANGENT_RECORD:
+            raise KeyError(f"tangent_record: {which!r} is neither 'temperature' nor 'tangent'")
+        npos, nlevels = self.tangent_record_info()[:2]
+        a = np.empty((npos, nlevels, self.grid.Nh), dtype=np.float64)
+        self._check(self._lib.trm_tangent_record_download(self._ctx, _capi.TANGENT_RECORD[which], a.ctypes.data if a.size else None), "trm_tangent_record_download")
+        return a
+
     # -- reverse-mode gradients (trm_adjoint_*) with respect to the initial internal energy: what the tangent covers ---------------
     def open_adjoint(self, capacity, checkpoint_every=None):
         """Cotangent fields of internal energy, temperature and liquid fraction (zero) and a tape of `capacity` slots, one
@@ -1110,6 +1145,47 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, 
             st.close_tangent()
 
 
+def record_jvp(integ: ModelIntegrator, positions, levels, d_internal_energy=0.0, d_boundary=None, d_params=None, steps=None):
+    """`jvp` sampled at a record's positions: the integrator is stepped `steps` times (None: to the last position) with its own dt,
+    and the temperature and its tangent are stored on `levels` behind the steps `positions` lists (step counts, strictly increasing,
+    0 = the initial state) inside the tangent launches -- one attach and one step_tangent (trm_tangent_record_attach).  Returns
+    (T, dT), each [npos][nlevels][Nh]: the model's samples and J v at the samples for the seeds v = (`d_internal_energy`,
+    `d_boundary`, `d_params`) of `jvp`.  Zero seeds give the record the model itself produces.  State and clock end where `run`
+    leaves them.  Coverage, refusals and option handling of `jvp`."""
+    if not isinstance(integ.timestepper, ForwardEuler):
+        raise ValueError("record_jvp: ForwardEuler only")
+    if integ._has_time_dependence() or integ._windowed():
+        raise ValueError("record_jvp: boundary conditions and inputs must be constant over the run")
+    positions = [int(q) for q in np.asarray(positions).reshape(-1)]
+    if not positions or positions[0] < 0 or any(b <= a for a, b in zip(positions, positions[1:])):
+        raise ValueError("record_jvp: the positions must be >= 0 and strictly increasing, one sample per position")
+    steps = positions[-1] if steps is None else int(steps)
+    st = integ.state
+    opened = not getattr(st, "_tangent_open", False)
+    if opened:
+        st.open_tangent()
+    attached = False
+    try:
+        with _derivative_series(integ, params=d_params is not None):
+            st.set_tangent("internal_energy", d_internal_energy)
+            for (var, side), values in (d_boundary or {}).items():
+                if _series_driven(integ, var, side):
+                    st.set_bc_series_tangent(var, side, values)
+                else:
+                    st.set_bc_tangent(var, side, values)
+            if d_params is not None:
+                st.set_param_tangent(d_params)
+            st.attach_tangent_record(positions, levels)
+            attached = True
+            st.step_tangent(integ.timestepper.dt, steps)
+            return st.tangent_record("temperature"), st.tangent_record("tangent")
+    finally:
+        if opened:
+            st.close_tangent()
+        elif attached:
+            st.detach_tangent_record()
+
+
 def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=None, liquid_water_fraction=None,
         checkpoint_every=None, wrt_boundary=False, wrt_params=False):
     """Reverse-mode derivative of `run!(integ; steps)`: the integrator is stepped `steps` times with its own dt (state and clock end
@@ -1286,6 +1362,51 @@ def record_gradient(integ: ModelIntegrator, record: TemperatureRecord, steps=Non
             st.close_adjoint()
         else:
             st.detach_record()
+
+
+def _normal_equation_sums(T, S, values, weight):
+    """(misfit [Nh], b [q][Nh], A [q][q][Nh]) of the samples T [npos][nlevels][Nh], their sensitivities S [q][npos][nlevels][Nh] and a
+    record: r = T - values, misfit = sum 1/2 w r r, b_q = sum w s_q r, A_qq' = sum w s_q s_q'.  float64, positions ascending, levels in
+    list order, one term at a time; a NaN sample or a weight that is not > 0 counts for nothing."""
+    nq, Nh = len(S), T.shape[2]
+    misfit, b, A = np.zeros(Nh), np.zeros((nq, Nh)), np.zeros((nq, nq, Nh))
+    for k in range(T.shape[0]):
+        for j in range(T.shape[1]):
+            w = np.ones(Nh) if weight is None else np.asarray(weight[k, j], dtype=np.float64)
+            r = T[k, j] - values[k, j]
+            use = (w > 0.0) & ~np.isnan(r)
+            w, r = np.where(use, w, 0.0), np.where(use, r, 0.0)
+            misfit = misfit + 0.5 * w * r * r
+            for q in range(nq):
+                sq = np.where(use, S[q][k, j], 0.0)
+                b[q] = b[q] + w * sq * r
+                for q2 in range(nq):
+                    A[q, q2] = A[q, q2] + w * sq * np.where(use, S[q2][k, j], 0.0)
+    return misfit, b, A
+
+
+def record_normal_equations(integ: ModelIntegrator, record: TemperatureRecord, params):
+    """The Gauss-Newton normal equations of the misfit of `run!(integ; steps = record.steps[-1])` to a temperature record in the thermal
+    parameters `params` (names of `jvp`'s `d_params`), per column: (misfit [Nh], b [q][Nh], A [q][q][Nh]) with r = T - values,
+    misfit = sum 1/2 w r^2, b_q = sum w s_q r (the gradient of the misfit), A_qq' = sum w s_q s_q', s_q = dT/d(parameter q) at the
+    samples.  One `record_jvp` with a unit seed per name; state and clock are restored in between and afterwards
+    (`checkpoint` / `restore`), so the integrator is left where it was.  The sums run in float64 on the host, positions ascending,
+    levels in list order, one term at a time; a NaN sample or a weight that is not > 0 counts for nothing.  `record.steps` must be
+    strictly increasing."""
+    if not record.steps or any(b <= a for a, b in zip(record.steps, record.steps[1:])):
+        raise ValueError("record_normal_equations: the record's steps must be strictly increasing, one sample per position")
+    params = list(params)
+    if not params:
+        raise ValueError("record_normal_equations: no parameter")
+    start = checkpoint(integ)
+    T, S = None, []
+    for name in params:
+        restore(integ, start)
+        T_q, dT_q = record_jvp(integ, record.steps, record.levels, d_params={name: 1.0})
+        T = T_q if T is None else T
+        S.append(dT_q)
+    restore(integ, start)
+    return _normal_equation_sums(T, S, record.values, record.weight)
 
 
 def current_time(integrator: ModelIntegrator) -> float:
