@@ -68,7 +68,7 @@ def default_params(**overrides):
 def build(force=False):
     """Compile the restatement (gcc only; no reference sources are involved)."""
     so = os.path.join(_HERE, "build", "libterrarium_oracle.so")
-    src = [os.path.join(_HERE, f) for f in ("oracle_capi.cpp", "terrarium_oracle.hpp", "Makefile")]
+    src = [os.path.join(_HERE, f) for f in ("oracle_capi.cpp", "terrarium_oracle.hpp", "vegetation_oracle.hpp", "Makefile")]
     stale = (not os.path.exists(so)) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src)
     if force or stale:
         subprocess.check_call(["make", "-C", _HERE, "-s"] + (["-B"] if force else []))
@@ -412,7 +412,8 @@ VEG_SCALARS = dict(lambda_NPP=0, LAI_b=1, Lambda_loc=2, C_veg_tend=3, f_deciduou
                    temperature_stress=19, c_1=20, c_2=21, Vc_max=22, JE=23, JC=24, Rd=25, Ag=26, resp_Rd=27, resp_An=28,
                    f_temp_air=29, f_temp_soil=30, resp10=31, Rm=32, Rg=33, Ra=34, NPP=35, root_density=36, plant_available_water=37,
                    canopy_interception=38, canopy_saturation_fraction=39, canopy_water_removal=40, w_can_tendency=41,
-                   precip_ground=42, transpiration=43, evaporation_ground=44, evaporation_canopy=45, canopy_ground_resistance=46)
+                   precip_ground=42, transpiration=43, evaporation_ground=44, evaporation_canopy=45, canopy_ground_resistance=46,
+                   transpiration_wide_f64_model=47, transpiration_wide_f32_model=48)
 
 
 def _veg_lib():
@@ -420,6 +421,8 @@ def _veg_lib():
     if not getattr(lib, "_veg_ready", False):
         lib.trm_oracle_veg_create.restype = C.c_void_p
         lib.trm_oracle_veg_create.argtypes = [C.c_int, C.c_long, C.POINTER(VegParamsD), C.POINTER(ParamsD)]
+        lib.trm_oracle_veg_create_wide.restype = C.c_void_p
+        lib.trm_oracle_veg_create_wide.argtypes = [C.c_int, C.c_long, C.POINTER(VegParamsD), C.POINTER(ParamsD)]
         lib.trm_oracle_veg_destroy.argtypes = [C.c_void_p]
         lib.trm_oracle_veg_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.trm_oracle_veg_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -442,15 +445,26 @@ def veg_scalar(name, *args, params=None):
 
 
 class VegetationOracle:
-    """The standalone VegetationModel (src/models/vegetation/vegetation_model.jl) on `num_columns` points."""
+    """The standalone VegetationModel (src/models/vegetation/vegetation_model.jl) on `num_columns` points.
 
-    def __init__(self, num_columns, veg_params=None, params=None, dtype=np.float64):
+    dtype / model as in Oracle: dtype = np.longdouble evaluates the model of precision `model` (np.float64 by default, or
+    np.float32) in long double -- its parameters, literals and conductance floor stay the model's, and every array handed in is
+    rounded to `model` first."""
+
+    def __init__(self, num_columns, veg_params=None, params=None, dtype=np.float64, model=None):
         self.lib = _veg_lib()
         self.dtype = np.dtype(dtype)
+        self.wide = self.dtype == np.dtype(np.longdouble) and self.dtype != np.float64
+        self.model = np.dtype(model) if model is not None else (np.dtype(np.float64) if self.wide else self.dtype)
+        assert self.wide or self.model == self.dtype, "a model precision other than the arithmetic's needs dtype=np.longdouble"
         self.Nh = int(num_columns)
         self.veg_params = veg_params if veg_params is not None else default_vegetation_params()
         self.params = params if params is not None else default_params()
-        self.h = self.lib.trm_oracle_veg_create({np.dtype(np.float64): 0, np.dtype(np.float32): 1}.get(self.dtype, 2), self.Nh, C.byref(self.veg_params), C.byref(self.params))
+        if self.wide:
+            assert wide_available(), "np.longdouble is not a wider format than float64 on this platform"
+            self.h = self.lib.trm_oracle_veg_create_wide(_MODEL_CODE[self.model], self.Nh, C.byref(self.veg_params), C.byref(self.params))
+        else:
+            self.h = self.lib.trm_oracle_veg_create(0 if self.dtype == np.float64 else 1, self.Nh, C.byref(self.veg_params), C.byref(self.params))
 
     def __del__(self):
         try:
@@ -462,7 +476,7 @@ class VegetationOracle:
 
     def set(self, name, value):
         a = np.empty(self.Nh, dtype=self.dtype)
-        a[...] = value
+        a[...] = np.asarray(value, dtype=self.model).astype(self.dtype) if self.wide else value
         assert self.lib.trm_oracle_veg_set(self.h, VEG_FIELDS[name], a.ctypes.data) == 0, name
 
     def get(self, name):

@@ -257,20 +257,24 @@ void trm_oracle_update_skin_temperature(OracleHandle* h) { DISPATCH(h, o->update
 // ---- vegetation (oracle/vegetation_oracle.hpp) ---------------------------------------------------------------------
 struct VegHandle {
     int precision;
-    int model;      // (DISPATCH reads it; the vegetation oracle has one wide instance)
+    int model;      // wide only: 0 = Float64 model (w), 1 = Float32 model (wf), as in OracleHandle
     VegetationOracle<double>* d;
     VegetationOracle<float>* f;
-    VegetationOracle<wide_t>* w;
-    VegetationOracle<wide_t>* wf;   // never set: the Float32-model slot of DISPATCH
+    VegetationOracle<wide_t, double>* w;
+    VegetationOracle<wide_t, float>* wf;
 };
-VegHandle* trm_oracle_veg_create(int precision, long nh, const VegParamsD* vp, const ParamsD* cp) {
-    VegHandle* h = new VegHandle{precision, 0, nullptr, nullptr, nullptr, nullptr};
+static VegHandle* veg_create(int precision, int model, long nh, const VegParamsD* vp, const ParamsD* cp) {
+    VegHandle* h = new VegHandle{precision, model != 0, nullptr, nullptr, nullptr, nullptr};
     if (precision == PREC_F64) h->d = new VegetationOracle<double>(nh, *vp, *cp);
     else if (precision == PREC_F32) h->f = new VegetationOracle<float>(nh, *vp, *cp);
-    else h->w = new VegetationOracle<wide_t>(nh, *vp, *cp);
+    else if (model == 0) h->w = new VegetationOracle<wide_t, double>(nh, *vp, *cp);
+    else h->wf = new VegetationOracle<wide_t, float>(nh, *vp, *cp);
     return h;
 }
-void trm_oracle_veg_destroy(VegHandle* h) { if (h) { delete h->d; delete h->f; delete h->w; delete h; } }
+VegHandle* trm_oracle_veg_create(int precision, long nh, const VegParamsD* vp, const ParamsD* cp) { return veg_create(precision, 0, nh, vp, cp); }
+// precision code 2 with the model precision it restates (0 = Float64, 1 = Float32)
+VegHandle* trm_oracle_veg_create_wide(int model, long nh, const VegParamsD* vp, const ParamsD* cp) { return veg_create(PREC_WIDE, model, nh, vp, cp); }
+void trm_oracle_veg_destroy(VegHandle* h) { if (h) { delete h->d; delete h->f; delete h->w; delete h->wf; delete h; } }
 int trm_oracle_veg_set(VegHandle* h, int id, const void* src) {
     DISPATCH_T(h, { auto* v = o->field(id); if (!v) return 1; std::memcpy(v->data(), src, sizeof(T) * o->Nh); });
     return 0;
@@ -334,6 +338,8 @@ double trm_oracle_veg_scalar(const VegParamsD* vp, int what, const double* x) {
         case 41: return canopy_w_can_tendency(x[0], x[1], x[2]);
         case 42: return canopy_precip_ground(x[0], x[1], x[2]);
         case 43: return canopy_transpiration(x[0], x[1], x[2]);
+        case 47: return (double)canopy_transpiration<wide_t, double>(x[0], x[1], x[2]);   // the wide instances' floor: the model's,
+        case 48: return (double)canopy_transpiration<wide_t, float>(x[0], x[1], x[2]);    // not sqrt(eps(long double))
         case 44: return canopy_evaporation_ground(x[0], x[1], x[2], x[3]);
         case 45: return canopy_evaporation_canopy(x[0], x[1], x[2]);
         case 46: return canopy_ground_resistance(p, x[0], x[1], x[2]);

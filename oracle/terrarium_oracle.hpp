@@ -476,7 +476,7 @@ template <class NF, class MF = NF> class Oracle {
     // LandModel(vegetation = VegetationCarbon) (land_model.jl:24-25,79-97): the vegetation state, the canopy water store and
     // the canopy evapotranspiration fluxes; plant available water per cell (halo layout) and the static root fractions per level
     bool veg_on = false;
-    VegetationOracle<NF> veg;
+    VegetationOracle<NF, MF> veg;
     FieldVec<NF> w_can, G_w_can, I_can, R_can, f_can, rain_ground, E_can, transp, SAI, paw;
     std::vector<NF> root_frac;
 
@@ -574,7 +574,7 @@ template <class NF, class MF = NF> class Oracle {
     }
     // LandModel(grid; soil, vegetation): switch the vegetation and canopy processes on
     void enable_vegetation(const VegParamsD& vp) {
-        veg = VegetationOracle<NF>(Nh, vp, pd);
+        veg = VegetationOracle<NF, MF>(Nh, vp, pd);
         veg_on = true;
         for (auto* v : {&w_can, &G_w_can, &I_can, &R_can, &f_can, &rain_ground, &E_can, &transp, &SAI}) first_touch(*v, 1, NF(0));
         first_touch(paw, Nz + 2, NF(0));
@@ -881,7 +881,7 @@ template <class NF, class MF = NF> class Oracle {
             NF ra = aerodynamic_resistance(i);
             NF re = canopy_ground_resistance(veg.p, veg.LAI[i], SAI[i], jl_max(wind[i], p.min_windspeed));
             NF beta = ground_resistance_factor(i);
-            transp[i] = canopy_transpiration(dqs, ra, veg.gw_can[i]);
+            transp[i] = canopy_transpiration<NF, MF>(dqs, ra, veg.gw_can[i]);
             evap[i] = canopy_evaporation_ground(dqg, beta, ra, re);
             E_can[i] = canopy_evaporation_canopy(dqs, f_can[i], ra);
         }

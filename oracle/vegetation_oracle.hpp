@@ -9,6 +9,10 @@
 // (src/models/vegetation/vegetation_model.jl:34-49) by the explicit time steppers.  Written from the Julia sources as
 // text; pinned by the reference's unit tests under test/vegetation/ (tests/test_oracle_vegetation.py).
 // (included by terrarium_oracle.hpp just in front of its Oracle class: the Julia Base helpers, Params and compute_vpd come from there)
+//
+// <NF, MF> as in terrarium_oracle.hpp: NF is the arithmetic type, MF the number format of the model restated (NF by default).
+// The parameters (model_veg_params), the literals the reference converts to its number format (model_literal) and
+// sqrt(eps(NF)) of the conductance floor are the model's; with MF = NF every expression is what it was before MF existed.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -38,6 +42,13 @@ struct VegParamsD {   // plain doubles across the C API; field order = include/t
     // PALADYNCanopyInterception (canopy_interception.jl:37-49) and PALADYNCanopyEvapotranspiration.C_can (canopy_evapotranspiration.jl:33-40)
     double alpha_int, canopy_k_ext, w_can_max, tau_w, C_can;
 };
+
+// the parameters as the model's number format holds them (convert(MF, x)); the identity for MF = double
+template <class MF> inline VegParamsD model_veg_params(VegParamsD d) {
+    double* q = &d.tau25;
+    for (int n = 0; n < 40; ++n) q[n] = (double)MF(q[n]);
+    return d;
+}
 
 template <class NF> struct VegParams {
     NF tau25, Kc25, Ko25, q10_tau, q10_Kc, q10_Ko, alpha_leaf, alpha_a, alpha_C3, cq, k_ext, T_CO2_high, T_CO2_low, T_photos_high,
@@ -88,18 +99,18 @@ template <class NF> inline NF veg_nu_tendency(const VegParams<NF>& p, NF LAI_b, 
     return (lam * NPP / C_veg) * ns * (NF(1) - nu) - gv * ns;
 }
 // stomatal_conductance.jl:45-65 compute_gw_can (its @assert preconditions are not restated)
-template <class NF> inline NF veg_gw_can(const VegParams<NF>& p, NF vpd, NF An, NF co2, NF LAI, NF beta) {
+template <class NF, class MF = NF> inline NF veg_gw_can(const VegParams<NF>& p, NF vpd, NF An, NF co2, NF LAI, NF beta) {
     NF g_min = p.g_min / 1000;
     NF g0 = g_min * (1 - std::exp(-p.k_ext * LAI)) * beta;
-    return g0 + NF(1.6) * (1 + p.g1 / std::sqrt(vpd)) * An / co2 * NF(1.0e6);
+    return g0 + model_literal<NF, MF>(1.6) * (1 + p.g1 / std::sqrt(vpd)) * An / co2 * NF(1.0e6);
 }
 // stomatal_conductance.jl:78-81 compute_λc
-template <class NF> inline NF veg_lambda_c(const VegParams<NF>& p, NF vpd) {
-    return NF(1) - NF(1) / (NF(1) + p.g1 / std::sqrt(vpd * NF(1.0e-3)));
+template <class NF, class MF = NF> inline NF veg_lambda_c(const VegParams<NF>& p, NF vpd) {
+    return NF(1) - NF(1) / (NF(1) + p.g1 / std::sqrt(vpd * model_literal<NF, MF>(1.0e-3)));
 }
 // photosynthesis.jl:93-98 compute_kinetic_parameters
-template <class NF> inline void veg_kinetic(const VegParams<NF>& p, NF T_air, NF& tau, NF& Kc, NF& Ko) {
-    NF e = (T_air - NF(25)) * NF(0.1);
+template <class NF, class MF = NF> inline void veg_kinetic(const VegParams<NF>& p, NF T_air, NF& tau, NF& Kc, NF& Ko) {
+    NF e = (T_air - NF(25)) * model_literal<NF, MF>(0.1);
     tau = p.tau25 * jl_pow(p.q10_tau, e);
     Kc = p.Kc25 * jl_pow(p.q10_Kc, e);
     Ko = p.Ko25 * jl_pow(p.q10_Ko, e);
@@ -114,13 +125,14 @@ template <class NF> inline NF veg_APAR(const VegParams<NF>& p, NF swdown, NF LAI
 }
 template <class NF> inline NF veg_pres_i(NF lambda_c, NF pres_a) { return lambda_c * pres_a; }                  // :155-158
 // photosynthesis.jl:165-188 compute_temperature_stress
-template <class NF> inline NF veg_temperature_stress(const VegParams<NF>& p, NF T_air) {
-    NF k1 = NF(2) * std::log(NF(1) / NF(0.99) - NF(1)) / (p.T_CO2_low - p.T_photos_low);
+template <class NF, class MF = NF> inline NF veg_temperature_stress(const VegParams<NF>& p, NF T_air) {
+    auto c = [](double x) { return model_literal<NF, MF>(x); };
+    NF k1 = NF(2) * std::log(NF(1) / c(0.99) - NF(1)) / (p.T_CO2_low - p.T_photos_low);
     NF k2 = NF(0.5) * (p.T_CO2_low + p.T_photos_low);
-    NF k3 = std::log(NF(0.99) / NF(0.01)) / (p.T_CO2_high - p.T_photos_high);
+    NF k3 = std::log(c(0.99) / c(0.01)) / (p.T_CO2_high - p.T_photos_high);
     if (p.T_CO2_low < T_air && T_air < p.T_CO2_high) {
         NF low = NF(1) / (NF(1) + std::exp(k1 * (k2 - T_air)));
-        NF high = NF(1) - NF(0.01) * std::exp(k3 * (T_air - p.T_photos_high));
+        NF high = NF(1) - c(0.01) * std::exp(k3 * (T_air - p.T_photos_high));
         return low * high;
     }
     return NF(0);
@@ -144,19 +156,19 @@ template <class NF> inline NF veg_Ag(const VegParams<NF>& p, NF c1, NF c2, NF AP
     return (s - std::sqrt(s * s - NF(4) * p.theta_r * JE * JC)) / (NF(2) * p.theta_r) * beta;
 }
 // photosynthesis.jl:290-337 compute_respiration_assimilation -> (Rd, An)
-template <class NF> inline void veg_respiration_assimilation(const VegParams<NF>& p, NF T_air, NF swdown, NF pres, NF co2, NF LAI, NF lambda_c, NF beta, NF& Rd, NF& An) {
-    NF pres_O2 = NF(0.209) * pres;                 // physics_utils.jl:16-20
-    NF pres_a = co2 * NF(1.0e-6) * pres;           // physics_utils.jl:27-30
+template <class NF, class MF = NF> inline void veg_respiration_assimilation(const VegParams<NF>& p, NF T_air, NF swdown, NF pres, NF co2, NF LAI, NF lambda_c, NF beta, NF& Rd, NF& An) {
+    NF pres_O2 = model_literal<NF, MF>(0.209) * pres;                 // physics_utils.jl:16-20
+    NF pres_a = co2 * model_literal<NF, MF>(1.0e-6) * pres;           // physics_utils.jl:27-30
     Rd = NF(0);
     An = NF(0);
     if (swdown > NF(0) && T_air > NF(-3)) {
         NF tau, Kc, Ko;
-        veg_kinetic(p, T_air, tau, Kc, Ko);
+        veg_kinetic<NF, MF>(p, T_air, tau, Kc, Ko);
         NF Gs = veg_Gamma_star(tau, pres_O2);
         if (LAI > NF(0)) {
             NF APAR = veg_APAR(p, swdown, LAI);
             NF pres_i = veg_pres_i(lambda_c, pres_a);
-            NF T_stress = veg_temperature_stress(p, T_air);
+            NF T_stress = veg_temperature_stress<NF, MF>(p, T_air);
             NF c1, c2;
             veg_assimilation_factors(p, Gs, T_stress, Kc, Ko, pres_i, pres_O2, c1, c2);
             NF Vc_max = veg_Vc_max(c1, APAR, Kc, Ko, Gs, pres_i, pres_O2);
@@ -166,27 +178,28 @@ template <class NF> inline void veg_respiration_assimilation(const VegParams<NF>
         }
     }
 }
-template <class NF> inline NF veg_GPP(NF An) { return An * NF(1.0e-3); }                                       // :345-348
+template <class NF, class MF = NF> inline NF veg_GPP(NF An) { return An * model_literal<NF, MF>(1.0e-3); }                                       // :345-348
 // autotrophic_respiration.jl:46-56 compute_f_temp
-template <class NF> inline void veg_f_temp(NF T_air, NF T_soil, NF& f_air, NF& f_soil) {
-    auto f = [](NF T) { return std::exp(NF(308.56) * (NF(1) / NF(56.02) - NF(1) / (NF(46.02) + T))); };
+template <class NF, class MF = NF> inline void veg_f_temp(NF T_air, NF T_soil, NF& f_air, NF& f_soil) {
+    auto c = [](double x) { return model_literal<NF, MF>(x); };
+    auto f = [c](NF T) { return std::exp(c(308.56) * (NF(1) / c(56.02) - NF(1) / (c(46.02) + T))); };
     f_soil = jl_boolmul(T_soil > 7, f(T_soil));
     f_air = f(T_air);
 }
-template <class NF> inline NF veg_resp10() { return NF(0.066); }                                                // :63-66
+template <class NF, class MF = NF> inline NF veg_resp10() { return model_literal<NF, MF>(0.066); }                                                // :63-66
 // autotrophic_respiration.jl:73-93 compute_Rm
-template <class NF> inline NF veg_Rm(const VegParams<NF>& p, NF T_air, NF T_soil, NF Rd, NF phen, NF C_veg) {
+template <class NF, class MF = NF> inline NF veg_Rm(const VegParams<NF>& p, NF T_air, NF T_soil, NF Rd, NF phen, NF C_veg) {
     NF fa, fs;
-    veg_f_temp(T_air, T_soil, fa, fs);
-    NF resp10 = veg_resp10<NF>();
+    veg_f_temp<NF, MF>(T_air, T_soil, fa, fs);
+    NF resp10 = veg_resp10<NF, MF>();
     NF R_leaf = Rd / NF(1000);
     NF R_stem = resp10 * fa * (p.awl * ((NF(2) / p.SLA) + p.awl)) / (C_veg * p.aws * p.cn_sapwood);
     NF R_root = resp10 * fs * phen * (NF(2) / p.SLA) / (p.SLA * C_veg * p.cn_root);
     return R_leaf + R_stem + R_root;
 }
 template <class NF> inline NF veg_Rg(NF GPP, NF Rm) { return NF(0.25) * (GPP - Rm); }                           // :100-103
-template <class NF> inline NF veg_Ra(const VegParams<NF>& p, NF T_air, NF T_soil, NF Rd, NF phen, NF C_veg, NF GPP) {   // :110-115
-    NF Rm = veg_Rm(p, T_air, T_soil, Rd, phen, C_veg);
+template <class NF, class MF = NF> inline NF veg_Ra(const VegParams<NF>& p, NF T_air, NF T_soil, NF Rd, NF phen, NF C_veg, NF GPP) {   // :110-115
+    NF Rm = veg_Rm<NF, MF>(p, T_air, T_soil, Rd, phen, C_veg);
     NF Rg = veg_Rg(GPP, Rm);
     return Rm + Rg;
 }
@@ -212,8 +225,9 @@ template <class NF> inline NF canopy_water_removal(const VegParams<NF>& p, NF w_
 template <class NF> inline NF canopy_w_can_tendency(NF I_can, NF E_can, NF R_can) { return I_can - E_can - R_can; }              // :100-106
 template <class NF> inline NF canopy_precip_ground(NF precip, NF I_can, NF R_can) { return precip - I_can + R_can; }             // :118-124
 // canopy evapotranspiration (evapotranspiration/canopy_evapotranspiration.jl:52-82, 163-176)
-template <class NF> inline NF canopy_transpiration(NF dq, NF ra, NF gw_can) {
-    NF rs = 1 / jl_max(gw_can, std::sqrt(std::numeric_limits<NF>::epsilon()));
+// (the floor of the conductance is sqrt(eps(NF)) of the model's number format, canopy_evapotranspiration.jl:53)
+template <class NF, class MF = NF> inline NF canopy_transpiration(NF dq, NF ra, NF gw_can) {
+    NF rs = 1 / jl_max(gw_can, NF(std::sqrt(std::numeric_limits<MF>::epsilon())));
     return dq / (ra + rs);
 }
 template <class NF> inline NF canopy_evaporation_ground(NF dq, NF beta, NF ra, NF re) { return beta * dq / (ra + re); }
@@ -223,7 +237,7 @@ template <class NF> inline NF canopy_ground_resistance(const VegParams<NF>& p, N
 }
 
 // ---- the standalone VegetationModel on Nh columns ------------------------------------------------------------------------
-template <class NF> class VegetationOracle {
+template <class NF, class MF = NF> class VegetationOracle {
   public:
     long Nh;
     VegParams<NF> p;
@@ -235,12 +249,12 @@ template <class NF> class VegetationOracle {
     long long iteration = 0;
 
     VegetationOracle() : Nh(0), c(ParamsD{}) {}
-    VegetationOracle(long nh, const VegParamsD& vp, const ParamsD& cp) : Nh(nh), p(vp), c(cp) {
+    VegetationOracle(long nh, const VegParamsD& vp, const ParamsD& cp) : Nh(nh), p(model_veg_params<MF>(vp)), c(model_params<MF>(cp)) {
         for (auto* v : {&C_veg, &nu, &G_C_veg, &G_nu, &LAI_b, &phen, &LAI, &gw_can, &lambda_c, &An, &Rd, &GPP, &Ra, &NPP, &daily_Rd}) v->assign(nh, NF(0));
         // input defaults (prescribed_atmosphere.jl:90-92,148,221-223,14; photosynthesis.jl:76; autotrophic_respiration.jl:38)
         Tair.assign(nh, NF(10));
         pres.assign(nh, NF(101325));
-        qair.assign(nh, NF(1.0e-3));
+        qair.assign(nh, model_literal<NF, MF>(1.0e-3));
         swd.assign(nh, NF(300));
         CO2.assign(nh, NF(380));
         smlf.assign(nh, NF(1));
@@ -259,15 +273,15 @@ template <class NF> class VegetationOracle {
             LAI_b[i] = veg_LAI_b(p, C_veg[i]);                                         // carbon dynamics
             phen[i] = veg_phenology_factor<NF>();                                      // phenology
             LAI[i] = veg_LAI(LAI_b[i]);
-            NF vpd = compute_vpd(c, pres[i], qair[i], Tair[i]);                        // stomatal conductance, with An of the
-            gw_can[i] = veg_gw_can(p, vpd, An[i], CO2[i], LAI[i], smlf[i]);            // previous evaluation (vegetation_carbon.jl:88-92)
-            lambda_c[i] = veg_lambda_c(p, vpd);
+            NF vpd = compute_vpd<NF, MF>(c, pres[i], qair[i], Tair[i]);                // stomatal conductance, with An of the
+            gw_can[i] = veg_gw_can<NF, MF>(p, vpd, An[i], CO2[i], LAI[i], smlf[i]);    // previous evaluation (vegetation_carbon.jl:88-92)
+            lambda_c[i] = veg_lambda_c<NF, MF>(p, vpd);
             NF rd, an;                                                                 // photosynthesis
-            veg_respiration_assimilation(p, Tair[i], swd[i], pres[i], CO2[i], LAI[i], lambda_c[i], smlf[i], rd, an);
+            veg_respiration_assimilation<NF, MF>(p, Tair[i], swd[i], pres[i], CO2[i], LAI[i], lambda_c[i], smlf[i], rd, an);
             Rd[i] = rd;
             An[i] = an;
-            GPP[i] = veg_GPP(an);
-            Ra[i] = veg_Ra(p, Tair[i], Tground[i], daily_Rd[i], phen[i], C_veg[i], GPP[i]);   // autotrophic respiration
+            GPP[i] = veg_GPP<NF, MF>(an);
+            Ra[i] = veg_Ra<NF, MF>(p, Tair[i], Tground[i], daily_Rd[i], phen[i], C_veg[i], GPP[i]);   // autotrophic respiration
             NPP[i] = veg_NPP(GPP[i], Ra[i]);
         }
     }
@@ -289,7 +303,7 @@ template <class NF> class VegetationOracle {
     void timestep_euler(double dt, bool finalize) {   // forward_euler.jl:19-31 on the VegetationModel (no closure)
         compute_auxiliary();
         compute_tendencies();
-        explicit_step(NF(dt));
+        explicit_step(NF(MF(dt)));
         time += dt;
         iteration += 1;
         if (finalize) compute_auxiliary();
@@ -298,14 +312,14 @@ template <class NF> class VegetationOracle {
         compute_auxiliary();
         compute_tendencies();
         VegetationOracle stage = *this;
-        stage.explicit_step(NF(dt));
+        stage.explicit_step(NF(MF(dt)));
         stage.compute_auxiliary();
         stage.compute_tendencies();
         for (long i = 0; i < Nh; ++i) {
             G_C_veg[i] = (G_C_veg[i] + stage.G_C_veg[i]) / NF(2);
             G_nu[i] = (G_nu[i] + stage.G_nu[i]) / NF(2);
         }
-        explicit_step(NF(dt));
+        explicit_step(NF(MF(dt)));
         time += dt;
         iteration += 1;
         if (finalize) compute_auxiliary();

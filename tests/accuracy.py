@@ -29,7 +29,10 @@ import workloads as W
 
 M_CAP = 8                # the issue's cap on M (see tests/test_gpu_accuracy.py for the measured M)
 MAX_LEFT_OUT = 1.0e-3    # fraction of a field's cells that may be left out for a regime flip
-REL_FIELDS = ("hydraulic_conductivity", "pressure_head", "saturation_water_ice", "evaporation_ground", "infiltration")
+# (transpiration and evaporation_canopy: sign-definite under the 0.1 Pa floor of the vapour pressure deficit, and spanning decades
+# through the floor of the canopy conductance; tests/test_accuracy_host.py checks that their r_orc is rounding-sized in fp32)
+REL_FIELDS = ("hydraulic_conductivity", "pressure_head", "saturation_water_ice", "evaporation_ground", "infiltration",
+              "transpiration", "evaporation_canopy")
 TENDENCIES = ("tend_internal_energy", "tend_saturation_water_ice", "tend_surface_excess_water")
 
 
@@ -64,6 +67,8 @@ def setup_oracle(w, wide=False, dx=0.0):
         o = oracle.Oracle(w["Nh"], w["thickness"], p, dtype=np.longdouble, model=w["dtype"], dx=dx)
     else:
         o = oracle.Oracle(w["Nh"], w["thickness"], p, dtype=w["dtype"], dx=dx)
+    if w.get("vegetation"):
+        o.enable_vegetation()
     for name, v in w["fields"].items():
         o.set(name, v)
     for (var, side), (kind, value) in w["bcs"].items():
@@ -228,9 +233,10 @@ class Case:
     N145 mask and ("synthetic", n) = n synthetic columns -- the last two run at full size on the device and are measured on
     `sample()`'s columns, the oracles running those columns alone with the full grid's dx."""
 
-    def __init__(self, config, hydraulics, dtype, Nz, nsteps, columns, heun=False, params=None, tag=""):
+    def __init__(self, config, hydraulics, dtype, Nz, nsteps, columns, heun=False, params=None, tag="", sat_scale=None):
         self.config, self.hydraulics, self.dtype, self.Nz, self.nsteps = config, hydraulics, np.dtype(dtype), Nz, nsteps
         self.columns, self.heun, self.params, self.tag = columns, heun, dict(params or {}), tag
+        self.sat_scale = sat_scale      # the workload's initial saturation times this factor (clipped to [0.05, 1] again)
 
     @property
     def id(self):
@@ -251,6 +257,8 @@ class Case:
             lat, lon = W.synthetic_columns(self.columns[1])
         w = W.make_workload(self.config, lat, lon, self.Nz, dtype=self.dtype, hydraulics=self.hydraulics)
         w["params"].update(self.params)
+        if self.sat_scale is not None:
+            w["fields"]["saturation_water_ice"] = np.clip(w["fields"]["saturation_water_ice"] * self.sat_scale, 0.05, 1.0)
         return rounded_workload(w)
 
     def sample(self, Nh):
@@ -327,4 +335,76 @@ FP64_N145 = [Case("land", "vg", f64, 32, 40, ("N145",)), Case("land", "default",
 # every exponent class of the run-time hydraulics: richards, 32 levels, 60 steps, fp64 and fp32
 EXPONENTS = [Case("richards", "default", nf, 32, 60, N72(60), params=ps) for nf in (f64, f32) for ps in EXPONENT_SETS]
 
-CASES = FP32_PARITY + FP32_DEEP + FP32_C5 + FP64_TOL + FP64_N145 + EXPONENTS
+
+# ---- vegetation ----------------------------------------------------------------------------------------
+# The LandModel coupled to VegetationCarbon ("landveg": van Genuchten, 130 N72 columns, 20 steps of 0.05 s) at 20 levels (level
+# pitch 32 of the cooperative 0-D kernel), 33 (pitch 64) and 70 (one thread per column, reference-order soil kernels), Euler and
+# Heun, fp64 and fp32.  The workload's saturation keeps every unfrozen cell above the field capacity: plant available water is
+# 1 or 0 throughout.  The "dry" variants scale the initial saturation by DRY so that (sat * porosity) * liq of the unfrozen
+# cells lies inside the ramp between the wilting point 0.05 and the field capacity 0.25: porosity 0.49 and the workload's
+# saturation in [0.76, 1] give a water content in [0.149, 0.196].
+DRY = 0.4
+VEG_COUPLED = [Case("landveg", "vg", nf, nz, 20, N72(130), heun=heun) for nf in (f64, f32) for nz in (20, 33, 70) for heun in (False, True)] + \
+              [Case("landveg", "vg", nf, nz, 20, N72(130), heun=heun, sat_scale=DRY, tag="-dry") for nf in (f64, f32) for nz in (20, 33) for heun in (False, True)]
+VEG_FIELDS = W.FIELDS_VEGETATION
+
+
+class VegetationCase:
+    """The standalone VegetationModel of tests/test_gpu_vegetation.py:make_pair (its forcing and initial state, same seed) against
+    VegetationOracle(dtype=longdouble, model=dtype): 777 columns, 30 steps of 1800 s.  Compared: PROG + AUX of that module.
+
+    WHERE IT IS MEASURED.  The reference applies its per-year carbon turnover rates per second (tests/workloads.py), so at 1800 s
+    the vegetation carbon changes sign and grows by a factor of about 130 every step: 6e64 after 30 steps in fp64.  After an odd
+    number of steps the leaf area is hugely negative and exp(-k LAI) of the conductance overflows in the model's format (not in
+    long double's); and the fp32 MODEL overflows altogether on the way -- every column is inf or NaN from step 19 on, in the fp32
+    oracle as on the device, while the wide instance stays finite, and nothing can be measured there.  The fields are therefore
+    compared after `measured` steps: the last step of the 30 at which every compared field of the SAME-PRECISION ORACLE is finite
+    in every column (30 in fp64; 16 in fp32 with Euler, 9 with Heun; the reference side alone decides).  After all 30 steps the tested values must be finite exactly where the
+    same-precision oracle's are (`final`)."""
+    n, nsteps, dt, seed = 777, 30, 1800.0, 1
+
+    def __init__(self, dtype, heun):
+        self.dtype, self.heun = np.dtype(dtype), heun
+        self.measured, self.final = None, None
+
+    @property
+    def id(self):
+        return f"vegetation-{self.dtype.name}-{self.n}-{'heun' if self.heun else 'euler'}"
+
+    def inputs(self):
+        """(forcing, carbon_vegetation, vegetation_area_fraction) as make_pair draws them"""
+        from test_gpu_vegetation import forcing
+        rng = np.random.default_rng(self.seed)
+        f = forcing(self.n, rng)
+        return f, rng.uniform(0.2, 25.0, self.n), rng.uniform(0.0, 0.9, self.n)
+
+    def workload(self):
+        return None
+
+    def references(self, w=None):
+        from test_gpu_vegetation import AUX, PROG
+        names = list(PROG + AUX)
+        f, C0, nu0 = self.inputs()
+        out = []
+        for wide in (False, True):
+            o = oracle.VegetationOracle(self.n, dtype=np.longdouble if wide else self.dtype, model=self.dtype)
+            for k, v in f.items():
+                o.set(k, np.asarray(v, dtype=self.dtype))
+            o.set("carbon_vegetation", np.asarray(C0, dtype=self.dtype))
+            o.set("vegetation_area_fraction", np.asarray(nu0, dtype=self.dtype))
+            snaps = []
+            for _ in range(self.nsteps):
+                o.timestep(self.dt, True, self.heun)
+                snaps.append(fields_of(o, names))
+            if not wide:
+                finite = [all(np.all(np.isfinite(v)) for v in q.values()) for q in snaps]
+                assert any(finite), self.id
+                self.measured = max(n + 1 for n in range(self.nsteps) if finite[n])
+                self.final = snaps[-1]
+            out.append(snaps[self.measured - 1])
+        return out[0], out[1], names, None
+
+
+VEG_STANDALONE = [VegetationCase(nf, heun) for nf in (f64, f32) for heun in (False, True)]
+
+CASES = FP32_PARITY + FP32_DEEP + FP32_C5 + FP64_TOL + FP64_N145 + EXPONENTS + VEG_COUPLED + VEG_STANDALONE

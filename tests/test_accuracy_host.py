@@ -1,6 +1,7 @@
 """The yardstick of tests/test_gpu_accuracy.py, checked without a GPU: the wide oracle (the model evaluated in long double)
-against the fp64 and fp32 oracles on every case of the accuracy suite, the model precision of the wide instance, and the
-metric itself -- it must reject mutants that the tolerance `tol * max(1, |x|)` of the parity tests accepts."""
+against the fp64 and fp32 oracles on every case of the accuracy suite, the model precision of the wide instance -- of the
+soil model and of the vegetation and canopy processes, whose conductance floor sqrt(eps) is the model's -- and the metric
+itself: it must reject mutants that the tolerance `tol * max(1, |x|)` of the parity tests accepts."""
 import numpy as np
 import pytest
 
@@ -31,6 +32,109 @@ def test_oracle_against_wide_oracle(case):
             assert np.isfinite(q["r_orc"]), q["name"]
         assert q["left_out"] == 0, (q["name"], q["left_out"])      # no regime flip between the oracle and the wide oracle
     assert A.violations(rows, case.dtype, 1) == []                  # the oracle passes its own yardstick with M = 1
+    if case in A.VEG_COUPLED:
+        # the vegetation fields of the coupled model lose a few eps to rounding and nothing else (measured: at most 8.1 eps in fp64,
+        # 13.6 eps in fp32).  A wide instance that does not restate the model -- the conductance floor sqrt(eps) taken from the
+        # arithmetic instead of the model put transpiration 9.8e-7 (fp64) and 3.8e-2 (fp32) of its maximum away -- trips this.
+        for q in rows:
+            if q["name"] in A.VEG_FIELDS:
+                assert q["e_orc"] < 64 * A.eps(case.dtype), (q["name"], q["e_orc"])
+            if q["name"] in ("transpiration", "evaporation_canopy"):
+                # per cell: rounding times the conditioning of the vapour pressure deficit e_sat(T) - e_air, which is floored at
+                # 0.1 Pa under an e_sat of up to 3.2e3 Pa (25 C): below 2^15 eps, or the field does not belong in REL_FIELDS
+                assert q["r_orc"] is not None and q["r_orc"] < 2.0 ** 15 * A.eps(case.dtype), (q["name"], q["r_orc"])
+    if case in A.VEG_STANDALONE:
+        assert case.measured == case.nsteps or case.dtype == np.float32, case.measured
+        print(f"  measured after {case.measured} of {case.nsteps} steps")
+
+
+@pytest.mark.parametrize("case", [c for c in A.VEG_COUPLED if c.sat_scale is not None], ids=lambda c: c.id)
+def test_dry_vegetation_cases_occupy_the_ramp(case):
+    """In the wide reference, at least a quarter of the cells of a dry case have 0 < plant_available_water < 1 after
+    initialisation and after every step of the run; the undried workload has none (which is why the dry cases exist)."""
+    w = case.workload()
+    ref = A.setup_oracle(w, wide=True)
+    ref.update_state(False)
+    fractions = []
+    for n in range(case.nsteps + 1):
+        paw = ref.get("plant_available_water")
+        fractions.append(float(np.mean((paw > 0) & (paw < 1))))
+        if n < case.nsteps:
+            (ref.timestep_heun if case.heun else ref.timestep)(w["dt"], True)
+    print(f"  {case.id}: cells inside the ramp {min(fractions):.3f} .. {max(fractions):.3f}")
+    assert min(fractions) >= 0.25, fractions
+    wet = A.Case(case.config, case.hydraulics, case.dtype, case.Nz, case.nsteps, case.columns, heun=case.heun)
+    o = A.setup_oracle(wet.workload(), wide=True)
+    o.update_state(False)
+    paw = o.get("plant_available_water")
+    assert not np.any((paw > 0) & (paw < 1))
+
+
+def _standalone_vegetation(case, model, wide=True, steps=5):
+    f, C0, nu0 = case.inputs()
+    o = oracle.VegetationOracle(case.n, dtype=np.longdouble if wide else model, model=model)
+    for k, v in f.items():
+        o.set(k, v)
+    o.set("carbon_vegetation", C0)
+    o.set("vegetation_area_fraction", nu0)
+    for _ in range(steps):
+        o.timestep(0.05, True, False)
+    return o
+
+
+def test_wide_vegetation_oracle_restates_the_model_of_its_model_precision():
+    """VegetationOracle(dtype=longdouble, model=float32) restates the fp32 MODEL -- parameters, literals and inputs rounded to
+    fp32 -- and not the fp64 one: the two wide instances differ by about eps(fp32) on a vegetation field, and the fp32-model one
+    agrees with the fp32 oracle to fp32 rounding."""
+    case = A.VegetationCase(np.float32, False)
+    w32, w64 = _standalone_vegetation(case, np.float32), _standalone_vegetation(case, np.float64)
+    o32 = _standalone_vegetation(case, np.float32, wide=False)
+    e32 = A.eps(np.float32)
+    for name in ("net_assimilation", "canopy_water_conductance", "autotrophic_respiration", "carbon_vegetation"):
+        a, b, c = w32.get(name), w64.get(name), o32.get(name).astype(np.longdouble)
+        assert a.dtype == b.dtype == np.longdouble
+        S = float(np.max(np.abs(a)))
+        d_models, d_orc = float(np.max(np.abs(a - b))) / S, float(np.max(np.abs(a - c))) / S
+        print(f"  {name:<28} wide(f32 model) - wide(f64 model) {d_models:.3e}   wide(f32 model) - f32 oracle {d_orc:.3e}")
+        assert e32 / 64 < d_models < 64 * e32, (name, d_models)      # the models differ by their parameters' and inputs' rounding
+        assert d_orc < 64 * e32, (name, d_orc)
+    # the Python wrapper refuses a model precision on the plain instances, as Oracle does
+    with pytest.raises(AssertionError):
+        oracle.VegetationOracle(4, dtype=np.float64, model=np.float32)
+
+
+@pytest.mark.parametrize("model", [np.float32, np.float64])
+def test_conductance_floor_of_the_wide_oracle_is_the_models(model):
+    """canopy_evapotranspiration.jl:53 floors the canopy conductance at sqrt(eps(NF)) of the MODEL's number format.  Dark columns
+    (no shortwave: no assimilation) over soil at the wilting point (soil moisture limiting factor 0) have conductance 0, so the
+    wide transpiration is dq / (ra + 1 / sqrt(eps(model))) to long-double rounding -- with dq recovered from the canopy
+    evaporation f_can dq / ra of the same evaluation -- and not dq / (ra + 1 / sqrt(eps(long double)))."""
+    n, L = 6, np.longdouble
+    thickness = np.array([0.05, 0.1, 0.2, 0.4])
+    p = oracle.default_params(flow=1, seb=1, swrc=1, unsat_k=1, vg_alpha=2.0, vg_n=2.0)
+    o = oracle.Oracle(n, thickness, p, dtype=L, model=model)
+    o.enable_vegetation()
+    wind = np.linspace(0.5, 4.0, n)
+    o.set("temperature", np.full((4, n), 5.0)); o.set("saturation_water_ice", np.full((4, n), 0.05))
+    o.set("skin_temperature", np.linspace(4.0, 9.0, n)); o.set("carbon_vegetation", np.linspace(1.0, 2.0, n))
+    o.set("canopy_water", np.linspace(1.0e-5, 6.0e-5, n)); o.set("SAI", np.full(n, 0.5)); o.set("windspeed", wind)
+    o.set("surface_shortwave_down", np.zeros(n))
+    o.initialize()
+    o.update_state(False)
+    assert np.all(o.get("soil_moisture_limiting_factor") == 0) and np.all(o.get("canopy_water_conductance") == 0)
+    transp, E_can, f_can = o.get("transpiration"), o.get("evaporation_canopy"), o.get("saturation_canopy_water")
+    assert np.all(f_can > 0) and np.all(transp > 0)
+    ra = 1 / (L(model(p.C_h)) * np.asarray(wind, dtype=model).astype(L))
+    floor = L(np.sqrt(model(np.finfo(model).eps)))
+    expected = (E_can * ra / f_can) / (ra + 1 / floor)
+    err = float(np.max(np.abs(transp - expected) / expected))
+    print(f"  model {np.dtype(model).name}: floor {float(floor):.4e}, transpiration against dq / (ra + 1 / floor): {err:.2e} relative")
+    assert err <= 16 * float(np.finfo(L).eps), err
+    wrong = (E_can * ra / f_can) / (ra + 1 / np.sqrt(np.finfo(L).eps))
+    assert np.all(transp > 40 * wrong)              # the arithmetic's epsilon: 45 (fp64 model) and 1e6 (fp32 model) times smaller
+    # the scalar entry point of the known-answer tests
+    name = "transpiration_wide_f32_model" if model == np.float32 else "transpiration_wide_f64_model"
+    assert oracle.veg_scalar(name, 1.0e-3, 100.0, 0.0) == pytest.approx(1.0e-3 / (100.0 + 1.0 / float(floor)), rel=1e-15)
 
 
 def test_wide_oracle_restates_the_model_of_its_model_precision():
