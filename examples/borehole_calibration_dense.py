@@ -44,7 +44,7 @@ def misfit_and_gradient(params, positions, levels, d_values, U0):
     st = integrator.state
     st.open_adjoint(-(-N_T // K), K)
     try:
-        from terrarium_jl_amd.integrator import _derivative_series
+        from terrarium_jl_amd.derivatives import _derivative_series
         with _derivative_series(integrator, params=True):
             st.attach_record(positions, levels, d_values)
             st.step_record(integrator.timestepper.dt, N_T)

@@ -8,39 +8,40 @@ using namespace trm;
 using namespace trmh;
 
 namespace trmh {
-// The derivative launchers: each ride's instantiation lives in a translation unit of its own (trm_host.hpp, trm_launch_derivative.inl)
-int TangentLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride) {
+// The derivative launchers: each ride's instantiation lives in a translation unit of its own, the record twin's in another (trm_host.hpp,
+// trm_launch_derivative.inl).  One selector: launch(ride constant, record constant) is the launcher's call; `refusal`: no instance
+template <class F> static int ride_launch(trm_ctx* c, Ride ride, bool record, const char* refusal, F&& launch) {
     int rc = NO_INSTANCE;
-    by_ride(ride, [&](auto r) { rc = tangent_step<decltype(r)::value>(c, dt, nsteps); });
-    return launched(c, rc, "k_column_tangent: a ride without an instance");
+    by_ride(ride, [&](auto r) { rc = record ? launch(r, std::true_type{}) : launch(r, std::false_type{}); });
+    return launched(c, rc, refusal);
 }
-// ... with a tangent record attached (trm_launch_column_tangent_record*.hip)
-int TangentRecordLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride) {
-    int rc = NO_INSTANCE;
-    by_ride(ride, [&](auto r) { rc = tangent_record_step<decltype(r)::value>(c, dt, nsteps); });
-    return launched(c, rc, "k_column_tangent_record: a ride without an instance");
+int TangentLaunch::step(trm_ctx* c, double dt, int nsteps, Ride ride, bool record) {
+    return ride_launch(c, ride, record, record ? "k_column_tangent_record: a ride without an instance" : "k_column_tangent: a ride without an instance",
+                       [&](auto r, auto rec) { return tangent_step<decltype(r)::value, decltype(rec)::value>(c, dt, nsteps); });
 }
 // k_closure_tangent reads no boundary value: it has the instances RIDE_NONE and RIDE_PARAM (trm_launch_column_tangent{,_param}.hip), and
 // every other ride takes RIDE_NONE's
 constexpr Ride closure_ride(Ride r) { return r == RIDE_PARAM ? RIDE_PARAM : RIDE_NONE; }
 int TangentLaunch::closure(trm_ctx* c, Ride ride) {
-    int rc = NO_INSTANCE;
-    by_ride(ride, [&](auto r) { rc = tangent_closure<closure_ride(decltype(r)::value)>(c); });
-    return launched(c, rc, "k_closure_tangent: a ride without an instance");
+    return ride_launch(c, ride, false, "k_closure_tangent: a ride without an instance", [&](auto r, auto) { return tangent_closure<closure_ride(decltype(r)::value)>(c); });
 }
-template <bool CKPT> static int backward_by_ride(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) {
-    int rc = NO_INSTANCE;
-    by_ride(ride, [&](auto r) { rc = adjoint_backward<CKPT, decltype(r)::value>(c, dt, nsteps, slot, fold); });
-    return launched(c, rc, "k_column_adjoint: a ride without an instance");
+template <bool CKPT> static int backward_launch(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride, bool record, int first) {
+    return ride_launch(c, ride, record, record ? "k_column_adjoint_record: a ride without an instance" : "k_column_adjoint: a ride without an instance", [&](auto r, auto rec) {
+        return adjoint_backward<CKPT, decltype(r)::value, decltype(rec)::value>(c, dt, nsteps, slot, fold, first);
+    });
 }
 int AdjointLaunch::record(trm_ctx* c, double dt, int nsteps, int slot, bool series) {
     return series ? adjoint_record<false, true>(c, dt, nsteps, slot, 0, 1) : adjoint_record<false, false>(c, dt, nsteps, slot, 0, 1);
 }
-int AdjointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) { return backward_by_ride<false>(c, dt, nsteps, slot, fold, ride); }
+int AdjointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride, bool record, int first) {
+    return backward_launch<false>(c, dt, nsteps, slot, fold, ride, record, first);
+}
 int CheckpointLaunch::record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every, bool series) {
     return series ? adjoint_record<true, true>(c, dt, nsteps, slot, first, every) : adjoint_record<true, false>(c, dt, nsteps, slot, first, every);
 }
-int CheckpointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride) { return backward_by_ride<true>(c, dt, nsteps, slot, fold, ride); }
+int CheckpointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride, bool record, int first) {
+    return backward_launch<true>(c, dt, nsteps, slot, fold, ride, record, first);
+}
 }  // namespace trmh
 
 namespace {
@@ -80,27 +81,23 @@ void drop_observations(trm_ctx* c) {
     c->observations.clear();
     c->tape_seg_closed = false;
 }
+// a record's position table, the device copy with it
+void drop_table(RecordTable& t) {
+    release(t.d_tables);
+    record_table_drop(t);
+}
 // the attached record (trm_adjoint_observe_record*): its tables, outputs and copies; the caller's device arrays are the caller's
 void drop_record(trm_ctx* c) {
     release(c->d_rec_owned);
     release(c->d_rec_out);
-    release(c->d_rec_tables);
+    drop_table(c->rec);
     c->d_rec_observed = c->d_rec_weight = nullptr;
-    c->rec_positions.clear();
-    c->rec_levels.clear();
-    c->rec_table_host.clear();
-    c->rec_npos = c->rec_nlevels = 0;
-    c->rec_table_n = -1;
     c->rec_swept = false;
 }
 // the tangent record (trm_tangent_record_attach): its samples and tables
 void drop_tangent_record(trm_ctx* c) {
     release(c->d_trec);
-    release(c->d_trec_tables);
-    c->trec_positions.clear();
-    c->trec_levels.clear();
-    c->trec_table_host.clear();
-    c->trec_npos = c->trec_nlevels = 0;
+    drop_table(c->trec);
     c->trec_position = 0;
 }
 void release_tape(trm_ctx* c) {
@@ -437,30 +434,29 @@ int attach_record(trm_ctx* c, int npos, const int32_t* positions, int nlevels, c
     }
     c->d_rec_observed = device ? (const double*)observed : c->d_rec_owned;
     c->d_rec_weight = !weight ? nullptr : device ? (const double*)weight : c->d_rec_owned + cells;
-    c->rec_positions.assign(positions, positions + npos);
-    c->rec_levels.assign(levels, levels + nlevels);
-    c->rec_npos = npos;
-    c->rec_nlevels = nlevels;
-    c->rec_table_n = -1;       // (the tables go up with the first sweep: they depend on the steps the tape holds then)
+    record_table_attach(c->rec, npos, positions, nlevels, levels);     // (the tables go up with the first sweep: they depend on the steps the tape holds then)
     c->rec_swept = false;
     return TRM_OK;
+}
+// The staged tables of a record (record_table_build) to the device, on the context's stream.  The caller waits for the stream before the
+// staging copy changes again
+int upload_table(trm_ctx* c, RecordTable& t, const std::string& who) {
+    const size_t bytes = t.host.size() * sizeof(int32_t);
+    if (alloc_if_null(t.d_tables, (bytes + 7) / 8 * 8) != hipSuccess) return fail(c, TRM_ENOMEM, who + ": the record's tables do not fit");
+    const hipError_t e = hipMemcpyAsync(t.d_tables, t.host.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    return e == hipSuccess ? TRM_OK : fail(c, TRM_EHIP, who + ": " + hipGetErrorString(e));
 }
 // row_of_level and row_of_position of a tape of n steps, in front of a sweep's first launch; a sweep over the count of the sweep before
 // finds them in place
 int record_tables(trm_ctx* c, int n, const char* who) {
-    if (c->rec_table_n == n && c->d_rec_tables) return TRM_OK;
+    if (c->rec.entries == n + 1 && c->rec.d_tables) return TRM_OK;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
-    release(c->d_rec_tables);
-    c->rec_table_n = -1;
-    c->rec_table_host = record_level_table(c->Nz, c->rec_levels);
-    const std::vector<int32_t> rows = record_position_table(n, c->rec_positions);
-    c->rec_table_host.insert(c->rec_table_host.end(), rows.begin(), rows.end());
-    const size_t bytes = c->rec_table_host.size() * sizeof(int32_t);
-    if (alloc_if_null(c->d_rec_tables, (bytes + 7) / 8 * 8) != hipSuccess) return fail(c, TRM_ENOMEM, std::string(who) + ": the record's tables do not fit");
-    TRM_HIP(c, hipMemcpyAsync(c->d_rec_tables, c->rec_table_host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    release(c->rec.d_tables);
+    record_table_build(c->rec, c->Nz, n);
+    const int rc = upload_table(c, c->rec, who);
+    if (rc) c->rec.entries = 0;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
-    c->rec_table_n = n;
-    return TRM_OK;
+    return rc;
 }
 }  // namespace
 
@@ -601,10 +597,10 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
         const int recorded = tangent_record_steps(c, m);
         if (recorded) m = recorded;
         int rc = nser ? Unfused<double>::upload_series_rows(c, dt, m) : Unfused<double>::update_inputs(c, c->state, c->time);
-        if (!rc) rc = recorded ? TangentRecordLaunch::step(c, dt, m, ride) : TangentLaunch::step(c, dt, m, ride);
+        if (!rc) rc = TangentLaunch::step(c, dt, m, ride, recorded != 0);
         if (rc) return rc;
         c->derivative_series = nser;
-        if (c->trec_npos) c->trec_position += m;
+        if (c->trec.npos) c->trec_position += m;
         tick(c, dt, m);
     }
     return derivative_steps_done(c);
@@ -619,16 +615,15 @@ int trm_tangent_record_attach(trm_ctx* c, int npos, const int32_t* positions, in
     if (int rc = tangent_record_attach_ok(c, npos, positions, nlevels, levels, who)) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     const std::string w(who);
-    c->trec_positions.assign(positions, positions + npos);
-    c->trec_levels.assign(levels, levels + nlevels);
-    c->trec_table_host = tangent_record_tables(c->Nz, c->trec_levels, c->trec_positions);
-    const size_t cell_bytes = rows_bytes(c, (long)npos * nlevels), table_bytes = c->trec_table_host.size() * sizeof(int32_t);
+    record_table_attach(c->trec, npos, positions, nlevels, levels);
+    record_table_build(c->trec, c->Nz, tangent_record_limit(c->trec.positions));
+    const size_t cell_bytes = rows_bytes(c, (long)npos * nlevels);
     int rc = TRM_OK;
     for (double*& q : c->d_trec)
         if (!rc && alloc_if_null(q, cell_bytes) != hipSuccess) rc = fail(c, TRM_ENOMEM, w + ": the samples do not fit");
-    if (!rc && alloc_if_null(c->d_trec_tables, (table_bytes + 7) / 8 * 8) != hipSuccess) rc = fail(c, TRM_ENOMEM, w + ": the record's tables do not fit");
+    if (!rc) rc = upload_table(c, c->trec, w);
     if (!rc) {
-        hipError_t e = hipMemcpyAsync(c->d_trec_tables, c->trec_table_host.data(), table_bytes, hipMemcpyHostToDevice, c->stream);
+        hipError_t e = hipSuccess;
         for (double* q : c->d_trec)
             if (e == hipSuccess) e = hipMemsetAsync(q, 0xFF, cell_bytes, c->stream);    // (every byte set: a NaN)
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -638,15 +633,13 @@ int trm_tangent_record_attach(trm_ctx* c, int npos, const int32_t* positions, in
         drop_tangent_record(c);
         return rc;
     }
-    c->trec_npos = npos;
-    c->trec_nlevels = nlevels;
     c->trec_position = 0;
     return TRM_OK;
 }
 int trm_tangent_record_rewind(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
     if (int rc = tangent_record_attached(c, "trm_tangent_record_rewind")) return rc;
-    for (double* q : c->d_trec) TRM_HIP(c, hipMemsetAsync(q, 0xFF, rows_bytes(c, (long)c->trec_npos * c->trec_nlevels), c->stream));
+    for (double* q : c->d_trec) TRM_HIP(c, hipMemsetAsync(q, 0xFF, rows_bytes(c, (long)c->trec.npos * c->trec.nlevels), c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     c->trec_position = 0;
     return TRM_OK;
@@ -663,7 +656,7 @@ int trm_tangent_record_download(trm_ctx* c, int which, void* host) {
     const char* who = "trm_tangent_record_download";
     if (int rc = tangent_record_attached(c, who)) return rc;
     if (int rc = which_ok(c, which, TRM_TANGENT_RECORD_TANGENT + 1, host, who, " (TRM_TANGENT_RECORD_*)")) return rc;
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_trec[which], rows_bytes(c, (long)c->trec_npos * c->trec_nlevels), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_trec[which], rows_bytes(c, (long)c->trec.npos * c->trec.nlevels), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
 }
@@ -679,8 +672,8 @@ int trm_tangent_record_device_ptr(trm_ctx* c, int which, void** dev) {
 int trm_tangent_record_info(const trm_ctx* c, int* npos, int* nlevels, int64_t* position, int64_t* bytes) {
     if (!c) return TRM_EINVAL;
     if (int rc = tangent_open(const_cast<trm_ctx*>(c), "trm_tangent_record_info")) return rc;
-    if (npos) *npos = c->trec_npos;
-    if (nlevels) *nlevels = c->trec_nlevels;
+    if (npos) *npos = c->trec.npos;
+    if (nlevels) *nlevels = c->trec.nlevels;
     if (position) *position = c->trec_position;
     if (bytes) *bytes = tangent_record_bytes(c);
     return TRM_OK;
@@ -861,7 +854,7 @@ int trm_adjoint_backward(trm_ctx* c) {
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTape);
     // An attached record (trm_adjoint_observe_record) is read inside the launches: no position of it is a launch boundary.  A record
     // longer than the tape is refused here, in front of everything the sweep does
-    const bool rec = c->rec_npos > 0;
+    const bool rec = c->rec.npos > 0;
     if (int rc = record_fits_tape(c, taped_steps(c), who)) return rc;
     if (rec)
         if (int rc = record_tables(c, taped_steps(c), who)) return rc;
@@ -891,7 +884,7 @@ int trm_adjoint_backward(trm_ctx* c) {
             const trm_ctx::TapeSegment seg = s > 0 ? c->tape_segs[s - 1] : trm_ctx::TapeSegment{0, 0, 0.0, 0};
             rc = inject_observations(c, seg.first + seg.len, true, !fold);   // (a segment ends at every observed position)
             if (!rc) rc = nser ? kept_rows(seg.first, seg.len) : TRM_OK;
-            if (!rc) rc = rec ? RecordLaunch::backward(c, true, seg.dt, seg.len, seg.slot, fold, ride, seg.first) : CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold, ride);
+            if (!rc) rc = CheckpointLaunch::backward(c, seg.dt, seg.len, seg.slot, fold, ride, rec, seg.first);
             if (!rc && fold) rc = inject_observations(c, n, false, true);
             if (rc) break;
             c->derivative_series = nser;
@@ -910,7 +903,7 @@ int trm_adjoint_backward(trm_ctx* c) {
             const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
             rc = inject_observations(c, end, true, !fold);
             if (!rc) rc = nser ? kept_rows(begin, end - begin) : TRM_OK;
-            if (!rc) rc = rec ? RecordLaunch::backward(c, false, dt_block, end - begin, begin, fold, ride, begin) : AdjointLaunch::backward(c, dt_block, end - begin, begin, fold, ride);
+            if (!rc) rc = AdjointLaunch::backward(c, dt_block, end - begin, begin, fold, ride, rec, begin);
             if (!rc && fold) rc = inject_observations(c, n, false, true);
             if (rc) break;
             c->derivative_series = nser;
@@ -998,7 +991,7 @@ int trm_adjoint_record_detach(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
     const char* who = "trm_adjoint_record_detach";
     if (int rc = adjoint_open(c, who)) return rc;
-    if (c->rec_npos == 0) return fail(c, TRM_EINVAL, std::string(who) + ": no record is attached (trm_adjoint_observe_record)");
+    if (c->rec.npos == 0) return fail(c, TRM_EINVAL, std::string(who) + ": no record is attached (trm_adjoint_observe_record)");
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     drop_record(c);
     return TRM_OK;
@@ -1006,7 +999,7 @@ int trm_adjoint_record_detach(trm_ctx* c) {
 int trm_adjoint_record_residual_download(trm_ctx* c, void* host) {
     TRM_ENTER_HEUN(c);
     if (int rc = record_results_ok(c, host, "trm_adjoint_record_residual_download")) return rc;
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out, rows_bytes(c, (long)c->rec_npos * c->rec_nlevels), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out, rows_bytes(c, (long)c->rec.npos * c->rec.nlevels), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
 }
@@ -1020,15 +1013,15 @@ int trm_adjoint_record_residual_device_ptr(trm_ctx* c, void** dev) {
 int trm_adjoint_record_misfit_download(trm_ctx* c, void* host) {
     TRM_ENTER_HEUN(c);
     if (int rc = record_results_ok(c, host, "trm_adjoint_record_misfit_download")) return rc;
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out + (size_t)c->rec_npos * (size_t)c->rec_nlevels * (size_t)c->Nh, rows_bytes(c), hipMemcpyDeviceToHost, c->stream));
+    TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out + (size_t)c->rec.npos * (size_t)c->rec.nlevels * (size_t)c->Nh, rows_bytes(c), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
 }
 int trm_adjoint_record_info(const trm_ctx* c, int* npos, int* nlevels, int64_t* bytes) {
     if (!c) return TRM_EINVAL;
     if (int rc = adjoint_open(const_cast<trm_ctx*>(c), "trm_adjoint_record_info")) return rc;
-    if (npos) *npos = c->rec_npos;
-    if (nlevels) *nlevels = c->rec_nlevels;
+    if (npos) *npos = c->rec.npos;
+    if (nlevels) *nlevels = c->rec.nlevels;
     if (bytes) *bytes = record_bytes(c);
     return TRM_OK;
 }

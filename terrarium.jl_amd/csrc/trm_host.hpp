@@ -28,6 +28,18 @@ struct FieldSet {
     void* raw[TRM_FIELD_COUNT];   // the allocations behind f[] (f = raw + the field's skew, see alloc_fields)
 };
 
+// The position table of a record, the adjoint's (trm_ctx::rec) or the tangent's (trm_ctx::trec): what the caller gave -- `positions` (step
+// counts) and `levels` (rows of the host layout), both strictly increasing; npos == 0: none attached -- and the int32 tables the kernels
+// index: row_of_level[Nz], then row_of_position[entries] (entries == 0: not built).  `host`: the staging copy, alive while its upload is
+// in flight; `d_tables`: the device copy.  The functions are record_table_* (below).
+struct RecordTable {
+    std::vector<int> positions, levels;
+    int npos = 0, nlevels = 0;
+    std::vector<int32_t> host;
+    double* d_tables = nullptr;
+    int entries = 0;
+};
+
 struct trm_ctx {
     int precision = TRM_F64;
     long Nh = 0;
@@ -236,31 +248,22 @@ struct trm_ctx {
     double* d_misfit = nullptr;
     bool tape_seg_closed = false;
     // An attached temperature record (trm_adjoint_observe_record*; DESIGN 4.8 "Attached records"): read inside the backward launches, kept
-    // across sweeps, dropped by a detach, a new tape or trm_adjoint_close.  `rec_positions` / `rec_levels`: what the caller gave (taped-step
-    // counts and rows of the host layout, both strictly increasing); rec_npos == 0: none attached.  `d_rec_observed` / `d_rec_weight`
-    // ([npos][nlevels][Nh]; the weights may be null): the library's copies in `d_rec_owned`, or the caller's device arrays (then
-    // d_rec_owned is null).  `d_rec_out`: the residuals [npos][nlevels][Nh] and behind them the misfit [Nh].  `d_rec_tables`: int32
-    // row_of_level[Nz], then row_of_position[rec_table_n + 1] as built for a tape of rec_table_n steps (-1: not built yet; a sweep over
-    // another count builds it again).  `rec_swept`: a sweep has run with this record, so the residuals and the misfit are its.
-    std::vector<int> rec_positions, rec_levels;
-    int rec_npos = 0, rec_nlevels = 0;
+    // across sweeps, dropped by a detach, a new tape or trm_adjoint_close.  `rec`: its positions (taped-step counts) and levels; the tables
+    // are built for a tape of rec.entries - 1 steps by the first sweep, and again by a sweep over another count.  `d_rec_observed` /
+    // `d_rec_weight` ([npos][nlevels][Nh]; the weights may be null): the library's copies in `d_rec_owned`, or the caller's device arrays
+    // (then d_rec_owned is null).  `d_rec_out`: the residuals [npos][nlevels][Nh] and behind them the misfit [Nh].  `rec_swept`: a sweep
+    // has run with this record, so the residuals and the misfit are its.
+    RecordTable rec;
     double* d_rec_owned = nullptr;
     const double *d_rec_observed = nullptr, *d_rec_weight = nullptr;
     double* d_rec_out = nullptr;
-    double* d_rec_tables = nullptr;
-    int rec_table_n = -1;
-    std::vector<int32_t> rec_table_host;   // (the staging copy of row_of_position: alive while its upload is in flight)
     bool rec_swept = false;
     // A tangent record (trm_tangent_record_attach; DESIGN 4.7 "Tangent records"): T and dT sampled inside the tangent launches, kept until
-    // a detach, trm_tangent_open or trm_tangent_close.  `trec_positions` / `trec_levels`: what the caller gave (tangent-step counts since
-    // the attach or the last rewind, and rows of the host layout, both strictly increasing); trec_npos == 0: none attached.  `d_trec`: the
-    // samples of T and of dT, [npos][nlevels][Nh] each, NaN where no launch has stored.  `d_trec_tables`: int32 row_of_level[Nz], then
-    // row_of_position[last position + 1].  `trec_position`: tangent steps run since the attach or the last rewind.
-    std::vector<int> trec_positions, trec_levels;
-    int trec_npos = 0, trec_nlevels = 0;
+    // a detach, trm_tangent_open or trm_tangent_close.  `trec`: its positions (tangent-step counts since the attach or the last rewind)
+    // and levels; the tables are built at the attach, up to tangent_record_limit.  `d_trec`: the samples of T and of dT,
+    // [npos][nlevels][Nh] each, NaN where no launch has stored.  `trec_position`: tangent steps run since the attach or the last rewind.
+    RecordTable trec;
     double* d_trec[2] = {};
-    double* d_trec_tables = nullptr;
-    std::vector<int32_t> trec_table_host;   // (the staging copy of the tables: alive while its upload is in flight)
     long long trec_position = 0;
     bool args_valid = false;
     void* args = nullptr;   // LaunchArgs<NF>*, owned
@@ -663,30 +666,35 @@ template <class NF, bool RICH, int PROG> struct ColumnLaunch { static int run(tr
 // the multi-step program with time averages accumulated in the launch (trm_launch_column_accum_*.hip)
 template <class NF, bool RICH> struct ColumnAccumLaunch { static int run(trm_ctx* c, double dt, int finalize, int nsteps, const AccumArgs& acc); };
 // ---- the derivative families of the heat-only fp64 run (trm_launch_derivative.inl) --------------------------------------------------
-// What rides along with a tangent step or a backward sweep is a Ride (trm_kernels.hpp).  The launchers, one explicit instantiation per
-// ride in trm_launch_column_{tangent,adjoint,adjoint_ckpt}{,_bc,_param,_series,_param_series}.hip (the two series records in trm_launch_column_adjoint_series.hip: the record carries no derivative, so both series rides share it)
-template <Ride R> int tangent_step(trm_ctx* c, double dt, int nsteps);
+// What rides along with a tangent step or a backward sweep is a Ride (trm_kernels.hpp); RECORD: the launch is the record twin of its
+// kernel, which samples the tangent record (k_column_tangent_record) or reads the attached temperature record (k_column_adjoint_record,
+// k_column_adjoint_ckpt_record) -- the same preconditions and arguments plus the record's, the same TRM_INFO_LAST_PROGRAM.  The launchers,
+// one explicit instantiation per ride in trm_launch_column_{tangent,adjoint,adjoint_ckpt}{,_record}{,_bc,_param,_series,_param_series}.hip
+// (the two series records in trm_launch_column_adjoint_series.hip: the record carries no derivative, so both series rides share it)
+constexpr bool NO_RECORD = false, WITH_RECORD = true;
+template <Ride R, bool RECORD> int tangent_step(trm_ctx* c, double dt, int nsteps);
 template <Ride R> int tangent_closure(trm_ctx* c);
 template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
-template <bool CKPT, Ride R> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
-// k_column_tangent / k_closure_tangent (fp64 NoFlow only); the closure knows the parameter seeds alone.  These three choose the
-// instantiation of the ride (trm_derivative_api.hip)
+// (`first`: the taped position of the launch's first step, read with RECORD alone)
+template <bool CKPT, Ride R, bool RECORD> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, int first);
+// k_column_tangent{,_record} / k_closure_tangent (fp64 NoFlow only); the closure knows the parameter seeds alone.  These choose the
+// instantiation of the ride, with a record or without (ride_launch, trm_derivative_api.hip)
 struct TangentLaunch {
-    static int step(trm_ctx* c, double dt, int nsteps, Ride ride);
+    static int step(trm_ctx* c, double dt, int nsteps, Ride ride, bool record);
     static int closure(trm_ctx* c, Ride ride);
 };
-// k_column_record / k_column_adjoint (fp64 NoFlow only): `slot` is the tape slot of the launch's first step; k_param_reduce ends a
-// sweep with parameter gradients on either tape (trm_launch_column_adjoint_param.hip)
+// k_column_record / k_column_adjoint{,_record} (fp64 NoFlow only): `slot` is the tape slot of the launch's first step; k_param_reduce ends
+// a sweep with parameter gradients on either tape (trm_launch_column_adjoint_param.hip)
 struct AdjointLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot, bool series);
-    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride);
+    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride, bool record, int first);
     static int param_reduce(trm_ctx* c);
 };
-// the strided k_column_record / k_column_adjoint_ckpt: the record stores before the steps `first`, `first + every`, ... of the launch
-// into the slots from `slot` on; the backward launch pulls lam through the segment of `nsteps` steps whose checkpoint is in `slot`
+// the strided k_column_record / k_column_adjoint_ckpt{,_record}: the record stores before the steps `first`, `first + every`, ... of the
+// launch into the slots from `slot` on; the backward launch pulls lam through the segment of `nsteps` steps whose checkpoint is in `slot`
 struct CheckpointLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every, bool series);
-    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride);
+    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride, bool record, int first);
 };
 // The tape of trm_step_record as the host keeps it (trm_ctx::tape_dt, or tape_segs when checkpointed): bookkeeping alone, no HIP call
 // (tests/derivative_preconditions.cpp).  Steps on the tape:
@@ -730,7 +738,7 @@ struct ObserveLaunch {
     static int misfit(trm_ctx* c, const trm_ctx::Observation& o);
     static int inject(trm_ctx* c, const trm_ctx::Observation& o, const double* U_p, bool lam, bool params);
 };
-// ---- attached records (trm_adjoint_observe_record*; trm_launch_record.hip) -- bookkeeping alone, no HIP call
+// ---- the position table of a record (RecordTable; trm_ctx::rec, trm_ctx::trec) -- bookkeeping alone, no HIP call
 // (tests/record_preconditions.cpp) ----
 // row_of_level[Nz]: the row of the record's level list a level has, -1 for a level it does not observe
 inline std::vector<int32_t> record_level_table(int Nz, const std::vector<int>& levels) {
@@ -738,21 +746,56 @@ inline std::vector<int32_t> record_level_table(int Nz, const std::vector<int>& l
     for (size_t j = 0; j < levels.size(); ++j) t[(size_t)levels[j]] = (int32_t)j;
     return t;
 }
-// row_of_position[n + 1] of a tape of n steps: the row of the record a taped position has, -1 without a sample.  Positions behind n
-// have no entry (the sweep refuses them first, record_fits_tape)
+// row_of_position[n + 1] of a run of n steps: the row of the record a position has, -1 without a sample.  Positions behind n have no
+// entry (the sweep refuses them first, record_fits_tape)
 inline std::vector<int32_t> record_position_table(int n, const std::vector<int>& positions) {
     std::vector<int32_t> t((size_t)n + 1, -1);
     for (size_t k = 0; k < positions.size(); ++k)
         if (positions[k] <= n) t[(size_t)positions[k]] = (int32_t)k;
     return t;
 }
+// What an attach checks of the caller's lists, in the words of the neighbouring calls: `counts` is what the positions count
+// ("taped-step", "tangent-step")
+inline int record_lists_ok(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const char* counts, const std::string& who) {
+    for (int k = 0; k < npos; ++k)
+        if (positions[k] < 0 || (k > 0 && positions[k] <= positions[k - 1]))
+            return fail(c, TRM_EINVAL, who + ": the positions are " + counts + " counts >= 0, strictly increasing");
+    for (int j = 0; j < nlevels; ++j)
+        if (levels[j] < 0 || levels[j] >= c->Nz || (j > 0 && levels[j] <= levels[j - 1]))
+            return fail(c, TRM_EINVAL, who + ": the levels are rows 0 ... " + std::to_string(c->Nz - 1) + " of the host layout, strictly increasing");
+    return TRM_OK;
+}
+// what an attach leaves: the lists, no table yet
+inline void record_table_attach(RecordTable& t, int npos, const int32_t* positions, int nlevels, const int32_t* levels) {
+    t.positions.assign(positions, positions + npos);
+    t.levels.assign(levels, levels + nlevels);
+    t.npos = npos;
+    t.nlevels = nlevels;
+    t.entries = 0;
+}
+// the staging copy of the tables for the positions 0 ... last.  It replaces the one before: no upload of that may be in flight
+inline void record_table_build(RecordTable& t, int Nz, int last) {
+    t.host = record_level_table(Nz, t.levels);
+    const std::vector<int32_t> rows = record_position_table(last, t.positions);
+    t.host.insert(t.host.end(), rows.begin(), rows.end());
+    t.entries = last + 1;
+}
+// the device tables as a launch whose first state is position `first` sees them
+inline const int32_t* record_row_of_level(const RecordTable& t) { return (const int32_t*)t.d_tables; }
+inline const int32_t* record_row_of_position(const RecordTable& t, int Nz, long long first) { return (const int32_t*)t.d_tables + Nz + first; }
+// a launch of `nsteps` steps from position `first` reads the entries first ... first + nsteps: all inside the table
+inline bool record_table_covers(const RecordTable& t, long long first, int nsteps) { return first >= 0 && nsteps >= 0 && first + nsteps < (long long)t.entries; }
+inline int64_t record_table_bytes(const RecordTable& t, int Nz) { return ((int64_t)Nz + t.entries) * 4; }
+// nothing attached.  The device tables are the caller's to free first (drop_table, trm_derivative_api.hip)
+inline void record_table_drop(RecordTable& t) { t = RecordTable{}; }
+
+// ---- attached records (trm_adjoint_observe_record*; trm_launch_record.hip) ----
 // what the library holds for an attached record: the tables, the residuals and the misfit, and its copies of a host record
 inline int64_t record_bytes(const trm_ctx* c) {
-    if (c->rec_npos == 0) return 0;
-    const int64_t cells = (int64_t)c->rec_npos * c->rec_nlevels * (int64_t)c->Nh * 8;
-    const int64_t tables = ((int64_t)c->Nz + (c->rec_table_n >= 0 ? (int64_t)c->rec_table_n + 1 : 0)) * 4;
+    if (c->rec.npos == 0) return 0;
+    const int64_t cells = (int64_t)c->rec.npos * c->rec.nlevels * (int64_t)c->Nh * 8;
     const int64_t owned = c->d_rec_owned ? cells * (c->d_rec_weight ? 2 : 1) : 0;
-    return owned + cells + (int64_t)c->Nh * 8 + tables;
+    return owned + cells + (int64_t)c->Nh * 8 + record_table_bytes(c->rec, c->Nz);
 }
 // What an attach checks before it touches the device, in the words of the neighbouring calls.  `host_weight`: the weights of the host
 // form (null: none given, or the device form, whose weights the library cannot read)
@@ -761,28 +804,24 @@ inline int record_attach_ok(trm_ctx* c, int npos, const int32_t* positions, int 
     const std::string w(who);
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, w + ": no adjoint is open (trm_adjoint_open)");
     if (npos < 1 || nlevels < 1 || !positions || !levels || !observed) return fail(c, TRM_EINVAL, w + ": bad argument (npos >= 1 positions, nlevels >= 1 levels, the observed temperatures)");
-    for (int k = 0; k < npos; ++k)
-        if (positions[k] < 0 || (k > 0 && positions[k] <= positions[k - 1])) return fail(c, TRM_EINVAL, w + ": the positions are taped-step counts >= 0, strictly increasing");
-    for (int j = 0; j < nlevels; ++j)
-        if (levels[j] < 0 || levels[j] >= c->Nz || (j > 0 && levels[j] <= levels[j - 1]))
-            return fail(c, TRM_EINVAL, w + ": the levels are rows 0 ... " + std::to_string(c->Nz - 1) + " of the host layout, strictly increasing");
+    if (int rc = record_lists_ok(c, npos, positions, nlevels, levels, "taped-step", w)) return rc;
     if (host_weight)
         for (size_t q = 0, end = (size_t)npos * (size_t)nlevels * (size_t)c->Nh; q < end; ++q)
             if (!(host_weight[q] >= 0.0)) return fail(c, TRM_EINVAL, w + ": a weight is negative or NaN");
-    if (c->rec_npos) return fail(c, TRM_EINVAL, w + ": a record is attached already (trm_adjoint_record_detach)");
+    if (c->rec.npos) return fail(c, TRM_EINVAL, w + ": a record is attached already (trm_adjoint_record_detach)");
     if (!c->observations.empty())
         return fail(c, TRM_EINVAL, w + ": per-position observations are registered (trm_adjoint_observe, trm_adjoint_observe_misfit): the two paths do not mix");
     return TRM_OK;
 }
 // trm_adjoint_observe / trm_adjoint_observe_misfit while a record is attached
 inline int record_excludes_observations(trm_ctx* c, const char* who) {
-    if (c->rec_npos == 0) return TRM_OK;
+    if (c->rec.npos == 0) return TRM_OK;
     return fail(c, TRM_EINVAL, std::string(who) + ": a temperature record is attached (trm_adjoint_observe_record): the two paths do not mix");
 }
 // a sweep over a tape of n steps: every position of the record is on it
 inline int record_fits_tape(trm_ctx* c, int n, const char* who) {
-    if (c->rec_npos == 0 || c->rec_positions.back() <= n) return TRM_OK;
-    return fail(c, TRM_EINVAL, std::string(who) + ": the attached record is longer than the tape: position " + std::to_string(c->rec_positions.back()) + " of " +
+    if (c->rec.npos == 0 || c->rec.positions.back() <= n) return TRM_OK;
+    return fail(c, TRM_EINVAL, std::string(who) + ": the attached record is longer than the tape: position " + std::to_string(c->rec.positions.back()) + " of " +
                                    std::to_string(n) + " taped steps");
 }
 // the residuals and the misfit are those of a sweep with this record
@@ -790,69 +829,45 @@ inline int record_results_ok(trm_ctx* c, const void* ptr, const char* who) {
     const std::string w(who);
     if (!c->d_adj[0]) return fail(c, TRM_EINVAL, w + ": no adjoint is open (trm_adjoint_open)");
     if (!ptr) return fail(c, TRM_EINVAL, w + ": bad argument");
-    if (c->rec_npos == 0) return fail(c, TRM_EINVAL, w + ": no record is attached (trm_adjoint_observe_record)");
+    if (c->rec.npos == 0) return fail(c, TRM_EINVAL, w + ": no record is attached (trm_adjoint_observe_record)");
     if (!c->rec_swept) return fail(c, TRM_EINVAL, w + ": no sweep has run with this record (trm_adjoint_backward)");
     return TRM_OK;
 }
-// The record-reading sweeps: k_column_adjoint_record / k_column_adjoint_ckpt_record (one explicit instantiation per tape and ride in
-// trm_launch_column_adjoint{,_ckpt}_record{,_bc,_param,_series,_param_series}.hip) and k_record_misfit (trm_launch_record.hip, with the
-// dispatch over the ride).  `first`: the taped position of the launch's first step.  TRM_INFO_LAST_PROGRAM is that of the same launch
-// without a record.
-template <bool CKPT, Ride R> int adjoint_backward_record(trm_ctx* c, double dt, int nsteps, int slot, int fold, int first);
+// k_record_misfit, which sums the residuals a sweep wrote into the misfit per column (trm_launch_record.hip)
 struct RecordLaunch {
-    static int backward(trm_ctx* c, bool ckpt, double dt, int nsteps, int slot, int fold, Ride ride, int first);
     static int misfit(trm_ctx* c);
 };
-// ---- tangent records (trm_tangent_record_*; trm_launch_tangent_record.inl) -- bookkeeping alone, no HIP call
-// (tests/tangent_record_preconditions.cpp) ----
+// ---- tangent records (trm_tangent_record_*) -- bookkeeping alone, no HIP call (tests/tangent_record_preconditions.cpp) ----
 // The last position a record launch may reach: the record's last position -- or 1 for a record of position 0 alone, whose sample is the
-// entry's of a launch that has a step to run
+// entry's of a launch that has a step to run (its table has two entries)
 inline int tangent_record_limit(const std::vector<int>& positions) { return std::max(positions.back(), 1); }
-// the tables of a tangent record: row_of_level[Nz], then row_of_position[last position + 1] ([2] for a record of position 0 alone)
-inline std::vector<int32_t> tangent_record_tables(int Nz, const std::vector<int>& levels, const std::vector<int>& positions) {
-    std::vector<int32_t> t = record_level_table(Nz, levels);
-    const std::vector<int32_t> rows = record_position_table(tangent_record_limit(positions), positions);
-    t.insert(t.end(), rows.begin(), rows.end());
-    return t;
-}
 // What an attach checks before it touches the device (the caller has checked that the derivatives cover the context)
 inline int tangent_record_attach_ok(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const char* who) {
     const std::string w(who);
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, w + ": no tangent is open (trm_tangent_open)");
     if (npos < 1 || nlevels < 1 || !positions || !levels) return fail(c, TRM_EINVAL, w + ": bad argument (npos >= 1 positions, nlevels >= 1 levels)");
-    for (int k = 0; k < npos; ++k)
-        if (positions[k] < 0 || (k > 0 && positions[k] <= positions[k - 1])) return fail(c, TRM_EINVAL, w + ": the positions are tangent-step counts >= 0, strictly increasing");
-    for (int j = 0; j < nlevels; ++j)
-        if (levels[j] < 0 || levels[j] >= c->Nz || (j > 0 && levels[j] <= levels[j - 1]))
-            return fail(c, TRM_EINVAL, w + ": the levels are rows 0 ... " + std::to_string(c->Nz - 1) + " of the host layout, strictly increasing");
-    if (c->trec_npos) return fail(c, TRM_EINVAL, w + ": a record is attached already (trm_tangent_record_detach)");
+    if (int rc = record_lists_ok(c, npos, positions, nlevels, levels, "tangent-step", w)) return rc;
+    if (c->trec.npos) return fail(c, TRM_EINVAL, w + ": a record is attached already (trm_tangent_record_detach)");
     return TRM_OK;
 }
 // the calls that need an attached record
 inline int tangent_record_attached(trm_ctx* c, const char* who) {
     const std::string w(who);
     if (!c->d_tan[0]) return fail(c, TRM_EINVAL, w + ": no tangent is open (trm_tangent_open)");
-    if (c->trec_npos == 0) return fail(c, TRM_EINVAL, w + ": no record is attached (trm_tangent_record_attach)");
+    if (c->trec.npos == 0) return fail(c, TRM_EINVAL, w + ": no record is attached (trm_tangent_record_attach)");
     return TRM_OK;
 }
 // Of the next `m` tangent steps, the ones a record launch runs: those up to the last position (0: the launch samples nothing and is the
 // record-free kernel's).  A launch never runs past the position table: the steps behind it are a launch of their own.
 inline int tangent_record_steps(const trm_ctx* c, int m) {
-    if (c->trec_npos == 0 || c->trec_position >= (long long)tangent_record_limit(c->trec_positions)) return 0;
-    return (int)std::min<long long>(m, (long long)tangent_record_limit(c->trec_positions) - c->trec_position);
+    if (c->trec.npos == 0 || c->trec_position >= (long long)tangent_record_limit(c->trec.positions)) return 0;
+    return (int)std::min<long long>(m, (long long)tangent_record_limit(c->trec.positions) - c->trec_position);
 }
 // what the library holds for a tangent record: both sample arrays and the tables
 inline int64_t tangent_record_bytes(const trm_ctx* c) {
-    if (c->trec_npos == 0) return 0;
-    return 2 * (int64_t)c->trec_npos * c->trec_nlevels * (int64_t)c->Nh * 8 + ((int64_t)c->Nz + (int64_t)tangent_record_limit(c->trec_positions) + 1) * 4;
+    if (c->trec.npos == 0) return 0;
+    return 2 * (int64_t)c->trec.npos * c->trec.nlevels * (int64_t)c->Nh * 8 + record_table_bytes(c->trec, c->Nz);
 }
-// k_column_tangent_record (one explicit instantiation per ride in trm_launch_column_tangent_record{,_bc,_param,_series,_param_series}.hip):
-// the launch of tangent_step<R> that stores T and dT at the record's positions.  TRM_INFO_LAST_PROGRAM is that of the same launch without
-// a record.  The dispatch over the ride is TangentRecordLaunch::step (trm_derivative_api.hip)
-template <Ride R> int tangent_record_step(trm_ctx* c, double dt, int nsteps);
-struct TangentRecordLaunch {
-    static int step(trm_ctx* c, double dt, int nsteps, Ride ride);
-};
 // The chain rule between the ten thermal parameters (TRM_THERMAL_PARAM_*, the order of trm_params) and the eight numbers the kernels
 // differentiate (make_dev_params): w[q] = d(derived number) / d(parameter q), with sk_i = sqrt(k_i), s0 = sqrt(k_mineral) frac_mineral +
 // sqrt(k_organic) frac_organic, C0 = c_mineral frac_mineral + c_organic frac_organic.  Parameter q feeds derived number

@@ -4,5 +4,5 @@
 
 namespace trmh {
 template int adjoint_record<false, false>(trm_ctx*, double, int, int, int, int);
-template int adjoint_backward<false, RIDE_NONE>(trm_ctx*, double, int, int, int);
+template int adjoint_backward<false, RIDE_NONE, NO_RECORD>(trm_ctx*, double, int, int, int, int);
 }  // namespace trmh

@@ -4,5 +4,5 @@
 
 namespace trmh {
 template int adjoint_record<true, false>(trm_ctx*, double, int, int, int, int);
-template int adjoint_backward<true, RIDE_NONE>(trm_ctx*, double, int, int, int);
+template int adjoint_backward<true, RIDE_NONE, NO_RECORD>(trm_ctx*, double, int, int, int, int);
 }  // namespace trmh

@@ -3,5 +3,5 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int adjoint_backward<true, RIDE_BC>(trm_ctx*, double, int, int, int);
+template int adjoint_backward<true, RIDE_BC, NO_RECORD>(trm_ctx*, double, int, int, int, int);
 }  // namespace trmh

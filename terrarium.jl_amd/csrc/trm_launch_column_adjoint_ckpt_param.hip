@@ -4,5 +4,5 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int adjoint_backward<true, RIDE_PARAM>(trm_ctx*, double, int, int, int);
+template int adjoint_backward<true, RIDE_PARAM, NO_RECORD>(trm_ctx*, double, int, int, int, int);
 }  // namespace trmh

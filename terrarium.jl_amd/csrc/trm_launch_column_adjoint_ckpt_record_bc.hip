@@ -1,8 +1,8 @@
 // trm_launch_column_adjoint_ckpt_record_bc.hip -- the launches of k_column_adjoint_ckpt_record<HYD, LPC, RIDE_BC> (both lanes-per-column layouts; trm_column_adjoint_ckpt.hpp): the
 // backward sweep of the checkpointed tape that reads an attached temperature record inside the launch (trm_adjoint_observe_record), with
 // the boundary gradients riding along (trm_adjoint_bc_open).
-#include "trm_launch_record.inl"
+#include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int adjoint_backward_record<true, RIDE_BC>(trm_ctx*, double, int, int, int, int);
+template int adjoint_backward<true, RIDE_BC, WITH_RECORD>(trm_ctx*, double, int, int, int, int);
 }  // namespace trmh

@@ -4,7 +4,7 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int adjoint_backward<false, RIDE_PARAM>(trm_ctx*, double, int, int, int);
+template int adjoint_backward<false, RIDE_PARAM, NO_RECORD>(trm_ctx*, double, int, int, int, int);
 
 int AdjointLaunch::param_reduce(trm_ctx* c) {
     if (!c->d_adj_param_out) return fail(c, TRM_EINVAL, "k_param_reduce: no accumulators");

@@ -6,5 +6,5 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int adjoint_backward<false, RIDE_PARAM_SERIES>(trm_ctx*, double, int, int, int);
+template int adjoint_backward<false, RIDE_PARAM_SERIES, NO_RECORD>(trm_ctx*, double, int, int, int, int);
 }  // namespace trmh

@@ -1,8 +1,8 @@
 // trm_launch_column_adjoint_record_param.hip -- the launches of k_column_adjoint_record<HYD, LPC, RIDE_PARAM> (both lanes-per-column layouts; trm_column_adjoint.hpp): the
 // backward sweep of the per-step tape that reads an attached temperature record inside the launch (trm_adjoint_observe_record), with
 // the boundary and the thermal-parameter gradients riding along (trm_adjoint_param_open).
-#include "trm_launch_record.inl"
+#include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int adjoint_backward_record<false, RIDE_PARAM>(trm_ctx*, double, int, int, int, int);
+template int adjoint_backward<false, RIDE_PARAM, WITH_RECORD>(trm_ctx*, double, int, int, int, int);
 }  // namespace trmh

@@ -7,5 +7,5 @@
 namespace trmh {
 template int adjoint_record<false, true>(trm_ctx*, double, int, int, int, int);
 template int adjoint_record<true, true>(trm_ctx*, double, int, int, int, int);
-template int adjoint_backward<false, RIDE_SERIES>(trm_ctx*, double, int, int, int);
+template int adjoint_backward<false, RIDE_SERIES, NO_RECORD>(trm_ctx*, double, int, int, int, int);
 }  // namespace trmh

@@ -3,6 +3,6 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int tangent_step<RIDE_NONE>(trm_ctx*, double, int);
+template int tangent_step<RIDE_NONE, NO_RECORD>(trm_ctx*, double, int);
 template int tangent_closure<RIDE_NONE>(trm_ctx*);
 }  // namespace trmh

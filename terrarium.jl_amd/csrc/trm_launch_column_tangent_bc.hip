@@ -3,5 +3,5 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int tangent_step<RIDE_BC>(trm_ctx*, double, int);
+template int tangent_step<RIDE_BC, NO_RECORD>(trm_ctx*, double, int);
 }  // namespace trmh

@@ -4,6 +4,6 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int tangent_step<RIDE_PARAM>(trm_ctx*, double, int);
+template int tangent_step<RIDE_PARAM, NO_RECORD>(trm_ctx*, double, int);
 template int tangent_closure<RIDE_PARAM>(trm_ctx*);
 }  // namespace trmh

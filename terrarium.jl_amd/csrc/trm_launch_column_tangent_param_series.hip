@@ -5,5 +5,5 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int tangent_step<RIDE_PARAM_SERIES>(trm_ctx*, double, int);
+template int tangent_step<RIDE_PARAM_SERIES, NO_RECORD>(trm_ctx*, double, int);
 }  // namespace trmh

@@ -1,8 +1,8 @@
 // trm_launch_column_tangent_record_param.hip -- the launches of k_column_tangent_record<HYD, LPC, RIDE_PARAM> (both lanes-per-column layouts;
 // trm_column_tangent_record.hpp): the forward-mode tangents with seeds on the thermal parameters (trm_tangent_param_set) with a tangent record attached
 // (trm_tangent_record_attach), T and dT sampled inside the launch.
-#include "trm_launch_tangent_record.inl"
+#include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int tangent_record_step<RIDE_PARAM>(trm_ctx*, double, int);
+template int tangent_step<RIDE_PARAM, WITH_RECORD>(trm_ctx*, double, int);
 }  // namespace trmh

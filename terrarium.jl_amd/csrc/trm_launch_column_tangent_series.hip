@@ -4,5 +4,5 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-template int tangent_step<RIDE_SERIES>(trm_ctx*, double, int);
+template int tangent_step<RIDE_SERIES, NO_RECORD>(trm_ctx*, double, int);
 }  // namespace trmh

@@ -1,9 +1,12 @@
 // trm_launch_derivative.inl -- the launches of the two derivative families of the heat-only fp64 SoilModel run: k_column_tangent
 // (trm_column_tangent.hpp), k_column_record / k_column_adjoint (trm_column_adjoint.hpp) and k_column_adjoint_ckpt
-// (trm_column_adjoint_ckpt.hpp), each with what rides along (Ride, trm_kernels.hpp).  Included by the trm_launch_column_tangent*.hip and
-// trm_launch_column_adjoint*.hip files, each of which instantiates the launchers of one family and ride.
+// (trm_column_adjoint_ckpt.hpp), each with what rides along (Ride, trm_kernels.hpp), and their record twins: k_column_tangent_record
+// (trm_column_tangent_record.hpp; DESIGN 4.7 "Tangent records"), k_column_adjoint_record and k_column_adjoint_ckpt_record (DESIGN 4.8
+// "Attached records").  Included by the trm_launch_column_tangent*.hip and trm_launch_column_adjoint*.hip files, each of which
+// instantiates the launcher of one family and ride, with a record or without.
 #include "trm_host.hpp"
 #include "trm_column_adjoint_ckpt.hpp"
+#include "trm_column_tangent_record.hpp"
 
 namespace trmh {
 
@@ -125,6 +128,47 @@ template <Ride R> int tangent_seeds_ok(trm_ctx* c, int nsteps, const std::string
     return TRM_OK;
 }
 
+// ---- the records a RECORD launch carries as its fifth kernel argument -------------------------------------------------------------
+// the attached temperature record as a backward launch whose first step is taped position `first` sees it
+inline RecordArgs record_args(const trm_ctx* c, int first) {
+    RecordArgs r;
+    r.row_of_level = record_row_of_level(c->rec);
+    r.row_of_position = record_row_of_position(c->rec, c->Nz, first);
+    r.observed = c->d_rec_observed;
+    r.weight = c->d_rec_weight;
+    r.residual = c->d_rec_out;
+    r.nlevels = c->rec.nlevels;
+    return r;
+}
+// the tables are those of this tape, and the launch's positions first ... first + nsteps are inside them
+inline int record_launch_ok(trm_ctx* c, int nsteps, int first, const std::string& who) {
+    if (c->rec.npos < 1 || !c->rec.d_tables || !c->d_rec_observed || !c->d_rec_out || c->rec.entries < 1)
+        return fail(c, TRM_EINVAL, who + ": no record is attached, or its tables are not built");
+    if (!record_table_covers(c->rec, first, nsteps)) return fail(c, TRM_EINVAL, who + ": the launch leaves the record's position table");
+    return TRM_OK;
+}
+// the tangent record as a launch whose first state is position `start` of the record's count sees it
+inline TangentRecordArgs tangent_record_args(const trm_ctx* c, long long start) {
+    TangentRecordArgs r;
+    r.row_of_level = record_row_of_level(c->trec);
+    r.row_of_position = record_row_of_position(c->trec, c->Nz, start);
+    r.T = c->d_trec[TRM_TANGENT_RECORD_TEMPERATURE];
+    r.dT = c->d_trec[TRM_TANGENT_RECORD_TANGENT];
+    r.nlevels = c->trec.nlevels;
+    r.sample_entry = start == 0 ? 1 : 0;
+    return r;
+}
+// the tables and the sample arrays are those of the attached record, and the launch's positions trec_position ... trec_position + nsteps
+// are inside the position table (the caller clips a launch to it: tangent_record_steps)
+inline int tangent_record_launch_ok(trm_ctx* c, int nsteps, const std::string& who) {
+    if (c->trec.npos < 1 || c->trec.nlevels < 1 || c->trec.positions.empty() || !c->trec.d_tables || !c->d_trec[0] || !c->d_trec[1])
+        return fail(c, TRM_EINVAL, who + ": no record is attached, or its tables are not built");
+    if ((int)c->trec.positions.size() != c->trec.npos || (int)c->trec.levels.size() != c->trec.nlevels || c->trec.nlevels > c->Nz)
+        return fail(c, TRM_EINVAL, who + ": the sample arrays do not have the attached shape");
+    if (!record_table_covers(c->trec, c->trec_position, nsteps)) return fail(c, TRM_EINVAL, who + ": the launch leaves the record's position table");
+    return TRM_OK;
+}
+
 // ---- the dispatch over (hydraulics instance, lanes per column): launch(H, LPC), both std::integral_constant -----------------------
 template <class F> int by_instance(trm_ctx* c, F&& launch) {
     int rc = TRM_OK;
@@ -137,17 +181,21 @@ inline int derivative_program_id(int family, int hyd, int lpc, int generic, int 
 }
 
 // ---- one launch function per kernel template ----------------------------------------------------------------------------------------
-template <Ride R> int tangent_step(trm_ctx* c, double dt, int nsteps) {
-    const std::string who = ride_name("k_column_tangent", R, true);
+template <Ride R, bool RECORD> int tangent_step(trm_ctx* c, double dt, int nsteps) {
+    const std::string who = ride_name(RECORD ? "k_column_tangent_record" : "k_column_tangent", R, true);
     if (int rc = tangent_seeds_ok<R>(c, nsteps, who)) return rc;
+    if constexpr (RECORD)
+        if (int rc = tangent_record_launch_ok(c, nsteps, who)) return rc;
     const LaunchArgs<double>& la = launch_args<double>(c);
     const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
     TangentArgs<R> ta;
     fill_tangent(c, ta, ride_has_series(R));
     fill_tangent_seeds(c, ta);
+    const TangentRecordArgs r = RECORD ? tangent_record_args(c, c->trec_position) : TangentRecordArgs{};
     return by_instance(c, [&](auto h, auto lpc) {
         constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        hipLaunchKernelGGL((k_column_tangent<H, LPC, R>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, ta);
+        if constexpr (RECORD) hipLaunchKernelGGL((k_column_tangent_record<H, LPC, R>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, ta, r);
+        else hipLaunchKernelGGL((k_column_tangent<H, LPC, R>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, ta);
         TRM_HIP(c, hipGetLastError());
         c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_TANGENT, H, LPC, ta.generic,
                                                 (ride_has_bc(R) ? PROGRAM_BC_SEEDS : 0) | (ride_has_params(R) ? (int)TRM_PROGRAM_PARAMETERS : 0));
@@ -194,11 +242,14 @@ template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, i
 }
 
 // the backward launch of a block of the per-step tape (k_column_adjoint) or, CKPT, of one segment of the checkpointed tape
-// (k_column_adjoint_ckpt: the segment's states in dynamic LDS, 2 KiB per step and workgroup)
-template <bool CKPT, Ride R> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    const std::string who = ride_name(CKPT ? "k_column_adjoint_ckpt" : "k_column_adjoint", R, false);
+// (k_column_adjoint_ckpt: the segment's states in dynamic LDS, 2 KiB per step and workgroup); RECORD: their twins that read the attached
+// temperature record, `first` the taped position of the launch's first step
+template <bool CKPT, Ride R, bool RECORD> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, int first) {
+    const std::string who = ride_name(CKPT ? (RECORD ? "k_column_adjoint_ckpt_record" : "k_column_adjoint_ckpt") : (RECORD ? "k_column_adjoint_record" : "k_column_adjoint"), R, false);
     if (int rc = CKPT ? segment_range_ok(c, nsteps, slot, who) : tape_range_ok(c, nsteps, slot, who)) return rc;
     if (int rc = gradients_ok<R>(c, nsteps, who)) return rc;
+    if constexpr (RECORD)
+        if (int rc = record_launch_ok(c, nsteps, first, who)) return rc;
     const LaunchArgs<double>& la = launch_args<double>(c);
     const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_EULER);
     SweepArgs<CKPT, R> aa;
@@ -208,13 +259,16 @@ template <bool CKPT, Ride R> int adjoint_backward(trm_ctx* c, double dt, int nst
         aa.first = 0;
         aa.every = 1;
     }
+    const RecordArgs r = RECORD ? record_args(c, first) : RecordArgs{};
     const int bits = PROGRAM_BACKWARD | (CKPT ? PROGRAM_CHECKPOINTED : 0) | (ride_has_bc(R) ? PROGRAM_BC_GRADIENT : 0) | (ride_has_params(R) ? (int)TRM_PROGRAM_PARAMETERS : 0);
+    const size_t lds = CKPT ? (size_t)nsteps * TRM_STEP_BLOCK * sizeof(double) : 0;
     return by_instance(c, [&](auto h, auto lpc) {
         constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        if constexpr (CKPT)
-            hipLaunchKernelGGL((k_column_adjoint_ckpt<H, LPC, R>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), (size_t)nsteps * TRM_STEP_BLOCK * sizeof(double),
-                               c->stream, la.state, la.p, a, aa);
-        else hipLaunchKernelGGL((k_column_adjoint<H, LPC, R>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
+        const dim3 grid = column_grid(c, LPC), block(TRM_STEP_BLOCK);
+        if constexpr (CKPT && RECORD) hipLaunchKernelGGL((k_column_adjoint_ckpt_record<H, LPC, R>), grid, block, lds, c->stream, la.state, la.p, a, aa, r);
+        else if constexpr (CKPT) hipLaunchKernelGGL((k_column_adjoint_ckpt<H, LPC, R>), grid, block, lds, c->stream, la.state, la.p, a, aa);
+        else if constexpr (RECORD) hipLaunchKernelGGL((k_column_adjoint_record<H, LPC, R>), grid, block, lds, c->stream, la.state, la.p, a, aa, r);
+        else hipLaunchKernelGGL((k_column_adjoint<H, LPC, R>), grid, block, lds, c->stream, la.state, la.p, a, aa);
         TRM_HIP(c, hipGetLastError());
         c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT, H, LPC, aa.generic, bits);
         return (int)TRM_OK;

@@ -1071,344 +1071,6 @@ class ModelIntegrator:
             any(callable(v) for v in self.inputs.values())
 
 
-# the (variable, side) pairs whose boundary value the heat-only step reads, and the kinds that read it
-_BOUNDARY_DERIVATIVE_KINDS = {"temperature": ("value", "gradient"), "internal_energy": ("flux",)}
-
-
-def _series_driven(integ, var, side):
-    """The boundary condition on (var, side) is a device-resident time series: a FieldTimeSeries or a time-indexed raster source."""
-    value = integ.boundary_conditions.get((var, side), (None, None))[1]
-    return isinstance(value, FieldTimeSeries) or (isinstance(value, RasterInputSource) and not value.static)
-
-
-class _derivative_series:
-    """Sets the option `derivative_series` for the duration of a jvp / vjp call where a boundary series drives the run, and
-    `derivative_series_params` with it where the call carries thermal-parameter seeds or asks for their gradient (`params`)."""
-
-    def __init__(self, integ, params=False):
-        self.st = integ.state
-        self.wanted = any(_series_driven(integ, var, side) for var, side in integ.boundary_conditions)
-        self.params = self.wanted and bool(params)
-
-    def __enter__(self):
-        self.before = self.st.get_option("derivative_series")
-        self.before_params = self.st.get_option("derivative_series_params")
-        if self.wanted:
-            self.st.set_option("derivative_series", 1)
-        if self.params:
-            self.st.set_option("derivative_series_params", 1)
-        return self
-
-    def __exit__(self, *exc):
-        if self.params:
-            self.st.set_option("derivative_series_params", self.before_params)
-        if self.wanted:
-            self.st.set_option("derivative_series", self.before)
-        return False
-
-
-def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, d_params=None) -> dict:
-    """Forward-mode derivative of `run!(integ; steps)` with respect to the initial internal energy: the integrator is stepped `steps`
-    times with its own dt, its state carrying the tangent seeded by `d_internal_energy` ([Nz][Nh], or anything that broadcasts to
-    it).  Returns {"internal_energy", "temperature", "liquid_water_fraction"}: the tangents of those fields after the last step.
-    `d_boundary` = {(var, side): values}: seeds d(value) of boundary conditions, [Nh] or a scalar each -- a Value or a Gradient on
-    `temperature`, a Flux on `internal_energy` -- held over the run like the values themselves (trm_tangent_bc_upload).
-    For a pair driven by a `FieldTimeSeries` or a time-indexed raster source the seeds have the series' shape, [nt][Nh]: d(node value)
-    of every node of the record (trm_tangent_bc_series_upload); the option `derivative_series` is set for the duration of the call.
-    `d_params` = {name: value}: seeds on the thermal parameters (`k_mineral`, `c_water`, ...: trm_tangent_param_set).  They go together
-    with a boundary series, and with seeds on its nodes, in one run: the option `derivative_series_params` is set for the duration of
-    the call as well.
-    The heat-only SoilModel in fp64 with ForwardEuler and boundary conditions that are constant over the run or whole-record time
-    series (trm_step_tangent); callables, state functions and windowed sources are refused."""
-    if not isinstance(integ.timestepper, ForwardEuler):
-        raise ValueError("jvp: ForwardEuler only")
-    if integ._has_time_dependence() or integ._windowed():
-        raise ValueError("jvp: boundary conditions and inputs must be constant over the run")
-    st = integ.state
-    opened = not getattr(st, "_tangent_open", False)
-    if opened:
-        st.open_tangent()
-    try:
-        with _derivative_series(integ, params=d_params is not None):
-            st.set_tangent("internal_energy", d_internal_energy)
-            for (var, side), values in (d_boundary or {}).items():
-                if _series_driven(integ, var, side):
-                    st.set_bc_series_tangent(var, side, values)
-                else:
-                    st.set_bc_tangent(var, side, values)
-            if d_params is not None:
-                st.set_param_tangent(d_params)
-            st.step_tangent(integ.timestepper.dt, int(steps))
-            return {name: st.tangent(name) for name in _capi.TANGENT}
-    finally:
-        if opened:
-            st.close_tangent()
-
-
-def record_jvp(integ: ModelIntegrator, positions, levels, d_internal_energy=0.0, d_boundary=None, d_params=None, steps=None):
-    """`jvp` sampled at a record's positions: the integrator is stepped `steps` times (None: to the last position) with its own dt,
-    and the temperature and its tangent are stored on `levels` behind the steps `positions` lists (step counts, strictly increasing,
-    0 = the initial state) inside the tangent launches -- one attach and one step_tangent (trm_tangent_record_attach).  Returns
-    (T, dT), each [npos][nlevels][Nh]: the model's samples and J v at the samples for the seeds v = (`d_internal_energy`,
-    `d_boundary`, `d_params`) of `jvp`.  Zero seeds give the record the model itself produces.  State and clock end where `run`
-    leaves them.  Coverage, refusals and option handling of `jvp`."""
-    if not isinstance(integ.timestepper, ForwardEuler):
-        raise ValueError("record_jvp: ForwardEuler only")
-    if integ._has_time_dependence() or integ._windowed():
-        raise ValueError("record_jvp: boundary conditions and inputs must be constant over the run")
-    positions = [int(q) for q in np.asarray(positions).reshape(-1)]
-    if not positions or positions[0] < 0 or any(b <= a for a, b in zip(positions, positions[1:])):
-        raise ValueError("record_jvp: the positions must be >= 0 and strictly increasing, one sample per position")
-    steps = positions[-1] if steps is None else int(steps)
-    st = integ.state
-    opened = not getattr(st, "_tangent_open", False)
-    if opened:
-        st.open_tangent()
-    attached = False
-    try:
-        with _derivative_series(integ, params=d_params is not None):
-            st.set_tangent("internal_energy", d_internal_energy)
-            for (var, side), values in (d_boundary or {}).items():
-                if _series_driven(integ, var, side):
-                    st.set_bc_series_tangent(var, side, values)
-                else:
-                    st.set_bc_tangent(var, side, values)
-            if d_params is not None:
-                st.set_param_tangent(d_params)
-            st.attach_tangent_record(positions, levels)
-            attached = True
-            st.step_tangent(integ.timestepper.dt, steps)
-            return st.tangent_record("temperature"), st.tangent_record("tangent")
-    finally:
-        if opened:
-            st.close_tangent()
-        elif attached:
-            st.detach_tangent_record()
-
-
-def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=None, liquid_water_fraction=None,
-        checkpoint_every=None, wrt_boundary=False, wrt_params=False):
-    """Reverse-mode derivative of `run!(integ; steps)`: the integrator is stepped `steps` times with its own dt (state and clock end
-    where `run` leaves them), then the given cotangents of the final temperature, internal energy and liquid water fraction ([Nz][Nh],
-    or anything that broadcasts to it; None: zero) are pulled back.  Returns dL/dU_0 as [Nz][Nh], L the sum of the three inner
-    products.  One tape slot per step (trm_step_record, trm_adjoint_backward); with `checkpoint_every` = K one slot per K steps, the
-    states in between formed again by the backward sweep -- the same gradient bit for bit.  The coverage and refusals of `jvp`.
-    With `wrt_boundary` it returns (dL/dU_0, {(var, side): dL/d(value) as [Nh]}) for the boundary conditions of the integrator whose
-    value the run reads -- a Value or a Gradient on `temperature`, a Flux on `internal_energy` -- from the same sweep
-    (trm_adjoint_bc_open); a pair driven by a `FieldTimeSeries` or a time-indexed raster source gets dL/d(node value) as [nt][Nh], the
-    shape of its record (trm_adjoint_bc_series_download; the option `derivative_series` is set for the duration of the call).
-    With `wrt_params` it appends {name: dL/d(parameter) as [Nh]} for the ten thermal parameters, each column's
-    share (trm_adjoint_param_open): (dL/dU_0, params), or (dL/dU_0, boundary, params) with `wrt_boundary` as well.  On a run driven by
-    a boundary series too: one sweep gives dL/dU_0, the node gradients and the ten parameter gradients (the option
-    `derivative_series_params` is set for the duration of the call)."""
-    if not isinstance(integ.timestepper, ForwardEuler):
-        raise ValueError("vjp: ForwardEuler only")
-    if integ._has_time_dependence() or integ._windowed():
-        raise ValueError("vjp: boundary conditions and inputs must be constant over the run")
-    st = integ.state
-    steps = int(steps)
-    opened = not getattr(st, "_adjoint_open", False)
-    if checkpoint_every is None:
-        if opened or st.adjoint_checkpoints() != (0, 0, max(steps, 1)):
-            st.open_adjoint(max(steps, 1))
-    else:
-        K = int(checkpoint_every)
-        slots = max(-(-steps // max(K, 1)), 1)
-        if opened or st.adjoint_checkpoints() != (K, 0, slots):
-            st.open_adjoint(slots, K)
-    try:
-        with _derivative_series(integ, params=wrt_params):
-            st.step_record(integ.timestepper.dt, steps)
-            for name, w in (("internal_energy", internal_energy), ("temperature", temperature), ("liquid_water_fraction", liquid_water_fraction)):
-                st.set_cotangent(name, 0.0 if w is None else w)
-            if wrt_boundary:
-                st.open_bc_gradient()
-            if wrt_params:
-                st.open_param_gradient()
-            st.adjoint_backward()
-            g = st.cotangent("internal_energy")
-            if not wrt_boundary and not wrt_params:
-                return g
-            out = [g]
-            if wrt_boundary:
-                pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
-                out.append({(var, side): st.bc_series_gradient(var, side) if _series_driven(integ, var, side) else st.bc_gradient(var, side)
-                            for var, side in pairs})
-            if wrt_params:
-                out.append({name: st.param_gradient(name) for name in _capi.THERMAL_PARAMS})
-            return tuple(out)
-    finally:
-        if opened:
-            st.close_adjoint()
-
-
-class TemperatureRecord:
-    """A temperature record as a borehole logger leaves it: `values[nobs][nlevels][Nh]` at the step counts `steps` (non-decreasing,
-    0 = the initial state) on the rows `levels` of the host layout (row 0 = bottom layer, strictly increasing).  `weight` >= 0
-    broadcasts to the shape of `values` (None: 1); a NaN in `values` is a gap and counts for nothing."""
-
-    def __init__(self, steps, levels, values, weight=None):
-        self.steps = [int(s) for s in np.asarray(steps).reshape(-1)]
-        self.levels = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
-        self.values = np.asarray(values, dtype=np.float64)
-        if self.values.ndim != 3 or self.values.shape[:2] != (len(self.steps), self.levels.size):
-            raise ValueError("TemperatureRecord: values must be [len(steps)][len(levels)][Nh]")
-        if any(s < 0 for s in self.steps) or any(b < a for a, b in zip(self.steps, self.steps[1:])):
-            raise ValueError("TemperatureRecord: steps must be >= 0 and non-decreasing")
-        self.weight = None if weight is None else np.broadcast_to(np.asarray(weight, dtype=np.float64), self.values.shape)
-
-
-def _tape_slots(positions, steps, K):
-    """Slots a run of `steps` taped steps observed at `positions` takes: one per step, or, checkpointed every K, ceil(stretch / K) over
-    the stretches between observed positions (an observation closes the open segment)."""
-    if K is None:
-        return max(steps, 1)
-    cuts = sorted({0, steps} | {p for p in positions if 0 < p < steps})
-    return max(sum(-(-(b - a) // K) for a, b in zip(cuts, cuts[1:])), 1)
-
-
-def misfit_gradient(integ: ModelIntegrator, record: TemperatureRecord, steps=None, checkpoint_every=None, wrt_boundary=False,
-                    wrt_params=False):
-    """The misfit L = sum_k sum_levels 1/2 w (T_{steps_k} - values_k)^2 of `run!(integ; steps)` to a temperature record, per column,
-    and its gradient from one forward run and one backward sweep: the integrator is stepped `steps` times (None: to the last
-    observation) with its own dt, the record's samples registered where the run reaches their step counts
-    (trm_adjoint_observe_misfit), then everything is pulled back at once.  Returns (L as [Nh], dL/dU_0 as [Nz][Nh]) and behind them
-    what `vjp` appends for `wrt_boundary` and `wrt_params`.  The tape is sized here: one slot per step, or with `checkpoint_every` = K
-    the sum of ceil(stretch / K) over the stretches between observed positions.  Coverage, refusals and option handling of `vjp`."""
-    if not isinstance(integ.timestepper, ForwardEuler):
-        raise ValueError("misfit_gradient: ForwardEuler only")
-    if integ._has_time_dependence() or integ._windowed():
-        raise ValueError("misfit_gradient: boundary conditions and inputs must be constant over the run")
-    st = integ.state
-    last = record.steps[-1] if record.steps else 0
-    steps = last if steps is None else int(steps)
-    if steps < last:
-        raise ValueError("misfit_gradient: the record has observations behind the last step")
-    K = None if checkpoint_every is None else int(checkpoint_every)
-    opened = not getattr(st, "_adjoint_open", False)
-    st.open_adjoint(_tape_slots(record.steps, steps, K), K)
-    try:
-        with _derivative_series(integ, params=wrt_params):
-            dt, at = integ.timestepper.dt, 0
-            for k, s in enumerate(record.steps):
-                if s > at:
-                    st.step_record(dt, s - at)
-                    at = s
-                st.observe_misfit(record.levels, record.values[k], None if record.weight is None else record.weight[k])
-            if steps > at:
-                st.step_record(dt, steps - at)
-            for name in ("internal_energy", "temperature", "liquid_water_fraction"):
-                st.set_cotangent(name, 0.0)
-            if wrt_boundary:
-                st.open_bc_gradient()
-            if wrt_params:
-                st.open_param_gradient()
-            out = [st.misfit()]
-            st.adjoint_backward()
-            out.append(st.cotangent("internal_energy"))
-            if wrt_boundary:
-                pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
-                out.append({(var, side): st.bc_series_gradient(var, side) if _series_driven(integ, var, side) else st.bc_gradient(var, side)
-                            for var, side in pairs})
-            if wrt_params:
-                out.append({name: st.param_gradient(name) for name in _capi.THERMAL_PARAMS})
-            return tuple(out)
-    finally:
-        if opened:
-            st.close_adjoint()
-
-
-def record_gradient(integ: ModelIntegrator, record: TemperatureRecord, steps=None, checkpoint_every=None, wrt_boundary=False,
-                    wrt_params=False):
-    """What `misfit_gradient` returns, from a record that is attached once and read inside the backward launches
-    (trm_adjoint_observe_record): one attach, one step_record(dt, steps) and one sweep.  No sample is a launch boundary or takes a
-    slot: the tape has `steps` slots, or ceil(steps / K) with `checkpoint_every` = K, however dense the record.  `record.steps` must
-    be strictly increasing (one sample per position), otherwise ValueError.  Coverage, refusals and option handling of `vjp`."""
-    if not isinstance(integ.timestepper, ForwardEuler):
-        raise ValueError("record_gradient: ForwardEuler only")
-    if integ._has_time_dependence() or integ._windowed():
-        raise ValueError("record_gradient: boundary conditions and inputs must be constant over the run")
-    if not record.steps or any(b <= a for a, b in zip(record.steps, record.steps[1:])):
-        raise ValueError("record_gradient: the record's steps must be strictly increasing, one sample per position")
-    st = integ.state
-    last = record.steps[-1]
-    steps = last if steps is None else int(steps)
-    if steps < last:
-        raise ValueError("record_gradient: the record has observations behind the last step")
-    K = None if checkpoint_every is None else int(checkpoint_every)
-    opened = not getattr(st, "_adjoint_open", False)
-    st.open_adjoint(_tape_slots([], steps, K), K)
-    try:
-        with _derivative_series(integ, params=wrt_params):
-            st.attach_record(record.steps, record.levels, record.values, record.weight)
-            st.step_record(integ.timestepper.dt, steps)
-            for name in ("internal_energy", "temperature", "liquid_water_fraction"):
-                st.set_cotangent(name, 0.0)
-            if wrt_boundary:
-                st.open_bc_gradient()
-            if wrt_params:
-                st.open_param_gradient()
-            st.adjoint_backward()
-            out = [st.record_misfit(), st.cotangent("internal_energy")]
-            if wrt_boundary:
-                pairs = [(var, side) for (var, side), (kind, _) in integ.boundary_conditions.items() if kind in _BOUNDARY_DERIVATIVE_KINDS.get(var, ())]
-                out.append({(var, side): st.bc_series_gradient(var, side) if _series_driven(integ, var, side) else st.bc_gradient(var, side)
-                            for var, side in pairs})
-            if wrt_params:
-                out.append({name: st.param_gradient(name) for name in _capi.THERMAL_PARAMS})
-            return tuple(out)
-    finally:
-        if opened:
-            st.close_adjoint()
-        else:
-            st.detach_record()
-
-
-def _normal_equation_sums(T, S, values, weight):
-    """(misfit [Nh], b [q][Nh], A [q][q][Nh]) of the samples T [npos][nlevels][Nh], their sensitivities S [q][npos][nlevels][Nh] and a
-    record: r = T - values, misfit = sum 1/2 w r r, b_q = sum w s_q r, A_qq' = sum w s_q s_q'.  float64, positions ascending, levels in
-    list order, one term at a time; a NaN sample or a weight that is not > 0 counts for nothing."""
-    nq, Nh = len(S), T.shape[2]
-    misfit, b, A = np.zeros(Nh), np.zeros((nq, Nh)), np.zeros((nq, nq, Nh))
-    for k in range(T.shape[0]):
-        for j in range(T.shape[1]):
-            w = np.ones(Nh) if weight is None else np.asarray(weight[k, j], dtype=np.float64)
-            r = T[k, j] - values[k, j]
-            use = (w > 0.0) & ~np.isnan(r)
-            w, r = np.where(use, w, 0.0), np.where(use, r, 0.0)
-            misfit = misfit + 0.5 * w * r * r
-            for q in range(nq):
-                sq = np.where(use, S[q][k, j], 0.0)
-                b[q] = b[q] + w * sq * r
-                for q2 in range(nq):
-                    A[q, q2] = A[q, q2] + w * sq * np.where(use, S[q2][k, j], 0.0)
-    return misfit, b, A
-
-
-def record_normal_equations(integ: ModelIntegrator, record: TemperatureRecord, params):
-    """The Gauss-Newton normal equations of the misfit of `run!(integ; steps = record.steps[-1])` to a temperature record in the thermal
-    parameters `params` (names of `jvp`'s `d_params`), per column: (misfit [Nh], b [q][Nh], A [q][q][Nh]) with r = T - values,
-    misfit = sum 1/2 w r^2, b_q = sum w s_q r (the gradient of the misfit), A_qq' = sum w s_q s_q', s_q = dT/d(parameter q) at the
-    samples.  One `record_jvp` with a unit seed per name; state and clock are restored in between and afterwards
-    (`checkpoint` / `restore`), so the integrator is left where it was.  The sums run in float64 on the host, positions ascending,
-    levels in list order, one term at a time; a NaN sample or a weight that is not > 0 counts for nothing.  `record.steps` must be
-    strictly increasing."""
-    if not record.steps or any(b <= a for a, b in zip(record.steps, record.steps[1:])):
-        raise ValueError("record_normal_equations: the record's steps must be strictly increasing, one sample per position")
-    params = list(params)
-    if not params:
-        raise ValueError("record_normal_equations: no parameter")
-    start = checkpoint(integ)
-    T, S = None, []
-    for name in params:
-        restore(integ, start)
-        T_q, dT_q = record_jvp(integ, record.steps, record.levels, d_params={name: 1.0})
-        T = T_q if T is None else T
-        S.append(dT_q)
-    restore(integ, start)
-    return _normal_equation_sums(T, S, record.values, record.weight)
-
-
 def current_time(integrator: ModelIntegrator) -> float:
     return integrator.state.clock()[0]
 
@@ -1691,3 +1353,15 @@ def zspacings(obj) -> np.ndarray:
     grid = getattr(obj, "grid", obj)
     grid = getattr(grid, "grid", grid) if not hasattr(grid, "thickness") else grid
     return np.asarray(grid.thickness, dtype=np.float64)[::-1].copy()
+
+
+# The derivative drivers live in derivatives.py, which imports this module; their names stay importable from here, as they were
+_IN_DERIVATIVES = ("jvp", "record_jvp", "vjp", "TemperatureRecord", "misfit_gradient", "record_gradient", "record_normal_equations",
+                   "_series_driven", "_derivative_series", "_tape_slots", "_normal_equation_sums")
+
+
+def __getattr__(name):
+    if name in _IN_DERIVATIVES:
+        from . import derivatives
+        return getattr(derivatives, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

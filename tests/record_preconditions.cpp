@@ -1,5 +1,5 @@
 // The host-side bookkeeping of attached temperature records (trm_host.hpp) on contexts built by hand: no GPU call.  The level and
-// position tables the backward kernels index, the slot counting of the checkpointed tape with a record attached (no position closes a
+// position tables the backward kernels index and the RecordTable that holds them (shared with the tangent records), the slot counting of the checkpointed tape with a record attached (no position closes a
 // segment), and every refusal of the attach, the mixing rules, the sweep and the downloads with its text.
 // Built with the host sanitizers and run by `make -C terrarium.jl_amd/csrc check-preconditions` (cross-compiles; runs without a GPU).
 #include "trm_host.hpp"
@@ -74,10 +74,8 @@ int main() {
     c.observations.clear();
     assert(record_excludes_observations(&c, "trm_adjoint_observe") == TRM_OK);
     // ---- what an attach leaves (attach_record, trm_derivative_api.hip), and what follows from it
-    c.rec_positions.assign(positions, positions + 4);
-    c.rec_levels.assign(levels, levels + 3);
-    c.rec_npos = 4;
-    c.rec_nlevels = 3;
+    record_table_attach(c.rec, 4, positions, 3, levels);
+    assert(c.rec.npos == 4 && c.rec.nlevels == 3 && c.rec.entries == 0 && c.rec.host.empty());
     assert(refused(record_attach_ok(&c, 4, positions, 3, levels, observed.data(), nullptr, who), "a record is attached already (trm_adjoint_record_detach)"));
     assert(refused(record_excludes_observations(&c, "trm_adjoint_observe"), "trm_adjoint_observe: a temperature record is attached"));
     assert(refused(record_excludes_observations(&c, "trm_adjoint_observe_misfit"), "the two paths do not mix"));
@@ -92,7 +90,7 @@ int main() {
     c.d_rec_owned = &dummy;
     assert(record_bytes(&c) == 2 * cells + 5 * 8 + 6 * 4);
     c.d_rec_weight = &dummy;
-    c.rec_table_n = 6;
+    record_table_build(c.rec, c.Nz, 6);
     assert(record_bytes(&c) == 3 * cells + 5 * 8 + (6 + 7) * 4);
     c.d_rec_owned = nullptr;
     // ---- slot counting: K = 4, the run of the tests in the pieces 3 + 2 + 1 -- no position closes a segment
@@ -112,8 +110,8 @@ int main() {
     // a dense record on 24 steps, K = 8: three slots
     trm_ctx d;
     d.ckpt_interval = 8;
-    d.rec_npos = 25;
-    for (int p = 0; p <= 24; ++p) d.rec_positions.push_back(p);
+    d.rec.npos = 25;
+    for (int p = 0; p <= 24; ++p) d.rec.positions.push_back(p);
     assert(tape_slots_needed(&d, dt, 24) == 3);
     tape_append(&d, dt, 24);
     assert(tape_slots_used(&d) == 3 && record_fits_tape(&d, taped_steps(&d), "trm_adjoint_backward") == TRM_OK);
@@ -122,6 +120,43 @@ int main() {
     assert(record_fits_tape(&e, 0, "trm_adjoint_backward") == TRM_OK && record_bytes(&e) == 0);
     e.d_adj[0] = &dummy;
     assert(refused(record_results_ok(&e, &dummy, "trm_adjoint_record_misfit_download"), "no record is attached (trm_adjoint_observe_record)"));
+    // ---- the position table both records share (RecordTable), at the smallest shapes: Nz = 2 with one level.  The device copy is stood
+    // in for by a host copy made where record_tables (trm_derivative_api.hip) uploads, so every read below is a read the sanitizer sees
+    trm_ctx s;
+    s.Nz = 2;
+    s.Nh = 1;
+    s.d_adj[0] = &dummy;
+    const int32_t top[1] = {1}, ends[2] = {0, 3};
+    assert(record_attach_ok(&s, 2, ends, 1, top, observed.data(), nullptr, who) == TRM_OK);
+    record_table_attach(s.rec, 2, ends, 1, top);
+    assert(record_bytes(&s) == 2 * 8 + 8 + 2 * 4 && !record_table_covers(s.rec, 0, 0));           // (no position entry before the first sweep)
+    // a sweep over a tape of 3 steps: the record's last position is the tape's length
+    assert(record_fits_tape(&s, 3, "trm_adjoint_backward") == TRM_OK);
+    record_table_build(s.rec, s.Nz, 3);
+    assert(s.rec.entries == 4 && (s.rec.host == std::vector<int32_t>{-1, 0, /* positions */ 0, -1, -1, 1}) && record_bytes(&s) == 2 * 8 + 8 + (2 + 4) * 4);
+    std::vector<int32_t> device3 = s.rec.host;
+    s.rec.d_tables = (double*)device3.data();
+    assert(record_row_of_level(s.rec)[1] == 0 && record_row_of_position(s.rec, s.Nz, 0)[0] == 0 && record_row_of_position(s.rec, s.Nz, 3)[0] == 1);
+    assert(record_table_covers(s.rec, 0, 3) && record_table_covers(s.rec, 3, 0) && record_table_covers(s.rec, 1, 2));
+    assert(!record_table_covers(s.rec, 0, 4) && !record_table_covers(s.rec, 4, 0) && !record_table_covers(s.rec, -1, 1) && !record_table_covers(s.rec, 0, -1));
+    // a second sweep, over 5 steps: built again.  The staging copy is replaced, which is why record_tables waits for the stream on either
+    // side of its upload; the copy the device holds is untouched until the caller releases it
+    s.rec.d_tables = nullptr;
+    record_table_build(s.rec, s.Nz, 5);
+    assert(s.rec.entries == 6 && s.rec.host.size() == 2 + 6 && (device3 == std::vector<int32_t>{-1, 0, 0, -1, -1, 1}));
+    std::vector<int32_t> device5 = s.rec.host;
+    s.rec.d_tables = (double*)device5.data();
+    assert(record_table_covers(s.rec, 0, 5) && !record_table_covers(s.rec, 0, 6) && record_row_of_position(s.rec, s.Nz, 0)[3] == 1 && record_row_of_position(s.rec, s.Nz, 5)[0] == -1);
+    // drop, then a second attach: a record of position 0 alone on a tape of 0 steps -- one entry, the fold's
+    s.rec.d_tables = nullptr;
+    assert(refused(record_attach_ok(&s, 1, ends, 1, top, observed.data(), nullptr, who), "a record is attached already"));
+    record_table_drop(s.rec);
+    assert(s.rec.npos == 0 && s.rec.nlevels == 0 && s.rec.entries == 0 && s.rec.host.empty() && s.rec.positions.empty() && s.rec.levels.empty() && record_bytes(&s) == 0);
+    assert(record_attach_ok(&s, 1, ends, 1, top, observed.data(), nullptr, who) == TRM_OK);
+    record_table_attach(s.rec, 1, ends, 1, top);
+    assert(record_fits_tape(&s, 0, "trm_adjoint_backward") == TRM_OK);
+    record_table_build(s.rec, s.Nz, 0);
+    assert(s.rec.entries == 1 && (s.rec.host == std::vector<int32_t>{-1, 0, 0}) && record_table_covers(s.rec, 0, 0) && !record_table_covers(s.rec, 0, 1));
     std::printf("record preconditions ok\n");
     return 0;
 }

@@ -1,8 +1,8 @@
-// The host side of tangent records (trm_host.hpp, trm_launch_tangent_record.inl) on contexts built by hand: no GPU call.  The tables the
+// The host side of tangent records (trm_host.hpp, trm_launch_derivative.inl) on contexts built by hand: no GPU call.  The tables the
 // kernel indexes, every refusal of the attach with its text, how trm_step_tangent cuts its launches at the last position, and the
 // launcher's preconditions -- no launch may index the position table outside [0, last position].
 // Built with the host sanitizers and run by `make -C terrarium.jl_amd/csrc check-preconditions` (cross-compiles; runs without a GPU).
-#include "trm_launch_tangent_record.inl"
+#include "trm_launch_derivative.inl"
 #include <cassert>
 #include <cstdio>
 
@@ -22,11 +22,18 @@ using namespace trmh;
 static bool refused(int rc, const char* text) { return rc == TRM_EINVAL && last.find(text) != std::string::npos; }
 
 int main() {
-    // ---- the tables: row_of_level[Nz], then row_of_position[last + 1]
-    const std::vector<int32_t> t = tangent_record_tables(6, {0, 2, 5}, {0, 3, 5, 6});
-    assert((t == std::vector<int32_t>{0, -1, 1, -1, -1, 2, /* positions */ 0, -1, -1, 1, -1, 2, 3}));
-    assert((tangent_record_tables(2, {1}, {0}) == std::vector<int32_t>{-1, 0, 0, -1}));       // (position 0 alone: the entry's sample, and a step that has none)
-    assert((tangent_record_tables(1, {0}, {2}) == std::vector<int32_t>{0, -1, -1, 0}));       // (no sample at the entry)
+    // ---- the tables as an attach builds them: row_of_level[Nz], then row_of_position[last + 1]
+    auto tables = [](int Nz, std::vector<int> levels, std::vector<int> positions) {
+        RecordTable t;
+        t.levels = levels;
+        t.positions = positions;
+        record_table_build(t, Nz, tangent_record_limit(positions));
+        assert(t.entries == tangent_record_limit(positions) + 1 && t.host.size() == (size_t)(Nz + t.entries));
+        return t.host;
+    };
+    assert((tables(6, {0, 2, 5}, {0, 3, 5, 6}) == std::vector<int32_t>{0, -1, 1, -1, -1, 2, /* positions */ 0, -1, -1, 1, -1, 2, 3}));
+    assert((tables(2, {1}, {0}) == std::vector<int32_t>{-1, 0, 0, -1}));       // (position 0 alone: the entry's sample, and a step that has none)
+    assert((tables(1, {0}, {2}) == std::vector<int32_t>{0, -1, -1, 0}));       // (no sample at the entry)
 
     // ---- the attach on a context of Nz = 6, Nh = 5
     double dummy[4 * 3 * 5] = {};
@@ -60,32 +67,29 @@ int main() {
     assert(refused(tangent_record_launch_ok(&c, 1, "k"), "k: no record is attached, or its tables are not built"));
 
     // ---- what an attach leaves (trm_tangent_record_attach, trm_derivative_api.hip)
-    c.trec_positions.assign(positions, positions + 4);
-    c.trec_levels.assign(levels, levels + 3);
-    c.trec_npos = 4;
-    c.trec_nlevels = 3;
-    c.trec_table_host = tangent_record_tables(c.Nz, c.trec_levels, c.trec_positions);
+    record_table_attach(c.trec, 4, positions, 3, levels);
+    record_table_build(c.trec, c.Nz, tangent_record_limit(c.trec.positions));
     assert(refused(tangent_record_attach_ok(&c, 4, positions, 3, levels, who), "a record is attached already (trm_tangent_record_detach)"));
     assert(tangent_record_attached(&c, "trm_tangent_record_detach") == TRM_OK);
     assert(tangent_record_bytes(&c) == 2 * 4 * 3 * 5 * 8 + (6 + 7) * 4);
     // the launcher without device arrays
     assert(refused(tangent_record_launch_ok(&c, 1, "k"), "no record is attached, or its tables are not built"));
-    c.d_trec_tables = (double*)c.trec_table_host.data();
+    c.trec.d_tables = (double*)c.trec.host.data();
     c.d_trec[0] = dummy;
     assert(refused(tangent_record_launch_ok(&c, 1, "k"), "no record is attached, or its tables are not built"));
     c.d_trec[1] = dummy;
     assert(tangent_record_launch_ok(&c, 1, "k") == TRM_OK);
     // sample arrays of another shape than the attached one
-    c.trec_nlevels = 2;
+    c.trec.nlevels = 2;
     assert(refused(tangent_record_launch_ok(&c, 1, "k"), "k: the sample arrays do not have the attached shape"));
-    c.trec_nlevels = 3;
-    c.trec_npos = 5;
+    c.trec.nlevels = 3;
+    c.trec.npos = 5;
     assert(refused(tangent_record_launch_ok(&c, 1, "k"), "the sample arrays do not have the attached shape"));
-    c.trec_npos = 4;
+    c.trec.npos = 4;
 
     // ---- the launches of trm_step_tangent: up to 4 steps each, cut at the last position (6); every launch the launcher accepts reads
     // the entries start ... start + nsteps of a table of last + 1 entries, which the walk below does under the sanitizer
-    const int32_t* rows = c.trec_table_host.data() + c.Nz;
+    const int32_t* rows = c.trec.host.data() + c.Nz;
     const int total = 11, spl = 4;
     std::vector<int> recorded_launches, free_launches, sampled;
     for (int n = 0, m; n < total; n += m) {
@@ -95,7 +99,7 @@ int main() {
             m = recorded;
             assert(tangent_record_launch_ok(&c, m, "k") == TRM_OK);
             const TangentRecordArgs r = tangent_record_args(&c, c.trec_position);
-            assert(r.row_of_level == c.trec_table_host.data() && r.row_of_position == rows + c.trec_position && r.nlevels == 3);
+            assert(r.row_of_level == c.trec.host.data() && r.row_of_position == rows + c.trec_position && r.nlevels == 3);
             assert(r.sample_entry == (c.trec_position == 0 ? 1 : 0) && r.T == dummy && r.dT == dummy);
             if (r.sample_entry && r.row_of_position[0] >= 0) sampled.push_back(r.row_of_position[0]);
             for (int s = 0; s < m; ++s)
@@ -126,11 +130,11 @@ int main() {
     trm_ctx z;
     z.Nz = 2;
     z.Nh = 1;
-    z.trec_npos = z.trec_nlevels = 1;
-    z.trec_positions = {0};
-    z.trec_levels = {1};
-    z.trec_table_host = tangent_record_tables(z.Nz, z.trec_levels, z.trec_positions);
-    z.d_trec_tables = (double*)z.trec_table_host.data();
+    const int32_t entry[1] = {0}, top[1] = {1};
+    record_table_attach(z.trec, 1, entry, 1, top);
+    record_table_build(z.trec, z.Nz, tangent_record_limit(z.trec.positions));
+    assert(z.trec.entries == 2);
+    z.trec.d_tables = (double*)z.trec.host.data();
     z.d_trec[0] = z.d_trec[1] = dummy;
     assert(tangent_record_steps(&z, 3) == 1 && tangent_record_launch_ok(&z, 1, "k") == TRM_OK && tangent_record_bytes(&z) == 2 * 8 + (2 + 2) * 4);
     const TangentRecordArgs rz = tangent_record_args(&z, 0);

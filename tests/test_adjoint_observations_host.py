@@ -61,7 +61,7 @@ def test_python_interface():
 
 
 def test_temperature_record_and_tape_sizing():
-    from terrarium_jl_amd.integrator import _tape_slots
+    from terrarium_jl_amd.derivatives import _tape_slots
     rec = trm.TemperatureRecord([0, 3, 5, 6], [0, 2], np.zeros((4, 2, 5)), weight=2.0)
     assert rec.steps == [0, 3, 5, 6] and rec.levels.dtype == np.int32 and rec.weight.shape == (4, 2, 5)
     with pytest.raises(ValueError):

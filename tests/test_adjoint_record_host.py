@@ -68,7 +68,7 @@ def test_python_interface():
     assert names(D.observe_misfit) == ["self", "levels", "observed", "weight"]
     assert names(trm.vjp) == ["integ", "steps", "temperature", "internal_energy", "liquid_water_fraction", "checkpoint_every", "wrt_boundary", "wrt_params"]
     assert names(D.open_adjoint) == ["self", "capacity", "checkpoint_every"]
-    from terrarium_jl_amd.integrator import _tape_slots
+    from terrarium_jl_amd.derivatives import _tape_slots
     assert _tape_slots([0, 3, 5, 6], 6, 4) == 3 and _tape_slots([], 6, 4) == 2      # (the per-position path's count, and the attached record's)
 
 

@@ -48,8 +48,8 @@ def test_the_ride_is_built_and_the_exports_are_what_they_were():
     sources = {os.path.splitext(os.path.basename(f))[0] for f in glob.glob(os.path.join(CSRC, "*.hip"))}
     assert set(UNITS) <= sources                                            # (the Makefile compiles every *.hip of the directory)
     assert "$(wildcard *.hip)" in open(os.path.join(CSRC, "Makefile")).read()
-    instance = {UNITS[0]: r"template int tangent_step<RIDE_PARAM_SERIES>", UNITS[1]: r"template int adjoint_backward<false, RIDE_PARAM_SERIES>",
-                UNITS[2]: r"template int adjoint_backward<true, RIDE_PARAM_SERIES>"}
+    instance = {UNITS[0]: r"template int tangent_step<RIDE_PARAM_SERIES, NO_RECORD>", UNITS[1]: r"template int adjoint_backward<false, RIDE_PARAM_SERIES, NO_RECORD>",
+                UNITS[2]: r"template int adjoint_backward<true, RIDE_PARAM_SERIES, NO_RECORD>"}
     for unit, pattern in instance.items():
         assert re.search(pattern, open(os.path.join(CSRC, unit + ".hip")).read()), unit
     # the library holds the kernels of the three units: the three families instantiated at RIDE_PARAM_SERIES (the fifth value of

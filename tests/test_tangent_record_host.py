@@ -13,7 +13,7 @@ import pytest
 
 import tangent_record as TR
 import terrarium_jl_amd as trm
-from terrarium_jl_amd.integrator import _normal_equation_sums
+from terrarium_jl_amd.derivatives import _normal_equation_sums
 from test_gpu_derivative_edges import BROKEN, FACTOR, STEPS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,7 +39,7 @@ def test_the_five_rides_are_built():
     blob = open(trm._capi.LIB_PATH, "rb").read()
     for n, (suffix, ride) in enumerate(rides.items()):
         text = open(os.path.join(csrc, f"trm_launch_column_tangent_record{suffix}.hip")).read()
-        assert f"template int tangent_record_step<{ride}>" in text, suffix
+        assert f"template int tangent_step<{ride}, WITH_RECORD>" in text, suffix
         # the library holds the kernel at this ride in both lane layouts (<HYD, LPC, (trm::Ride)n> is spelled ILi<h>ELi<lpc>ELNS_4RideE<n>E)
         for lpc in (32, 64):
             assert re.search(b"23k_column_tangent_recordILi\\d+ELi%dELNS_4RideE%dE" % (lpc, n), blob), (suffix, lpc)
