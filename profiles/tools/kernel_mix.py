@@ -1,4 +1,4 @@
-"""Instruction mix of kernels in a device assembly listing:  hipcc ... -S --cuda-device-only -o /tmp/trm.s terrarium_hip.hip
+"""Instruction mix of kernels in a device assembly listing:  hipcc ... -S --cuda-device-only -o /tmp/trm.s trm_launch_vegetation.hip
    python profiles/tools/kernel_mix.py /tmp/trm.s k_surface_vegId"""
 import collections
 import re

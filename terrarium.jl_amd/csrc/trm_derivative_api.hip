@@ -1,7 +1,7 @@
 // trm_derivative_api.hip -- the derivative entry points of the C ABI (include/terrarium_hip.h): forward-mode tangents (trm_tangent_*,
 // trm_step_tangent; trm_column_tangent.hpp) and reverse-mode gradients (trm_adjoint_*, trm_step_record, trm_adjoint_backward;
 // trm_column_adjoint.hpp) of the heat-only fp64 run, what they refuse, and the derivative buffers of the context.  Host code alone: the
-// kernels are launched by the instantiations of trm_launch_derivative.inl, the transpositions by upload_3d / download_3d (terrarium_hip.hip).
+// kernels are launched by the instantiations of trm_launch_derivative.inl, the transpositions by upload_3d / download_3d (trm_field_io_api.hip).
 #include "trm_host.hpp"
 
 using namespace trm;

@@ -3,6 +3,7 @@
 // prune the combinations without an instance with `if constexpr` inside it.  A value outside a list reaches NO instance: the helper
 // returns false and the launcher refuses.  Plain C++17, no HIP call (tests/launch_dispatch.cpp).
 #pragma once
+#include "../../include/terrarium_hip.h"
 #include "trm_kernels.hpp"
 
 #include <cstddef>
@@ -29,6 +30,10 @@ template <class F> bool by_bool(bool b, F&& f) {
     else f(std::false_type{});
     return true;
 }
+// the number format of a context (trm_ctx::precision): f(NumberFormat<double>{}) or f(NumberFormat<float>{}); returns what f returns.
+// The one place the host code asks for the precision of a context; f runs after the test, so its arguments are evaluated as a ternary's
+template <class T> struct NumberFormat { using type = T; };
+template <class F> auto by_precision(int precision, F&& f) { return precision == TRM_F64 ? f(NumberFormat<double>{}) : f(NumberFormat<float>{}); }
 // what rides along with a derivative launch (Ride, trm_kernels.hpp): f(std::integral_constant<Ride, R>{}) for the ride that equals r
 template <Ride... Rs, class F> bool by_ride_value(int r, F&& f) {
     return ((r == Rs && (f(std::integral_constant<Ride, Rs>{}), true)) || ...);

@@ -1,8 +1,8 @@
 // trm_host.hpp -- host side shared by the translation units of libterrarium_hip.so: the context, the launch arguments and
 // the launch policies (which kernel instance a context takes).  The kernel instantiations are spread over the trm_launch_*.hip
-// files (one family per file, compiled in parallel); terrarium_hip.hip holds the context management, the step sequences and the
-// C ABI but its derivative entry points (trm_tangent_*, trm_adjoint_*, trm_step_tangent, trm_step_record), which trm_derivative_api.hip
-// holds; what the two share is declared here.  Nothing here is part of the ABI.
+// files (one family per file, compiled in parallel); the C ABI is spread over the trm_*_api.hip files: the context (trm_context_api.hip),
+// field I/O (trm_field_io_api.hip), time series (trm_series_api.hip), the step sequences (trm_step_api.hip), the communicators
+// (trm_comm_api.hip) and the derivatives (trm_derivative_api.hip); what they share is declared here.  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/terrarium_hip.h"
 #include "trm_kernels.hpp"
@@ -284,21 +284,30 @@ int fail(trm_ctx* ctx, int code, const std::string& msg);
             return ::trmh::fail(ctx, TRM_EHIP, std::string(#call) + ": " + hipGetErrorString(e__));     \
     } while (0)
 
-// ---- shared by the entry points of terrarium_hip.hip and trm_derivative_api.hip (defined, and described, in terrarium_hip.hip) ----
+// ---- shared by the entry points of the trm_*_api.hip files: everything that crosses between them, each defined (and described) in the
+// one file named.  trm_context_api.hip:
 int finish(trm_ctx* c, int rc);                 // the end of a launching entry point: waits for the stream unless TRM_OPT_ASYNC
 void tick(trm_ctx* c, double dt, int nsteps);   // tick! per step
 void bc_changed(trm_ctx* c);                    // a boundary condition has changed under an open tape
 void state_changed(trm_ctx* c);                 // ... the state has, under an open tangent or tape
 int flush_closure(trm_ctx* c);                  // T / liq into their arrays if the last step launches left them unstored
 int io_buffer(trm_ctx* c, size_t bytes);        // the staging buffer d_io, grown to `bytes`
-// Host data [Nz][Nh] to / from a 3-D device buffer [Nh][Nzp] through d_io, synchronised (instantiated for double and float).  `top`: the
-// [Nh] buffer of a Face field's top face, which travels as row Nz of the host array (null: Nz rows)
+// trm_field_io_api.hip: host data [Nz][Nh] to / from a 3-D device buffer [Nh][Nzp] through d_io, synchronised (instantiated for double and
+// float).  `top`: the [Nh] buffer of a Face field's top face, which travels as row Nz of the host array (null: Nz rows)
 template <class NF> int upload_3d(trm_ctx* c, const NF* host, NF* dev, NF* top = nullptr);
 template <class NF> int download_3d(trm_ctx* c, const NF* dev, NF* host, const NF* top = nullptr);
 // the derivative buffers of the context (d_tan*, d_adj*, d_tape) are freed here and nowhere else: the close calls, an open that fails,
 // trm_destroy (trm_derivative_api.hip)
 void release_tangent(trm_ctx* c);
 void release_adjoint(trm_ctx* c);
+// ... each named by the trm_<unit>_api.hip file that defines it.  Hidden: they serve the entry points alone and are no dynamic symbols
+#pragma GCC visibility push(hidden)
+int alloc_fields(trm_ctx* c, FieldSet& s);                     // context: the fields of `s` the context has and that are not allocated yet, zeroed; synchronised
+int fill_input_row(trm_ctx* c, int field, double value);       // context: every column of a 2-D field of the state set to `value`; synchronised
+int upload_field(trm_ctx* c, int field, const void* host);     // field_io: host data [rows][Nh] of the context's precision into a field of the state; synchronised
+int sync_copies(trm_ctx* c);                                   // series: every H2D copy of trm_series_append has finished (before a series buffer is freed or reallocated)
+int check_ctx_list(trm_ctx** ctxs, int n, const char* who);    // comm: n contexts that are shards of one grid, or the refusal `who` reports; clears their messages
+#pragma GCC visibility pop
 
 // TRM_ENTER: any entry point but the three of the two-call Heun step and the read-only ones.  A stage predicted by
 // trm_heun_predict belongs to the state and clock it was predicted from: whatever else runs in between drops it, and a later
@@ -350,7 +359,7 @@ template <class NF> struct LaunchArgs {
 inline long ncols(const trm_ctx* c) { return c->part >= 0 ? c->part_n[c->part] : c->Nh; }
 inline long first_col(const trm_ctx* c) { return c->part >= 0 ? c->part_lo[c->part] : 0; }
 // Launch arguments (DevParams, View of the state / the stage, StageView) are built once and reused by every launch (defined in
-// terrarium_hip.hip, instantiated for double and float)
+// trm_context_api.hip, instantiated for double and float)
 template <class NF> const LaunchArgs<NF>& launch_args(trm_ctx* c);
 template <class NF> const View<NF>& cached_view(trm_ctx* c, const FieldSet& s) {
     const LaunchArgs<NF>& a = launch_args<NF>(c);
@@ -379,7 +388,7 @@ struct PartScope {
     ~PartScope() { c->part = -1; }
 };
 
-// Time interpolation indices of a series at time t (defined in terrarium_hip.hip)
+// Time interpolation indices of a series at time t (defined in trm_series_api.hip)
 void series_time_indices(const std::vector<double>& times, int indexing, double t, int& n1, int& n2, double& f, double& g);
 
 // ---- launch policies: which kernel instance a context takes (pure host logic, shared by every translation unit) -------------
@@ -959,7 +968,7 @@ struct PackedLaunch {
     static int step(trm_ctx* c, double dt, int finalize);
     static int step_land(trm_ctx* c, double dt, int finalize);      // k_step_pk_land: the surface processes in the launch
 };
-// The hand-off of a launch that carries its own surface processes (k_column_land, k_step_pk_land; defined in terrarium_hip.hip):
+// The hand-off of a launch that carries its own surface processes (k_column_land, k_step_pk_land; defined in trm_context_api.hip):
 // refused unless the top-cell arrays are current (the surface workgroups read them), then the granule buffer, the launch's epoch
 // and the number of surface workgroups in front of the column workgroups.  `kernel` names the launch in the refusal.
 int front_args(trm_ctx* c, const char* kernel, FrontArgs& fa);
@@ -986,7 +995,7 @@ inline int accum_slot(int field) {
 }
 inline int accum_field(int slot) { return kAccumField[slot]; }
 
-// ---- the pure predicates of the step sequences (Ops, terrarium_hip.hip) and the StepPlan they give: no HIP call (tests/step_plan_preconditions.cpp)
+// ---- the pure predicates of the step sequences (Ops, trm_step_api.hip) and the StepPlan they give: no HIP call (tests/step_plan_preconditions.cpp)
 template <class NF> struct StepPolicy : Policy<NF> {
     using P = Policy<NF>;
     // the top-cell arrays (LandModel: T, sat, liq of the top cell, [Nh] each) can describe the state: they exist and no device

@@ -1,5 +1,5 @@
 /* fake_rccl.c -- TEST INFRASTRUCTURE, not product code: a stand-in for librccl.so that libterrarium_hip.so opens when
- * TRM_RCCL_LIBRARY names it (terrarium_hip.hip: rccl()).  It exports the seven entry points the library resolves and implements
+ * TRM_RCCL_LIBRARY names it (trm_comm_api.hip: rccl()).  It exports the seven entry points the library resolves and implements
  * them for n communicators in ONE process and ONE thread through host memory, so that the grouped call sequences of
  * trm_comm_init_all / trm_reduce_global_all / trm_status_global_all run with n > 1 on a one-GPU box.
  *
