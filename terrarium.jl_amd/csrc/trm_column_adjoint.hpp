@@ -181,46 +181,6 @@ TRM_DEV void param_grad_add_C(ParamGrad& acc, const Frac<double>& f, double Cbar
     acc.C0 = acc.C0 + Cbar;
 }
 
-// what the lane-per-level kernels of this file know about their lane (as k_column_tangent forms it)
-template <int LPC> TRM_DEV LaneInfo adjoint_lane(const View<double>& v, int& ii, size_t& e) {
-    constexpr int CPW = 64 / LPC;
-    LaneInfo ln;
-    ln.lane = threadIdx.x & 63;
-    const int wave = (int)((blockIdx.x * (unsigned)TRM_STEP_BLOCK + threadIdx.x) >> 6);
-    ln.k = ln.lane % LPC;
-    const int sub = ln.lane / LPC;
-    const int Nz = v.Nz, Nh = (int)v.Nh;
-    ln.is_bot = ln.k == 0;
-    ln.is_top = ln.k == Nz - 1;
-    ln.m_bot = wave_ballot(ln.is_bot);
-    ln.m_top = wave_ballot(ln.is_top);
-    const int i = wave * CPW + sub;
-    const bool colok = i < Nh;
-    ln.act = colok && ln.k < Nz;
-    ln.m_act = wave_ballot(colok) & wave_ballot(ln.k < Nz);
-    ii = colok ? i : Nh - 1;                             // (tail lanes carry clamped copies and store nothing)
-    e = (size_t)ii * (size_t)v.Nzp + (size_t)(ln.k < Nz ? ln.k : Nz - 1);
-    return ln;
-}
-
-// compute_z_bcs! terms as each program forms them (k_step_wave: flux_term_*; the column program: flux_term_*_nsz, selects)
-TRM_DEV void record_flux_U(const View<double>& v, const LaneInfo& ln, int ii, bool generic, ColumnBC<double>& bc) {
-    using NF = double;
-    const bool bU = v.bc.kind[0][0] == 2, tU = v.bc.kind[0][1] == 2;
-    if (generic) {
-        NF fU = 0.0;
-        if (ln.is_bot && bU) fU = flux_term_bottom(bcval(v, 0, 0)[ii], v.g);
-        if (ln.is_top && tU) fU = -flux_term_top(bcval(v, 0, 1)[ii], v.g);
-        bc.flux_U = fU;
-    } else {
-        NF eU_b = 0.0, eU_t = 0.0;
-        if (bU) eU_b = flux_term_bottom_nsz(bcval(v, 0, 0)[ii], v.g);
-        if (tU) eU_t = -flux_term_top_nsz(bcval(v, 0, 1)[ii], v.g);
-        const NF tU_term = ln.is_top ? eU_t : NF(0);
-        bc.flux_U = ln.is_bot ? eU_b : tU_term;
-    }
-}
-
 // `a.nsteps` ForwardEuler steps of the state, U_k stored into tape slot k before step k; the outputs are those of a finalizing trm_step.
 // STRIDED (trm_column_adjoint_ckpt.hpp: the record of a checkpointed tape): U_k is stored before the steps
 // aa.first, aa.first + aa.every, ... of the launch alone, into the slots from aa.tape on -- a wave-uniform branch, everything else the
@@ -233,8 +193,7 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v
     using NF = double;
     int ii;
     size_t e;
-    const LaneInfo ln = adjoint_lane<LPC>(v, ii, e);
-    const int Nz = v.Nz;
+    const LaneInfo ln = derivative_lane<LPC>(v, ii, e);
     const bool generic = aa.generic != 0;
     uint32_t viol = 0;
     bool bad = false;
@@ -247,14 +206,9 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v
     c.psi = 0.0;
     const LevelGeom<NF> L = level_geom(v, ln.k);
     // boundary inputs: constants over the launch
-    const NF bTb = v.bc.kind[2][0] == 1 ? bcval(v, 2, 0)[ii] : 0.0, bTt = v.bc.kind[2][1] == 1 ? bcval(v, 2, 1)[ii] : 0.0;
-    ColumnBC<NF> bc;
-    bc.bTb = bTb;
-    bc.bTt = bTt;
-    bc.flux_S = 0.0;
-    bc.has_U = true;
-    bc.has_S = false;
-    record_flux_U(v, ln, ii, generic, bc);
+    NF bTb, bTt;
+    temperature_boundary_values<false>(v, ii, generic, bTb, bTt);
+    ColumnBC<NF> bc = heat_bc(v, ln, ii, generic, bTb, bTt);
 
     Cell<NF> n = c;
     Frac<NF> f_new{};
@@ -278,29 +232,9 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_record(View<double> v
             NF unused_b = 0.0, unused_t = 0.0, unused_U = 0.0;
             series_boundary_step<false, true>(v, a, ln, ii, step, bc, nullptr, unused_b, unused_t, unused_U);
         }
-        const Frac<NF>* pre = step > 0 ? &f_new : nullptr;
-        const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
-                                       : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
-        NF gU = t.gU, gS = t.gS, z0;
-        column_advance<NF, false, LPC>(v, L, ln, Nz, bc, c.U, c.sat, gU, gS, a.dt, n, z0, bad);
-        f_new = column_closure<NF, false, HYD>(p, L, z0, n, viol);
-        gU_out = gU;
+        heat_step<HYD, LPC>(v, p, L, ln, ii, e, generic, bc, a.dt, c, step > 0, f_new, n, gU_out, viol, bad);
     }
-    // hydraulic_conductivity of the new state (a finalizing step: compute_auxiliary!)
-    const NF Kc_new = conductivity_hydraulic<NF, HYD, false>(p, n.liq, f_new);
-    const NF Kc_new_m = shfl_up1<NF, LPC>(Kc_new);
-    const NF Kmin_new = jl_min(Kc_new, Kc_new_m);
-    const NF Kf_out = (ln.is_bot || ln.is_top) ? Kc_new : Kmin_new;
-    if (ln.act) {
-        v.U[e] = n.U;
-        v.T[e] = n.T;
-        v.liq[e] = n.liq;
-        v.G_U[e] = gU_out;
-        v.Kf[e] = Kf_out;
-        if (ln.is_top) v.Kf_top[ii] = Kc_new;
-        viol |= bad ? 1u : 0u;
-    }
-    if (viol && ln.act) atomicOr(v.status, viol);
+    finalize_heat_outputs<HYD, LPC>(v, p, ln, ii, e, n, f_new, gU_out, viol, bad);
 }
 
 // the closure quantities a step forms at its state U_k: what an attached record's sample of position k is measured against
@@ -401,100 +335,11 @@ TRM_DEV double adjoint_step(const View<double>& v, const DevParams<double>& p, c
     return lam + via_T + via_liq;
 }
 
-// the end of the run: the cotangents of T_n and liq_n through the closure of the stored U_n, lam_n = wU + a_n wT + b_n wliq; wT = wliq = 0 after.
-// PGRAD: and wT through the heat capacity of that closure onto `pacc`
-template <bool PGRAD = false>
-TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, const LaneInfo& ln, size_t e, double sat, double& lam, double* lT,
-                          double* lliq, ParamGrad& pacc) {
-    using NF = double;
-    const NF U = v.U[e], wT = lT[e], wliq = lliq[e];
-    uint32_t viol_in = 0;
-    NF liq, T, via_T, via_liq, unused_liq, unused_T;
-    const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
-    const NF C = heat_capacity(p, f);
-    closure_tangent(p, U, sat, C, wT, unused_liq, via_T);
-    closure_tangent(p, U, sat, C, wliq, via_liq, unused_T);
-    lam = lam + via_T + via_liq;
-    if constexpr (PGRAD) param_grad_add_C(pacc, f, closure_param_slope(T, C) * wT);
-    if (ln.act) {
-        lT[e] = 0.0;
-        lliq[e] = 0.0;
-    }
-}
-
-// The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
-// BCGRAD: the boundary gradients ride along.  PGRAD: and the per-cell parameter sums.  SERIES: a.series_rows holds the rows of this
-// launch's taped steps, oldest first.
-template <int HYD, int LPC, Ride R>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, SweepArgs<false, R> aa) {
-    constexpr bool BCGRAD = ride_has_bc(R), PGRAD = ride_has_params(R), SERIES = ride_has_series(R);
-    using NF = double;
-    int ii;
-    size_t e;
-    const LaneInfo ln = adjoint_lane<LPC>(v, ii, e);
-    const bool generic = aa.generic != 0;
-    const NF sat = v.sat[e];
-    NF lam = aa.lU[e];
-    // the newest slot first; the load of the slot below is issued before the arithmetic of a step
-    const NF* slot = aa.tape + (size_t)(a.nsteps > 0 ? a.nsteps - 1 : 0) * (size_t)aa.slot_elems + e;
-    NF U_next = a.nsteps > 0 ? *slot : 0.0;
-    const LevelGeom<NF> L = level_geom(v, ln.k);
-    // the temperature boundary values: of a Value condition, and of a Gradient condition where the generic halo form reads them
-    const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
-    const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
-    ParamGrad pacc;
-    if constexpr (PGRAD) pacc = param_grad_load(aa.pg, e, aa.fold);
-    if (aa.fold) adjoint_fold<PGRAD>(v, p, ln, e, sat, lam, aa.lT, aa.lliq, pacc);
-    // Everything loaded so far is used here, in front of the loop: inside it the next slot's load is the only one in flight, and the wait
-    // for it sits where its value is taken, behind the arithmetic of the step
-    BcGrad acc;
-    if constexpr (PGRAD) {
-        acc = bc_grad_load(aa.g, ii, aa.fold);
-        asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt), "v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub),
-                     "v"(acc.Ut), "v"(pacc.sk_water), "v"(pacc.sk_ice), "v"(pacc.sk_air), "v"(pacc.s0), "v"(pacc.c_water), "v"(pacc.c_ice),
-                     "v"(pacc.c_air), "v"(pacc.C0));
-    } else if constexpr (BCGRAD) {
-        acc = bc_grad_load(aa.g, ii, aa.fold);
-        asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt), "v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub),
-                     "v"(acc.Ut));
-    } else asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt));
-    if constexpr (SERIES) {
-        // the step's temperature values are fetched with the tape slot of the step, a step ahead of their use
-        SeriesGrad sg;
-        NF bTb_next = bTb, bTt_next = bTt;
-        if (a.nsteps > 0) series_temperatures(a, ii, a.nsteps - 1, bTb_next, bTt_next);
-        for (int step = a.nsteps - 1; step >= 0; --step) {
-            const NF U = U_next, sTb = bTb_next, sTt = bTt_next;
-            if (step > 0) {
-                slot -= aa.slot_elems;
-                U_next = *slot;
-                series_temperatures(a, ii, step - 1, bTb_next, bTt_next);
-            }
-            BcGrad term;
-            lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, U, sat, lam, a.dt, sTb, sTt, generic, term, pacc);
-            series_grad_step(a, aa.sg, ln, ii, step, term, acc, sg);
-        }
-        series_grad_store(a, aa.sg, ln, ii, sg);
-    } else {
-        for (int step = a.nsteps - 1; step >= 0; --step) {
-            const NF U = U_next;
-            if (step > 0) {
-                slot -= aa.slot_elems;
-                U_next = *slot;
-            }
-            lam = adjoint_step<LPC, BCGRAD, PGRAD>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc, pacc);
-        }
-    }
-    if (ln.act) aa.lU[e] = lam;
-    if constexpr (BCGRAD) bc_grad_store(aa.g, ln, ii, acc);
-    if constexpr (PGRAD) param_grad_store(aa.pg, ln, e, pacc);
-}
-
 // ---- attached records (trm_adjoint_observe_record; DESIGN 4.8 "Attached records") ----------------------------------------------------
 // A temperature record attached to the open adjoint is read inside the backward launches: the loss gains 1/2 w (T_p - T_obs)^2 on the
 // record's levels at its positions, and position p is injected by the launch that pulls back step p, right behind that step's
 // adjoint_step, from the T, C and fractions the step has formed at U_p (StepClosure): lam gets a_p wT through closure_tangent, a
-// parameter sweep closure_param_slope(T, C) wT through param_grad_add_C.  Position n enters with the fold (adjoint_fold's OBS).
+// parameter sweep closure_param_slope(T, C) wT through param_grad_add_C.  Position n enters with the fold (adjoint_fold's RECORD).
 // The fifth kernel argument of the record-reading sweeps.  Lane = level: `row_of_level[Nz]` (-1: not observed) is read once per lane in
 // front of the loop; `row_of_position` points at the entry of the launch's first step in the table of the whole tape ([n + 1], -1: no
 // sample) and is indexed with the step of the launch, a wave-uniform index, so "is this step observed" is a scalar branch.  Arrays
@@ -545,21 +390,25 @@ TRM_DEV void record_inject(const DevParams<double>& p, const RecordArgs& r, cons
     lam = wT != 0.0 ? lam + via_T : lam;      // (a gap adds nothing, not even the sign of a zero)
     if constexpr (PGRAD) param_grad_add_C(pacc, cl.f, closure_param_slope(cl.T, cl.C) * wT);
 }
-// The fold of a record-reading sweep: adjoint_fold, with the cotangent of the record's sample of position n = the launch's last position
-// added to the final wT in front of the closure.  (A function of its own and not a parameter of adjoint_fold: with the parameter the
-// existing parameter sweeps came out of the compiler with the operands of two additions swapped.)
-template <bool PGRAD>
-TRM_DEV void record_fold(const View<double>& v, const DevParams<double>& p, const RecordArgs& r, const LaneInfo& ln, int ii, int j, int nsteps, size_t e, double sat,
-                         double& lam, double* lT, double* lliq, ParamGrad& pacc) {
+
+// the end of the run: the cotangents of T_n and liq_n through the closure of the stored U_n, lam_n = wU + a_n wT + b_n wliq; wT = wliq = 0 after.
+// PGRAD: and wT through the heat capacity of that closure onto `pacc`.  RECORD: and the cotangent of the record's sample `s` of position
+// n, the launch's last, added to the final wT in front of the closure.  (Under `if constexpr` and not a plain parameter: with the
+// parameter the parameter sweeps without a record came out of the compiler with the operands of two additions swapped.)
+template <bool PGRAD, bool RECORD, class Rec>
+TRM_DEV void adjoint_fold(const View<double>& v, const DevParams<double>& p, const LaneInfo& ln, size_t e, double sat, double& lam, double* lT,
+                          double* lliq, ParamGrad& pacc, const Rec& r, const RecordSample& s) {
     using NF = double;
-    const RecordSample s = record_fetch(r, r.row_of_position[nsteps], j, ii, v.Nh);
     const NF U = v.U[e], wT_final = lT[e], wliq = lliq[e];
     uint32_t viol_in = 0;
     NF liq, T, via_T, via_liq, unused_liq, unused_T;
     const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
     const NF C = heat_capacity(p, f);
-    const NF x = record_residual(r, s, T);
-    const NF wT = x != 0.0 ? wT_final + x : wT_final;          // (a gap adds nothing, not even the sign of a zero)
+    NF wT = wT_final;
+    if constexpr (RECORD) {
+        const NF x = record_residual(r, s, T);
+        wT = x != 0.0 ? wT_final + x : wT_final;               // (a gap adds nothing, not even the sign of a zero)
+    }
     closure_tangent(p, U, sat, C, wT, unused_liq, via_T);
     closure_tangent(p, U, sat, C, wliq, via_liq, unused_T);
     lam = lam + via_T + via_liq;
@@ -570,34 +419,49 @@ TRM_DEV void record_fold(const View<double>& v, const DevParams<double>& p, cons
     }
 }
 
-// k_column_adjoint with an attached record: the same sweep, and behind every step's adjoint_step the sample of the step's position.
-// The sample of a step is fetched where the slot of that step is, a step ahead; the fold takes position `a.nsteps` of the launch (n).
-template <int HYD, int LPC, Ride R>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, SweepArgs<false, R> aa, RecordArgs r) {
+// The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
+// BCGRAD: the boundary gradients ride along.  PGRAD: and the per-cell parameter sums.  SERIES: a.series_rows holds the rows of this
+// launch's taped steps, oldest first; the step's temperature values are fetched with the tape slot of the step, a step ahead of their use.
+// RECORD (`r`: RecordArgs, else NoRecord): and behind every step's adjoint_step the sample of the step's position, fetched where the slot
+// of that step is, a step ahead; the fold takes position `a.nsteps` of the launch (n).
+template <int HYD, int LPC, Ride R, bool RECORD, class Rec>
+TRM_DEV void adjoint_program(const View<double>& v, const DevParams<double>& p, const ColumnArgs<double>& a, const SweepArgs<false, R>& aa, const Rec& r) {
     constexpr bool BCGRAD = ride_has_bc(R), PGRAD = ride_has_params(R), SERIES = ride_has_series(R);
     using NF = double;
     int ii;
     size_t e;
-    const LaneInfo ln = adjoint_lane<LPC>(v, ii, e);
+    const LaneInfo ln = derivative_lane<LPC>(v, ii, e);
     const bool generic = aa.generic != 0;
     const NF sat = v.sat[e];
     NF lam = aa.lU[e];
-    const int j = ln.act ? r.row_of_level[ln.k] : -1;
+    int j = -1, row_next = -1;
+    if constexpr (RECORD) j = ln.act ? r.row_of_level[ln.k] : -1;
+    // the newest slot first; the load of the slot below is issued before the arithmetic of a step
     const NF* slot = aa.tape + (size_t)(a.nsteps > 0 ? a.nsteps - 1 : 0) * (size_t)aa.slot_elems + e;
     NF U_next = a.nsteps > 0 ? *slot : 0.0;
-    int row_next = a.nsteps > 0 ? r.row_of_position[a.nsteps - 1] : -1;
-    RecordSample s_next = record_fetch(r, row_next, j, ii, v.Nh);
+    RecordSample s_next;
+    if constexpr (RECORD) {
+        row_next = a.nsteps > 0 ? r.row_of_position[a.nsteps - 1] : -1;
+        s_next = record_fetch(r, row_next, j, ii, v.Nh);
+    }
     const LevelGeom<NF> L = level_geom(v, ln.k);
-    const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
-    const NF bTb = (kb == 1 || (generic && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0, bTt = (kt == 1 || (generic && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
+    NF bTb, bTt;
+    temperature_boundary_values<true>(v, ii, generic, bTb, bTt);
     ParamGrad pacc;
     if constexpr (PGRAD) pacc = param_grad_load(aa.pg, e, aa.fold);
-    if (aa.fold) record_fold<PGRAD>(v, p, r, ln, ii, j, a.nsteps, e, sat, lam, aa.lT, aa.lliq, pacc);
+    if (aa.fold) {
+        RecordSample s_fold;
+        if constexpr (RECORD) s_fold = record_fetch(r, r.row_of_position[a.nsteps], j, ii, v.Nh);
+        adjoint_fold<PGRAD, RECORD>(v, p, ln, e, sat, lam, aa.lT, aa.lliq, pacc, r, s_fold);
+    }
     BcGrad acc;
     if constexpr (BCGRAD) acc = bc_grad_load(aa.g, ii, aa.fold);
-    // as in k_column_adjoint: what the head has loaded is used in front of the loop, so that inside it the next slot and the next sample
-    // are the only loads in flight
-    asm volatile("" ::"v"(sat), "v"(lam), "v"(j), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt), "v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub), "v"(acc.Ut));
+    // Everything loaded so far is used here, in front of the loop: inside it the next slot's load (SERIES: and the next temperature
+    // values', RECORD: and the next sample's) is the only one in flight, and the wait for it sits where its value is taken, behind the
+    // arithmetic of the step
+    asm volatile("" ::"v"(sat), "v"(lam), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bTb), "v"(bTt));
+    if constexpr (RECORD) asm volatile("" ::"v"(j));
+    if constexpr (BCGRAD) asm volatile("" ::"v"(acc.Tb), "v"(acc.Tt), "v"(acc.Ub), "v"(acc.Ut));
     if constexpr (PGRAD)
         asm volatile("" ::"v"(pacc.sk_water), "v"(pacc.sk_ice), "v"(pacc.sk_air), "v"(pacc.s0), "v"(pacc.c_water), "v"(pacc.c_ice), "v"(pacc.c_air), "v"(pacc.C0));
     SeriesGrad sg;
@@ -611,22 +475,34 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_record(View<d
         if (step > 0) {
             slot -= aa.slot_elems;
             U_next = *slot;
-            row_next = r.row_of_position[step - 1];
-            s_next = record_fetch(r, row_next, j, ii, v.Nh);
+            if constexpr (RECORD) {
+                row_next = r.row_of_position[step - 1];
+                s_next = record_fetch(r, row_next, j, ii, v.Nh);
+            }
             if constexpr (SERIES) series_temperatures(a, ii, step - 1, bTb_next, bTt_next);
         }
+        // (SERIES: the step's four terms go through `term` onto the node sums; else adjoint_step adds them onto `acc`)
         StepClosure cl;
-        if constexpr (SERIES) {
-            BcGrad term;
-            lam = adjoint_step<LPC, BCGRAD, PGRAD, true>(v, p, L, ln, ii, U, sat, lam, a.dt, sTb, sTt, generic, term, pacc, &cl);
-            series_grad_step(a, aa.sg, ln, ii, step, term, acc, sg);
-        } else lam = adjoint_step<LPC, BCGRAD, PGRAD, true>(v, p, L, ln, ii, U, sat, lam, a.dt, bTb, bTt, generic, acc, pacc, &cl);
-        if (row >= 0) record_inject<PGRAD>(p, r, s, cl, U, sat, lam, pacc);
+        BcGrad term;
+        lam = adjoint_step<LPC, BCGRAD, PGRAD, RECORD>(v, p, L, ln, ii, U, sat, lam, a.dt, sTb, sTt, generic, SERIES ? term : acc, pacc, &cl);
+        if constexpr (SERIES) series_grad_step(a, aa.sg, ln, ii, step, term, acc, sg);
+        if constexpr (RECORD)
+            if (row >= 0) record_inject<PGRAD>(p, r, s, cl, U, sat, lam, pacc);
     }
     if constexpr (SERIES) series_grad_store(a, aa.sg, ln, ii, sg);
     if (ln.act) aa.lU[e] = lam;
     if constexpr (BCGRAD) bc_grad_store(aa.g, ln, ii, acc);
     if constexpr (PGRAD) param_grad_store(aa.pg, ln, e, pacc);
+}
+
+// the two wrappers of adjoint_program: without and with an attached record
+template <int HYD, int LPC, Ride R>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint(View<double> v, DevParams<double> p, ColumnArgs<double> a, SweepArgs<false, R> aa) {
+    adjoint_program<HYD, LPC, R, false>(v, p, a, aa, NoRecord{});
+}
+template <int HYD, int LPC, Ride R>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, SweepArgs<false, R> aa, RecordArgs r) {
+    adjoint_program<HYD, LPC, R, true>(v, p, a, aa, r);
 }
 
 // the misfit of an attached record after a sweep: one thread per column sums 1/2 w r^2 over the residuals the sweep wrote, positions in

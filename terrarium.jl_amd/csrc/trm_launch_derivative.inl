@@ -2,7 +2,9 @@
 // (trm_column_tangent.hpp), k_column_record / k_column_adjoint (trm_column_adjoint.hpp) and k_column_adjoint_ckpt
 // (trm_column_adjoint_ckpt.hpp), each with what rides along (Ride, trm_kernels.hpp), and their record twins: k_column_tangent_record
 // (trm_column_tangent_record.hpp; DESIGN 4.7 "Tangent records"), k_column_adjoint_record and k_column_adjoint_ckpt_record (DESIGN 4.8
-// "Attached records").  Included by the trm_launch_column_tangent*.hip and trm_launch_column_adjoint*.hip files, each of which
+// "Attached records").  A sweep and its record twin are the two wrappers of one device program (adjoint_program,
+// adjoint_ckpt_program <.., RECORD>); the two tangent kernels are two bodies.  Included by the
+// trm_launch_column_tangent*.hip and trm_launch_column_adjoint*.hip files, each of which
 // instantiates the launcher of one family and ride, with a record or without.
 #include "trm_host.hpp"
 #include "trm_column_adjoint_ckpt.hpp"

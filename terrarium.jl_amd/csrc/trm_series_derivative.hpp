@@ -1,4 +1,6 @@
-// trm_series_derivative.hpp -- boundary time series inside the derivative kernels (TRM_OPT_DERIVATIVE_SERIES; DESIGN 4.7 / 4.8 "Series").
+// trm_series_derivative.hpp -- boundary time series inside the derivative kernels (TRM_OPT_DERIVATIVE_SERIES; DESIGN 4.7 / 4.8 "Series"),
+// and, at the end, the building blocks every heat-only derivative kernel shares (the lane head, the boundary inputs, the primal step, the
+// finalising tail).
 //
 // k_column_tangent, k_column_record, k_column_adjoint and k_column_adjoint_ckpt <.., SERIES> evaluate the boundary series of the four
 // pairs the heat-only fast path reads -- SLOT_T_BOT, SLOT_T_TOP (Value), SLOT_FU_BOT, SLOT_FU_TOP (Flux) -- in front of every step, from
@@ -125,5 +127,110 @@ struct SeriesGradPtrs {
 struct SeriesGrad {
     SeriesNodeSums s[4];
 };
+
+// ---- what every heat-only derivative kernel is built from (the tangent programs of trm_column_tangent.hpp, k_column_record and the
+// sweeps of trm_column_adjoint.hpp and trm_column_adjoint_ckpt.hpp): each written once ------------------------------------------------------------
+// the fifth argument of a program that carries no record (a record's parts stand under `if constexpr (RECORD)`)
+struct NoRecord {};
+
+// what a lane-per-level kernel knows about its lane; `ii`: the lane's column, `e`: its cell
+template <int LPC> TRM_DEV LaneInfo derivative_lane(const View<double>& v, int& ii, size_t& e) {
+    constexpr int CPW = 64 / LPC;
+    LaneInfo ln;
+    ln.lane = threadIdx.x & 63;
+    const int wave = (int)((blockIdx.x * (unsigned)TRM_STEP_BLOCK + threadIdx.x) >> 6);
+    ln.k = ln.lane % LPC;
+    const int sub = ln.lane / LPC;
+    const int Nz = v.Nz, Nh = (int)v.Nh;
+    ln.is_bot = ln.k == 0;
+    ln.is_top = ln.k == Nz - 1;
+    ln.m_bot = wave_ballot(ln.is_bot);
+    ln.m_top = wave_ballot(ln.is_top);
+    const int i = wave * CPW + sub;
+    const bool colok = i < Nh;
+    ln.act = colok && ln.k < Nz;
+    ln.m_act = wave_ballot(colok) & wave_ballot(ln.k < Nz);
+    ii = colok ? i : Nh - 1;                             // (tail lanes carry clamped copies and store nothing)
+    e = (size_t)ii * (size_t)v.Nzp + (size_t)(ln.k < Nz ? ln.k : Nz - 1);
+    return ln;
+}
+
+// The temperature boundary values of the column, constants over a launch.  The primal programs (SWEEP = false: the tangent, the record)
+// take those of a Value condition alone: under the generic halos column_tendencies_generic and tendency_tangent read the value arrays
+// themselves.  The sweeps (SWEEP = true) take those of a Gradient condition as well where the halos are generic: adjoint_step forms
+// k_step_wave's halos from what the kernel has loaded, so that the tape's is the only load inside the sweep.
+template <bool SWEEP> TRM_DEV void temperature_boundary_values(const View<double>& v, int ii, bool generic, double& bTb, double& bTt) {
+    const int kb = v.bc.kind[2][0], kt = v.bc.kind[2][1];
+    const bool gradient = SWEEP && generic;
+    bTb = (kb == 1 || (gradient && kb == 3)) ? bcval(v, 2, 0)[ii] : 0.0;
+    bTt = (kt == 1 || (gradient && kt == 3)) ? bcval(v, 2, 1)[ii] : 0.0;
+}
+
+// the boundary inputs of a heat-only launch
+TRM_DEV ColumnBC<double> heat_bc(const View<double>& v, const LaneInfo& ln, int ii, bool generic, double bTb, double bTt) {
+    using NF = double;
+    ColumnBC<NF> bc;
+    bc.bTb = bTb;
+    bc.bTt = bTt;
+    bc.flux_S = 0.0;
+    bc.has_U = true;
+    bc.has_S = false;
+    // compute_z_bcs! terms as each program forms them (k_step_wave: flux_term_*; the column program: flux_term_*_nsz, selects)
+    const bool bU = v.bc.kind[0][0] == 2, tU = v.bc.kind[0][1] == 2;
+    if (generic) {
+        NF fU = 0.0;
+        if (ln.is_bot && bU) fU = flux_term_bottom(bcval(v, 0, 0)[ii], v.g);
+        if (ln.is_top && tU) fU = -flux_term_top(bcval(v, 0, 1)[ii], v.g);
+        bc.flux_U = fU;
+    } else {
+        NF eU_b = 0.0, eU_t = 0.0;
+        if (bU) eU_b = flux_term_bottom_nsz(bcval(v, 0, 0)[ii], v.g);
+        if (tU) eU_t = -flux_term_top_nsz(bcval(v, 0, 1)[ii], v.g);
+        const NF tU_term = ln.is_top ? eU_t : NF(0);
+        bc.flux_U = ln.is_bot ? eU_b : tU_term;
+    }
+    return bc;
+}
+
+// One primal ForwardEuler step of the cell `c` under `bc`, by the column program's own building blocks (so its bits are trm_step's):
+// the new cell into `n`, the step's tendency into `gU`, the fractions of the new state into `f`.  `have_f`: `f` holds the fractions of `c`
+// (the step before left them there) and column_tendencies takes them from it.
+// (Measured on the listings: with the fractions returned by value and a pointer argument, k_column_record without a stride came out with
+// its first step peeled, 1 029 instructions instead of 668.)
+template <int HYD, int LPC>
+TRM_DEV void heat_step(const View<double>& v, const DevParams<double>& p, const LevelGeom<double>& L, const LaneInfo& ln, int ii, size_t e,
+                       bool generic, const ColumnBC<double>& bc, double dt, const Cell<double>& c, bool have_f, Frac<double>& f, Cell<double>& n,
+                       double& gU, uint32_t& viol, bool& bad) {
+    using NF = double;
+    const Frac<NF>* pre = have_f ? &f : nullptr;
+    const Tendency<NF> t = generic ? column_tendencies_generic<NF, false, HYD, LPC>(v, p, L, ln, c, ii, (unsigned)(e * sizeof(NF)), false, viol)
+                                   : column_tendencies<NF, false, HYD, LPC>(v, p, L, ln, c, bc.bTb, bc.bTt, false, viol, pre);
+    NF g = t.gU, gS = t.gS, z0;
+    column_advance<NF, false, LPC>(v, L, ln, v.Nz, bc, c.U, c.sat, g, gS, dt, n, z0, bad);
+    f = column_closure<NF, false, HYD>(p, L, z0, n, viol);
+    gU = g;
+}
+
+// the outputs of a finalizing trm_step: the new state, the tendency of the last step, hydraulic_conductivity of the new state
+// (compute_auxiliary!) and the status flags
+template <int HYD, int LPC>
+TRM_DEV void finalize_heat_outputs(const View<double>& v, const DevParams<double>& p, const LaneInfo& ln, int ii, size_t e, const Cell<double>& n,
+                                   const Frac<double>& f_new, double gU_out, uint32_t viol, bool bad) {
+    using NF = double;
+    const NF Kc_new = conductivity_hydraulic<NF, HYD, false>(p, n.liq, f_new);
+    const NF Kc_new_m = shfl_up1<NF, LPC>(Kc_new);
+    const NF Kmin_new = jl_min(Kc_new, Kc_new_m);
+    const NF Kf_out = (ln.is_bot || ln.is_top) ? Kc_new : Kmin_new;
+    if (ln.act) {
+        v.U[e] = n.U;
+        v.T[e] = n.T;
+        v.liq[e] = n.liq;
+        v.G_U[e] = gU_out;
+        v.Kf[e] = Kf_out;
+        if (ln.is_top) v.Kf_top[ii] = Kc_new;
+        viol |= bad ? 1u : 0u;
+    }
+    if (viol && ln.act) atomicOr(v.status, viol);
+}
 
 }  // namespace trm
