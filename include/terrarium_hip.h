@@ -237,6 +237,14 @@ enum {
                                     /* parameter seeds or an open parameter gradient: one launch carries the node seeds / gradients of the      */
                                     /* series and the thermal parameters' (TRM_INFO_LAST_PROGRAM: bits 26 / 30 and 31).  0 (default): the two   */
                                     /* together are refused with TRM_EUNSUPPORTED.  Without TRM_OPT_DERIVATIVE_SERIES it changes nothing        */
+    ,TRM_OPT_DERIVATIVE_RICHARDS = 16 /* 1: the state-seed calls of the tangent -- trm_tangent_open, trm_tangent_upload, trm_tangent_download,   */
+                                    /* trm_tangent_device_ptr, trm_tangent_closure and trm_step_tangent -- accept an fp64 heat + Richards        */
+                                    /* SoilModel (ForwardEuler, Nz <= 64, the branch-free boundary kinds): seeds on the initial internal energy  */
+                                    /* and the initial saturation, tangents of internal energy, saturation, temperature, liquid fraction and      */
+                                    /* pressure head (TRM_TANGENT_SATURATION, TRM_TANGENT_PRESSURE_HEAD).  Every other derivative call -- seeds   */
+                                    /* on boundaries, parameters or series, tangent records, every trm_adjoint_* opener -- refuses a Richards      */
+                                    /* context with TRM_EUNSUPPORTED "on a Richards context: state seeds only".  0 (default): every derivative    */
+                                    /* call refuses a Richards context as "the heat-only SoilModel (NoFlow) only"                                 */
 };
 /* DIAGNOSTIC, read-only (trm_get_option): which fast paths the NEXT step will take -- what the library tracks about its own
  * buffers.  Tests pin them (a wrong value costs speed, never correctness, so nothing else would notice). */
@@ -266,7 +274,8 @@ enum {
     TRM_PROGRAM_PACKED_F32 = 4, TRM_PROGRAM_GENERIC_EULER = 5, TRM_PROGRAM_GENERIC_HEUN = 6, TRM_PROGRAM_COLUMN_LAND = 7,
     TRM_PROGRAM_DEEP = 8, TRM_PROGRAM_WIDE = 9, TRM_PROGRAM_LAND_INTERLEAVED = 10, TRM_PROGRAM_UNFUSED = 11, TRM_PROGRAM_VEGETATION = 12,
     TRM_PROGRAM_PACKED_LAND = 13, TRM_PROGRAM_COLUMN_TANGENT = 14,
-    TRM_PROGRAM_COLUMN_ADJOINT = 15
+    TRM_PROGRAM_COLUMN_ADJOINT = 15,
+    TRM_PROGRAM_COLUMN_TANGENT_RICHARDS = 16   /* trm_step_tangent on a Richards context: bits 8-9 the hydraulics, 10-11 lanes per column / 32 */
 };
 /* bits of TRM_INFO_LAST_PROGRAM beside the ones above (25-27 are per family: surface processes inline / time series in the multi-step
  * program, the program and the generic boundaries of the deep and wide columns): how the step's time averages were accumulated
@@ -631,8 +640,18 @@ int trm_average_close(trm_ctx* ctx, int handle);
  * head, or a per-cell vwc_forcing field.  Every other call that changes the state -- trm_step, trm_step_heun, the two-call Heun,
  * trm_explicit_step, trm_initialize, trm_invclosure, trm_upload of internal energy or saturation, trm_restore_state, trm_reset --
  * makes the tangent stale: trm_tangent_download of dT or dliq, trm_tangent_closure and trm_step_tangent return TRM_ESTALE until a
- * new trm_tangent_upload of dU seeds it again. */
-enum { TRM_TANGENT_INTERNAL_ENERGY = 0, TRM_TANGENT_TEMPERATURE = 1, TRM_TANGENT_LIQUID_WATER_FRACTION = 2 };
+ * new trm_tangent_upload of dU seeds it again.
+ * Heat + Richards, with TRM_OPT_DERIVATIVE_RICHARDS set: the seven calls above accept an fp64 SoilModel with RichardsEq on the branch-free
+ * boundary kinds.  trm_tangent_open allocates five fields there: the three above, TRM_TANGENT_SATURATION and TRM_TANGENT_PRESSURE_HEAD,
+ * which exist only while a tangent is open on a Richards context (on a NoFlow context the indices 3 and 4 are a bad argument).  The seeds
+ * are dU and dsat: trm_tangent_upload takes `which` 0 and 3 there, trm_tangent_download and trm_tangent_device_ptr 0 ... 4;
+ * trm_tangent_closure forms dT, dliq and dpsi from the stored state, dU and dsat; trm_step_tangent leaves the state of
+ * trm_step(ctx, dt, nsteps, 1) bit for bit -- saturation, pressure head, water table, surface_excess_water, hydraulic conductivity and the
+ * tendencies included -- and the five tangents (TRM_INFO_LAST_PROGRAM: TRM_PROGRAM_COLUMN_TANGENT_RICHARDS).  The tangent of
+ * surface_excess_water is not formed.  The staleness rules are the ones above (trm_upload of the saturation makes the tangent stale). */
+enum { TRM_TANGENT_INTERNAL_ENERGY = 0, TRM_TANGENT_TEMPERATURE = 1, TRM_TANGENT_LIQUID_WATER_FRACTION = 2,
+       TRM_TANGENT_SATURATION = 3,      /* Richards contexts only: the seed / tangent of saturation_water_ice */
+       TRM_TANGENT_PRESSURE_HEAD = 4 }; /* Richards contexts only: the tangent of pressure_head (an output: not uploaded) */
 int trm_tangent_open(trm_ctx* ctx);
 int trm_tangent_close(trm_ctx* ctx);
 int trm_tangent_upload(trm_ctx* ctx, int which, const void* host);

@@ -54,10 +54,12 @@ OPTION_INTERIOR = dict(interior_steps=13, info_interior_launches=108)
 OPTION_DERIVATIVE = dict(derivative_series=14, info_derivative_series=109)
 # ... and TRM_OPT_DERIVATIVE_SERIES_PARAMS (tests/test_param_series_host.py)
 OPTION_DERIVATIVE_PARAMS = dict(derivative_series_params=15)
+# ... and TRM_OPT_DERIVATIVE_RICHARDS (tests/test_tangent_richards_host.py)
+OPTION_DERIVATIVE_RICHARDS = dict(derivative_richards=16)
 
 
 def option_id(name: str) -> int:
-    for table in (OPTION, OPTION_LATER, OPTION_INTERIOR, OPTION_DERIVATIVE, OPTION_DERIVATIVE_PARAMS):
+    for table in (OPTION, OPTION_LATER, OPTION_INTERIOR, OPTION_DERIVATIVE, OPTION_DERIVATIVE_PARAMS, OPTION_DERIVATIVE_RICHARDS):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -65,7 +67,7 @@ def option_id(name: str) -> int:
 KERNEL = dict(fused=0, unfused=1)
 # TRM_INFO_LAST_PROGRAM (include/terrarium_hip.h: TRM_PROGRAM_*; trm_host.hpp: program_id)
 PROGRAM = ("none", "column_euler", "column_heun", "column_multi", "packed_f32", "generic_euler", "generic_heun", "column_land", "deep", "wide",
-           "land_interleaved", "unfused", "vegetation", "packed_land", "column_tangent", "column_adjoint")
+           "land_interleaved", "unfused", "vegetation", "packed_land", "column_tangent", "column_adjoint", "column_tangent_richards")
 DERIVE = ("none", "T_liq", "liq", "liq_psi", "all")
 
 
@@ -125,6 +127,17 @@ EXPORTS = (
 THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
 # forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
 TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
+# ... and the two that exist only while a tangent is open on a Richards context (TRM_OPT_DERIVATIVE_RICHARDS).  A table of its own: the one
+# above is pinned as a whole (tests/test_tangent_host.py); tangent_id looks a name up in both
+TANGENT_RICHARDS = dict(saturation=3, pressure_head=4)
+
+
+def tangent_id(name: str) -> int:
+    for table in (TANGENT, TANGENT_RICHARDS):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
+
 # what a tangent record samples (TRM_TANGENT_RECORD_*)
 TANGENT_RECORD = dict(temperature=0, tangent=1)
 # the checkpointed tape of the adjoint (trm_adjoint_open_checkpointed): TRM_ADJOINT_MAX_INTERVAL, TRM_ADJOINT_DEFAULT_INTERVAL

@@ -142,9 +142,13 @@ void release_adjoint(trm_ctx* c) {
 namespace {
 // ---- what the derivatives cover, and what rides along ------------------------------------------------------------------------------
 // what the tangent and adjoint programs cover: the heat-only fp64 SoilModel in columns of one level per lane
-const char* derivative_unsupported(const trm_ctx* c) {
+// `state_seeds`: the caller is one of the six calls that TRM_OPT_DERIVATIVE_RICHARDS opens to a heat + Richards context
+bool richards(const trm_ctx* c) { return c->params.flow == TRM_FLOW_RICHARDS; }
+const char* kRichardsStateSeedsOnly = "on a Richards context: state seeds only";
+const char* derivative_unsupported(const trm_ctx* c, bool state_seeds = false) {
     if (c->precision != TRM_F64) return "fp64 contexts only";
-    if (c->params.flow == TRM_FLOW_RICHARDS) return "the heat-only SoilModel (NoFlow) only";
+    if (richards(c) && !c->opt_derivative_richards) return "the heat-only SoilModel (NoFlow) only";
+    if (richards(c) && !state_seeds) return kRichardsStateSeedsOnly;
     if (c->params.seb || c->veg_mode != TRM_VEGETATION_OFF) return "not the LandModel or vegetation";
     if (c->Nz > 64) return "columns of at most 64 levels";
     return nullptr;
@@ -181,8 +185,13 @@ int params_with_series_ok(trm_ctx* c, bool params, const char* who) {
     return fail(c, TRM_EUNSUPPORTED, std::string(who) + ": no thermal-parameter seeds or gradients together with a time series unless TRM_OPT_DERIVATIVE_SERIES_PARAMS is set");
 }
 // ... and what a step needs besides: constant inputs, no accumulation, the temperature halos of the heat-only programs
-const char* derivative_step_unsupported(const trm_ctx* c) {
-    if (const char* why = derivative_unsupported(c)) return why;
+const char* derivative_step_unsupported(const trm_ctx* c, bool state_seeds = false) {
+    if (const char* why = derivative_unsupported(c, state_seeds)) return why;
+    if (richards(c)) {      // (k_column_tangent_rich: constant boundary values, the branch-free kinds)
+        if (!c->series.empty()) return "no time series may be attached";
+        if (c->opt_vwc_field) return "no per-cell vwc_forcing field";
+        if (Policy<double>::generic_bcs(c)) return "on a Richards context: the branch-free boundary kinds only (no Value or Gradient condition on saturation, liquid fraction or pressure head, no Gradient on temperature)";
+    }
     if (!c->series.empty()) {
         if (!c->opt_derivative_series) return "no time series may be attached";
         if (const char* why = derivative_series_unsupported(c)) return why;
@@ -223,6 +232,10 @@ int require_open(trm_ctx* c, const void* open, const char* who, const char* feat
     return open ? TRM_OK : fail(c, TRM_EINVAL, std::string(who) + ": no " + feature + " open (" + opener + ")");
 }
 int tangent_open(trm_ctx* c, const char* who) { return require_open(c, c->d_tan[0], who, "tangent is", "trm_tangent_open"); }
+// the tangent fields of the context: dU, dT, dliq, and on a Richards context dsat and dpsi
+int tangent_fields(const trm_ctx* c) { return richards(c) ? TRM_TANGENT_PRESSURE_HEAD + 1 : TRM_TANGENT_LIQUID_WATER_FRACTION + 1; }
+// a call the Richards tangent does not cover, on a context with one open
+int richards_state_seeds_only(trm_ctx* c, const char* who) { return richards(c) ? fail(c, TRM_EUNSUPPORTED, std::string(who) + ": " + kRichardsStateSeedsOnly) : TRM_OK; }
 int adjoint_open(trm_ctx* c, const char* who) { return require_open(c, c->d_adj[0], who, "adjoint is", "trm_adjoint_open"); }
 // ... and an index in [0, bound) with a non-null pointer (`hint`: what the index counts, appended to the refusal)
 int which_ok(trm_ctx* c, int which, int bound, const void* ptr, const char* who, const char* hint = "") {
@@ -465,10 +478,11 @@ extern "C" {
 // ---- forward-mode tangents of the heat-only step (trm_column_tangent.hpp) ---------------------------------------------------
 int trm_tangent_open(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
-    if (const char* why = derivative_unsupported(c)) return refuse(c, "trm_tangent_open", why);
+    if (const char* why = derivative_unsupported(c, true)) return refuse(c, "trm_tangent_open", why);
     const size_t bytes = field_bytes(c);
     int rc = TRM_OK;
-    for (double*& q : c->d_tan) {
+    for (int f = 0; f < tangent_fields(c); ++f) {
+        double*& q = c->d_tan[f];
         if (const hipError_t e = alloc_if_null(q, bytes)) {
             release_tangent(c);
             return fail(c, TRM_EHIP, std::string("hipMalloc((void**)&q, bytes): ") + hipGetErrorString(e));
@@ -497,6 +511,7 @@ int trm_tangent_bc_series_upload(trm_ctx* c, int bc_var, int side, int nt, const
     TRM_ENTER_HEUN(c);
     const char* who = "trm_tangent_bc_series_upload";
     if (int rc = tangent_open(c, who)) return rc;
+    if (int rc = richards_state_seeds_only(c, who)) return rc;
     int slot = -1;
     const trm_ctx::Series* sr = nullptr;
     if (int rc = bc_series_args(c, bc_var, side, who, slot, sr)) return rc;
@@ -513,6 +528,7 @@ int trm_tangent_bc_upload(trm_ctx* c, int bc_var, int side, const void* host) {
     TRM_ENTER_HEUN(c);
     const char* who = "trm_tangent_bc_upload";
     if (int rc = tangent_open(c, who)) return rc;
+    if (int rc = richards_state_seeds_only(c, who)) return rc;
     int slot = -1;
     if (int rc = bc_pair_args(c, bc_var, side, host, who, "its seeds have the series' shape (trm_tangent_bc_series_upload)", slot)) return rc;
     if (int rc = alloc_tangent_bc_seeds(c, who)) return rc;
@@ -543,7 +559,9 @@ int trm_tangent_param_set(trm_ctx* c, const double seed[TRM_THERMAL_PARAM_COUNT]
 int trm_tangent_upload(trm_ctx* c, int which, const void* host) {
     TRM_ENTER_HEUN(c);
     if (int rc = tangent_open(c, "trm_tangent_upload")) return rc;
-    if (int rc = which_ok(c, which, TRM_TANGENT_LIQUID_WATER_FRACTION + 1, host, "trm_tangent_upload")) return rc;
+    if (int rc = which_ok(c, which, tangent_fields(c), host, "trm_tangent_upload")) return rc;
+    // (a Richards context takes its two seeds: dT, dliq and dpsi are the closure's)
+    if (richards(c) && which != TRM_TANGENT_INTERNAL_ENERGY && which != TRM_TANGENT_SATURATION) return which_ok(c, -1, 0, host, "trm_tangent_upload");
     if (int rc = upload_3d<double>(c, (const double*)host, c->d_tan[which])) return rc;
     if (which == TRM_TANGENT_INTERNAL_ENERGY) c->tan_stale = false;
     return TRM_OK;
@@ -551,14 +569,14 @@ int trm_tangent_upload(trm_ctx* c, int which, const void* host) {
 int trm_tangent_download(trm_ctx* c, int which, void* host) {
     TRM_ENTER_HEUN(c);
     if (int rc = tangent_open(c, "trm_tangent_download")) return rc;
-    if (int rc = which_ok(c, which, TRM_TANGENT_LIQUID_WATER_FRACTION + 1, host, "trm_tangent_download")) return rc;
-    if (which != TRM_TANGENT_INTERNAL_ENERGY && c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_download") + kStaleTangent);
+    if (int rc = which_ok(c, which, tangent_fields(c), host, "trm_tangent_download")) return rc;
+    if (which != TRM_TANGENT_INTERNAL_ENERGY && which != TRM_TANGENT_SATURATION && c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_download") + kStaleTangent);
     return download_3d<double>(c, c->d_tan[which], (double*)host);
 }
 int trm_tangent_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_elems) {
     TRM_ENTER_HEUN(c);
     if (int rc = tangent_open(c, "trm_tangent_device_ptr")) return rc;
-    if (int rc = which_ok(c, which, TRM_TANGENT_LIQUID_WATER_FRACTION + 1, dev, "trm_tangent_device_ptr")) return rc;
+    if (int rc = which_ok(c, which, tangent_fields(c), dev, "trm_tangent_device_ptr")) return rc;
     if (int rc = which_ok(c, 0, 1, pitch_elems, "trm_tangent_device_ptr")) return rc;
     *dev = c->d_tan[which];
     *pitch_elems = c->Nzp;
@@ -567,8 +585,9 @@ int trm_tangent_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_ele
 int trm_tangent_closure(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
     if (int rc = tangent_open(c, "trm_tangent_closure")) return rc;
-    if (const char* why = derivative_unsupported(c)) return refuse(c, "trm_tangent_closure", why);
+    if (const char* why = derivative_unsupported(c, true)) return refuse(c, "trm_tangent_closure", why);
     if (c->tan_stale) return fail(c, TRM_ESTALE, std::string("trm_tangent_closure") + kStaleTangent);
+    if (richards(c)) return finish(c, TangentRichLaunch::closure(c));
     return finish(c, TangentLaunch::closure(c, tangent_ride(c, 0)));
 }
 int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
@@ -576,10 +595,23 @@ int trm_step_tangent(trm_ctx* c, double dt, int nsteps) {
     const char* who = "trm_step_tangent";
     if (int rc = tangent_open(c, who)) return rc;
     if (nsteps < 0) return fail(c, TRM_EINVAL, "trm_step_tangent: nsteps < 0");
-    if (const char* why = derivative_step_unsupported(c)) return refuse(c, who, why);
+    if (const char* why = derivative_step_unsupported(c, true)) return refuse(c, who, why);
     const int nser = derivative_series_count(c);
     if (int rc = params_with_series_ok(c, c->tan_param_seeded, who)) return rc;
     if (c->tan_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTangent);
+    if (richards(c)) {      // (state seeds alone: no ride, no record, no series -- the launches of trm_step's multi-step program)
+        bc_changed(c);
+        const int spl = derivative_steps_per_launch(c);
+        for (int n = 0, m; n < nsteps; n += m) {
+            m = std::min(spl, nsteps - n);
+            int rc = Unfused<double>::update_inputs(c, c->state, c->time);
+            if (!rc) rc = TangentRichLaunch::step(c, dt, m);
+            if (rc) return rc;
+            c->derivative_series = 0;
+            tick(c, dt, m);
+        }
+        return derivative_steps_done(c);
+    }
     if (nser) {   // series ride with the boundary-seeded instances: the per-column seeds, and zeros for a series nobody has seeded
         if (int rc = alloc_tangent_bc_seeds(c, who)) return rc;
         for (const auto& sr : c->series) {

@@ -173,9 +173,10 @@ struct trm_ctx {
     struct Average { int field = -1; double* d_sum = nullptr; double window = 0.0; int64_t steps = 0; };
     std::vector<Average> averages;
     double* d_acc_partial[trm::ACC_SLOTS] = {};   // the fused path's partials of a field with more than one open accumulator
-    // forward-mode tangents (trm_tangent_*): dU, dT, dliq in the device layout of a 3-D field ([Nh][Nzp] doubles), null while closed.
+    // forward-mode tangents (trm_tangent_*): dU, dT, dliq in the device layout of a 3-D field ([Nh][Nzp] doubles), null while closed; on a
+    // Richards context (TRM_OPT_DERIVATIVE_RICHARDS) also dsat and dpsi, which are allocated there and nowhere else.
     // `tan_stale`: another call has changed the state since the tangent was seeded (trm_tangent_upload of dU clears it).
-    double* d_tan[3] = {};
+    double* d_tan[5] = {};
     bool tan_stale = false;
     // the seeds of the boundary values (trm_tangent_bc_upload), [Nh] doubles each: d(temperature value) bottom, top, d(internal-energy
     // flux) bottom, top.  Allocated by the first upload, zeroed by trm_tangent_open; `tan_bc_seeded`: one has been uploaded since
@@ -193,6 +194,8 @@ struct trm_ctx {
     int opt_derivative_series = 0, derivative_series = 0;
     // TRM_OPT_DERIVATIVE_SERIES_PARAMS: thermal-parameter seeds / gradients ride together with the series (RIDE_PARAM_SERIES)
     int opt_derivative_series_params = 0;
+    // TRM_OPT_DERIVATIVE_RICHARDS: the tangent's state-seed calls accept a heat + Richards context (k_column_tangent_rich)
+    int opt_derivative_richards = 0;
     // the seeds of the seriesed pairs (trm_tangent_bc_series_upload), [nt][Nh] doubles in the order of d_tan_bc, `tan_bcs_nt` their
     // levels; null: none yet (trm_step_tangent allocates zeros).  Zeroed by trm_tangent_open, freed by trm_tangent_close.
     double* d_tan_bcs[4] = {};
@@ -691,6 +694,12 @@ template <bool CKPT, Ride R, bool RECORD> int adjoint_backward(trm_ctx* c, doubl
 struct TangentLaunch {
     static int step(trm_ctx* c, double dt, int nsteps, Ride ride, bool record);
     static int closure(trm_ctx* c, Ride ride);
+};
+// k_column_tangent_rich / k_closure_tangent_rich (fp64 heat + Richards, state seeds alone: TRM_OPT_DERIVATIVE_RICHARDS), both in
+// trm_launch_column_tangent_rich.hip
+struct TangentRichLaunch {
+    static int step(trm_ctx* c, double dt, int nsteps);
+    static int closure(trm_ctx* c);
 };
 // k_column_record / k_column_adjoint{,_record} (fp64 NoFlow only): `slot` is the tape slot of the launch's first step; k_param_reduce ends
 // a sweep with parameter gradients on either tape (trm_launch_column_adjoint_param.hip)

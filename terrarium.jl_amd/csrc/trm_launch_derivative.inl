@@ -9,6 +9,7 @@
 #include "trm_host.hpp"
 #include "trm_column_adjoint_ckpt.hpp"
 #include "trm_column_tangent_record.hpp"
+#include "trm_column_tangent_rich.hpp"
 
 namespace trmh {
 
@@ -217,6 +218,46 @@ template <Ride R> int tangent_closure(trm_ctx* c) {
     hipLaunchKernelGGL((k_closure_tangent<R>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, la.state, la.p, ta);
     TRM_HIP(c, hipGetLastError());
     return TRM_OK;
+}
+
+// ---- the heat + Richards tangent (k_column_tangent_rich, trm_column_tangent_rich.hpp; TRM_OPT_DERIVATIVE_RICHARDS): state seeds alone, no
+// ride.  Templates so that only the translation unit that instantiates them (trm_launch_column_tangent_rich.hip) holds the kernels.
+// The preconditions: a Richards context, the branch-free boundary kinds (the generic halos are not part of the kernel), the five fields
+inline int tangent_rich_ok(trm_ctx* c, const std::string& who) {
+    if (c->params.flow != TRM_FLOW_RICHARDS) return fail(c, TRM_EINVAL, who + ": a Richards context only");
+    if (Policy<double>::generic_bcs(c)) return fail(c, TRM_EINVAL, who + ": the generic boundary kinds");
+    return arrays_ok(c, c->d_tan, who, "tangent fields");
+}
+inline RichTangentArgs rich_tangent_args(const trm_ctx* c) {
+    return RichTangentArgs{c->d_tan[TRM_TANGENT_INTERNAL_ENERGY], c->d_tan[TRM_TANGENT_SATURATION], c->d_tan[TRM_TANGENT_TEMPERATURE],
+                           c->d_tan[TRM_TANGENT_LIQUID_WATER_FRACTION], c->d_tan[TRM_TANGENT_PRESSURE_HEAD]};
+}
+template <class = void> int tangent_step_rich(trm_ctx* c, double dt, int nsteps) {
+    const std::string who = "k_column_tangent_rich";
+    if (int rc = tangent_rich_ok(c, who)) return rc;
+    if (nsteps < 0) return fail(c, TRM_EINVAL, who + ": bad launch");
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
+    const RichTangentArgs ta = rich_tangent_args(c);
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        hipLaunchKernelGGL((k_column_tangent_rich<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, ta);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_TANGENT_RICHARDS, H, LPC, 0, 0);
+        return (int)TRM_OK;
+    });
+}
+template <class = void> int tangent_closure_rich(trm_ctx* c) {
+    if (int rc = tangent_rich_ok(c, "k_closure_tangent_rich")) return rc;
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const size_t cells = (size_t)c->Nh * (size_t)c->Nzp;
+    const RichTangentArgs ta = rich_tangent_args(c);
+    int rc = TRM_OK;
+    by_hyd(Policy<double>::hyd(c), [&](auto h) {
+        hipLaunchKernelGGL((k_closure_tangent_rich<decltype(h)::value>), dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, la.state, la.p, ta);
+        if (hipGetLastError() != hipSuccess) rc = fail(c, TRM_EHIP, "k_closure_tangent_rich: the launch failed");
+    });
+    return rc;
 }
 
 // k_column_record on the per-step tape (`slot`: of the launch's first step) or STRIDED on the checkpointed one (the stores before the

@@ -1,7 +1,8 @@
 """Derivatives of the heat-only SoilModel run through a `ModelIntegrator`: forward-mode tangents (`jvp`, `record_jvp`), reverse-mode
 gradients (`vjp`) and the misfit to a temperature record with its gradient (`misfit_gradient`, `record_gradient`,
-`record_normal_equations`).  The drivers issue the calls of `DeviceState` (trm_tangent_*, trm_adjoint_*); the two skeletons they share
-are `_tangent_run` and `_taped`."""
+`record_normal_equations`).  `jvp` alone also covers the heat + Richards run, with seeds on the initial internal energy and saturation
+(the option `derivative_richards`).  The drivers issue the calls of `DeviceState` (trm_tangent_*, trm_adjoint_*); the two skeletons they
+share are `_tangent_run` and `_taped`."""
 from contextlib import contextmanager
 
 import numpy as np
@@ -9,6 +10,7 @@ import numpy as np
 from . import _capi
 from .io import RasterInputSource
 from .integrator import FieldTimeSeries, ForwardEuler, ModelIntegrator, checkpoint, restore
+from .models import RichardsEq
 
 # the (variable, side) pairs whose boundary value the heat-only step reads, and the kinds that read it
 _BOUNDARY_DERIVATIVE_KINDS = {"temperature": ("value", "gradient"), "internal_energy": ("flux",)}
@@ -55,11 +57,41 @@ def _refuse_uncovered(integ, who):
         raise ValueError(f"{who}: boundary conditions and inputs must be constant over the run")
 
 
-def _tangent_run(integ, steps, d_internal_energy, d_boundary, d_params, record, result):
+class _derivative_richards:
+    """Sets the option `derivative_richards` for the duration of a jvp call on a heat + Richards integrator."""
+
+    def __init__(self, integ):
+        self.st = integ.state
+        self.wanted = _richards(integ)
+
+    def __enter__(self):
+        if self.wanted:      # (a heat-only run makes the calls it always made)
+            self.before = self.st.get_option("derivative_richards")
+            self.st.set_option("derivative_richards", 1)
+        return self
+
+    def __exit__(self, *exc):
+        if self.wanted:
+            self.st.set_option("derivative_richards", self.before)
+        return False
+
+
+def _richards(integ):
+    """The integrator's model has RichardsEq (read off the model, not the state: a heat-only run makes the calls it always made)."""
+    hydrology = getattr(getattr(getattr(integ, "model", None), "soil", None), "hydrology", None)
+    return isinstance(getattr(hydrology, "vertical_flow", None), RichardsEq)
+
+
+def _tangent_run(integ, steps, d_internal_energy, d_boundary, d_params, record, result, d_saturation=None):
     """The tangent drivers: opens the tangent unless it is open, sets the series options, seeds U, the boundary pairs and the
     parameters, attaches `record` = (positions, levels) if one is given, steps, and returns `result(state)`.  On the way out it closes
     the tangent if it opened it, and otherwise detaches the record it attached."""
     st = integ.state
+    with _derivative_richards(integ):
+        return _tangent_run_open(integ, st, steps, d_internal_energy, d_boundary, d_params, record, result, d_saturation)
+
+
+def _tangent_run_open(integ, st, steps, d_internal_energy, d_boundary, d_params, record, result, d_saturation):
     opened = not getattr(st, "_tangent_open", False)
     if opened:
         st.open_tangent()
@@ -67,6 +99,8 @@ def _tangent_run(integ, steps, d_internal_energy, d_boundary, d_params, record, 
     try:
         with _derivative_series(integ, params=d_params is not None):
             st.set_tangent("internal_energy", d_internal_energy)
+            if _richards(integ):
+                st.set_tangent("saturation", 0.0 if d_saturation is None else d_saturation)
             for (var, side), values in (d_boundary or {}).items():
                 if _series_driven(integ, var, side):
                     st.set_bc_series_tangent(var, side, values)
@@ -140,10 +174,27 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, 
     with a boundary series, and with seeds on its nodes, in one run: the option `derivative_series_params` is set for the duration of
     the call as well.
     The heat-only SoilModel in fp64 with ForwardEuler and boundary conditions that are constant over the run or whole-record time
-    series (trm_step_tangent); callables, state functions and windowed sources are refused."""
+    series (trm_step_tangent); callables, state functions and windowed sources are refused.
+    On an integrator with `RichardsEq` (heat + Richards, the branch-free boundary kinds, constant boundary values) the seeds are the
+    state's: `d_internal_energy` may be a dict {"internal_energy": dU, "saturation": dsat} (each [Nz][Nh], or anything that broadcasts
+    to it; one left out is zero) -- a plain value seeds the internal energy alone -- and the result holds five tangents: `saturation`
+    and `pressure_head` beside the three above.  The option `derivative_richards` is set for the duration of the call.  `d_boundary`
+    and `d_params` are refused there; a saturation seed on a heat-only integrator raises a ValueError (its saturation is a constant)."""
     _refuse_uncovered(integ, "jvp")
+    d_saturation = None
+    if isinstance(d_internal_energy, dict):
+        unknown = sorted(set(d_internal_energy) - {"internal_energy", "saturation"})
+        if unknown:
+            raise KeyError(f"jvp: no state seed {unknown[0]!r} (internal_energy, saturation)")
+        d_saturation = d_internal_energy.get("saturation")
+        d_internal_energy = d_internal_energy.get("internal_energy", 0.0)
+    names = list(_capi.TANGENT)
+    if _richards(integ):
+        names += list(_capi.TANGENT_RICHARDS)
+    elif d_saturation is not None:
+        raise ValueError("jvp: saturation seeds need an integrator with RichardsEq (the heat-only run keeps its saturation)")
     return _tangent_run(integ, int(steps), d_internal_energy, d_boundary, d_params, None,
-                        lambda st: {name: st.tangent(name) for name in _capi.TANGENT})
+                        lambda st: {name: st.tangent(name) for name in names}, d_saturation)
 
 
 def record_jvp(integ: ModelIntegrator, positions, levels, d_internal_energy=0.0, d_boundary=None, d_params=None, steps=None):

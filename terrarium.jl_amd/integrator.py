@@ -422,10 +422,11 @@ class DeviceState:
         self._tangent_open = False
 
     def set_tangent(self, name, value):
-        """Seeds a tangent field ([Nz][Nh], or anything that broadcasts to it); `internal_energy` is the seed dU."""
+        """Seeds a tangent field ([Nz][Nh], or anything that broadcasts to it); `internal_energy` is the seed dU, and on a Richards
+        context (option `derivative_richards`) `saturation` the seed dsat."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
         a[...] = value
-        self._check(self._lib.trm_tangent_upload(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_tangent_upload")
+        self._check(self._lib.trm_tangent_upload(self._ctx, _capi.tangent_id(name), a.ctypes.data), "trm_tangent_upload")
 
     def set_bc_tangent(self, var, side, values):
         """Seeds the boundary value of (`var`, `side`) -- `temperature` (a Value or a Gradient condition) or `internal_energy` (a Flux),
@@ -457,9 +458,9 @@ class DeviceState:
         self._check(self._lib.trm_tangent_param_set(self._ctx, a), "trm_tangent_param_set")
 
     def tangent(self, name) -> np.ndarray:
-        """A tangent field as [Nz][Nh] (row 0 = bottom layer)."""
+        """A tangent field as [Nz][Nh] (row 0 = bottom layer); `saturation` and `pressure_head` on a Richards context."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
-        self._check(self._lib.trm_tangent_download(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_tangent_download")
+        self._check(self._lib.trm_tangent_download(self._ctx, _capi.tangent_id(name), a.ctypes.data), "trm_tangent_download")
         return a
 
     def tangent_closure(self):
