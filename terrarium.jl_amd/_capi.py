@@ -8,15 +8,16 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRM_LIBRARY", os.path.join(_HERE, "libterrarium_hip.so"))  # override: kernel-tuning experiments
 
+# One literal table per enum of the header, named by its prefix: a name is the enumerator's without the prefix, in lower case
 TRM_F64, TRM_F32 = 0, 1
-FLOW = dict(noflow=0, richards=1)
-SWRC = dict(brooks_corey=0, van_genuchten=1)
-UNSATK = dict(linear=0, van_genuchten=1)
-HALO = dict(reference_zero=0, mirror=1)
-BC_KIND = dict(noflux=0, value=1, flux=2, gradient=3)
-SIDE = dict(bottom=0, top=1)
-BC_VAR = dict(internal_energy=0, saturation_water_ice=1, temperature=2, liquid_water_fraction=3, pressure_head=4)
-FIELD = dict(
+FLOW = dict(noflow=0, richards=1)                                   # TRM_FLOW_*
+SWRC = dict(brooks_corey=0, van_genuchten=1)                        # TRM_SWRC_*
+UNSATK = dict(linear=0, van_genuchten=1)                            # TRM_UNSATK_*
+HALO = dict(reference_zero=0, mirror=1)                             # TRM_HALO_*
+BC_KIND = dict(noflux=0, value=1, flux=2, gradient=3)               # TRM_BC_*
+SIDE = dict(bottom=0, top=1)                                        # TRM_BOTTOM, TRM_TOP
+BC_VAR = dict(internal_energy=0, saturation_water_ice=1, temperature=2, liquid_water_fraction=3, pressure_head=4)    # TRM_BCV_*
+FIELD = dict(                                                       # TRM_FIELD_* (SAI: TRM_FIELD_STEM_AREA_INDEX)
     internal_energy=0, saturation_water_ice=1, temperature=2, liquid_water_fraction=3, pressure_head=4,
     hydraulic_conductivity=5, tend_internal_energy=6, tend_saturation_water_ice=7, surface_excess_water=8,
     tend_surface_excess_water=9, water_table=10, skin_temperature=11, ground_heat_flux=12, surface_shortwave_up=13,
@@ -35,36 +36,19 @@ FIELD = dict(
 INPUT_FIELDS = ("air_temperature", "air_pressure", "windspeed", "specific_humidity", "rainfall",
                 "surface_shortwave_down", "surface_longwave_down", "albedo", "emissivity", "CO2",
                 "soil_moisture_limiting_factor", "daily_leaf_respiration", "vegetation_ground_temperature", "SAI")
-VEGETATION = dict(off=0, standalone=1, coupled=2)
+VEGETATION = dict(off=0, standalone=1, coupled=2)                   # TRM_VEGETATION_*
 VEG_PARAM_NAMES = ("tau25 Kc25 Ko25 q10_tau q10_Kc q10_Ko alpha_leaf alpha_a alpha_C3 cq k_ext T_CO2_high T_CO2_low T_photos_high "
                    "T_photos_low theta_r g1 g_min cn_sapwood cn_root aws SLA awl LAI_min LAI_max gamma_L gamma_R gamma_S nu_seed "
                    "gamma_v_min root_a root_b wilting_point field_capacity C_mass alpha_int canopy_k_ext w_can_max tau_w C_can").split()
-REDUCE = dict(sum=0, min=1, max=2, hasnan=3, volume_integral_z=4)
+REDUCE = dict(sum=0, min=1, max=2, hasnan=3, volume_integral_z=4)   # TRM_REDUCE_*
+# TRM_OPT_* and, as info_*, TRM_INFO_* (asynchronous: TRM_OPT_ASYNC)
 OPTION = dict(asynchronous=0, step_kernel=1, write_kf_every_step=2, vwc_forcing_field=3, packed_f32=4,
               derive_closure_fields=5, steps_per_launch=6, pipeline_parts=7, single_step_program=8, bc_signature=9, zero_gradient_fast=10, surface_in_launch=11,
+              defer_closure_stores=12, interior_steps=13, derivative_series=14, derivative_series_params=15, derivative_richards=16,
               info_top_arrays_current=100, info_closure_consistent=101, info_bc_signature=102, info_generic_boundary_kernels=103,
-              info_last_program=105)
-# Options and info keys added after the table above was pinned name by name (tests/test_host_and_abi.py maps every entry of OPTION
-# through a fixed list): looked up by option_id beside it; tests/test_deferred_closure_abi.py holds their header agreement.
-OPTION_LATER = dict(defer_closure_stores=12, info_closure_stored=106, info_materializations=107)
-# ... and that table is pinned as a whole by the same test: the keys of TRM_OPT_INTERIOR_STEPS have one of their own
-# (tests/test_interior_steps_abi.py)
-OPTION_INTERIOR = dict(interior_steps=13, info_interior_launches=108)
-# ... and those of TRM_OPT_DERIVATIVE_SERIES (tests/test_series_derivative_host.py)
-OPTION_DERIVATIVE = dict(derivative_series=14, info_derivative_series=109)
-# ... and TRM_OPT_DERIVATIVE_SERIES_PARAMS (tests/test_param_series_host.py)
-OPTION_DERIVATIVE_PARAMS = dict(derivative_series_params=15)
-# ... and TRM_OPT_DERIVATIVE_RICHARDS (tests/test_tangent_richards_host.py)
-OPTION_DERIVATIVE_RICHARDS = dict(derivative_richards=16)
-
-
-def option_id(name: str) -> int:
-    for table in (OPTION, OPTION_LATER, OPTION_INTERIOR, OPTION_DERIVATIVE, OPTION_DERIVATIVE_PARAMS, OPTION_DERIVATIVE_RICHARDS):
-        if name in table:
-            return table[name]
-    raise KeyError(name)
-
-KERNEL = dict(fused=0, unfused=1)
+              info_last_program=105, info_closure_stored=106, info_materializations=107, info_interior_launches=108,
+              info_derivative_series=109)
+KERNEL = dict(fused=0, unfused=1)                                   # TRM_KERNEL_*
 # TRM_INFO_LAST_PROGRAM (include/terrarium_hip.h: TRM_PROGRAM_*; trm_host.hpp: program_id)
 PROGRAM = ("none", "column_euler", "column_heun", "column_multi", "packed_f32", "generic_euler", "generic_heun", "column_land", "deep", "wide",
            "land_interleaved", "unfused", "vegetation", "packed_land", "column_tangent", "column_adjoint", "column_tangent_richards")
@@ -94,7 +78,7 @@ def decode_program(pid: int) -> dict:
 PROGRAM_AVERAGES_IN_LAUNCH, PROGRAM_AVERAGES_AFTER_LAUNCH = 1 << 28, 1 << 29
 # TRM_PROGRAM_PARAMETERS: a derivative launch that carried the thermal parameters (trm_tangent_param_set, trm_adjoint_param_open)
 PROGRAM_PARAMETERS = 1 << 31
-STATUS_NAN, STATUS_COMPOSITION, STATUS_HANDOFF_TIMEOUT = 1, 2, 4
+STATUS_NAN, STATUS_COMPOSITION, STATUS_HANDOFF_TIMEOUT = 1, 2, 4     # TRM_STATUS_* (COMPOSITION: TRM_STATUS_COMPOSITION_OUT_OF_RANGE)
 TRM_OK, TRM_EINVAL, TRM_EHIP, TRM_ENOMEM, TRM_EUNSUPPORTED, TRM_ESTALE, TRM_ECOMM = range(7)
 
 EXPORTS = (
@@ -125,24 +109,15 @@ EXPORTS = (
     "trm_tangent_record_device_ptr trm_tangent_record_info").split()
 # the thermal parameters the tangent and the adjoint differentiate (TRM_THERMAL_PARAM_*), in the order of trm_params
 THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
-# forward-mode tangents (trm_tangent_*): the tangent fields by the names of the state fields they belong to
-TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
-# ... and the two that exist only while a tangent is open on a Richards context (TRM_OPT_DERIVATIVE_RICHARDS).  A table of its own: the one
-# above is pinned as a whole (tests/test_tangent_host.py); tangent_id looks a name up in both
-TANGENT_RICHARDS = dict(saturation=3, pressure_head=4)
-
-
-def tangent_id(name: str) -> int:
-    for table in (TANGENT, TANGENT_RICHARDS):
-        if name in table:
-            return table[name]
-    raise KeyError(name)
-
+# TRM_TANGENT_*: the tangent fields by the names of the state fields they belong to; saturation and pressure_head on Richards contexts only
+TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2, saturation=3, pressure_head=4)
+# TRM_ADJOINT_*: the cotangent fields
+ADJOINT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
 # what a tangent record samples (TRM_TANGENT_RECORD_*)
 TANGENT_RECORD = dict(temperature=0, tangent=1)
 # the checkpointed tape of the adjoint (trm_adjoint_open_checkpointed): TRM_ADJOINT_MAX_INTERVAL, TRM_ADJOINT_DEFAULT_INTERVAL
 ADJOINT_MAX_INTERVAL, ADJOINT_DEFAULT_INTERVAL = 32, 16
-TIME_INDEXING = dict(linear=0, clamp=1, cyclical=2, raster=3)
+TIME_INDEXING = dict(linear=0, clamp=1, cyclical=2, raster=3)       # TRM_TIME_*
 
 
 class TrmGrid(C.Structure):

@@ -188,11 +188,11 @@ def jvp(integ: ModelIntegrator, d_internal_energy, steps: int, d_boundary=None, 
             raise KeyError(f"jvp: no state seed {unknown[0]!r} (internal_energy, saturation)")
         d_saturation = d_internal_energy.get("saturation")
         d_internal_energy = d_internal_energy.get("internal_energy", 0.0)
-    names = list(_capi.TANGENT)
-    if _richards(integ):
-        names += list(_capi.TANGENT_RICHARDS)
-    elif d_saturation is not None:
+    if d_saturation is not None and not _richards(integ):
         raise ValueError("jvp: saturation seeds need an integrator with RichardsEq (the heat-only run keeps its saturation)")
+    # (the tangent fields a context holds are the ids below a count: tangent_fields, trm_derivative_api.hip)
+    count = _capi.TANGENT["pressure_head" if _richards(integ) else "liquid_water_fraction"] + 1
+    names = [name for name, which in _capi.TANGENT.items() if which < count]
     return _tangent_run(integ, int(steps), d_internal_energy, d_boundary, d_params, None,
                         lambda st: {name: st.tangent(name) for name in names}, d_saturation)
 

@@ -426,7 +426,7 @@ class DeviceState:
         context (option `derivative_richards`) `saturation` the seed dsat."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
         a[...] = value
-        self._check(self._lib.trm_tangent_upload(self._ctx, _capi.tangent_id(name), a.ctypes.data), "trm_tangent_upload")
+        self._check(self._lib.trm_tangent_upload(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_tangent_upload")
 
     def set_bc_tangent(self, var, side, values):
         """Seeds the boundary value of (`var`, `side`) -- `temperature` (a Value or a Gradient condition) or `internal_energy` (a Flux),
@@ -460,7 +460,7 @@ class DeviceState:
     def tangent(self, name) -> np.ndarray:
         """A tangent field as [Nz][Nh] (row 0 = bottom layer); `saturation` and `pressure_head` on a Richards context."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
-        self._check(self._lib.trm_tangent_download(self._ctx, _capi.tangent_id(name), a.ctypes.data), "trm_tangent_download")
+        self._check(self._lib.trm_tangent_download(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_tangent_download")
         return a
 
     def tangent_closure(self):
@@ -528,12 +528,12 @@ class DeviceState:
         """The cotangent of a final field ([Nz][Nh], or anything that broadcasts to it)."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
         a[...] = value
-        self._check(self._lib.trm_adjoint_upload(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_adjoint_upload")
+        self._check(self._lib.trm_adjoint_upload(self._ctx, _capi.ADJOINT[name], a.ctypes.data), "trm_adjoint_upload")
 
     def cotangent(self, name) -> np.ndarray:
         """A cotangent field as [Nz][Nh] (row 0 = bottom layer); after adjoint_backward `internal_energy` is dL/dU_0."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
-        self._check(self._lib.trm_adjoint_download(self._ctx, _capi.TANGENT[name], a.ctypes.data), "trm_adjoint_download")
+        self._check(self._lib.trm_adjoint_download(self._ctx, _capi.ADJOINT[name], a.ctypes.data), "trm_adjoint_download")
         return a
 
     def open_bc_gradient(self):
@@ -591,7 +591,7 @@ class DeviceState:
             if w is None:
                 continue
             lv, a = self._observed(levels, w)
-            self._check(self._lib.trm_adjoint_observe(self._ctx, _capi.TANGENT[name], lv.size, lv.ctypes.data, a.ctypes.data), "trm_adjoint_observe")
+            self._check(self._lib.trm_adjoint_observe(self._ctx, _capi.ADJOINT[name], lv.size, lv.ctypes.data, a.ctypes.data), "trm_adjoint_observe")
 
     def observe_misfit(self, levels, observed, weight=None):
         """1/2 w (T - observed)^2 on `levels` of the temperature held now joins the loss, per column (trm_adjoint_observe_misfit):
@@ -789,11 +789,11 @@ class DeviceState:
     def set_option(self, option, value):
         if option == "step_kernel" and isinstance(value, str):
             value = _capi.KERNEL[value]
-        self._check(self._lib.trm_set_option(self._ctx, _capi.option_id(option), int(value)), "trm_set_option")
+        self._check(self._lib.trm_set_option(self._ctx, _capi.OPTION[option], int(value)), "trm_set_option")
 
     def get_option(self, option) -> int:
         v = C.c_int()
-        self._check(self._lib.trm_get_option(self._ctx, _capi.option_id(option), C.byref(v)), "trm_get_option")
+        self._check(self._lib.trm_get_option(self._ctx, _capi.OPTION[option], C.byref(v)), "trm_get_option")
         return int(v.value)
 
     def last_program(self) -> dict:

@@ -1,28 +1,24 @@
 """Reverse-mode gradients without a GPU: the C ABI of trm_adjoint_* / trm_step_record and its Python binding."""
 import ctypes
-import os
-import re
 
+import abi_header
 import terrarium_jl_amd as trm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("trm_adjoint_open", "trm_adjoint_close", "trm_adjoint_upload", "trm_adjoint_download", "trm_adjoint_device_ptr",
          "trm_adjoint_tape", "trm_step_record", "trm_adjoint_backward")
 
 
 def test_library_exports_the_adjoint_entry_points():
-    header = open(os.path.join(ROOT, "include", "terrarium_hip.h")).read()
     lib = ctypes.CDLL(trm._capi.LIB_PATH)
     for name in NAMES:
-        assert re.search(r"\bint\s+" + name + r"\(", header), name
+        assert name in abi_header.functions(), name
         assert hasattr(lib, name) and name in trm._capi.EXPORTS, name
-    enum = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(TRM_[A-Z0-9_]+)\s*=\s*(\d+)", header)}
+    enum = abi_header.enums()
     # the cotangent fields take the tangent's field codes
     for field in ("INTERNAL_ENERGY", "TEMPERATURE", "LIQUID_WATER_FRACTION"):
-        assert enum["TRM_ADJOINT_" + field] == enum["TRM_TANGENT_" + field], field
+        assert enum["TRM_ADJOINT_" + field] == enum["TRM_TANGENT_" + field] == trm._capi.ADJOINT[field.lower()], field
     assert enum["TRM_PROGRAM_COLUMN_ADJOINT"] == 15 == trm._capi.PROGRAM.index("column_adjoint")
     assert enum["TRM_PROGRAM_COLUMN_TANGENT"] == 14
-    assert re.search(r"#define\s+TRM_ABI_VERSION\s+20\b", header) and trm._capi.lib().trm_abi_version() == 20
 
 
 def test_no_context_is_refused_without_a_gpu():

@@ -2,34 +2,18 @@
 import os
 import re
 
+import abi_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _enum():
-    header = open(os.path.join(ROOT, "include", "terrarium_hip.h")).read()
-    return header, {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(TRM_[A-Z0-9_]+)\s*=\s*(\d+)", header)}
-
-
 def test_later_options_agree_with_the_header():
+    """(the whole table, its one id space and the ABI version: tests/test_abi_tables.py)"""
     from terrarium_jl_amd import _capi
-    _, enum = _enum()
-    names = {"defer_closure_stores": "TRM_OPT_DEFER_CLOSURE_STORES", "info_closure_stored": "TRM_INFO_CLOSURE_STORED",
-             "info_materializations": "TRM_INFO_MATERIALIZATIONS"}
-    assert set(_capi.OPTION_LATER) == set(names)
-    for name, key in names.items():
-        assert enum[key] == _capi.OPTION_LATER[name] == _capi.option_id(name), name
-    assert (enum["TRM_OPT_DEFER_CLOSURE_STORES"], enum["TRM_INFO_CLOSURE_STORED"], enum["TRM_INFO_MATERIALIZATIONS"]) == (12, 106, 107)
-    # one id space: no value is used twice, no name sits in both tables
-    assert not set(_capi.OPTION) & set(_capi.OPTION_LATER)
-    ids = list(_capi.OPTION.values()) + list(_capi.OPTION_LATER.values())
-    assert len(ids) == len(set(ids))
-    for name, oid in _capi.OPTION.items():
-        assert _capi.option_id(name) == oid
-
-
-def test_abi_version_unchanged():
-    header, _ = _enum()
-    assert int(re.search(r"#define\s+TRM_ABI_VERSION\s+(\d+)", header).group(1)) == 20
+    enum = abi_header.enums()
+    assert enum["TRM_OPT_DEFER_CLOSURE_STORES"] == 12 == _capi.OPTION["defer_closure_stores"]
+    assert enum["TRM_INFO_CLOSURE_STORED"] == 106 == _capi.OPTION["info_closure_stored"]
+    assert enum["TRM_INFO_MATERIALIZATIONS"] == 107 == _capi.OPTION["info_materializations"]
 
 
 def test_column_args_layout_unchanged():

@@ -65,7 +65,7 @@ def test_land_with_forcing_series(hydraulics, dtype, tol):
 
 def test_series_equals_host_interpolation():
     """Independent of the oracle: stepping with a device series == stepping one step at a time with the inputs
-    interpolated on the host by v2 * f + v1 * (1 - f) (the formula in include/terrarium_hip.h)."""
+    interpolated on the host by v2 * f + v1 * (1 - f) (the formula in the C header, at TRM_TIME_*)."""
     lat, lon = small_columns(64)
     w = W.make_workload("land", lat, lon, 32)
     a, b = W.setup_device(w), W.setup_device(w)

@@ -10,7 +10,7 @@ import workloads as W
 
 pytestmark = pytest.mark.gpu
 
-T_TOP, LAND = 2, 64      # BCSIG bits (include/terrarium_hip.h: TRM_INFO_BC_SIGNATURE)
+T_TOP, LAND = 2, 64      # BCSIG bits (the C header: TRM_INFO_BC_SIGNATURE)
 
 
 def steady_program(w, steps_per_launch=1, heun=False, nsteps=3):

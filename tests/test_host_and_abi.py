@@ -1,32 +1,24 @@
-"""CPU-only checks: the C ABI library loads and exports every symbol include/terrarium_hip.h declares
+"""CPU-only checks: the C ABI library loads and exports every symbol the C header declares
 (no compute without a GPU), and the host-side mirror of the reference interface behaves."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import terrarium_jl_amd as trm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "terrarium_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(trm_[a-z_0-9]+)\s*\(", text)))
-
-
 def test_library_exports_every_declared_symbol():
-    names = declared_symbols()
+    names = abi_header.functions()
     assert len(names) >= 30
     lib = ctypes.CDLL(trm._capi.LIB_PATH)
     for n in names:
         assert hasattr(lib, n), f"libterrarium_hip.so does not export {n}"
     assert sorted(trm._capi.EXPORTS) == names  # the Python binding covers the whole ABI, nothing more
-    header = open(os.path.join(ROOT, "include", "terrarium_hip.h")).read()
-    assert lib.trm_abi_version() == int(re.search(r"#define\s+TRM_ABI_VERSION\s+(\d+)", header).group(1))
 
 
 def test_default_params_match_reference_defaults():
@@ -153,39 +145,21 @@ def test_simulation_schedules():
 
 
 def test_python_constants_match_the_header():
-    """Field ids, option ids, error codes and the vegetation parameter layout of terrarium.jl_amd/_capi.py and oracle/oracle.py
-    against include/terrarium_hip.h (the header is the contract; the Python tables are copies)."""
+    """The oracle's field ids and the vegetation parameter layout of terrarium.jl_amd/_capi.py and oracle/oracle.py against the header
+    (the header is the contract; the Python tables are copies: every enum table of _capi is held to it by tests/test_abi_tables.py)."""
     import re
     import oracle
     from terrarium_jl_amd import _capi
-    header = open(os.path.join(ROOT, "include", "terrarium_hip.h")).read()
-    enum = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(TRM_[A-Z0-9_]+)\s*=\s*(\d+)", header)}
-    alias = dict(SAI="STEM_AREA_INDEX", tend_internal_energy="TEND_INTERNAL_ENERGY")
-    for name, fid in _capi.FIELD.items():
-        key = "TRM_FIELD_" + alias.get(name, name).upper()
-        assert enum[key] == fid, (name, key)
-    assert enum["TRM_FIELD_COUNT"] == max(_capi.FIELD.values()) + 1 == len(_capi.FIELD)
+    enum, header = abi_header.enums(), abi_header.text()
     for name, fid in oracle.FIELDS.items():          # the oracle's table is a subset with the same ids
-        assert _capi.FIELD[name] == fid, name
-    for name, oid in _capi.OPTION.items():
-        key = {"asynchronous": "TRM_OPT_ASYNC", "step_kernel": "TRM_OPT_STEP_KERNEL", "write_kf_every_step": "TRM_OPT_WRITE_KF_EVERY_STEP",
-               "vwc_forcing_field": "TRM_OPT_VWC_FORCING_FIELD", "packed_f32": "TRM_OPT_PACKED_F32",
-               "derive_closure_fields": "TRM_OPT_DERIVE_CLOSURE_FIELDS", "steps_per_launch": "TRM_OPT_STEPS_PER_LAUNCH",
-               "pipeline_parts": "TRM_OPT_PIPELINE_PARTS", "single_step_program": "TRM_OPT_SINGLE_STEP_PROGRAM",
-               "info_top_arrays_current": "TRM_INFO_TOP_ARRAYS_CURRENT", "info_closure_consistent": "TRM_INFO_CLOSURE_CONSISTENT",
-               "bc_signature": "TRM_OPT_BC_SIGNATURE", "info_bc_signature": "TRM_INFO_BC_SIGNATURE",
-               "zero_gradient_fast": "TRM_OPT_ZERO_GRADIENT_FAST", "info_generic_boundary_kernels": "TRM_INFO_GENERIC_BOUNDARY_KERNELS",
-               "surface_in_launch": "TRM_OPT_SURFACE_IN_LAUNCH", "info_last_program": "TRM_INFO_LAST_PROGRAM"}[name]
-        assert enum[key] == oid, name
+        assert _capi.FIELD[name] == fid == enum["TRM_FIELD_" + dict(SAI="STEM_AREA_INDEX").get(name, name).upper()], name
     for code, key in enumerate(("TRM_OK", "TRM_EINVAL", "TRM_EHIP", "TRM_ENOMEM", "TRM_EUNSUPPORTED", "TRM_ESTALE", "TRM_ECOMM")):
-        assert enum[key] == code
-    assert _capi.VEGETATION == dict(off=enum["TRM_VEGETATION_OFF"], standalone=enum["TRM_VEGETATION_STANDALONE"], coupled=enum["TRM_VEGETATION_COUPLED"])
+        assert enum[key] == code == getattr(_capi, key)
     # vegetation parameter struct: the doubles of the header in order
     body = header[header.index("typedef struct trm_vegetation_params {"):header.index("} trm_vegetation_params;")]
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     names = [n.strip() for decl in re.findall(r"double([^;]+);", body) for n in decl.split(",")]
     assert names == list(_capi.VEG_PARAM_NAMES) == [f[0] for f in oracle.VegParamsD._fields_]
-    assert int(re.search(r"#define TRM_ABI_VERSION (\d+)", header).group(1)) == _capi.lib().trm_abi_version()
 
 
 # test/utils.jl:50-59 (piecewise_linear) and soil_model_init.jl:86-114
@@ -243,7 +217,7 @@ def _julia_struct_fields(name):
 
 
 def test_c_host_sees_the_struct_layout_the_julia_shim_declares(tmp_path):
-    """tests/abi_host.c -- a plain C program built with gcc against include/terrarium_hip.h that dlopens the library -- prints
+    """tests/abi_host.c -- a plain C program built with gcc against the C header that dlopens the library -- prints
     sizeof / offsetof of trm_grid, trm_params, trm_vegetation_params.  They must equal (a) the layout a Julia `ccall` derives
     from the structs INTEGRATION.md declares (C layout rules applied to the declared field order and types) and (b) the ctypes
     mirror the Python tests drive the library through."""

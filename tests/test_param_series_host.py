@@ -12,6 +12,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 import terrarium_jl_amd as trm
 import param_series_derivatives as PS
 from test_gpu_derivative_edges import BROKEN, FACTOR, SERIES_CASES, case_id
@@ -21,22 +22,11 @@ CSRC = os.path.join(ROOT, "terrarium.jl_amd", "csrc")
 UNITS = ("trm_launch_column_tangent_param_series", "trm_launch_column_adjoint_param_series", "trm_launch_column_adjoint_ckpt_param_series")
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "terrarium_hip.h")).read()
-
-
-def test_option_id_agrees_with_the_header():
+def test_option_agrees_with_the_header():
+    """(the whole table, its one id space and the ABI version: tests/test_abi_tables.py)"""
     capi = trm._capi
-    value = int(re.search(r"\bTRM_OPT_DERIVATIVE_SERIES_PARAMS\s*=\s*(\d+)", _header()).group(1))
-    assert value == 15 == capi.option_id("derivative_series_params")
-    # one id space: no table uses the name or the value twice, and the tables pinned by earlier tests are what they were
-    tables = (capi.OPTION, capi.OPTION_LATER, capi.OPTION_INTERIOR, capi.OPTION_DERIVATIVE, capi.OPTION_DERIVATIVE_PARAMS)
-    names = [n for t in tables for n in t]
-    ids = [v for t in tables for v in t.values()]
-    assert len(set(names)) == len(names) and len(set(ids)) == len(ids)
-    assert capi.OPTION_DERIVATIVE == dict(derivative_series=14, info_derivative_series=109)
-    # the ABI version stays: no entry point was added
-    assert re.search(r"#define\s+TRM_ABI_VERSION\s+20\b", _header()) and capi.lib().trm_abi_version() == 20
+    assert abi_header.enums()["TRM_OPT_DERIVATIVE_SERIES_PARAMS"] == 15 == capi.OPTION["derivative_series_params"]
+    assert (capi.OPTION["derivative_series"], capi.OPTION["info_derivative_series"]) == (14, 109)
     # a launch of the ride reports the bits both families have: nothing new to decode
     prog = capi.decode_program(14 | 1 << 26 | capi.PROGRAM_PARAMETERS)
     assert prog["boundary_seeds"] and prog["parameter_seeds"]
@@ -63,8 +53,7 @@ def test_the_ride_is_built_and_the_exports_are_what_they_were():
     for name in trm._capi.EXPORTS:
         assert hasattr(lib, name), name
     assert not any("param_series" in name or "series_param" in name for name in trm._capi.EXPORTS)
-    declared = set(re.findall(r"^(?:int|const char\*|void)\s+(trm_\w+)\(", _header(), flags=re.M))
-    assert declared == set(trm._capi.EXPORTS)
+    assert set(abi_header.functions()) == set(trm._capi.EXPORTS)
 
 
 def test_python_signatures_are_unchanged():

@@ -1,32 +1,26 @@
 """The heat + Richards tangent without a GPU: the option, the two `which` values and the program family in the header and in the Python
 tables, and the Python interface."""
 import inspect
-import os
-import re
 
 import pytest
 
+import abi_header
 import terrarium_jl_amd as trm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAPI = trm._capi
 
 
-def header_enum():
-    header = open(os.path.join(ROOT, "include", "terrarium_hip.h")).read()
-    return header, {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(TRM_[A-Z0-9_]+)\s*=\s*(\d+)", header)}
-
-
 def test_header_and_tables_agree():
-    header, enum = header_enum()
-    assert enum["TRM_OPT_DERIVATIVE_RICHARDS"] == 16 == CAPI.option_id("derivative_richards")
-    assert CAPI.TANGENT_RICHARDS == dict(saturation=enum["TRM_TANGENT_SATURATION"], pressure_head=enum["TRM_TANGENT_PRESSURE_HEAD"]) == dict(saturation=3, pressure_head=4)
-    assert [CAPI.tangent_id(x) for x in ("internal_energy", "temperature", "liquid_water_fraction", "saturation", "pressure_head")] == [0, 1, 2, 3, 4]
+    """(the whole tables and the ABI version: tests/test_abi_tables.py)"""
+    enum = abi_header.enums()
+    assert enum["TRM_OPT_DERIVATIVE_RICHARDS"] == 16 == CAPI.OPTION["derivative_richards"]
+    assert enum["TRM_TANGENT_SATURATION"] == 3 == CAPI.TANGENT["saturation"] and enum["TRM_TANGENT_PRESSURE_HEAD"] == 4 == CAPI.TANGENT["pressure_head"]
+    assert [CAPI.TANGENT[x] for x in ("internal_energy", "temperature", "liquid_water_fraction", "saturation", "pressure_head")] == [0, 1, 2, 3, 4]
     with pytest.raises(KeyError):
-        CAPI.tangent_id("hydraulic_conductivity")
-    assert enum["TRM_PROGRAM_COLUMN_TANGENT_RICHARDS"] == 16 == CAPI.PROGRAM.index("column_tangent_richards")
-    assert re.search(r"#define\s+TRM_ABI_VERSION\s+20\b", header)          # (no new entry point)
-    assert "on a Richards context: state seeds only" in header
+        CAPI.TANGENT["hydraulic_conductivity"]
+    family = "column_tangent_richards"
+    assert enum["TRM_PROGRAM_" + family.upper()] == 16 == CAPI.PROGRAM.index(family)
+    assert "on a Richards context: state seeds only" in abi_header.text()
 
 
 def test_decode_program_names_the_family():

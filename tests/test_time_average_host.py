@@ -1,13 +1,10 @@
 """Time averages without a GPU: the AveragedTimeInterval schedule and the C ABI of the accumulators."""
 import ctypes
-import os
-import re
 
 import pytest
 
+import abi_header
 import terrarium_jl_amd as trm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_window_starts_and_ends_are_event_times():
@@ -37,11 +34,9 @@ def test_bad_windows_are_refused(interval, window):
 
 
 def test_library_exports_the_average_entry_points():
-    header = open(os.path.join(ROOT, "include", "terrarium_hip.h")).read()
-    assert int(re.search(r"#define\s+TRM_ABI_VERSION\s+(\d+)", header).group(1)) == 20
     lib = ctypes.CDLL(trm._capi.LIB_PATH)
     for name in ("trm_average_open", "trm_average_reset", "trm_average_read", "trm_average_close"):
-        assert re.search(r"\bint\s+" + name + r"\(", header), name
+        assert name in abi_header.functions(), name
         assert hasattr(lib, name) and name in trm._capi.EXPORTS, name
     assert lib.trm_average_open(None, 2, None) == trm._capi.TRM_EINVAL       # no context: refused, no GPU needed
     assert trm._capi.decode_program(3 | trm._capi.PROGRAM_AVERAGES_IN_LAUNCH)["averages"] == "in_launch"
