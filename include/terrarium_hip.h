@@ -245,6 +245,15 @@ enum {
                                     /* on boundaries, parameters or series, tangent records, every trm_adjoint_* opener -- refuses a Richards      */
                                     /* context with TRM_EUNSUPPORTED "on a Richards context: state seeds only".  0 (default): every derivative    */
                                     /* call refuses a Richards context as "the heat-only SoilModel (NoFlow) only"                                 */
+    ,TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT = 17 /* 1: the per-step tape of the adjoint -- trm_adjoint_open, trm_adjoint_close, trm_adjoint_upload,  */
+                                    /* trm_adjoint_download, trm_adjoint_device_ptr, trm_adjoint_tape, trm_step_record and trm_adjoint_backward   */
+                                    /* -- accepts what TRM_OPT_DERIVATIVE_RICHARDS opens to the tangent: cotangents of the final internal energy, */
+                                    /* saturation, temperature, liquid fraction and pressure head (TRM_ADJOINT_SATURATION,                        */
+                                    /* TRM_ADJOINT_PRESSURE_HEAD), gradients with respect to the initial internal energy and saturation.          */
+                                    /* trm_adjoint_open_checkpointed, trm_adjoint_bc_open, trm_adjoint_param_open, every trm_adjoint_observe*     */
+                                    /* and trm_adjoint_record_* refuse a Richards context with TRM_EUNSUPPORTED "on a Richards context:           */
+                                    /* final-state cotangents on a per-step tape only".  Independent of TRM_OPT_DERIVATIVE_RICHARDS, which the    */
+                                    /* tangent calls still need.  0 (default): every adjoint call answers a Richards context as without it        */
 };
 /* DIAGNOSTIC, read-only (trm_get_option): which fast paths the NEXT step will take -- what the library tracks about its own
  * buffers.  Tests pin them (a wrong value costs speed, never correctness, so nothing else would notice). */
@@ -275,7 +284,8 @@ enum {
     TRM_PROGRAM_DEEP = 8, TRM_PROGRAM_WIDE = 9, TRM_PROGRAM_LAND_INTERLEAVED = 10, TRM_PROGRAM_UNFUSED = 11, TRM_PROGRAM_VEGETATION = 12,
     TRM_PROGRAM_PACKED_LAND = 13, TRM_PROGRAM_COLUMN_TANGENT = 14,
     TRM_PROGRAM_COLUMN_ADJOINT = 15,
-    TRM_PROGRAM_COLUMN_TANGENT_RICHARDS = 16   /* trm_step_tangent on a Richards context: bits 8-9 the hydraulics, 10-11 lanes per column / 32 */
+    TRM_PROGRAM_COLUMN_TANGENT_RICHARDS = 16,  /* trm_step_tangent on a Richards context: bits 8-9 the hydraulics, 10-11 lanes per column / 32 */
+    TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS = 17   /* trm_step_record and trm_adjoint_backward on a Richards context: the same bits */
 };
 /* bits of TRM_INFO_LAST_PROGRAM beside the ones above (25-27 are per family: surface processes inline / time series in the multi-step
  * program, the program and the generic boundaries of the deep and wide columns): how the step's time averages were accumulated
@@ -788,8 +798,22 @@ int trm_tangent_record_info(const trm_ctx* ctx, int* npos, int* nlevels, int64_t
  * needs before it launches anything: TRM_EINVAL with nothing stepped if they do not fit.  Its launches are still those of trm_step, so
  * one may straddle segment boundaries.  trm_adjoint_backward issues one launch per segment, newest first.  trm_adjoint_tape reports
  * the steps taped and capacity_slots x interval.  TRM_INFO_LAST_PROGRAM carries bit 27 for the launches of a checkpointed tape.
- * Errors as above; TRM_EINVAL for capacity_slots < 1 or an interval out of range. */
-enum { TRM_ADJOINT_INTERNAL_ENERGY = 0, TRM_ADJOINT_TEMPERATURE = 1, TRM_ADJOINT_LIQUID_WATER_FRACTION = 2 };
+ * Errors as above; TRM_EINVAL for capacity_slots < 1 or an interval out of range.
+ *
+ * Heat + Richards, with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT set: trm_adjoint_open, _close, _upload, _download, _device_ptr, trm_adjoint_tape,
+ * trm_step_record and trm_adjoint_backward accept what the Richards tangent covers (fp64, Nz <= 64, the branch-free boundary kinds, constant
+ * boundary values, no series, no vwc_forcing field).  L = <wU, U_n> + <wsat, sat_n> + <wT, T_n> + <wliq, liq_n> + <wpsi, psi_n>;
+ * trm_adjoint_open allocates five cotangent fields there, all five uploadable (on a NoFlow context the indices 3 and 4 are a bad
+ * argument), and a slot of the tape is 2 x Nh x Nzp x 8 bytes: the internal energy and the saturation before a step.  After
+ * trm_adjoint_backward TRM_ADJOINT_INTERNAL_ENERGY holds dL/dU_0, TRM_ADJOINT_SATURATION holds dL/dsat_0 and the other three are zero: the
+ * transpose of the linear map trm_step_tangent applies there, branch for branch.  trm_step_record leaves what trm_step(ctx, dt, nsteps, 1)
+ * leaves, bit for bit; the stored T, liq and psi are taken to be the closures of the stored U and sat.  TRM_INFO_LAST_PROGRAM of both calls is
+ * TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS.  The staleness rules are the ones above (trm_upload of the saturation makes a tape that holds steps
+ * stale).  The checkpointed tape, boundary, parameter and series gradients, observations and records refuse a Richards context with
+ * TRM_EUNSUPPORTED "on a Richards context: final-state cotangents on a per-step tape only". */
+enum { TRM_ADJOINT_INTERNAL_ENERGY = 0, TRM_ADJOINT_TEMPERATURE = 1, TRM_ADJOINT_LIQUID_WATER_FRACTION = 2,
+       TRM_ADJOINT_SATURATION = 3,      /* Richards contexts only: the cotangent of saturation_water_ice, and dL/dsat_0 after a sweep */
+       TRM_ADJOINT_PRESSURE_HEAD = 4 }; /* Richards contexts only: the cotangent of pressure_head */
 int trm_adjoint_open(trm_ctx* ctx, int capacity_steps);
 int trm_adjoint_close(trm_ctx* ctx);
 int trm_adjoint_upload(trm_ctx* ctx, int which, const void* host);

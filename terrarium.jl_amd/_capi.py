@@ -45,13 +45,15 @@ REDUCE = dict(sum=0, min=1, max=2, hasnan=3, volume_integral_z=4)   # TRM_REDUCE
 OPTION = dict(asynchronous=0, step_kernel=1, write_kf_every_step=2, vwc_forcing_field=3, packed_f32=4,
               derive_closure_fields=5, steps_per_launch=6, pipeline_parts=7, single_step_program=8, bc_signature=9, zero_gradient_fast=10, surface_in_launch=11,
               defer_closure_stores=12, interior_steps=13, derivative_series=14, derivative_series_params=15, derivative_richards=16,
+              derivative_richards_adjoint=17,
               info_top_arrays_current=100, info_closure_consistent=101, info_bc_signature=102, info_generic_boundary_kernels=103,
               info_last_program=105, info_closure_stored=106, info_materializations=107, info_interior_launches=108,
               info_derivative_series=109)
 KERNEL = dict(fused=0, unfused=1)                                   # TRM_KERNEL_*
 # TRM_INFO_LAST_PROGRAM (include/terrarium_hip.h: TRM_PROGRAM_*; trm_host.hpp: program_id)
 PROGRAM = ("none", "column_euler", "column_heun", "column_multi", "packed_f32", "generic_euler", "generic_heun", "column_land", "deep", "wide",
-           "land_interleaved", "unfused", "vegetation", "packed_land", "column_tangent", "column_adjoint", "column_tangent_richards")
+           "land_interleaved", "unfused", "vegetation", "packed_land", "column_tangent", "column_adjoint", "column_tangent_richards",
+           "column_adjoint_richards")
 DERIVE = ("none", "T_liq", "liq", "liq_psi", "all")
 
 
@@ -111,8 +113,8 @@ EXPORTS = (
 THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
 # TRM_TANGENT_*: the tangent fields by the names of the state fields they belong to; saturation and pressure_head on Richards contexts only
 TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2, saturation=3, pressure_head=4)
-# TRM_ADJOINT_*: the cotangent fields
-ADJOINT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2)
+# TRM_ADJOINT_*: the cotangent fields, the tangent fields' ids; saturation and pressure_head on Richards contexts only
+ADJOINT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2, saturation=3, pressure_head=4)
 # what a tangent record samples (TRM_TANGENT_RECORD_*)
 TANGENT_RECORD = dict(temperature=0, tangent=1)
 # the checkpointed tape of the adjoint (trm_adjoint_open_checkpointed): TRM_ADJOINT_MAX_INTERVAL, TRM_ADJOINT_DEFAULT_INTERVAL

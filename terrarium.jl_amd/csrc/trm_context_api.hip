@@ -719,7 +719,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
     c->heun_pending = false;
     // (an option that changes which program the next step takes: the arrays are made current here, not by whatever runs next)
     if (c->closure_deferred && option != TRM_OPT_ASYNC && option != TRM_OPT_WRITE_KF_EVERY_STEP && option != TRM_OPT_INTERIOR_STEPS && option != TRM_OPT_DERIVATIVE_SERIES &&
-        option != TRM_OPT_DERIVATIVE_SERIES_PARAMS && option != TRM_OPT_DERIVATIVE_RICHARDS &&
+        option != TRM_OPT_DERIVATIVE_SERIES_PARAMS && option != TRM_OPT_DERIVATIVE_RICHARDS && option != TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT &&
         !(option == TRM_OPT_DEFER_CLOSURE_STORES && value != 0)) {
         TRM_HIP(c, hipSetDevice(c->device));
         if (int rf = flush_closure(c)) return rf;
@@ -763,6 +763,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
         case TRM_OPT_DERIVATIVE_SERIES: c->opt_derivative_series = value != 0; return TRM_OK;
         case TRM_OPT_DERIVATIVE_SERIES_PARAMS: c->opt_derivative_series_params = value != 0; return TRM_OK;
         case TRM_OPT_DERIVATIVE_RICHARDS: c->opt_derivative_richards = value != 0; return TRM_OK;
+        case TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT: c->opt_derivative_richards_adjoint = value != 0; return TRM_OK;
         default: break;
     }
     return fail(c, TRM_EINVAL, "trm_set_option: unknown option or value");
@@ -790,6 +791,7 @@ int trm_get_option(const trm_ctx* c, int option, int* value) {
         case TRM_OPT_DERIVATIVE_SERIES: *value = c->opt_derivative_series; return TRM_OK;
         case TRM_OPT_DERIVATIVE_SERIES_PARAMS: *value = c->opt_derivative_series_params; return TRM_OK;
         case TRM_OPT_DERIVATIVE_RICHARDS: *value = c->opt_derivative_richards; return TRM_OK;
+        case TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT: *value = c->opt_derivative_richards_adjoint; return TRM_OK;
         case TRM_INFO_DERIVATIVE_SERIES: *value = c->derivative_series; return TRM_OK;
         case TRM_INFO_LAST_PROGRAM: *value = c->last_program; return TRM_OK;
         case TRM_INFO_GENERIC_BOUNDARY_KERNELS: *value = by_precision(c->precision, [&](auto nf) { return trmh::Policy<typename decltype(nf)::type>::generic_bcs(c); }) ? 1 : 0; return TRM_OK;

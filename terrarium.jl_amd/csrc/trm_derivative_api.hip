@@ -145,10 +145,14 @@ namespace {
 // `state_seeds`: the caller is one of the six calls that TRM_OPT_DERIVATIVE_RICHARDS opens to a heat + Richards context
 bool richards(const trm_ctx* c) { return c->params.flow == TRM_FLOW_RICHARDS; }
 const char* kRichardsStateSeedsOnly = "on a Richards context: state seeds only";
-const char* derivative_unsupported(const trm_ctx* c, bool state_seeds = false) {
+// `tape`: the caller is one of the per-step tape's calls that TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT opens to such a context; with that
+// option at 0 they answer as every other call does
+const char* kRichardsTapeOnly = "on a Richards context: final-state cotangents on a per-step tape only";
+const char* derivative_unsupported(const trm_ctx* c, bool state_seeds = false, bool tape = false) {
     if (c->precision != TRM_F64) return "fp64 contexts only";
-    if (richards(c) && !c->opt_derivative_richards) return "the heat-only SoilModel (NoFlow) only";
-    if (richards(c) && !state_seeds) return kRichardsStateSeedsOnly;
+    const bool taped = tape && c->opt_derivative_richards_adjoint;      // (independent of TRM_OPT_DERIVATIVE_RICHARDS)
+    if (richards(c) && !taped && !c->opt_derivative_richards) return "the heat-only SoilModel (NoFlow) only";
+    if (richards(c) && !taped && !state_seeds) return kRichardsStateSeedsOnly;
     if (c->params.seb || c->veg_mode != TRM_VEGETATION_OFF) return "not the LandModel or vegetation";
     if (c->Nz > 64) return "columns of at most 64 levels";
     return nullptr;
@@ -185,8 +189,8 @@ int params_with_series_ok(trm_ctx* c, bool params, const char* who) {
     return fail(c, TRM_EUNSUPPORTED, std::string(who) + ": no thermal-parameter seeds or gradients together with a time series unless TRM_OPT_DERIVATIVE_SERIES_PARAMS is set");
 }
 // ... and what a step needs besides: constant inputs, no accumulation, the temperature halos of the heat-only programs
-const char* derivative_step_unsupported(const trm_ctx* c, bool state_seeds = false) {
-    if (const char* why = derivative_unsupported(c, state_seeds)) return why;
+const char* derivative_step_unsupported(const trm_ctx* c, bool state_seeds = false, bool tape = false) {
+    if (const char* why = derivative_unsupported(c, state_seeds, tape)) return why;
     if (richards(c)) {      // (k_column_tangent_rich: constant boundary values, the branch-free kinds)
         if (!c->series.empty()) return "no time series may be attached";
         if (c->opt_vwc_field) return "no per-cell vwc_forcing field";
@@ -237,6 +241,14 @@ int tangent_fields(const trm_ctx* c) { return richards(c) ? TRM_TANGENT_PRESSURE
 // a call the Richards tangent does not cover, on a context with one open
 int richards_state_seeds_only(trm_ctx* c, const char* who) { return richards(c) ? fail(c, TRM_EUNSUPPORTED, std::string(who) + ": " + kRichardsStateSeedsOnly) : TRM_OK; }
 int adjoint_open(trm_ctx* c, const char* who) { return require_open(c, c->d_adj[0], who, "adjoint is", "trm_adjoint_open"); }
+// the cotangent fields of the context: wU, wT, wliq, and on a Richards context wsat and wpsi
+int adjoint_fields(const trm_ctx* c) { return richards(c) ? TRM_ADJOINT_PRESSURE_HEAD + 1 : TRM_ADJOINT_LIQUID_WATER_FRACTION + 1; }
+// the fields of a tape slot: U_k, and on a Richards context sat_k behind it
+size_t tape_slot_fields(const trm_ctx* c) { return richards(c) ? 2 : 1; }
+// a call the Richards adjoint does not cover, with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT set: refused before anything else happens
+int richards_tape_only(trm_ctx* c, const char* who) {
+    return richards(c) && c->opt_derivative_richards_adjoint ? fail(c, TRM_EUNSUPPORTED, std::string(who) + ": " + kRichardsTapeOnly) : TRM_OK;
+}
 // ... and an index in [0, bound) with a non-null pointer (`hint`: what the index counts, appended to the refusal)
 int which_ok(trm_ctx* c, int which, int bound, const void* ptr, const char* who, const char* hint = "") {
     return which >= 0 && which < bound && ptr ? TRM_OK : fail(c, TRM_EINVAL, std::string(who) + ": bad argument" + hint);
@@ -304,22 +316,24 @@ int open_adjoint_bc(trm_ctx* c, bool only_new, const char* who) {
 }
 // trm_adjoint_open (`interval` 0: `capacity` slots, one per step) and trm_adjoint_open_checkpointed (`capacity` checkpoint slots)
 int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who) {
-    if (const char* why = derivative_unsupported(c)) return refuse(c, who.c_str(), why);
+    if (interval)
+        if (int rc = richards_tape_only(c, who.c_str())) return rc;
+    if (const char* why = derivative_unsupported(c, false, interval == 0)) return refuse(c, who.c_str(), why);
     TRM_HIP(c, hipStreamSynchronize(c->stream));
-    const size_t bytes = field_bytes(c);
+    const size_t bytes = field_bytes(c), slot_bytes = bytes * tape_slot_fields(c);
     if (capacity != c->tape_cap || interval != c->ckpt_interval) {
         release_tape(c);
-        if (alloc_if_null(c->d_tape, (size_t)capacity * bytes) != hipSuccess) {
+        if (alloc_if_null(c->d_tape, (size_t)capacity * slot_bytes) != hipSuccess) {
             const bool was_open = c->d_adj[0] != nullptr;
             release_adjoint(c);
-            return fail(c, TRM_ENOMEM, who + ": a tape of " + std::to_string(capacity) + (interval ? " checkpoints x " : " steps x ") + std::to_string(bytes) +
+            return fail(c, TRM_ENOMEM, who + ": a tape of " + std::to_string(capacity) + (interval ? " checkpoints x " : " steps x ") + std::to_string(slot_bytes) +
                                            " bytes does not fit" + (was_open ? " (the adjoint that was open is closed)" : ""));
         }
         c->tape_cap = capacity;
         c->ckpt_interval = interval;
     }
-    for (double*& q : c->d_adj)
-        if (int rc = ensure(c, q, bytes, true, who, "the cotangent fields do not fit")) {
+    for (int f = 0; f < adjoint_fields(c); ++f)
+        if (int rc = ensure(c, c->d_adj[f], bytes, true, who, "the cotangent fields do not fit")) {
             release_adjoint(c);
             return rc;
         }
@@ -393,6 +407,7 @@ int register_observation(trm_ctx* c, int kind, int nlevels, const int32_t* level
 }
 // what both registrations check first
 int observe_args(trm_ctx* c, int nlevels, const int32_t* levels, const void* host, const char* who) {
+    if (int rc = richards_tape_only(c, who)) return rc;
     if (int rc = adjoint_open(c, who)) return rc;
     if (int rc = record_excludes_observations(c, who)) return rc;
     if (int rc = observed_levels_ok(c, nlevels, levels, who)) return rc;
@@ -426,6 +441,7 @@ int inject_observations(trm_ctx* c, int p, bool lam, bool params) {
 // The record joins the open adjoint: the level table, the residuals and the misfit are the library's; `observed` / `weight` are host arrays
 // the library copies once (`device` false) or device arrays it keeps by pointer
 int attach_record(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* observed, const void* weight, bool device, const char* who) {
+    if (int rc = richards_tape_only(c, who)) return rc;
     if (int rc = record_attach_ok(c, npos, positions, nlevels, levels, observed, device ? nullptr : (const double*)weight, who)) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     const size_t cells = (size_t)npos * (size_t)nlevels * (size_t)c->Nh, cell_bytes = cells * sizeof(double);
@@ -741,6 +757,7 @@ int trm_adjoint_close(trm_ctx* c) {
 }
 int trm_adjoint_bc_open(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
+    if (int rc = richards_tape_only(c, "trm_adjoint_bc_open")) return rc;
     if (int rc = adjoint_open(c, "trm_adjoint_bc_open")) return rc;
     return open_adjoint_bc(c, false, "trm_adjoint_bc_open");
 }
@@ -783,6 +800,7 @@ int trm_adjoint_bc_device_ptr(trm_ctx* c, int bc_var, int side, void** dev) {
 int trm_adjoint_param_open(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
     const char* who = "trm_adjoint_param_open";
+    if (int rc = richards_tape_only(c, who)) return rc;
     // (a context the adjoint does not cover has none open: it is told why, not to open one)
     if (const char* why = derivative_unsupported(c)) return refuse(c, who, why);
     if (int rc = adjoint_open(c, who)) return rc;
@@ -817,19 +835,19 @@ int trm_adjoint_param_device_ptr(trm_ctx* c, int which, void** dev) {
 int trm_adjoint_upload(trm_ctx* c, int which, const void* host) {
     TRM_ENTER_HEUN(c);
     if (int rc = adjoint_open(c, "trm_adjoint_upload")) return rc;
-    if (int rc = which_ok(c, which, TRM_ADJOINT_LIQUID_WATER_FRACTION + 1, host, "trm_adjoint_upload")) return rc;
+    if (int rc = which_ok(c, which, adjoint_fields(c), host, "trm_adjoint_upload")) return rc;
     return upload_3d<double>(c, (const double*)host, c->d_adj[which]);
 }
 int trm_adjoint_download(trm_ctx* c, int which, void* host) {
     TRM_ENTER_HEUN(c);
     if (int rc = adjoint_open(c, "trm_adjoint_download")) return rc;
-    if (int rc = which_ok(c, which, TRM_ADJOINT_LIQUID_WATER_FRACTION + 1, host, "trm_adjoint_download")) return rc;
+    if (int rc = which_ok(c, which, adjoint_fields(c), host, "trm_adjoint_download")) return rc;
     return download_3d<double>(c, c->d_adj[which], (double*)host);
 }
 int trm_adjoint_device_ptr(trm_ctx* c, int which, void** dev, int64_t* pitch_elems) {
     TRM_ENTER_HEUN(c);
     if (int rc = adjoint_open(c, "trm_adjoint_device_ptr")) return rc;
-    if (int rc = which_ok(c, which, TRM_ADJOINT_LIQUID_WATER_FRACTION + 1, dev, "trm_adjoint_device_ptr")) return rc;
+    if (int rc = which_ok(c, which, adjoint_fields(c), dev, "trm_adjoint_device_ptr")) return rc;
     if (int rc = which_ok(c, 0, 1, pitch_elems, "trm_adjoint_device_ptr")) return rc;
     *dev = c->d_adj[which];
     *pitch_elems = c->Nzp;
@@ -852,12 +870,27 @@ int trm_step_record(trm_ctx* c, double dt, int nsteps) {
     if (need > c->tape_cap - used)
         return fail(c, TRM_EINVAL, "trm_step_record: " + std::to_string(nsteps) + (K ? " steps need " + std::to_string(need) + " checkpoints (" : " steps do not fit the tape (") +
                                        std::to_string(used) + " of " + std::to_string(c->tape_cap) + " slots taken)");
-    if (const char* why = derivative_step_unsupported(c)) return refuse(c, who, why);
+    if (const char* why = derivative_step_unsupported(c, false, true)) return refuse(c, who, why);
     const int nser = derivative_series_count(c);
     if (int rc = params_with_series_ok(c, c->d_adj_param_out != nullptr, who)) return rc;
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTape);
     if (nsteps > 0) c->tan_stale = true;       // (a state-changing call for an open tangent)
     const int spl = derivative_steps_per_launch(c);
+    if (richards(c)) {      // (final-state cotangents alone: no series, no ride -- the launches of trm_step's multi-step program)
+        for (int n = 0, m; n < nsteps; n += m) {
+            m = std::min(spl, nsteps - n);
+            int rc = Unfused<double>::update_inputs(c, c->state, c->time);
+            if (!rc) rc = AdjointRichLaunch::record(c, dt, m, (int)c->tape_dt.size());
+            if (rc) {
+                c->adj_stale = taped_steps(c) > 0;
+                return rc;
+            }
+            c->derivative_series = 0;
+            tape_append(c, dt, m);
+            tick(c, dt, m);
+        }
+        return derivative_steps_done(c);
+    }
     for (int n = 0, m; n < nsteps; n += m) {
         m = std::min(spl, nsteps - n);
         // (with series: the rows of the launch's steps stay with the tape, [taped step][series])
@@ -880,10 +913,31 @@ int trm_adjoint_backward(trm_ctx* c) {
     TRM_ENTER(c);
     const char* who = "trm_adjoint_backward";
     if (int rc = adjoint_open(c, who)) return rc;
-    if (const char* why = derivative_step_unsupported(c)) return refuse(c, who, why);
+    if (const char* why = derivative_step_unsupported(c, false, true)) return refuse(c, who, why);
     const int nser = derivative_series_count(c);
     if (int rc = params_with_series_ok(c, c->d_adj_param_out != nullptr, who)) return rc;
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTape);
+    if (richards(c)) {
+        // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch folds
+        // the cotangents of T, liq and psi in (an empty tape: that launch alone)
+        const int spl = derivative_steps_per_launch(c);
+        int end = (int)c->tape_dt.size(), fold = 1;
+        do {
+            int begin = end;
+            while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
+            const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
+            if (int rc = AdjointRichLaunch::backward(c, dt_block, end - begin, begin, fold)) {
+                c->adj_stale = true;       // (lam is part way down the tape)
+                return rc;
+            }
+            c->derivative_series = 0;
+            end = begin;
+            fold = 0;
+        } while (end > 0);
+        c->tape_dt.clear();
+        c->adj_stale = false;
+        return finish(c, TRM_OK);
+    }
     // An attached record (trm_adjoint_observe_record) is read inside the launches: no position of it is a launch boundary.  A record
     // longer than the tape is refused here, in front of everything the sweep does
     const bool rec = c->rec.npos > 0;
@@ -1022,6 +1076,7 @@ int trm_adjoint_observe_record_device(trm_ctx* c, int npos, const int32_t* posit
 int trm_adjoint_record_detach(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
     const char* who = "trm_adjoint_record_detach";
+    if (int rc = richards_tape_only(c, who)) return rc;
     if (int rc = adjoint_open(c, who)) return rc;
     if (c->rec.npos == 0) return fail(c, TRM_EINVAL, std::string(who) + ": no record is attached (trm_adjoint_observe_record)");
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -1030,6 +1085,7 @@ int trm_adjoint_record_detach(trm_ctx* c) {
 }
 int trm_adjoint_record_residual_download(trm_ctx* c, void* host) {
     TRM_ENTER_HEUN(c);
+    if (int rc = richards_tape_only(c, "trm_adjoint_record_residual_download")) return rc;
     if (int rc = record_results_ok(c, host, "trm_adjoint_record_residual_download")) return rc;
     TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out, rows_bytes(c, (long)c->rec.npos * c->rec.nlevels), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -1037,6 +1093,7 @@ int trm_adjoint_record_residual_download(trm_ctx* c, void* host) {
 }
 int trm_adjoint_record_residual_device_ptr(trm_ctx* c, void** dev) {
     TRM_ENTER_HEUN(c);
+    if (int rc = richards_tape_only(c, "trm_adjoint_record_residual_device_ptr")) return rc;
     if (int rc = record_results_ok(c, dev, "trm_adjoint_record_residual_device_ptr")) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     *dev = c->d_rec_out;
@@ -1044,6 +1101,7 @@ int trm_adjoint_record_residual_device_ptr(trm_ctx* c, void** dev) {
 }
 int trm_adjoint_record_misfit_download(trm_ctx* c, void* host) {
     TRM_ENTER_HEUN(c);
+    if (int rc = richards_tape_only(c, "trm_adjoint_record_misfit_download")) return rc;
     if (int rc = record_results_ok(c, host, "trm_adjoint_record_misfit_download")) return rc;
     TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out + (size_t)c->rec.npos * (size_t)c->rec.nlevels * (size_t)c->Nh, rows_bytes(c), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -1051,6 +1109,7 @@ int trm_adjoint_record_misfit_download(trm_ctx* c, void* host) {
 }
 int trm_adjoint_record_info(const trm_ctx* c, int* npos, int* nlevels, int64_t* bytes) {
     if (!c) return TRM_EINVAL;
+    if (int rc = richards_tape_only(const_cast<trm_ctx*>(c), "trm_adjoint_record_info")) return rc;
     if (int rc = adjoint_open(const_cast<trm_ctx*>(c), "trm_adjoint_record_info")) return rc;
     if (npos) *npos = c->rec.npos;
     if (nlevels) *nlevels = c->rec.nlevels;

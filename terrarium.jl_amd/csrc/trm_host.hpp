@@ -196,6 +196,8 @@ struct trm_ctx {
     int opt_derivative_series_params = 0;
     // TRM_OPT_DERIVATIVE_RICHARDS: the tangent's state-seed calls accept a heat + Richards context (k_column_tangent_rich)
     int opt_derivative_richards = 0;
+    // TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT: the per-step tape of the adjoint accepts a heat + Richards context (k_column_adjoint_rich)
+    int opt_derivative_richards_adjoint = 0;
     // the seeds of the seriesed pairs (trm_tangent_bc_series_upload), [nt][Nh] doubles in the order of d_tan_bc, `tan_bcs_nt` their
     // levels; null: none yet (trm_step_tangent allocates zeros).  Zeroed by trm_tangent_open, freed by trm_tangent_close.
     double* d_tan_bcs[4] = {};
@@ -203,7 +205,9 @@ struct trm_ctx {
     // reverse-mode gradients (trm_adjoint_*): the cotangent fields of U, T, liq in the same layout, and the tape of trm_step_record --
     // `tape_cap` slots of [Nh][Nzp] doubles, slot k the internal energy before taped step k, `tape_dt[k]` that step's dt.  `adj_stale`:
     // another call has changed the state or a boundary condition since the first taped step (state_changed / bc_changed below).
-    double* d_adj[3] = {};
+    // On a Richards context (TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT) also the cotangent fields of sat and psi, allocated there and nowhere
+    // else, and a slot is two fields: the internal energy and, behind it, the saturation before the step.
+    double* d_adj[5] = {};
     // the boundary-gradient accumulators (trm_adjoint_bc_open), [Nh] doubles each, in the order of d_tan_bc; null: the sweep runs the
     // instances without
     double* d_adj_bc[4] = {};
@@ -700,6 +704,12 @@ struct TangentLaunch {
 struct TangentRichLaunch {
     static int step(trm_ctx* c, double dt, int nsteps);
     static int closure(trm_ctx* c);
+};
+// k_column_record_rich / k_column_adjoint_rich (fp64 heat + Richards, final-state cotangents on the per-step tape alone:
+// TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT), both in trm_launch_column_adjoint_rich.hip; `slot` is the tape slot of the launch's first step
+struct AdjointRichLaunch {
+    static int record(trm_ctx* c, double dt, int nsteps, int slot);
+    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
 };
 // k_column_record / k_column_adjoint{,_record} (fp64 NoFlow only): `slot` is the tape slot of the launch's first step; k_param_reduce ends
 // a sweep with parameter gradients on either tape (trm_launch_column_adjoint_param.hip)

@@ -10,6 +10,7 @@
 #include "trm_column_adjoint_ckpt.hpp"
 #include "trm_column_tangent_record.hpp"
 #include "trm_column_tangent_rich.hpp"
+#include "trm_column_adjoint_rich.hpp"
 
 namespace trmh {
 
@@ -258,6 +259,52 @@ template <class = void> int tangent_closure_rich(trm_ctx* c) {
         if (hipGetLastError() != hipSuccess) rc = fail(c, TRM_EHIP, "k_closure_tangent_rich: the launch failed");
     });
     return rc;
+}
+
+// ---- the heat + Richards adjoint (k_column_record_rich / k_column_adjoint_rich, trm_column_adjoint_rich.hpp;
+// TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT): final-state cotangents on the per-step tape, no ride.  Templates so that only the translation unit
+// that instantiates them (trm_launch_column_adjoint_rich.hip) holds the kernels.  A slot holds two fields, U_k and sat_k.
+// The preconditions: a Richards context, the branch-free boundary kinds, the five cotangent fields, the launch's slots inside the tape
+inline int adjoint_rich_ok(trm_ctx* c, int nsteps, int slot, const std::string& who) {
+    if (c->params.flow != TRM_FLOW_RICHARDS) return fail(c, TRM_EINVAL, who + ": a Richards context only");
+    if (Policy<double>::generic_bcs(c)) return fail(c, TRM_EINVAL, who + ": the generic boundary kinds");
+    if (int rc = arrays_ok(c, c->d_adj, who, "cotangent fields")) return rc;
+    if (!c->d_tape || c->ckpt_interval != 0) return fail(c, TRM_EINVAL, who + ": no per-step tape");
+    return tape_range_ok(c, nsteps, slot, who);
+}
+inline long long rich_slot_elems(const trm_ctx* c) { return (long long)c->Nh * (long long)c->Nzp; }
+inline RichTapeArgs rich_tape_args(const trm_ctx* c, int slot) { return RichTapeArgs{c->d_tape + (size_t)slot * 2 * (size_t)rich_slot_elems(c), rich_slot_elems(c)}; }
+inline RichSweepArgs rich_sweep_args(const trm_ctx* c, int slot, int fold) {
+    return RichSweepArgs{c->d_adj[TRM_ADJOINT_INTERNAL_ENERGY], c->d_adj[TRM_ADJOINT_SATURATION], c->d_adj[TRM_ADJOINT_TEMPERATURE],
+                         c->d_adj[TRM_ADJOINT_LIQUID_WATER_FRACTION], c->d_adj[TRM_ADJOINT_PRESSURE_HEAD], rich_tape_args(c, slot).tape, rich_slot_elems(c), fold};
+}
+template <class = void> int adjoint_record_rich(trm_ctx* c, double dt, int nsteps, int slot) {
+    const std::string who = "k_column_record_rich";
+    if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
+    const RichTapeArgs aa = rich_tape_args(c, slot);
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        hipLaunchKernelGGL((k_column_record_rich<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, 0);
+        return (int)TRM_OK;
+    });
+}
+template <class = void> int adjoint_backward_rich(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
+    const std::string who = "k_column_adjoint_rich";
+    if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
+    const RichSweepArgs aa = rich_sweep_args(c, slot, fold);
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        hipLaunchKernelGGL((k_column_adjoint_rich<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, 0);
+        return (int)TRM_OK;
+    });
 }
 
 // k_column_record on the per-step tape (`slot`: of the launch's first step) or STRIDED on the checkpointed one (the stores before the

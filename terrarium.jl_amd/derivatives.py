@@ -1,7 +1,8 @@
 """Derivatives of the heat-only SoilModel run through a `ModelIntegrator`: forward-mode tangents (`jvp`, `record_jvp`), reverse-mode
 gradients (`vjp`) and the misfit to a temperature record with its gradient (`misfit_gradient`, `record_gradient`,
-`record_normal_equations`).  `jvp` alone also covers the heat + Richards run, with seeds on the initial internal energy and saturation
-(the option `derivative_richards`).  The drivers issue the calls of `DeviceState` (trm_tangent_*, trm_adjoint_*); the two skeletons they
+`record_normal_equations`).  `jvp` also covers the heat + Richards run, with seeds on the initial internal energy and saturation
+(the option `derivative_richards`), and so does `vjp`, with cotangents of the five final fields on the per-step tape (the option
+`derivative_richards_adjoint`).  The drivers issue the calls of `DeviceState` (trm_tangent_*, trm_adjoint_*); the two skeletons they
 share are `_tangent_run` and `_taped`."""
 from contextlib import contextmanager
 
@@ -58,21 +59,23 @@ def _refuse_uncovered(integ, who):
 
 
 class _derivative_richards:
-    """Sets the option `derivative_richards` for the duration of a jvp call on a heat + Richards integrator."""
+    """Sets the option `derivative_richards` for the duration of a jvp call on a heat + Richards integrator -- for a vjp call,
+    `option` = `derivative_richards_adjoint`."""
 
-    def __init__(self, integ):
+    def __init__(self, integ, option="derivative_richards"):
         self.st = integ.state
+        self.option = option
         self.wanted = _richards(integ)
 
     def __enter__(self):
         if self.wanted:      # (a heat-only run makes the calls it always made)
-            self.before = self.st.get_option("derivative_richards")
-            self.st.set_option("derivative_richards", 1)
+            self.before = self.st.get_option(self.option)
+            self.st.set_option(self.option, 1)
         return self
 
     def __exit__(self, *exc):
         if self.wanted:
-            self.st.set_option("derivative_richards", self.before)
+            self.st.set_option(self.option, self.before)
         return False
 
 
@@ -227,8 +230,38 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
     With `wrt_params` it appends {name: dL/d(parameter) as [Nh]} for the ten thermal parameters, each column's
     share (trm_adjoint_param_open): (dL/dU_0, params), or (dL/dU_0, boundary, params) with `wrt_boundary` as well.  On a run driven by
     a boundary series too: one sweep gives dL/dU_0, the node gradients and the ten parameter gradients (the option
-    `derivative_series_params` is set for the duration of the call)."""
+    `derivative_series_params` is set for the duration of the call).
+    On an integrator with `RichardsEq` (what `jvp` covers there) the cotangents are the five final fields': `internal_energy` may be a
+    dict {"internal_energy": wU, "saturation": wsat, "temperature": wT, "liquid_water_fraction": wliq, "pressure_head": wpsi} (each
+    [Nz][Nh], or anything that broadcasts to it; one left out is zero; `temperature` and `liquid_water_fraction` may also come as the
+    arguments above) and the result is {"internal_energy": dL/dU_0, "saturation": dL/dsat_0}, L the sum of the five inner products:
+    the transpose of `jvp` there.  The option `derivative_richards_adjoint` is set for the duration of the call.  `checkpoint_every`,
+    `wrt_boundary` and `wrt_params` raise a ValueError there; a `saturation` or `pressure_head` cotangent on a heat-only integrator
+    raises a ValueError (neither field is a function of the initial internal energy)."""
     _refuse_uncovered(integ, "vjp")
+    saturation = pressure_head = None
+    if isinstance(internal_energy, dict):
+        given = dict(internal_energy)
+        unknown = sorted(set(given) - set(_capi.ADJOINT))
+        if unknown:
+            raise KeyError(f"vjp: no cotangent {unknown[0]!r} ({', '.join(_capi.ADJOINT)})")
+        if ("temperature" in given and temperature is not None) or ("liquid_water_fraction" in given and liquid_water_fraction is not None):
+            raise ValueError("vjp: a cotangent is given twice, as an argument and in the dict")
+        temperature, liquid_water_fraction = given.get("temperature", temperature), given.get("liquid_water_fraction", liquid_water_fraction)
+        saturation, pressure_head, internal_energy = given.get("saturation"), given.get("pressure_head"), given.get("internal_energy")
+    if _richards(integ):
+        for name, value in (("checkpoint_every", checkpoint_every is not None), ("wrt_boundary", wrt_boundary), ("wrt_params", wrt_params)):
+            if value:
+                raise ValueError(f"vjp: no {name} on an integrator with RichardsEq (final-state cotangents on a per-step tape only)")
+        steps = int(steps)
+        with _derivative_richards(integ, "derivative_richards_adjoint"), _taped(integ, max(steps, 1), None, False, reuse=True) as st:
+            st.step_record(integ.timestepper.dt, steps)
+            for name, w in zip(_capi.ADJOINT, (internal_energy, temperature, liquid_water_fraction, saturation, pressure_head)):
+                st.set_cotangent(name, 0.0 if w is None else w)
+            st.adjoint_backward()
+            return {name: st.cotangent(name) for name in ("internal_energy", "saturation")}
+    if saturation is not None or pressure_head is not None:
+        raise ValueError("vjp: saturation and pressure_head cotangents need an integrator with RichardsEq (the heat-only run keeps its saturation)")
     steps = int(steps)
     K = None if checkpoint_every is None else int(checkpoint_every)
     slots = max(steps, 1) if K is None else max(-(-steps // max(K, 1)), 1)

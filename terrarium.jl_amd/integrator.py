@@ -525,13 +525,15 @@ class DeviceState:
         self._record_arrays = None
 
     def set_cotangent(self, name, value):
-        """The cotangent of a final field ([Nz][Nh], or anything that broadcasts to it)."""
+        """The cotangent of a final field ([Nz][Nh], or anything that broadcasts to it); on a Richards context (option
+        `derivative_richards_adjoint`) also of `saturation` and `pressure_head`."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
         a[...] = value
         self._check(self._lib.trm_adjoint_upload(self._ctx, _capi.ADJOINT[name], a.ctypes.data), "trm_adjoint_upload")
 
     def cotangent(self, name) -> np.ndarray:
-        """A cotangent field as [Nz][Nh] (row 0 = bottom layer); after adjoint_backward `internal_energy` is dL/dU_0."""
+        """A cotangent field as [Nz][Nh] (row 0 = bottom layer); after adjoint_backward `internal_energy` is dL/dU_0 and, on a
+        Richards context, `saturation` is dL/dsat_0."""
         a = np.empty((self.grid.Nz, self.grid.Nh), dtype=np.float64)
         self._check(self._lib.trm_adjoint_download(self._ctx, _capi.ADJOINT[name], a.ctypes.data), "trm_adjoint_download")
         return a
