@@ -254,6 +254,12 @@ enum {
                                     /* and trm_adjoint_record_* refuse a Richards context with TRM_EUNSUPPORTED "on a Richards context:           */
                                     /* final-state cotangents on a per-step tape only".  Independent of TRM_OPT_DERIVATIVE_RICHARDS, which the    */
                                     /* tangent calls still need.  0 (default): every adjoint call answers a Richards context as without it        */
+    ,TRM_OPT_DERIVATIVE_RICHARDS_PARAMS = 18 /* 1, together with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT = 1: trm_adjoint_param_open on a Richards   */
+                                    /* context with an open per-step adjoint opens the gradients with respect to the seven hydraulic             */
+                                    /* parameters (TRM_HYDRAULIC_PARAM_*), and trm_adjoint_backward forms them in the same sweep                  */
+                                    /* (TRM_INFO_LAST_PROGRAM: bit 31).  trm_adjoint_bc_open, the checkpointed tape, observations and records     */
+                                    /* stay refused there.  0 (default), or without that option: every call answers a Richards context as         */
+                                    /* without it                                                                                                  */
 };
 /* DIAGNOSTIC, read-only (trm_get_option): which fast paths the NEXT step will take -- what the library tracks about its own
  * buffers.  Tests pin them (a wrong value costs speed, never correctness, so nothing else would notice). */
@@ -293,7 +299,8 @@ enum {
  * set while no accumulator is open. */
 enum { TRM_PROGRAM_AVERAGES_IN_LAUNCH = 268435456 /* 1 << 28 */, TRM_PROGRAM_AVERAGES_AFTER_LAUNCH = 536870912 /* 1 << 29 */ };
 /* ... and bit 31, the last one the two derivative families leave free (25-27 and 30 are taken there, 28-29 above): the launch carried
- * seeds on, or formed the gradient with respect to, the thermal parameters (trm_tangent_param_set, trm_adjoint_param_open).  The id is an
+ * seeds on, or formed the gradient with respect to, the thermal parameters (trm_tangent_param_set, trm_adjoint_param_open) or, in the
+ * family TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, the hydraulic parameters (TRM_OPT_DERIVATIVE_RICHARDS_PARAMS).  The id is an
  * int: with this bit it reads as a negative number, and the bits are those of its two's complement. */
 enum { TRM_PROGRAM_PARAMETERS = (-2147483647 - 1) /* bit 31 */ };
 enum {
@@ -810,7 +817,8 @@ int trm_tangent_record_info(const trm_ctx* ctx, int* npos, int* nlevels, int64_t
  * leaves, bit for bit; the stored T, liq and psi are taken to be the closures of the stored U and sat.  TRM_INFO_LAST_PROGRAM of both calls is
  * TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS.  The staleness rules are the ones above (trm_upload of the saturation makes a tape that holds steps
  * stale).  The checkpointed tape, boundary, parameter and series gradients, observations and records refuse a Richards context with
- * TRM_EUNSUPPORTED "on a Richards context: final-state cotangents on a per-step tape only". */
+ * TRM_EUNSUPPORTED "on a Richards context: final-state cotangents on a per-step tape only".  (The hydraulic parameters:
+ * TRM_OPT_DERIVATIVE_RICHARDS_PARAMS, beside trm_adjoint_param_open below.) */
 enum { TRM_ADJOINT_INTERNAL_ENERGY = 0, TRM_ADJOINT_TEMPERATURE = 1, TRM_ADJOINT_LIQUID_WATER_FRACTION = 2,
        TRM_ADJOINT_SATURATION = 3,      /* Richards contexts only: the cotangent of saturation_water_ice, and dL/dsat_0 after a sweep */
        TRM_ADJOINT_PRESSURE_HEAD = 4 }; /* Richards contexts only: the cotangent of pressure_head */
@@ -886,7 +894,37 @@ int trm_adjoint_bc_series_device_ptr(trm_ctx* ctx, int bc_var, int side, void** 
  * boundary gradients are bit for bit what the sweep without parameter gradients gives.
  * Errors: TRM_EUNSUPPORTED where the adjoint is; TRM_EINVAL without a context or an open adjoint, for _download / _device_ptr before
  * trm_adjoint_param_open, a `which` outside 0 ... TRM_THERMAL_PARAM_COUNT - 1, a NULL pointer, and for trm_adjoint_param_open when one
- * of the five conductivities is <= 0; TRM_ENOMEM. */
+ * of the five conductivities is <= 0; TRM_ENOMEM.
+ *
+ * Heat + Richards, with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT and TRM_OPT_DERIVATIVE_RICHARDS_PARAMS both set: the three calls serve the seven
+ * hydraulic parameters of trm_params (TRM_HYDRAULIC_PARAM_*: K_sat, theta_res, bc_psi_s, bc_lambda, vg_alpha, vg_n, impedance) on what the
+ * per-step tape covers there (fp64, ForwardEuler, Nz <= 64, the branch-free boundary kinds with constant values, no series, no
+ * vwc_forcing field).
+ *   trm_adjoint_param_open(ctx)             on a Richards context with an open per-step adjoint: allocates seven per-cell accumulators
+ *                                           (Nh x Nzp doubles each) and the per-column results, zero.  It does NOT imply
+ *                                           trm_adjoint_bc_open, which stays refused there.  From then on trm_adjoint_backward runs the
+ *                                           accumulating instances (TRM_INFO_LAST_PROGRAM: family 17 with bit 31) and ends with one
+ *                                           reduction launch.  trm_adjoint_open keeps them (zeroed); trm_adjoint_close frees them.
+ *   trm_adjoint_param_download(ctx, which, host) / trm_adjoint_param_device_ptr(ctx, which, &dev)
+ *                                           `which` one of the seven TRM_HYDRAULIC_PARAM_* ids, which continue the thermal ids (one id
+ *                                           space); num_columns doubles: each column's share of dL/d(parameter).
+ * The gradient is the sum over the taped steps and the cells of Kcbar dKc/dp + psibar dpsi/dp -- Kcbar and psibar the cotangents of a
+ * cell's hydraulic conductivity and pressure head in the step's transpose -- plus wpsi dpsi/dp at the stored final state.  A parameter
+ * the context's hydraulics never read gives exact zeros (vg_alpha, vg_n, impedance under Brooks-Corey with the linear conductivity;
+ * bc_psi_s, bc_lambda under van Genuchten).  d(x^a)/da = x^a ln x, and 0 where x^a is 0; a zero cotangent in front of a slope gives 0
+ * whatever the slope, so zero cotangents give exactly zero gradients and scaling them by a power of two scales the gradients bit for bit;
+ * a cell flagged as an illegal composition gives NaN.  The sums do not depend on TRM_OPT_STEPS_PER_LAUNCH or on how the trm_step_record
+ * calls were split, and dL/dU_0 and dL/dsat_0 are bit for bit those of the sweep without the parameter gradient.
+ * Errors: with either option at 0 the calls answer a Richards context as above.  TRM_EINVAL "bad argument" for the thermal ids 0 ... 9
+ * on a Richards context, for the hydraulic ids on a NoFlow context, and for a NULL pointer; TRM_EINVAL without an open adjoint or before
+ * trm_adjoint_param_open; TRM_ENOMEM.  Forward-mode seeds on these parameters, and porosity, rho_soc and vwc_forcing as parameters, are
+ * not provided. */
+enum {
+    TRM_HYDRAULIC_PARAM_K_SAT = 10,     /* = TRM_THERMAL_PARAM_COUNT: one id space with the thermal ids */
+    TRM_HYDRAULIC_PARAM_THETA_RES = 11, TRM_HYDRAULIC_PARAM_BC_PSI_S = 12, TRM_HYDRAULIC_PARAM_BC_LAMBDA = 13,
+    TRM_HYDRAULIC_PARAM_VG_ALPHA = 14, TRM_HYDRAULIC_PARAM_VG_N = 15, TRM_HYDRAULIC_PARAM_IMPEDANCE = 16,
+    TRM_HYDRAULIC_PARAM_COUNT = 7
+};
 int trm_adjoint_param_open(trm_ctx* ctx);
 int trm_adjoint_param_download(trm_ctx* ctx, int which, void* host);
 int trm_adjoint_param_device_ptr(trm_ctx* ctx, int which, void** dev);

@@ -45,7 +45,7 @@ REDUCE = dict(sum=0, min=1, max=2, hasnan=3, volume_integral_z=4)   # TRM_REDUCE
 OPTION = dict(asynchronous=0, step_kernel=1, write_kf_every_step=2, vwc_forcing_field=3, packed_f32=4,
               derive_closure_fields=5, steps_per_launch=6, pipeline_parts=7, single_step_program=8, bc_signature=9, zero_gradient_fast=10, surface_in_launch=11,
               defer_closure_stores=12, interior_steps=13, derivative_series=14, derivative_series_params=15, derivative_richards=16,
-              derivative_richards_adjoint=17,
+              derivative_richards_adjoint=17, derivative_richards_params=18,
               info_top_arrays_current=100, info_closure_consistent=101, info_bc_signature=102, info_generic_boundary_kernels=103,
               info_last_program=105, info_closure_stored=106, info_materializations=107, info_interior_launches=108,
               info_derivative_series=109)
@@ -71,6 +71,8 @@ def decode_program(pid: int) -> dict:
     if d["family"] == "column_adjoint":
         d.update(generic_boundaries=bool(extra & 1), backward=bool(extra & 2), checkpointed=bool(extra & 4), boundary_gradient=bool(extra & 32),
                  parameter_gradient=bool(pid & PROGRAM_PARAMETERS))
+    if d["family"] == "column_adjoint_richards" and pid & PROGRAM_PARAMETERS:      # (the ids without the bit decode as they always did)
+        d.update(hydraulic_parameter_gradient=True)
     if d["family"] in ("deep", "wide"):
         d.update(program=("euler", "heun", "multi")[extra & 3], generic_boundaries=bool(extra & 4))
     if pid & (PROGRAM_AVERAGES_IN_LAUNCH | PROGRAM_AVERAGES_AFTER_LAUNCH):
@@ -78,7 +80,8 @@ def decode_program(pid: int) -> dict:
     return d
 # TRM_PROGRAM_AVERAGES_*: how the last step accumulated the open time averages (trm_average_open)
 PROGRAM_AVERAGES_IN_LAUNCH, PROGRAM_AVERAGES_AFTER_LAUNCH = 1 << 28, 1 << 29
-# TRM_PROGRAM_PARAMETERS: a derivative launch that carried the thermal parameters (trm_tangent_param_set, trm_adjoint_param_open)
+# TRM_PROGRAM_PARAMETERS: a derivative launch that carried the thermal parameters (trm_tangent_param_set, trm_adjoint_param_open), or in
+# the family column_adjoint_richards the hydraulic ones (derivative_richards_params)
 PROGRAM_PARAMETERS = 1 << 31
 STATUS_NAN, STATUS_COMPOSITION, STATUS_HANDOFF_TIMEOUT = 1, 2, 4     # TRM_STATUS_* (COMPOSITION: TRM_STATUS_COMPOSITION_OUT_OF_RANGE)
 TRM_OK, TRM_EINVAL, TRM_EHIP, TRM_ENOMEM, TRM_EUNSUPPORTED, TRM_ESTALE, TRM_ECOMM = range(7)
@@ -111,6 +114,9 @@ EXPORTS = (
     "trm_tangent_record_device_ptr trm_tangent_record_info").split()
 # the thermal parameters the tangent and the adjoint differentiate (TRM_THERMAL_PARAM_*), in the order of trm_params
 THERMAL_PARAMS = ("k_water", "k_ice", "k_air", "k_mineral", "k_organic", "c_water", "c_ice", "c_air", "c_mineral", "c_organic")
+# the hydraulic parameters the heat + Richards adjoint differentiates (TRM_HYDRAULIC_PARAM_*): name -> id, one id space with the thermal
+# parameters (K_sat = TRM_THERMAL_PARAM_COUNT); the names of trm_params' hydraulics line
+HYDRAULIC_PARAMS = dict(K_sat=10, theta_res=11, bc_psi_s=12, bc_lambda=13, vg_alpha=14, vg_n=15, impedance=16)
 # TRM_TANGENT_*: the tangent fields by the names of the state fields they belong to; saturation and pressure_head on Richards contexts only
 TANGENT = dict(internal_energy=0, temperature=1, liquid_water_fraction=2, saturation=3, pressure_head=4)
 # TRM_ADJOINT_*: the cotangent fields, the tangent fields' ids; saturation and pressure_head on Richards contexts only

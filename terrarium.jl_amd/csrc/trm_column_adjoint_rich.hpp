@@ -26,6 +26,25 @@
 // pre-repair saturation again with the column program's own building blocks, so they are the primal's bits.  T, liq and psi of a launch's
 // first state are taken to be the closures of the stored U and sat, as k_column_tangent_rich takes them.
 // lamU and lamS stay in registers over the taped steps of a launch, newest first; each lane owns its cell, nothing is atomic.
+//
+// Hydraulic parameters (PARAMS; TRM_OPT_DERIVATIVE_RICHARDS_PARAMS, DESIGN 4.8 "Richards parameters").  The step's transpose holds Kcbar, the
+// cotangent of the cell's hydraulic conductivity, and psibar, that of its pressure head; dL/dp of a hydraulic parameter p is the sum over the
+// taped steps and the cells of Kcbar dKc/dp + psibar dpsi/dp, plus wpsi dpsi/dp at the stored final state (the fold).  Each lane forms the
+// slopes of its own cell from the primal's intermediates (r, u, g, x, xe, ie, t, I_ice), adds its terms to one register per parameter the
+// instance reads, newest step first, and carries them from launch to launch through per-cell arrays; k_hyd_param_reduce adds a column's
+// cells from the bottom up.
+//   psi, Brooks-Corey   theta_res through dr/dtheta_res = (r - 1) / theta_span; psi_s: -r^(-1/lambda), -1 where the primal takes
+//                       theta >= por; lambda through the exponent, d(-1/lambda) = dlambda / lambda^2
+//   psi, van Genuchten  theta_res through r; alpha: -psi_m / alpha; n through both exponents, d(-1/m) = dn / (n - 1)^2 and
+//                       d(1/n) = -dn / n^2; every slope 0 in a saturated cell
+//   Kc, linear          K_sat: water / por
+//   Kc, Mualem          K_sat: Kc's factors without it, the sign of fabs kept; impedance: -ln 10 (1 - liq) Kc on every path of
+//                       ice_impedance; n through e1 = n / (n + 1) and e2 = (n - 1) / n, de1 = dn / (n + 1)^2, de2 = dn / n^2
+// The compile-time-exponent instances have the exponent slopes all the same: the instance is chosen by the value.
+// Conventions: d(x^a)/da = x^a ln x (fp64 log), and 0 where the power itself is 0 (a frozen cell's x = 0; the Mualem term at x = 1); a
+// zero cotangent in front of a slope gives 0 whatever the slope, so zero cotangents give exactly zero gradients and scaling them by a
+// power of two scales the gradients bit for bit; a cell the primal flags as an illegal composition gives NaN.  lamU and lamS are
+// formed by the operations of the sweep without the parameters: gU and gsat are its bits.
 #pragma once
 #include "trm_column_tangent_rich.hpp"
 
@@ -43,6 +62,48 @@ struct RichSweepArgs {
     long long slot_elems;
     int fold;                 // 1 in the first launch of a sweep: wT, wliq, wpsi through the closures of the stored state, zero after
 };
+
+// The hydraulic parameters in the order of TRM_HYDRAULIC_PARAM_* (which counts from TRM_THERMAL_PARAM_COUNT on)
+enum { HP_K_SAT = 0, HP_THETA_RES = 1, HP_BC_PSI_S = 2, HP_BC_LAMBDA = 3, HP_VG_ALPHA = 4, HP_VG_N = 5, HP_IMPEDANCE = 6, HP_COUNT = 7 };
+// Fifth kernel argument of k_column_adjoint_rich_params and first of k_hyd_param_reduce: the per-cell accumulators, [Nh][Nzp] each
+struct HydParamPtrs {
+    double* g[HP_COUNT];
+};
+// the sums a lane carries, one register pair each (named members, not an array: nothing here is ever indexed at run time); an instance
+// touches the parameters its hydraulics read (hyd_param_mask), the others are dead registers
+struct HydParamSums {
+    double K_sat, theta_res, bc_psi_s, bc_lambda, vg_alpha, vg_n, impedance;
+};
+// the parameters an instance's hydraulics can read, a bit per HP_*: the reference default reads the Brooks-Corey curve and K_sat, n = 2
+// the van Genuchten pair; the run-time instance decides per launch and leaves the sums of the others at their stored zeros
+template <int HYD> constexpr unsigned hyd_param_mask();
+// a launch's first and last act on the sums: from and to the per-cell arrays `hp` at element e, the parameters of the instance alone
+#define TRM_HYD_SUMS(F) F(HP_K_SAT, K_sat) F(HP_THETA_RES, theta_res) F(HP_BC_PSI_S, bc_psi_s) F(HP_BC_LAMBDA, bc_lambda) F(HP_VG_ALPHA, vg_alpha) F(HP_VG_N, vg_n) F(HP_IMPEDANCE, impedance)
+// (`fresh`: the first launch of a sweep starts every sum from 0, whatever an earlier sweep left in the arrays)
+template <int HYD> TRM_DEV void hyd_sums_load(HydParamSums& acc, const HydParamPtrs& hp, size_t e, bool fresh) {
+    constexpr unsigned mask = hyd_param_mask<HYD>();
+#define TRM_HYD_LOAD(Q, NAME) acc.NAME = ((mask >> Q & 1u) && !fresh) ? hp.g[Q][e] : 0.0;
+    TRM_HYD_SUMS(TRM_HYD_LOAD)
+#undef TRM_HYD_LOAD
+}
+template <int HYD> TRM_DEV void hyd_sums_store(const HydParamSums& acc, const HydParamPtrs& hp, size_t e) {
+    constexpr unsigned mask = hyd_param_mask<HYD>();
+#define TRM_HYD_STORE(Q, NAME) if (mask >> Q & 1u) hp.g[Q][e] = acc.NAME;
+    TRM_HYD_SUMS(TRM_HYD_STORE)
+#undef TRM_HYD_STORE
+}
+// (the loads are waited for where this stands)
+template <int HYD> TRM_DEV void hyd_sums_use(const HydParamSums& acc) {
+    constexpr unsigned mask = hyd_param_mask<HYD>();
+#define TRM_HYD_USE(Q, NAME) if (mask >> Q & 1u) asm volatile("" ::"v"(acc.NAME));
+    TRM_HYD_SUMS(TRM_HYD_USE)
+#undef TRM_HYD_USE
+}
+template <int HYD> constexpr unsigned hyd_param_mask() {
+    return HYD == HYD_BC_LINEAR ? (1u << HP_K_SAT | 1u << HP_THETA_RES | 1u << HP_BC_PSI_S | 1u << HP_BC_LAMBDA)
+         : HYD == HYD_VG_N2   ? (1u << HP_K_SAT | 1u << HP_THETA_RES | 1u << HP_VG_ALPHA | 1u << HP_VG_N | 1u << HP_IMPEDANCE)
+                              : (1u << HP_COUNT) - 1u;
+}
 
 // the boundary inputs both kernels hold over a launch, as k_column_tangent_rich forms them
 TRM_DEV ColumnBC<double> rich_column_bc(const View<double>& v, const LaneInfo& ln, int ii) {
@@ -257,10 +318,104 @@ template <int HYD> TRM_DEV double pressure_head_transpose(const DevParams<double
     return psibar == 0.0 ? 0.0 : pressure_head_tangent<HYD>(p, sat, 1.0) * psibar;
 }
 
-// the transposed step at the taped state (U, sat): (lamU, lamS) of the state after the step -> of the state before it
-template <int HYD, int LPC>
+// d(x^a)/da da for xa = x^a as the primal formed it: xa ln x da, and 0 where the power is 0
+TRM_DEV double pow_exponent_tangent(double x, double xa, double da) { return xa == 0.0 ? 0.0 : (xa * log(x)) * da; }
+
+// psibar dpsi/dp of pressure_head<double, HYD, true>(p, sat, ...) for the retention curve's parameters: a step's terms of their sums (the
+// other members 0).  Terms are formed in locals and leave in one place, so that the sums stay in registers wherever this is inlined.
+template <int HYD> TRM_DEV HydParamSums pressure_head_param_terms(const DevParams<double>& p, double sat, double psibar) {
+    double t_res = 0.0, t_psi_s = 0.0, t_lam = 0.0, t_alpha = 0.0, t_n = 0.0;
+    const double theta = sat * p.por;
+    const bool unsat = theta < p.por;
+    const bool vg = HYD == HYD_VG_N2 || (HYD == HYD_GENERIC && p.swrc == 1);
+    if (psibar != 0.0 && (unsat || !vg)) {
+        const double r = div_const_nsz(theta - p.theta_res, p.theta_span, p.rtheta_span);
+        const double dr = div_const(r - 1.0, p.theta_span, p.rtheta_span);       // dr/dtheta_res
+        if (vg) {
+            const double n = HYD == HYD_VG_N2 ? 2.0 : p.vg_n.y;
+            double u, g;
+            if (HYD == HYD_VG_N2) {
+                const double rr = div_nr(1.0, r);
+                u = rr * rr;
+                g = sqrt_(u - 1.0);
+            } else {
+                u = jl_pow(r, p.vg_neg_inv_m);
+                g = jl_pow(u - 1.0, p.vg_inv_n);
+            }
+            const double um1 = u - 1.0, nm1 = n - 1.0;
+            const double du_r = pow_tangent(r, u, p.vg_neg_inv_m.y, dr);
+            // d(-1/m) = dn / (n - 1)^2, d(1/n) = -dn / n^2
+            const double du_n = pow_exponent_tangent(r, u, div_nr(1.0, nm1 * nm1));
+            const double dg_n = pow_exponent_tangent(um1, g, -div_nr(1.0, n * n)) + pow_tangent(um1, g, p.vg_inv_n.y, du_n);
+            t_res = psibar * (p.neg_inv_alpha * pow_tangent(um1, g, p.vg_inv_n.y, du_r));
+            t_alpha = psibar * -div_nr(p.neg_inv_alpha * g, p.vg_alpha);
+            t_n = psibar * (p.neg_inv_alpha * dg_n);
+        } else {
+            const double ra = HYD == HYD_BC_LINEAR ? pow_int_m5(r) : jl_pow(r, p.bc_neg_inv_lambda);
+            const double lam = p.bc_lambda.y;
+            // d(-1/lambda) = dlambda / lambda^2
+            const double d_res = -p.bc_psi_s * pow_tangent(r, ra, p.bc_neg_inv_lambda.y, dr);
+            const double d_lam = -p.bc_psi_s * pow_exponent_tangent(r, ra, div_nr(1.0, lam * lam));
+            t_psi_s = psibar * (unsat ? -ra : -1.0);
+            t_res = unsat ? psibar * d_res : 0.0;
+            t_lam = unsat ? psibar * d_lam : 0.0;
+        }
+    }
+    return HydParamSums{0.0, t_res, t_psi_s, t_lam, t_alpha, t_n, 0.0};
+}
+
+// Kcbar dKc/dp of conductivity_hydraulic<double, HYD, false>(p, liq, f) = Kc for the conductivity's parameters, likewise; `legal`:
+// hydraulic_legal of the cell
+template <int HYD>
+TRM_DEV HydParamSums hydraulic_conductivity_param_terms(const DevParams<double>& p, double liq, const Frac<double>& f, double Kc, double Kcbar, bool legal) {
+    const bool vg = HYD == HYD_VG_N2 || (HYD == HYD_GENERIC && p.unsat_k != 0);
+    const bool zero = Kcbar == 0.0;
+    double t_ksat, t_n = 0.0, t_imp = 0.0;
+    if (!vg) {
+        t_ksat = zero ? 0.0 : Kcbar * div_nr(f.water, f.water + f.ice + f.air);
+    } else {
+        const double n = HYD == HYD_VG_N2 ? 2.0 : p.vg_n.y;
+        const double x = div_const(f.water, p.por, p.rpor);
+        const double I_ice = ice_impedance(p, liq);
+        double xe, ie;
+        if (HYD == HYD_VG_N2) {
+            const double c = cbrt_(x);
+            xe = c * c;
+            ie = sqrt_(1.0 - xe);
+        } else {
+            xe = jl_pow(x, p.vgk_e1);
+            ie = jl_pow(1.0 - xe, p.vgk_e2);
+        }
+        const double inner = 1.0 - xe, t = 1.0 - ie;
+        const double sx = sqrt_(x), tt = t * t;
+        const double B = I_ice * sx * tt, A = p.K_sat * B;
+        // de1 = dn / (n + 1)^2, de2 = dn / n^2
+        const double np1 = n + 1.0;
+        const double dinner = -pow_exponent_tangent(x, xe, div_nr(1.0, np1 * np1));
+        const double dt = -(pow_exponent_tangent(inner, ie, div_nr(1.0, n * n)) + pow_tangent(inner, ie, p.vgk_e2.y, dinner));
+        const double dA_n = p.K_sat * (I_ice * sx * (2.0 * t * dt));
+        const double d_ksat = A < 0.0 ? -B : B;
+        const double d_n = A < 0.0 ? -dA_n : dA_n;
+        const double d_imp = -((2.302585092994046 * (1.0 - liq)) * Kc);
+        const double nan = Limits<double>::nan();
+        t_ksat = legal ? (zero ? 0.0 : Kcbar * d_ksat) : nan;
+        t_n = legal ? (zero ? 0.0 : Kcbar * d_n) : nan;
+        t_imp = legal ? (zero ? 0.0 : Kcbar * d_imp) : nan;
+    }
+    return HydParamSums{t_ksat, 0.0, 0.0, 0.0, 0.0, t_n, t_imp};
+}
+// acc += t, the parameters of the instance alone
+template <int HYD> TRM_DEV void hyd_sums_add(HydParamSums& acc, const HydParamSums& t) {
+    constexpr unsigned mask = hyd_param_mask<HYD>();
+#define TRM_HYD_ADD(Q, NAME) if (mask >> Q & 1u) acc.NAME = acc.NAME + t.NAME;
+    TRM_HYD_SUMS(TRM_HYD_ADD)
+#undef TRM_HYD_ADD
+}
+
+// PARAMS: the cell's terms of the hydraulic-parameter gradients go onto `acc` beside it
+template <int HYD, int LPC, bool PARAMS = false>
 TRM_DEV void adjoint_step_rich(const View<double>& v, const DevParams<double>& p, const LevelGeom<double>& L, const LaneInfo& ln, int Nz, double U, double sat,
-                               double dt, const ColumnBC<double>& bc, double& lamU, double& lamS) {
+                               double dt, const ColumnBC<double>& bc, double& lamU, double& lamS, HydParamSums* acc = nullptr) {
     const bool is_bot = ln.is_bot, is_top = ln.is_top;
     // ---- the primal of the step, by the column program's building blocks
     uint32_t viol = 0;
@@ -353,6 +508,10 @@ TRM_DEV void adjoint_step_rich(const View<double>& v, const DevParams<double>& p
     closure_transpose_rich(p, U, sat, c.liq, T, C, Tbar, lK, wbar, ibar, abar, wK, uOut, sOut);
     lamU = lamU + uOut;
     lamS = mS + sOut + pressure_head_transpose<HYD>(p, sat, psibar);
+    if constexpr (PARAMS) {
+        hyd_sums_add<HYD>(*acc, hydraulic_conductivity_param_terms<HYD>(p, c.liq, f, Kc, Kcbar, legal));
+        hyd_sums_add<HYD>(*acc, pressure_head_param_terms<HYD>(p, sat, psibar));
+    }
 }
 
 // The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
@@ -400,6 +559,73 @@ __global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_rich(View<dou
     if (ln.act) {
         aa.lU[e] = lamU;
         aa.lsat[e] = lamS;
+    }
+}
+
+// The same sweep with the hydraulic-parameter gradients (adjoint_step_rich's PARAMS): the lanes carry the sums of `hp` beside lamU and
+// lamS, from the per-cell arrays and back to them; the first launch of a sweep starts them from 0 and adds the fold's wpsi dpsi/dp at the
+// stored final state.
+// A kernel body of its own beside k_column_adjoint_rich, statement for statement: routed through one shared device function, that
+// kernel's instances came out with another register allocation, and they are to stay the ones they are.
+template <int HYD, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_rich_params(View<double> v, DevParams<double> p, ColumnArgs<double> a, RichSweepArgs aa, HydParamPtrs hp) {
+    using NF = double;
+    int ii;
+    size_t e;
+    const LaneInfo ln = derivative_lane<LPC>(v, ii, e);
+    const int Nz = v.Nz;
+    NF lamU = aa.lU[e], lamS = aa.lsat[e];
+    const size_t stride = 2 * (size_t)aa.slot_elems;
+    const NF* slot = aa.tape + (size_t)(a.nsteps > 0 ? a.nsteps - 1 : 0) * stride + e;
+    NF U_next = a.nsteps > 0 ? slot[0] : 0.0, sat_next = a.nsteps > 0 ? slot[aa.slot_elems] : 0.0;
+    const LevelGeom<NF> L = level_geom(v, ln.k);
+    const ColumnBC<NF> bc = rich_column_bc(v, ln, ii);
+    HydParamSums acc;
+    hyd_sums_load<HYD>(acc, hp, e, aa.fold != 0);
+    if (aa.fold) {
+        const NF U = v.U[e], sat = v.sat[e], wT = aa.lT[e], wliq = aa.lliq[e], wpsi = aa.lpsi[e];
+        uint32_t viol_in = 0;
+        NF liq, T, uOut, sOut;
+        const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
+        closure_transpose_rich(p, U, sat, liq, T, heat_capacity(p, f), wT, wliq, 0.0, 0.0, 0.0, 0.0, uOut, sOut);
+        lamU = lamU + uOut;
+        lamS = lamS + sOut + pressure_head_transpose<HYD>(p, sat, wpsi);
+        hyd_sums_add<HYD>(acc, pressure_head_param_terms<HYD>(p, sat, wpsi));
+        if (ln.act) {
+            aa.lT[e] = 0.0;
+            aa.lliq[e] = 0.0;
+            aa.lpsi[e] = 0.0;
+        }
+    }
+    asm volatile("" ::"v"(lamU), "v"(lamS), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bc.bTb), "v"(bc.bTt), "v"(bc.flux_S));
+    hyd_sums_use<HYD>(acc);
+    for (int step = a.nsteps - 1; step >= 0; --step) {
+        const NF U = U_next, sat = sat_next;
+        if (step > 0) {
+            slot -= stride;
+            U_next = slot[0];
+            sat_next = slot[aa.slot_elems];
+        }
+        adjoint_step_rich<HYD, LPC, true>(v, p, L, ln, Nz, U, sat, a.dt, bc, lamU, lamS, &acc);
+    }
+    if (ln.act) {
+        aa.lU[e] = lamU;
+        aa.lsat[e] = lamS;
+        hyd_sums_store<HYD>(acc, hp, e);
+    }
+}
+
+// trm_adjoint_backward's last launch with the hydraulic-parameter gradients open: one thread per column adds each parameter's cells from
+// the bottom up -- out[q][Nh], q in the order of TRM_HYDRAULIC_PARAM_*.  A template, so that only the translation unit that launches it
+// holds a copy.
+template <class Ptrs> __global__ void __launch_bounds__(256) k_hyd_param_reduce(Ptrs g, double* out, long long Nh, int Nz, int Nzp) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= Nh) return;
+    for (int q = 0; q < HP_COUNT; ++q) {
+        const double* col = g.g[q] + (size_t)i * (size_t)Nzp;
+        double s = 0.0;
+        for (int k = 0; k < Nz; ++k) s = s + col[k];
+        out[(size_t)q * (size_t)Nh + (size_t)i] = s;
     }
 }
 

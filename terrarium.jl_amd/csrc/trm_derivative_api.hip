@@ -134,6 +134,8 @@ void release_adjoint(trm_ctx* c) {
     std::fill(std::begin(c->adj_bcs_nt), std::end(c->adj_bcs_nt), 0L);
     release(c->d_adj_param);
     release(c->d_adj_param_out);
+    release(c->d_adj_hyd);
+    release(c->d_adj_hyd_out);
     release(c->d_misfit);
     release_tape(c);
 }
@@ -343,6 +345,8 @@ int open_adjoint(trm_ctx* c, int capacity, int interval, const std::string& who)
     for (int s = 0; s < 4; ++s) if (!rc) rc = zero(c, c->d_adj_bcs[s], rows_bytes(c, c->adj_bcs_nt[s]));
     for (double* q : c->d_adj_param) if (!rc) rc = zero(c, q, bytes);
     if (!rc) rc = zero(c, c->d_adj_param_out, rows_bytes(c, TRM_THERMAL_PARAM_COUNT));
+    for (double* q : c->d_adj_hyd) if (!rc) rc = zero(c, q, bytes);
+    if (!rc) rc = zero(c, c->d_adj_hyd_out, rows_bytes(c, TRM_HYDRAULIC_PARAM_COUNT));
     if (!rc) rc = zero(c, c->d_misfit, rows_bytes(c));
     if (rc) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -370,11 +374,39 @@ int adjoint_bc_series_args(trm_ctx* c, int bc_var, int side, const void* ptr, co
     nt = sr->cap;
     return alloc_series_shaped(c, c->d_adj_bcs[slot], c->adj_bcs_nt[slot], nt, who);
 }
-// a thermal-parameter gradient
-int adjoint_param_args(trm_ctx* c, int which, const void* ptr, const char* who) {
+// a parameter gradient: `row` its num_columns doubles -- a thermal parameter's, or on a Richards context with the hydraulic-parameter
+// gradients open (TRM_OPT_DERIVATIVE_RICHARDS_PARAMS) one of the seven TRM_HYDRAULIC_PARAM_* ids', which count on from the thermal ones
+int adjoint_param_args(trm_ctx* c, int which, const void* ptr, const char* who, double*& row) {
     if (int rc = adjoint_open(c, who)) return rc;
+    if (richards(c) && c->d_adj_hyd_out) {
+        const int at = hyd_param_row(which);
+        if (int rc = which_ok(c, at, TRM_HYDRAULIC_PARAM_COUNT, ptr, who, " (TRM_HYDRAULIC_PARAM_*)")) return rc;
+        row = c->d_adj_hyd_out + (size_t)at * (size_t)c->Nh;
+        return TRM_OK;
+    }
     if (int rc = require_open(c, c->d_adj_param_out, who, "parameter gradients are", "trm_adjoint_param_open")) return rc;
-    return which_ok(c, which, TRM_THERMAL_PARAM_COUNT, ptr, who, " (TRM_THERMAL_PARAM_*)");
+    if (int rc = which_ok(c, which, TRM_THERMAL_PARAM_COUNT, ptr, who, " (TRM_THERMAL_PARAM_*)")) return rc;
+    row = c->d_adj_param_out + (size_t)which * (size_t)c->Nh;
+    return TRM_OK;
+}
+// TRM_OPT_DERIVATIVE_RICHARDS_PARAMS takes effect together with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT alone, on a Richards context
+bool hydraulic_params_enabled(const trm_ctx* c) { return richards(c) && c->opt_derivative_richards_adjoint && c->opt_derivative_richards_params; }
+// trm_adjoint_param_open there: the seven per-cell accumulators and the per-column results, zero; no boundary accumulators
+int open_hydraulic_params(trm_ctx* c, const char* who) {
+    if (const char* why = derivative_unsupported(c, false, true)) return refuse(c, who, why);
+    if (int rc = adjoint_open(c, who)) return rc;
+    if (c->ckpt_interval != 0) return refuse(c, who, kRichardsTapeOnly);
+    int rc = TRM_OK;
+    for (double*& q : c->d_adj_hyd)
+        if (!rc) rc = ensure(c, q, field_bytes(c), true, who, "the accumulators do not fit");
+    if (!rc) rc = ensure(c, c->d_adj_hyd_out, rows_bytes(c, TRM_HYDRAULIC_PARAM_COUNT), true, who, "the accumulators do not fit");
+    if (rc) {
+        release(c->d_adj_hyd);
+        release(c->d_adj_hyd_out);
+        return rc;
+    }
+    TRM_HIP(c, hipStreamSynchronize(c->stream));
+    return TRM_OK;
 }
 // ---- adjoint observations ------------------------------------------------------------------------------------------------------------
 // the level list of an observation: rows of the host layout, strictly increasing
@@ -800,6 +832,7 @@ int trm_adjoint_bc_device_ptr(trm_ctx* c, int bc_var, int side, void** dev) {
 int trm_adjoint_param_open(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
     const char* who = "trm_adjoint_param_open";
+    if (hydraulic_params_enabled(c)) return open_hydraulic_params(c, who);
     if (int rc = richards_tape_only(c, who)) return rc;
     // (a context the adjoint does not cover has none open: it is told why, not to open one)
     if (const char* why = derivative_unsupported(c)) return refuse(c, who, why);
@@ -821,15 +854,17 @@ int trm_adjoint_param_open(trm_ctx* c) {
 }
 int trm_adjoint_param_download(trm_ctx* c, int which, void* host) {
     TRM_ENTER_HEUN(c);
-    if (int rc = adjoint_param_args(c, which, host, "trm_adjoint_param_download")) return rc;
-    TRM_HIP(c, hipMemcpyAsync(host, c->d_adj_param_out + (size_t)which * (size_t)c->Nh, rows_bytes(c), hipMemcpyDeviceToHost, c->stream));
+    double* row = nullptr;
+    if (int rc = adjoint_param_args(c, which, host, "trm_adjoint_param_download", row)) return rc;
+    TRM_HIP(c, hipMemcpyAsync(host, row, rows_bytes(c), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     return TRM_OK;
 }
 int trm_adjoint_param_device_ptr(trm_ctx* c, int which, void** dev) {
     TRM_ENTER_HEUN(c);
-    if (int rc = adjoint_param_args(c, which, dev, "trm_adjoint_param_device_ptr")) return rc;
-    *dev = c->d_adj_param_out + (size_t)which * (size_t)c->Nh;
+    double* row = nullptr;
+    if (int rc = adjoint_param_args(c, which, dev, "trm_adjoint_param_device_ptr", row)) return rc;
+    *dev = row;
     return TRM_OK;
 }
 int trm_adjoint_upload(trm_ctx* c, int which, const void* host) {
@@ -919,14 +954,16 @@ int trm_adjoint_backward(trm_ctx* c) {
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTape);
     if (richards(c)) {
         // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch folds
-        // the cotangents of T, liq and psi in (an empty tape: that launch alone)
+        // the cotangents of T, liq and psi in (an empty tape: that launch alone).  With the hydraulic-parameter gradients open the
+        // launches are the accumulating instances, and k_hyd_param_reduce ends the sweep
+        const bool hyd = c->d_adj_hyd_out != nullptr;
         const int spl = derivative_steps_per_launch(c);
         int end = (int)c->tape_dt.size(), fold = 1;
         do {
             int begin = end;
             while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
             const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
-            if (int rc = AdjointRichLaunch::backward(c, dt_block, end - begin, begin, fold)) {
+            if (int rc = hyd ? AdjointRichLaunch::backward_params(c, dt_block, end - begin, begin, fold) : AdjointRichLaunch::backward(c, dt_block, end - begin, begin, fold)) {
                 c->adj_stale = true;       // (lam is part way down the tape)
                 return rc;
             }
@@ -936,7 +973,7 @@ int trm_adjoint_backward(trm_ctx* c) {
         } while (end > 0);
         c->tape_dt.clear();
         c->adj_stale = false;
-        return finish(c, TRM_OK);
+        return finish(c, hyd ? AdjointRichLaunch::param_reduce(c) : TRM_OK);
     }
     // An attached record (trm_adjoint_observe_record) is read inside the launches: no position of it is a launch boundary.  A record
     // longer than the tape is refused here, in front of everything the sweep does

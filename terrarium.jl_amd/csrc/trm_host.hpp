@@ -198,6 +198,9 @@ struct trm_ctx {
     int opt_derivative_richards = 0;
     // TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT: the per-step tape of the adjoint accepts a heat + Richards context (k_column_adjoint_rich)
     int opt_derivative_richards_adjoint = 0;
+    // TRM_OPT_DERIVATIVE_RICHARDS_PARAMS: together with the option above, trm_adjoint_param_open opens the gradients with respect to the
+    // seven hydraulic parameters on such a context (k_column_adjoint_rich_params)
+    int opt_derivative_richards_params = 0;
     // the seeds of the seriesed pairs (trm_tangent_bc_series_upload), [nt][Nh] doubles in the order of d_tan_bc, `tan_bcs_nt` their
     // levels; null: none yet (trm_step_tangent allocates zeros).  Zeroed by trm_tangent_open, freed by trm_tangent_close.
     double* d_tan_bcs[4] = {};
@@ -221,6 +224,11 @@ struct trm_ctx {
     std::vector<trm::SeriesRow> tape_rows;
     double* d_adj_param[8] = {};
     double* d_adj_param_out = nullptr;
+    // the hydraulic-parameter accumulators of a Richards context (trm_adjoint_param_open under TRM_OPT_DERIVATIVE_RICHARDS_PARAMS): seven
+    // per-cell fields [Nh][Nzp] in the order of TRM_HYDRAULIC_PARAM_*, and the result of k_hyd_param_reduce,
+    // [TRM_HYDRAULIC_PARAM_COUNT][Nh]; null: the sweep runs the instances without
+    double* d_adj_hyd[7] = {};
+    double* d_adj_hyd_out = nullptr;
     double* d_tape = nullptr;
     int tape_cap = 0;
     std::vector<double> tape_dt;
@@ -706,11 +714,22 @@ struct TangentRichLaunch {
     static int closure(trm_ctx* c);
 };
 // k_column_record_rich / k_column_adjoint_rich (fp64 heat + Richards, final-state cotangents on the per-step tape alone:
-// TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT), both in trm_launch_column_adjoint_rich.hip; `slot` is the tape slot of the launch's first step
+// TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT), both in trm_launch_column_adjoint_rich.hip; `slot` is the tape slot of the launch's first step.
+// backward_params / param_reduce: the sweep that carries the hydraulic-parameter gradients and the reduction that ends it
+// (k_column_adjoint_rich_params, k_hyd_param_reduce; trm_launch_column_adjoint_rich_param.hip)
 struct AdjointRichLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot);
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int backward_params(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int param_reduce(trm_ctx* c);
 };
+// the row of a TRM_HYDRAULIC_PARAM_* id in the result [TRM_HYDRAULIC_PARAM_COUNT][Nh], -1 for any other number (the thermal ids, which
+// the hydraulic ones count on from, included)
+inline int hyd_param_row(int which) {
+    static_assert(TRM_HYDRAULIC_PARAM_K_SAT == TRM_THERMAL_PARAM_COUNT, "one id space with the thermal ids");
+    const int row = which - TRM_HYDRAULIC_PARAM_K_SAT;
+    return row >= 0 && row < TRM_HYDRAULIC_PARAM_COUNT ? row : -1;
+}
 // k_column_record / k_column_adjoint{,_record} (fp64 NoFlow only): `slot` is the tape slot of the launch's first step; k_param_reduce ends
 // a sweep with parameter gradients on either tape (trm_launch_column_adjoint_param.hip)
 struct AdjointLaunch {

@@ -307,6 +307,44 @@ template <class = void> int adjoint_backward_rich(trm_ctx* c, double dt, int nst
     });
 }
 
+// ---- ... with the hydraulic-parameter gradients (k_column_adjoint_rich_params / k_hyd_param_reduce; TRM_OPT_DERIVATIVE_RICHARDS_PARAMS,
+// trm_adjoint_param_open on such a context): the same sweep, the seven per-cell accumulators beside it.  Instantiated by
+// trm_launch_column_adjoint_rich_param.hip alone.  The preconditions: the sweep's, and the accumulators and their result
+inline HydParamPtrs hyd_param_ptrs(const trm_ctx* c) {
+    HydParamPtrs g;
+    for (int q = 0; q < HP_COUNT; ++q) g.g[q] = c->d_adj_hyd[q];
+    return g;
+}
+static_assert(TRM_HYDRAULIC_PARAM_COUNT == HP_COUNT, "hyd_param_row (trm_host.hpp) counts the kernel's sums");
+inline int hyd_params_ok(trm_ctx* c, const std::string& who) {
+    if (!c->d_adj_hyd_out) return fail(c, TRM_EINVAL, who + ": no accumulators");
+    return arrays_ok(c, c->d_adj_hyd, who, "accumulators");
+}
+template <class = void> int adjoint_backward_rich_params(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
+    const std::string who = "k_column_adjoint_rich (parameter gradients)";
+    if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
+    if (int rc = hyd_params_ok(c, who)) return rc;
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
+    const RichSweepArgs aa = rich_sweep_args(c, slot, fold);
+    const HydParamPtrs hp = hyd_param_ptrs(c);
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        hipLaunchKernelGGL((k_column_adjoint_rich_params<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa, hp);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, (int)TRM_PROGRAM_PARAMETERS);
+        return (int)TRM_OK;
+    });
+}
+template <class = void> int adjoint_rich_param_reduce(trm_ctx* c) {
+    if (c->params.flow != TRM_FLOW_RICHARDS) return fail(c, TRM_EINVAL, "k_hyd_param_reduce: a Richards context only");
+    if (int rc = hyd_params_ok(c, "k_hyd_param_reduce")) return rc;
+    hipLaunchKernelGGL((k_hyd_param_reduce<HydParamPtrs>), dim3((unsigned)((c->Nh + 255) / 256)), dim3(256), 0, c->stream, hyd_param_ptrs(c), c->d_adj_hyd_out,
+                       (long long)c->Nh, c->Nz, c->Nzp);
+    TRM_HIP(c, hipGetLastError());
+    return TRM_OK;
+}
+
 // k_column_record on the per-step tape (`slot`: of the launch's first step) or STRIDED on the checkpointed one (the stores before the
 // steps first, first + every, ... go into the slots from `slot` on); SERIES: with the boundary series evaluated in the launch
 template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every) {

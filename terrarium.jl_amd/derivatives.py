@@ -273,6 +273,35 @@ def vjp(integ: ModelIntegrator, steps: int, temperature=None, internal_energy=No
         return tuple(out) if len(out) > 1 else out[0]
 
 
+def hydraulic_parameter_gradient(integ: ModelIntegrator, steps: int, cotangents: dict):
+    """`vjp` on an integrator with `RichardsEq`, with the gradients with respect to the seven hydraulic parameters from the same sweep:
+    the integrator is stepped `steps` times with its own dt, then `cotangents` -- the dict `vjp` takes there, {"internal_energy": wU,
+    "saturation": wsat, "temperature": wT, "liquid_water_fraction": wliq, "pressure_head": wpsi}, one left out is zero -- are pulled
+    back.  Returns ({"internal_energy": dL/dU_0, "saturation": dL/dsat_0}, {name: dL/d(parameter) as [Nh]}) for the names `K_sat`,
+    `theta_res`, `bc_psi_s`, `bc_lambda`, `vg_alpha`, `vg_n`, `impedance`: each column's share, their sum the gradient of the scalar L
+    (trm_adjoint_param_open under TRM_OPT_DERIVATIVE_RICHARDS_PARAMS).  A parameter the model's hydraulics never read gives zeros.  The
+    state gradients are bit for bit `vjp`'s.  The options `derivative_richards_adjoint` and `derivative_richards_params` are set for the
+    duration of the call.  The coverage of `vjp` there; an integrator without `RichardsEq` raises a ValueError."""
+    _refuse_uncovered(integ, "hydraulic_parameter_gradient")
+    if not _richards(integ):
+        raise ValueError("hydraulic_parameter_gradient: needs an integrator with RichardsEq (the heat-only run reads no hydraulic parameter)")
+    given = dict(cotangents)
+    unknown = sorted(set(given) - set(_capi.ADJOINT))
+    if unknown:
+        raise KeyError(f"hydraulic_parameter_gradient: no cotangent {unknown[0]!r} ({', '.join(_capi.ADJOINT)})")
+    steps = int(steps)
+    with _derivative_richards(integ, "derivative_richards_adjoint"), _derivative_richards(integ, "derivative_richards_params"), \
+            _taped(integ, max(steps, 1), None, False, reuse=True) as st:
+        st.step_record(integ.timestepper.dt, steps)
+        for name in _capi.ADJOINT:
+            w = given.get(name)
+            st.set_cotangent(name, 0.0 if w is None else w)
+        st.open_param_gradient()
+        st.adjoint_backward()
+        return ({name: st.cotangent(name) for name in ("internal_energy", "saturation")},
+                {name: st.param_gradient(name) for name in _capi.HYDRAULIC_PARAMS})
+
+
 class TemperatureRecord:
     """A temperature record as a borehole logger leaves it: `values[nobs][nlevels][Nh]` at the step counts `steps` (non-decreasing,
     0 = the initial state) on the rows `levels` of the host layout (row 0 = bottom layer, strictly increasing).  `weight` >= 0

@@ -560,14 +560,17 @@ class DeviceState:
 
     def open_param_gradient(self):
         """From now on adjoint_backward also forms dL/d(thermal parameter) per column, and the boundary gradients with it
-        (trm_adjoint_param_open); needs an open adjoint."""
+        (trm_adjoint_param_open); needs an open adjoint.  On a Richards context with the options `derivative_richards_adjoint` and
+        `derivative_richards_params` set: dL/d(hydraulic parameter) per column instead (`_capi.HYDRAULIC_PARAMS`), no boundary gradients."""
         self._check(self._lib.trm_adjoint_param_open(self._ctx), "trm_adjoint_param_open")
 
     def param_gradient(self, name) -> np.ndarray:
         """dL/d(parameter `name`) of each column's share of L as [Nh], after adjoint_backward; the sum over the columns is the
-        gradient of the scalar L (trm_adjoint_param_download)."""
+        gradient of the scalar L (trm_adjoint_param_download).  `name`: a thermal parameter (`_capi.THERMAL_PARAMS`), or on a Richards
+        context a hydraulic one (`_capi.HYDRAULIC_PARAMS`: K_sat, theta_res, bc_psi_s, bc_lambda, vg_alpha, vg_n, impedance)."""
         a = np.empty(self.grid.Nh, dtype=np.float64)
-        self._check(self._lib.trm_adjoint_param_download(self._ctx, _capi.THERMAL_PARAMS.index(name), a.ctypes.data), "trm_adjoint_param_download")
+        which = _capi.HYDRAULIC_PARAMS[name] if name in _capi.HYDRAULIC_PARAMS else _capi.THERMAL_PARAMS.index(name)
+        self._check(self._lib.trm_adjoint_param_download(self._ctx, which, a.ctypes.data), "trm_adjoint_param_download")
         return a
 
     def step_record(self, dt, nsteps=1):
