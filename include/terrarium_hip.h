@@ -260,6 +260,16 @@ enum {
                                     /* (TRM_INFO_LAST_PROGRAM: bit 31).  trm_adjoint_bc_open, the checkpointed tape, observations and records     */
                                     /* stay refused there.  0 (default), or without that option: every call answers a Richards context as         */
                                     /* without it                                                                                                  */
+    ,TRM_OPT_DERIVATIVE_RICHARDS_RECORD = 19 /* 1, together with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT = 1: the seven attached-record calls --     */
+                                    /* trm_adjoint_observe_record, trm_adjoint_observe_record_device, trm_adjoint_record_detach,                  */
+                                    /* trm_adjoint_record_residual_download, trm_adjoint_record_residual_device_ptr,                              */
+                                    /* trm_adjoint_record_misfit_download and trm_adjoint_record_info -- accept a Richards context with an open   */
+                                    /* per-step adjoint.  The record observes saturation_water_ice (a soil-moisture record) and is read inside    */
+                                    /* the backward launches, with or without the hydraulic-parameter gradients of the option above               */
+                                    /* (TRM_INFO_LAST_PROGRAM is that of the same launch without a record).  The per-position calls               */
+                                    /* (trm_adjoint_observe, trm_adjoint_observe_misfit), trm_adjoint_open_checkpointed and trm_adjoint_bc_open   */
+                                    /* stay refused there.  0 (default), or without that option: every call answers a Richards context as         */
+                                    /* without it                                                                                                  */
 };
 /* DIAGNOSTIC, read-only (trm_get_option): which fast paths the NEXT step will take -- what the library tracks about its own
  * buffers.  Tests pin them (a wrong value costs speed, never correctness, so nothing else would notice). */
@@ -818,7 +828,8 @@ int trm_tangent_record_info(const trm_ctx* ctx, int* npos, int* nlevels, int64_t
  * TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS.  The staleness rules are the ones above (trm_upload of the saturation makes a tape that holds steps
  * stale).  The checkpointed tape, boundary, parameter and series gradients, observations and records refuse a Richards context with
  * TRM_EUNSUPPORTED "on a Richards context: final-state cotangents on a per-step tape only".  (The hydraulic parameters:
- * TRM_OPT_DERIVATIVE_RICHARDS_PARAMS, beside trm_adjoint_param_open below.) */
+ * TRM_OPT_DERIVATIVE_RICHARDS_PARAMS, beside trm_adjoint_param_open below.  Soil-moisture records: TRM_OPT_DERIVATIVE_RICHARDS_RECORD,
+ * beside trm_adjoint_observe_record below.) */
 enum { TRM_ADJOINT_INTERNAL_ENERGY = 0, TRM_ADJOINT_TEMPERATURE = 1, TRM_ADJOINT_LIQUID_WATER_FRACTION = 2,
        TRM_ADJOINT_SATURATION = 3,      /* Richards contexts only: the cotangent of saturation_water_ice, and dL/dsat_0 after a sweep */
        TRM_ADJOINT_PRESSURE_HEAD = 4 }; /* Richards contexts only: the cotangent of pressure_head */
@@ -1007,7 +1018,21 @@ int trm_adjoint_observations(const trm_ctx* ctx, int* count, int64_t* bytes);
  * Errors: TRM_EINVAL without a context or an open adjoint, npos < 1, nlevels < 1, NULL pointers, positions negative or not strictly
  * increasing, a level outside 0 ... Nz-1 or out of order, a negative or NaN host weight, a second attach without a detach, the mixing
  * rules, a download before a sweep has run with this record; trm_adjoint_backward: TRM_EINVAL, before anything is launched and with the
- * tape left usable, for a record with a position behind the taped steps; TRM_ENOMEM. */
+ * tape left usable, for a record with a position behind the taped steps; TRM_ENOMEM.
+ *
+ * Heat + Richards, with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT and TRM_OPT_DERIVATIVE_RICHARDS_RECORD both set: the seven calls accept a
+ * Richards context with an open per-step adjoint, and the record observes saturation_water_ice -- what a soil-moisture probe logs.
+ * The arrays, the lifetime, the staleness rules, the validation of an attach and the refusal of a record longer than the tape are the
+ * ones above, with `observed` holding saturations: L = sum_k sum_j 1/2 w (sat_{p_k}[level_j] - sat_obs)^2 per column, residuals
+ * r = sat_p - sat_obs (+0 for a gap), the misfit summed as above.  trm_adjoint_backward gives the gradient of L plus the final
+ * cotangents with respect to the initial internal energy and saturation and, with the hydraulic-parameter gradients open
+ * (TRM_OPT_DERIVATIVE_RICHARDS_PARAMS), the seven hydraulic parameters, from one sweep.  Saturation is a state variable: the sample
+ * of position p is added to the saturation cotangent itself, right behind the pull-back of step p (position n: in front of the fold),
+ * and reaches the parameters through the steps below it.  Per cell the order is the sample of n, the fold, steps > p, the sample of
+ * p, step p - 1, ...: gradients, residuals and misfit do not depend on TRM_OPT_STEPS_PER_LAUNCH or on how the trm_step_record calls
+ * were split.  A gap adds nothing, not even the sign of a zero: a record of NaNs or of weights 0 gives the sweep without a record,
+ * bit for bit.  Temperature, liquid-water or pressure-head records, the per-position calls and the checkpointed tape stay refused on
+ * a Richards context.  With either option at 0 the seven calls answer a Richards context as before. */
 int trm_adjoint_observe_record(trm_ctx* ctx, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* observed, const void* weight);
 int trm_adjoint_observe_record_device(trm_ctx* ctx, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* d_observed, const void* d_weight);
 int trm_adjoint_record_detach(trm_ctx* ctx);

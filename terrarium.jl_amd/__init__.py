@@ -32,7 +32,7 @@ from .integrator import (ForwardEuler, Heun, PrescribedSurfaceTemperature, Presc
                          timestep, run, current_time, compute_auxiliary, compute_tendencies, closure, invclosure,
                          update_state, default_dt, is_adaptive, iteration, time_step, reset, get_grid, znodes, zspacings,
                          checkpoint, restore, restart_fields, DeviceGroup)
-from .derivatives import jvp, vjp, hydraulic_parameter_gradient, TemperatureRecord, misfit_gradient, record_gradient, record_jvp, record_normal_equations
+from .derivatives import jvp, vjp, hydraulic_parameter_gradient, soil_moisture_gradient, SoilMoistureRecord, TemperatureRecord, misfit_gradient, record_gradient, record_jvp, record_normal_equations
 from ._capi import TerrariumHipError
 from .io import Hdf5File, RasterInputSource
 from .simulation import Simulation, Callback, IterationInterval, TimeInterval, AveragedTimeInterval, SnapshotWriter, run_simulation

@@ -45,7 +45,7 @@ REDUCE = dict(sum=0, min=1, max=2, hasnan=3, volume_integral_z=4)   # TRM_REDUCE
 OPTION = dict(asynchronous=0, step_kernel=1, write_kf_every_step=2, vwc_forcing_field=3, packed_f32=4,
               derive_closure_fields=5, steps_per_launch=6, pipeline_parts=7, single_step_program=8, bc_signature=9, zero_gradient_fast=10, surface_in_launch=11,
               defer_closure_stores=12, interior_steps=13, derivative_series=14, derivative_series_params=15, derivative_richards=16,
-              derivative_richards_adjoint=17, derivative_richards_params=18,
+              derivative_richards_adjoint=17, derivative_richards_params=18, derivative_richards_record=19,
               info_top_arrays_current=100, info_closure_consistent=101, info_bc_signature=102, info_generic_boundary_kernels=103,
               info_last_program=105, info_closure_stored=106, info_materializations=107, info_interior_launches=108,
               info_derivative_series=109)

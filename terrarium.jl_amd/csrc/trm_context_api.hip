@@ -765,6 +765,7 @@ int trm_set_option(trm_ctx* c, int option, int value) {
         case TRM_OPT_DERIVATIVE_RICHARDS: c->opt_derivative_richards = value != 0; return TRM_OK;
         case TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT: c->opt_derivative_richards_adjoint = value != 0; return TRM_OK;
         case TRM_OPT_DERIVATIVE_RICHARDS_PARAMS: c->opt_derivative_richards_params = value != 0; return TRM_OK;
+        case TRM_OPT_DERIVATIVE_RICHARDS_RECORD: c->opt_derivative_richards_record = value != 0; return TRM_OK;
         default: break;
     }
     return fail(c, TRM_EINVAL, "trm_set_option: unknown option or value");
@@ -794,6 +795,7 @@ int trm_get_option(const trm_ctx* c, int option, int* value) {
         case TRM_OPT_DERIVATIVE_RICHARDS: *value = c->opt_derivative_richards; return TRM_OK;
         case TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT: *value = c->opt_derivative_richards_adjoint; return TRM_OK;
         case TRM_OPT_DERIVATIVE_RICHARDS_PARAMS: *value = c->opt_derivative_richards_params; return TRM_OK;
+        case TRM_OPT_DERIVATIVE_RICHARDS_RECORD: *value = c->opt_derivative_richards_record; return TRM_OK;
         case TRM_INFO_DERIVATIVE_SERIES: *value = c->derivative_series; return TRM_OK;
         case TRM_INFO_LAST_PROGRAM: *value = c->last_program; return TRM_OK;
         case TRM_INFO_GENERIC_BOUNDARY_KERNELS: *value = by_precision(c->precision, [&](auto nf) { return trmh::Policy<typename decltype(nf)::type>::generic_bcs(c); }) ? 1 : 0; return TRM_OK;

@@ -148,8 +148,7 @@ namespace {
 bool richards(const trm_ctx* c) { return c->params.flow == TRM_FLOW_RICHARDS; }
 const char* kRichardsStateSeedsOnly = "on a Richards context: state seeds only";
 // `tape`: the caller is one of the per-step tape's calls that TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT opens to such a context; with that
-// option at 0 they answer as every other call does
-const char* kRichardsTapeOnly = "on a Richards context: final-state cotangents on a per-step tape only";
+// option at 0 they answer as every other call does (the refusal of the others: richards_tape_only, trm_host.hpp)
 const char* derivative_unsupported(const trm_ctx* c, bool state_seeds = false, bool tape = false) {
     if (c->precision != TRM_F64) return "fp64 contexts only";
     const bool taped = tape && c->opt_derivative_richards_adjoint;      // (independent of TRM_OPT_DERIVATIVE_RICHARDS)
@@ -247,10 +246,6 @@ int adjoint_open(trm_ctx* c, const char* who) { return require_open(c, c->d_adj[
 int adjoint_fields(const trm_ctx* c) { return richards(c) ? TRM_ADJOINT_PRESSURE_HEAD + 1 : TRM_ADJOINT_LIQUID_WATER_FRACTION + 1; }
 // the fields of a tape slot: U_k, and on a Richards context sat_k behind it
 size_t tape_slot_fields(const trm_ctx* c) { return richards(c) ? 2 : 1; }
-// a call the Richards adjoint does not cover, with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT set: refused before anything else happens
-int richards_tape_only(trm_ctx* c, const char* who) {
-    return richards(c) && c->opt_derivative_richards_adjoint ? fail(c, TRM_EUNSUPPORTED, std::string(who) + ": " + kRichardsTapeOnly) : TRM_OK;
-}
 // ... and an index in [0, bound) with a non-null pointer (`hint`: what the index counts, appended to the refusal)
 int which_ok(trm_ctx* c, int which, int bound, const void* ptr, const char* who, const char* hint = "") {
     return which >= 0 && which < bound && ptr ? TRM_OK : fail(c, TRM_EINVAL, std::string(who) + ": bad argument" + hint);
@@ -473,7 +468,7 @@ int inject_observations(trm_ctx* c, int p, bool lam, bool params) {
 // The record joins the open adjoint: the level table, the residuals and the misfit are the library's; `observed` / `weight` are host arrays
 // the library copies once (`device` false) or device arrays it keeps by pointer
 int attach_record(trm_ctx* c, int npos, const int32_t* positions, int nlevels, const int32_t* levels, const void* observed, const void* weight, bool device, const char* who) {
-    if (int rc = richards_tape_only(c, who)) return rc;
+    if (int rc = richards_tape_only(c, who, true)) return rc;
     if (int rc = record_attach_ok(c, npos, positions, nlevels, levels, observed, device ? nullptr : (const double*)weight, who)) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     const size_t cells = (size_t)npos * (size_t)nlevels * (size_t)c->Nh, cell_bytes = cells * sizeof(double);
@@ -956,14 +951,21 @@ int trm_adjoint_backward(trm_ctx* c) {
         // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch folds
         // the cotangents of T, liq and psi in (an empty tape: that launch alone).  With the hydraulic-parameter gradients open the
         // launches are the accumulating instances, and k_hyd_param_reduce ends the sweep
-        const bool hyd = c->d_adj_hyd_out != nullptr;
+        // An attached soil-moisture record (TRM_OPT_DERIVATIVE_RICHARDS_RECORD) is read inside the launches, by the record twins of the two
+        // sweeps; one longer than the tape is refused here, in front of everything the sweep does.  Without one the launches are the ones above
+        const bool hyd = c->d_adj_hyd_out != nullptr, rec = c->rec.npos > 0;
+        if (int rc = record_fits_tape(c, taped_steps(c), who)) return rc;
+        if (rec)
+            if (int rc = record_tables(c, taped_steps(c), who)) return rc;
         const int spl = derivative_steps_per_launch(c);
         int end = (int)c->tape_dt.size(), fold = 1;
         do {
             int begin = end;
             while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
             const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
-            if (int rc = hyd ? AdjointRichLaunch::backward_params(c, dt_block, end - begin, begin, fold) : AdjointRichLaunch::backward(c, dt_block, end - begin, begin, fold)) {
+            const auto launch = rec ? (hyd ? AdjointRichLaunch::backward_params_record : AdjointRichLaunch::backward_record)
+                                    : (hyd ? AdjointRichLaunch::backward_params : AdjointRichLaunch::backward);
+            if (int rc = launch(c, dt_block, end - begin, begin, fold)) {
                 c->adj_stale = true;       // (lam is part way down the tape)
                 return rc;
             }
@@ -971,6 +973,14 @@ int trm_adjoint_backward(trm_ctx* c) {
             end = begin;
             fold = 0;
         } while (end > 0);
+        if (rec) {                 // (the residuals the launches wrote, summed in front of k_hyd_param_reduce)
+            const int rc = RecordLaunch::misfit(c);
+            c->rec_swept = rc == TRM_OK;
+            if (rc) {
+                c->adj_stale = true;
+                return rc;
+            }
+        }
         c->tape_dt.clear();
         c->adj_stale = false;
         return finish(c, hyd ? AdjointRichLaunch::param_reduce(c) : TRM_OK);
@@ -1113,7 +1123,7 @@ int trm_adjoint_observe_record_device(trm_ctx* c, int npos, const int32_t* posit
 int trm_adjoint_record_detach(trm_ctx* c) {
     TRM_ENTER_HEUN(c);
     const char* who = "trm_adjoint_record_detach";
-    if (int rc = richards_tape_only(c, who)) return rc;
+    if (int rc = richards_tape_only(c, who, true)) return rc;
     if (int rc = adjoint_open(c, who)) return rc;
     if (c->rec.npos == 0) return fail(c, TRM_EINVAL, std::string(who) + ": no record is attached (trm_adjoint_observe_record)");
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -1122,7 +1132,7 @@ int trm_adjoint_record_detach(trm_ctx* c) {
 }
 int trm_adjoint_record_residual_download(trm_ctx* c, void* host) {
     TRM_ENTER_HEUN(c);
-    if (int rc = richards_tape_only(c, "trm_adjoint_record_residual_download")) return rc;
+    if (int rc = richards_tape_only(c, "trm_adjoint_record_residual_download", true)) return rc;
     if (int rc = record_results_ok(c, host, "trm_adjoint_record_residual_download")) return rc;
     TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out, rows_bytes(c, (long)c->rec.npos * c->rec.nlevels), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -1130,7 +1140,7 @@ int trm_adjoint_record_residual_download(trm_ctx* c, void* host) {
 }
 int trm_adjoint_record_residual_device_ptr(trm_ctx* c, void** dev) {
     TRM_ENTER_HEUN(c);
-    if (int rc = richards_tape_only(c, "trm_adjoint_record_residual_device_ptr")) return rc;
+    if (int rc = richards_tape_only(c, "trm_adjoint_record_residual_device_ptr", true)) return rc;
     if (int rc = record_results_ok(c, dev, "trm_adjoint_record_residual_device_ptr")) return rc;
     TRM_HIP(c, hipStreamSynchronize(c->stream));
     *dev = c->d_rec_out;
@@ -1138,7 +1148,7 @@ int trm_adjoint_record_residual_device_ptr(trm_ctx* c, void** dev) {
 }
 int trm_adjoint_record_misfit_download(trm_ctx* c, void* host) {
     TRM_ENTER_HEUN(c);
-    if (int rc = richards_tape_only(c, "trm_adjoint_record_misfit_download")) return rc;
+    if (int rc = richards_tape_only(c, "trm_adjoint_record_misfit_download", true)) return rc;
     if (int rc = record_results_ok(c, host, "trm_adjoint_record_misfit_download")) return rc;
     TRM_HIP(c, hipMemcpyAsync(host, c->d_rec_out + (size_t)c->rec.npos * (size_t)c->rec.nlevels * (size_t)c->Nh, rows_bytes(c), hipMemcpyDeviceToHost, c->stream));
     TRM_HIP(c, hipStreamSynchronize(c->stream));
@@ -1146,7 +1156,7 @@ int trm_adjoint_record_misfit_download(trm_ctx* c, void* host) {
 }
 int trm_adjoint_record_info(const trm_ctx* c, int* npos, int* nlevels, int64_t* bytes) {
     if (!c) return TRM_EINVAL;
-    if (int rc = richards_tape_only(const_cast<trm_ctx*>(c), "trm_adjoint_record_info")) return rc;
+    if (int rc = richards_tape_only(const_cast<trm_ctx*>(c), "trm_adjoint_record_info", true)) return rc;
     if (int rc = adjoint_open(const_cast<trm_ctx*>(c), "trm_adjoint_record_info")) return rc;
     if (npos) *npos = c->rec.npos;
     if (nlevels) *nlevels = c->rec.nlevels;

@@ -201,6 +201,9 @@ struct trm_ctx {
     // TRM_OPT_DERIVATIVE_RICHARDS_PARAMS: together with the option above, trm_adjoint_param_open opens the gradients with respect to the
     // seven hydraulic parameters on such a context (k_column_adjoint_rich_params)
     int opt_derivative_richards_params = 0;
+    // TRM_OPT_DERIVATIVE_RICHARDS_RECORD: together with TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT, the seven attached-record calls accept such a
+    // context: a soil-moisture record read inside the backward launches (k_column_adjoint_rich_record)
+    int opt_derivative_richards_record = 0;
     // the seeds of the seriesed pairs (trm_tangent_bc_series_upload), [nt][Nh] doubles in the order of d_tan_bc, `tan_bcs_nt` their
     // levels; null: none yet (trm_step_tangent allocates zeros).  Zeroed by trm_tangent_open, freed by trm_tangent_close.
     double* d_tan_bcs[4] = {};
@@ -716,11 +719,16 @@ struct TangentRichLaunch {
 // k_column_record_rich / k_column_adjoint_rich (fp64 heat + Richards, final-state cotangents on the per-step tape alone:
 // TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT), both in trm_launch_column_adjoint_rich.hip; `slot` is the tape slot of the launch's first step.
 // backward_params / param_reduce: the sweep that carries the hydraulic-parameter gradients and the reduction that ends it
-// (k_column_adjoint_rich_params, k_hyd_param_reduce; trm_launch_column_adjoint_rich_param.hip)
+// (k_column_adjoint_rich_params, k_hyd_param_reduce; trm_launch_column_adjoint_rich_param.hip).  backward_record /
+// backward_params_record: the two sweeps reading the attached soil-moisture record (k_column_adjoint_rich_record,
+// k_column_adjoint_rich_params_record; trm_launch_column_adjoint_rich_record.hip, trm_launch_column_adjoint_rich_param_record.hip); the
+// taped position of their first step is `slot`
 struct AdjointRichLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot);
     static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
     static int backward_params(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int backward_record(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int backward_params_record(trm_ctx* c, double dt, int nsteps, int slot, int fold);
     static int param_reduce(trm_ctx* c);
 };
 // the row of a TRM_HYDRAULIC_PARAM_* id in the result [TRM_HYDRAULIC_PARAM_COUNT][Nh], -1 for any other number (the thermal ids, which
@@ -879,6 +887,18 @@ inline int record_results_ok(trm_ctx* c, const void* ptr, const char* who) {
     if (c->rec.npos == 0) return fail(c, TRM_EINVAL, w + ": no record is attached (trm_adjoint_observe_record)");
     if (!c->rec_swept) return fail(c, TRM_EINVAL, w + ": no sweep has run with this record (trm_adjoint_backward)");
     return TRM_OK;
+}
+// A heat + Richards context under TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT: the calls its adjoint does not cover are refused before anything
+// else happens.  `record_call`: the caller is one of the seven attached-record calls, which TRM_OPT_DERIVATIVE_RICHARDS_RECORD opens to such
+// a context (a soil-moisture record, DESIGN 4.8 "Richards records"); with either option at 0 every call answers as without it
+inline const char* const kRichardsTapeOnly = "on a Richards context: final-state cotangents on a per-step tape only";
+inline bool richards_record_enabled(const trm_ctx* c) {
+    return c->params.flow == TRM_FLOW_RICHARDS && c->opt_derivative_richards_adjoint && c->opt_derivative_richards_record;
+}
+inline int richards_tape_only(trm_ctx* c, const char* who, bool record_call = false) {
+    if (c->params.flow != TRM_FLOW_RICHARDS || !c->opt_derivative_richards_adjoint) return TRM_OK;
+    if (record_call && richards_record_enabled(c)) return TRM_OK;
+    return fail(c, TRM_EUNSUPPORTED, std::string(who) + ": " + kRichardsTapeOnly);
 }
 // k_record_misfit, which sums the residuals a sweep wrote into the misfit per column (trm_launch_record.hip)
 struct RecordLaunch {

@@ -11,6 +11,7 @@
 #include "trm_column_tangent_record.hpp"
 #include "trm_column_tangent_rich.hpp"
 #include "trm_column_adjoint_rich.hpp"
+#include "trm_column_adjoint_rich_record.hpp"
 
 namespace trmh {
 
@@ -343,6 +344,46 @@ template <class = void> int adjoint_rich_param_reduce(trm_ctx* c) {
                        (long long)c->Nh, c->Nz, c->Nzp);
     TRM_HIP(c, hipGetLastError());
     return TRM_OK;
+}
+
+// ---- ... and with an attached soil-moisture record (k_column_adjoint_rich_record / k_column_adjoint_rich_params_record,
+// trm_column_adjoint_rich_record.hpp; TRM_OPT_DERIVATIVE_RICHARDS_RECORD): the two sweeps above with the record as their last kernel
+// argument.  On the per-step tape the taped position of the launch's first step is its slot.  Instantiated by
+// trm_launch_column_adjoint_rich_record.hip and trm_launch_column_adjoint_rich_param_record.hip alone.  The preconditions: the sweep's,
+// and record_launch_ok.  TRM_INFO_LAST_PROGRAM is that of the same launch without a record
+template <class = void> int adjoint_backward_rich_record(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
+    const std::string who = "k_column_adjoint_rich_record";
+    if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
+    if (int rc = record_launch_ok(c, nsteps, slot, who)) return rc;
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
+    const RichSweepArgs aa = rich_sweep_args(c, slot, fold);
+    const RecordArgs r = record_args(c, slot);
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        hipLaunchKernelGGL((k_column_adjoint_rich_record<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa, r);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, 0);
+        return (int)TRM_OK;
+    });
+}
+template <class = void> int adjoint_backward_rich_params_record(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
+    const std::string who = "k_column_adjoint_rich_record (parameter gradients)";
+    if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
+    if (int rc = hyd_params_ok(c, who)) return rc;
+    if (int rc = record_launch_ok(c, nsteps, slot, who)) return rc;
+    const LaunchArgs<double>& la = launch_args<double>(c);
+    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
+    const RichSweepArgs aa = rich_sweep_args(c, slot, fold);
+    const HydParamPtrs hp = hyd_param_ptrs(c);
+    const RecordArgs r = record_args(c, slot);
+    return by_instance(c, [&](auto h, auto lpc) {
+        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
+        hipLaunchKernelGGL((k_column_adjoint_rich_params_record<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa, hp, r);
+        TRM_HIP(c, hipGetLastError());
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, (int)TRM_PROGRAM_PARAMETERS);
+        return (int)TRM_OK;
+    });
 }
 
 // k_column_record on the per-step tape (`slot`: of the launch's first step) or STRIDED on the checkpointed one (the stores before the

@@ -4,7 +4,7 @@ gradients (`vjp`) and the misfit to a temperature record with its gradient (`mis
 (the option `derivative_richards`), and so does `vjp`, with cotangents of the five final fields on the per-step tape (the option
 `derivative_richards_adjoint`).  The drivers issue the calls of `DeviceState` (trm_tangent_*, trm_adjoint_*); the two skeletons they
 share are `_tangent_run` and `_taped`."""
-from contextlib import contextmanager
+from contextlib import ExitStack, contextmanager
 
 import numpy as np
 
@@ -316,6 +316,60 @@ class TemperatureRecord:
         if any(s < 0 for s in self.steps) or any(b < a for a, b in zip(self.steps, self.steps[1:])):
             raise ValueError("TemperatureRecord: steps must be >= 0 and non-decreasing")
         self.weight = None if weight is None else np.broadcast_to(np.asarray(weight, dtype=np.float64), self.values.shape)
+
+
+class SoilMoistureRecord(TemperatureRecord):
+    """A soil-moisture record as a probe logs it: `values[nobs][nlevels][Nh]` are saturations (saturation_water_ice, 0 ... 1) at the
+    step counts `steps` (non-decreasing, 0 = the initial state) on the rows `levels` of the host layout (row 0 = bottom layer, strictly
+    increasing).  `weight` >= 0 broadcasts to the shape of `values` (None: 1); a NaN in `values` is a gap and counts for nothing.  The
+    shape rules of `TemperatureRecord`; read by `soil_moisture_gradient` (the option `derivative_richards_record`)."""
+
+    def __init__(self, steps, levels, values, weight=None):
+        try:
+            super().__init__(steps, levels, values, weight)
+        except ValueError as err:
+            raise ValueError(str(err).replace("TemperatureRecord", "SoilMoistureRecord")) from None
+
+
+def soil_moisture_gradient(integ: ModelIntegrator, record: SoilMoistureRecord, steps=None, cotangents=None, wrt_params=False):
+    """The misfit L = sum_k sum_levels 1/2 w (sat_{steps_k} - values_k)^2 of `run!(integ; steps)` to a soil-moisture record, per column,
+    and the gradient of L plus the final cotangents, on an integrator with `RichardsEq`: one attach, one step_record(dt, steps) and one
+    sweep, the record read inside the backward launches (trm_adjoint_observe_record under TRM_OPT_DERIVATIVE_RICHARDS_RECORD).  The
+    integrator is stepped `steps` times (None: to the last observation) with its own dt.  `cotangents` is the dict `vjp` takes there
+    (None: all zero).  Returns (L as [Nh], {"internal_energy": dL/dU_0, "saturation": dL/dsat_0}) and, with `wrt_params`, a third item
+    {name: dL/d(parameter) as [Nh]} for the seven hydraulic parameters of `hydraulic_parameter_gradient`.  The options
+    `derivative_richards_adjoint`, `derivative_richards_record` and, with `wrt_params`, `derivative_richards_params` are set for the
+    duration of the call.  `record.steps` must be strictly increasing (one sample per position) and none may lie behind `steps`,
+    otherwise ValueError, as from `record_gradient`; an integrator without `RichardsEq` raises a ValueError.  The coverage of `vjp`."""
+    _refuse_uncovered(integ, "soil_moisture_gradient")
+    if not _richards(integ):
+        raise ValueError("soil_moisture_gradient: needs an integrator with RichardsEq (the heat-only run keeps its saturation)")
+    if not record.steps or any(b <= a for a, b in zip(record.steps, record.steps[1:])):
+        raise ValueError("soil_moisture_gradient: the record's steps must be strictly increasing, one sample per position")
+    last = record.steps[-1]
+    steps = last if steps is None else int(steps)
+    if steps < last:
+        raise ValueError("soil_moisture_gradient: the record has observations behind the last step")
+    given = dict(cotangents or {})
+    unknown = sorted(set(given) - set(_capi.ADJOINT))
+    if unknown:
+        raise KeyError(f"soil_moisture_gradient: no cotangent {unknown[0]!r} ({', '.join(_capi.ADJOINT)})")
+    with ExitStack() as options:
+        for name in ("derivative_richards_adjoint", "derivative_richards_record") + (("derivative_richards_params",) if wrt_params else ()):
+            options.enter_context(_derivative_richards(integ, name))
+        with _taped(integ, max(steps, 1), None, False, detach=True) as st:
+            st.attach_record(record.steps, record.levels, record.values, record.weight)
+            st.step_record(integ.timestepper.dt, steps)
+            for name in _capi.ADJOINT:
+                w = given.get(name)
+                st.set_cotangent(name, 0.0 if w is None else w)
+            if wrt_params:
+                st.open_param_gradient()
+            st.adjoint_backward()          # (the residuals and the misfit are the sweep's)
+            out = [st.record_misfit(), {name: st.cotangent(name) for name in ("internal_energy", "saturation")}]
+            if wrt_params:
+                out.append({name: st.param_gradient(name) for name in _capi.HYDRAULIC_PARAMS})
+            return tuple(out)
 
 
 def _tape_slots(positions, steps, K):

@@ -625,7 +625,9 @@ class DeviceState:
         tape or close_adjoint.  `observed[npos][nlevels][Nh]` and `weight` (None: 1) are numpy arrays (or anything that broadcasts to the
         shape), copied once (trm_adjoint_observe_record), or float64 torch tensors of that shape on the context's device, kept by
         pointer without a copy (trm_adjoint_observe_record_device; their weights are not validated: one that is not > 0 counts as 0).
-        No position is a launch boundary and none takes a checkpoint slot."""
+        No position is a launch boundary and none takes a checkpoint slot.
+        On a Richards context with the options `derivative_richards_adjoint` and `derivative_richards_record` set the record is a
+        soil-moisture record: `observed` holds saturations and the loss gains 1/2 w (sat_p - observed)^2 (per-step tape only)."""
         pos = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1)
         lv = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
         shape = (pos.size, lv.size, self.grid.Nh)
@@ -649,7 +651,8 @@ class DeviceState:
                     "trm_adjoint_observe_record")
 
     def detach_record(self):
-        """Drops the attached record (trm_adjoint_record_detach)."""
+        """Drops the attached record (trm_adjoint_record_detach); on a Richards context it needs the option `derivative_richards_record`,
+        as every record call does there."""
         self._check(self._lib.trm_adjoint_record_detach(self._ctx), "trm_adjoint_record_detach")
         self._record_arrays = None
 
@@ -660,14 +663,16 @@ class DeviceState:
         return int(n.value), int(m.value), int(b.value)
 
     def record_residuals(self) -> np.ndarray:
-        """T_p - observed of the last sweep as [npos][nlevels][Nh], +0 for a gap (trm_adjoint_record_residual_download)."""
+        """T_p - observed of the last sweep as [npos][nlevels][Nh], +0 for a gap (trm_adjoint_record_residual_download); on a Richards
+        context (option `derivative_richards_record`) sat_p - observed."""
         npos, nlevels, _ = self.record_info()
         a = np.empty((npos, nlevels, self.grid.Nh), dtype=np.float64)
         self._check(self._lib.trm_adjoint_record_residual_download(self._ctx, a.ctypes.data if a.size else None), "trm_adjoint_record_residual_download")
         return a
 
     def record_misfit(self) -> np.ndarray:
-        """Each column's misfit to the attached record as the last sweep found it, [Nh] (trm_adjoint_record_misfit_download)."""
+        """Each column's misfit to the attached record as the last sweep found it, [Nh] (trm_adjoint_record_misfit_download); on a
+        Richards context (option `derivative_richards_record`) the misfit to the soil-moisture record."""
         a = np.empty(self.grid.Nh, dtype=np.float64)
         self._check(self._lib.trm_adjoint_record_misfit_download(self._ctx, a.ctypes.data), "trm_adjoint_record_misfit_download")
         return a
