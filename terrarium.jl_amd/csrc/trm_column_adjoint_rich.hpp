@@ -45,7 +45,18 @@
 // zero cotangent in front of a slope gives 0 whatever the slope, so zero cotangents give exactly zero gradients and scaling them by a
 // power of two scales the gradients bit for bit; a cell the primal flags as an illegal composition gives NaN.  lamU and lamS are
 // formed by the operations of the sweep without the parameters: gU and gsat are its bits.
+//
+// Soil-moisture records (RECORD; TRM_OPT_DERIVATIVE_RICHARDS_RECORD, DESIGN 4.8 "Richards records").  The record is the heat-only path's
+// (RecordArgs, RecordSample, record_fetch, record_residual: trm_column_adjoint.hpp), with the taped saturation passed where that path
+// passes the temperature: the loss gains 1/2 w (sat_p - sat_obs)^2 on the record's levels at its positions.  Saturation is a state
+// variable, so a sample is a cotangent of the state itself: the owning lane adds w (sat_p - sat_obs) to lamS, through no closure, and
+// the sample has no direct term in the hydraulic-parameter sums -- they feel it through lamS in the steps below.  Position p < n enters
+// right behind adjoint_step_rich of the step at (U_p, sat_p), from the `sat` the loop already holds; position n enters in the fold from
+// the stored sat_n, in front of the fold's own terms.  The sums of a cell are therefore in the order sample of n, fold, steps > p, sample
+// of p, step p - 1, ..., whatever the launches: gradients, residuals and misfit do not depend on TRM_OPT_STEPS_PER_LAUNCH or on how the
+// trm_step_record calls were split.  One lane owns a cell and a position occurs once: nothing is atomic, nothing goes to LDS.
 #pragma once
+#include "trm_column_adjoint.hpp"
 #include "trm_column_tangent_rich.hpp"
 
 namespace trm {
@@ -514,105 +525,111 @@ TRM_DEV void adjoint_step_rich(const View<double>& v, const DevParams<double>& p
     }
 }
 
-// The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
-template <int HYD, int LPC>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_rich(View<double> v, DevParams<double> p, ColumnArgs<double> a, RichSweepArgs aa) {
-    using NF = double;
-    int ii;
-    size_t e;
-    const LaneInfo ln = derivative_lane<LPC>(v, ii, e);
-    const int Nz = v.Nz;
-    NF lamU = aa.lU[e], lamS = aa.lsat[e];
-    // the newest slot first; the loads of the slot below are issued before the arithmetic of a step
-    const size_t stride = 2 * (size_t)aa.slot_elems;
-    const NF* slot = aa.tape + (size_t)(a.nsteps > 0 ? a.nsteps - 1 : 0) * stride + e;
-    NF U_next = a.nsteps > 0 ? slot[0] : 0.0, sat_next = a.nsteps > 0 ? slot[aa.slot_elems] : 0.0;
-    const LevelGeom<NF> L = level_geom(v, ln.k);
-    const ColumnBC<NF> bc = rich_column_bc(v, ln, ii);
-    if (aa.fold) {
-        // the end of the run: wT, wliq and wpsi through the closures of the stored (U_n, sat_n); zero after
-        const NF U = v.U[e], sat = v.sat[e], wT = aa.lT[e], wliq = aa.lliq[e], wpsi = aa.lpsi[e];
-        uint32_t viol_in = 0;
-        NF liq, T, uOut, sOut;
-        const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
-        closure_transpose_rich(p, U, sat, liq, T, heat_capacity(p, f), wT, wliq, 0.0, 0.0, 0.0, 0.0, uOut, sOut);
-        lamU = lamU + uOut;
-        lamS = lamS + sOut + pressure_head_transpose<HYD>(p, sat, wpsi);
-        if (ln.act) {
-            aa.lT[e] = 0.0;
-            aa.lliq[e] = 0.0;
-            aa.lpsi[e] = 0.0;
-        }
-    }
-    // Everything loaded so far is used here, in front of the loop: inside it the next slot's two loads are the only ones in flight, and the
-    // wait for them sits where their values are taken, behind the arithmetic of the step
-    asm volatile("" ::"v"(lamU), "v"(lamS), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bc.bTb), "v"(bc.bTt), "v"(bc.flux_S));
-    for (int step = a.nsteps - 1; step >= 0; --step) {
-        const NF U = U_next, sat = sat_next;
-        if (step > 0) {
-            slot -= stride;
-            U_next = slot[0];
-            sat_next = slot[aa.slot_elems];
-        }
-        adjoint_step_rich<HYD, LPC>(v, p, L, ln, Nz, U, sat, a.dt, bc, lamU, lamS);
-    }
-    if (ln.act) {
-        aa.lU[e] = lamU;
-        aa.lsat[e] = lamS;
-    }
+// the sample `s` of the state whose saturation is `sat`: the owning lane writes the residual and adds the sample's cotangent to lamS
+TRM_DEV void record_inject_rich(const RecordArgs& r, const RecordSample& s, double sat, double& lamS) {
+    const double x = record_residual(r, s, sat);
+    lamS = x != 0.0 ? lamS + x : lamS;      // (a gap adds nothing, not even the sign of a zero)
 }
 
-// The same sweep with the hydraulic-parameter gradients (adjoint_step_rich's PARAMS): the lanes carry the sums of `hp` beside lamU and
-// lamS, from the per-cell arrays and back to them; the first launch of a sweep starts them from 0 and adds the fold's wpsi dpsi/dp at the
-// stored final state.
-// A kernel body of its own beside k_column_adjoint_rich, statement for statement: routed through one shared device function, that
-// kernel's instances came out with another register allocation, and they are to stay the ones they are.
-template <int HYD, int LPC>
-__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_rich_params(View<double> v, DevParams<double> p, ColumnArgs<double> a, RichSweepArgs aa, HydParamPtrs hp) {
+// what stands in for `hp` in a sweep without PARAMS (for `r` without RECORD: NoRecord)
+struct NoHydParams {};
+
+// The backward sweep over the `a.nsteps` tape slots of this launch, newest first; a.dt is their common dt.
+// PARAMS (`hp`: HydParamPtrs, else NoHydParams): the lanes carry the sums of `hp` beside lamU and lamS, from the per-cell arrays and back
+// to them (adjoint_step_rich's PARAMS); the first launch of a sweep starts them from 0 and adds the fold's wpsi dpsi/dp at the stored
+// final state, behind the fold's own terms.
+// RECORD (`r`: RecordArgs, else NoRecord): behind every step's adjoint_step_rich the sample of the step's position, fetched where the
+// slot of that step is, a step ahead; the fold takes position `a.nsteps` of the launch (n) in front of its own terms.
+// One program for the four kernels below.  Against four bodies of their own (the shape before) its 24 instances have the same occupancy,
+// no scratch and at most as many VGPRs, give the same bits, and trm_adjoint_backward takes the same time within the run's noise in all
+// six legs of profiles/tools/adjoint_richards_record_cost.py (EXPERIMENTS R30.1, profiles/r30/).
+template <int HYD, int LPC, bool PARAMS, bool RECORD, class Hp, class Rec>
+TRM_DEV void adjoint_rich_program(const View<double>& v, const DevParams<double>& p, const ColumnArgs<double>& a, const RichSweepArgs& aa, const Hp& hp, const Rec& r) {
     using NF = double;
     int ii;
     size_t e;
     const LaneInfo ln = derivative_lane<LPC>(v, ii, e);
     const int Nz = v.Nz;
     NF lamU = aa.lU[e], lamS = aa.lsat[e];
+    int j = -1, row_next = -1;
+    if constexpr (RECORD) j = ln.act ? r.row_of_level[ln.k] : -1;
+    // the newest slot first; the loads of the slot below (RECORD: and of that step's sample) are issued before the arithmetic of a step
     const size_t stride = 2 * (size_t)aa.slot_elems;
     const NF* slot = aa.tape + (size_t)(a.nsteps > 0 ? a.nsteps - 1 : 0) * stride + e;
     NF U_next = a.nsteps > 0 ? slot[0] : 0.0, sat_next = a.nsteps > 0 ? slot[aa.slot_elems] : 0.0;
+    RecordSample s_next;
+    if constexpr (RECORD) {
+        row_next = a.nsteps > 0 ? r.row_of_position[a.nsteps - 1] : -1;
+        s_next = record_fetch(r, row_next, j, ii, v.Nh);
+    }
     const LevelGeom<NF> L = level_geom(v, ln.k);
     const ColumnBC<NF> bc = rich_column_bc(v, ln, ii);
     HydParamSums acc;
-    hyd_sums_load<HYD>(acc, hp, e, aa.fold != 0);
+    if constexpr (PARAMS) hyd_sums_load<HYD>(acc, hp, e, aa.fold != 0);
     if (aa.fold) {
+        // the end of the run: wT, wliq and wpsi through the closures of the stored (U_n, sat_n); zero after
         const NF U = v.U[e], sat = v.sat[e], wT = aa.lT[e], wliq = aa.lliq[e], wpsi = aa.lpsi[e];
+        RecordSample s_fold;
+        if constexpr (RECORD) s_fold = record_fetch(r, r.row_of_position[a.nsteps], j, ii, v.Nh);
         uint32_t viol_in = 0;
         NF liq, T, uOut, sOut;
         const Frac<NF> f = energy_closure_wave<NF, 0>(p, U, sat, liq, T, viol_in);
         closure_transpose_rich(p, U, sat, liq, T, heat_capacity(p, f), wT, wliq, 0.0, 0.0, 0.0, 0.0, uOut, sOut);
+        if constexpr (RECORD) record_inject_rich(r, s_fold, sat, lamS);
         lamU = lamU + uOut;
         lamS = lamS + sOut + pressure_head_transpose<HYD>(p, sat, wpsi);
-        hyd_sums_add<HYD>(acc, pressure_head_param_terms<HYD>(p, sat, wpsi));
+        if constexpr (PARAMS) hyd_sums_add<HYD>(acc, pressure_head_param_terms<HYD>(p, sat, wpsi));
         if (ln.act) {
             aa.lT[e] = 0.0;
             aa.lliq[e] = 0.0;
             aa.lpsi[e] = 0.0;
         }
     }
+    // Everything loaded so far is used here, in front of the loop: inside it the next slot's two loads (RECORD: and the next sample's) are
+    // the only ones in flight, and the wait for them sits where their values are taken, behind the arithmetic of the step
     asm volatile("" ::"v"(lamU), "v"(lamS), "v"(L.rdzc), "v"(L.rdzf_lo), "v"(L.rdzf_hi), "v"(bc.bTb), "v"(bc.bTt), "v"(bc.flux_S));
-    hyd_sums_use<HYD>(acc);
+    if constexpr (RECORD) asm volatile("" ::"v"(j));
+    if constexpr (PARAMS) hyd_sums_use<HYD>(acc);
     for (int step = a.nsteps - 1; step >= 0; --step) {
         const NF U = U_next, sat = sat_next;
+        const RecordSample s = s_next;
+        const int row = row_next;
         if (step > 0) {
             slot -= stride;
             U_next = slot[0];
             sat_next = slot[aa.slot_elems];
+            if constexpr (RECORD) {
+                row_next = r.row_of_position[step - 1];
+                s_next = record_fetch(r, row_next, j, ii, v.Nh);
+            }
         }
-        adjoint_step_rich<HYD, LPC, true>(v, p, L, ln, Nz, U, sat, a.dt, bc, lamU, lamS, &acc);
+        adjoint_step_rich<HYD, LPC, PARAMS>(v, p, L, ln, Nz, U, sat, a.dt, bc, lamU, lamS, PARAMS ? &acc : nullptr);
+        if constexpr (RECORD)
+            if (row >= 0) record_inject_rich(r, s, sat, lamS);
     }
     if (ln.act) {
         aa.lU[e] = lamU;
         aa.lsat[e] = lamS;
-        hyd_sums_store<HYD>(acc, hp, e);
+        if constexpr (PARAMS) hyd_sums_store<HYD>(acc, hp, e);
     }
+}
+
+// the four wrappers of adjoint_rich_program: the sweep alone, with the hydraulic-parameter sums `hp`, with the record `r`, with both
+template <int HYD, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_rich(View<double> v, DevParams<double> p, ColumnArgs<double> a, RichSweepArgs aa) {
+    adjoint_rich_program<HYD, LPC, false, false>(v, p, a, aa, NoHydParams{}, NoRecord{});
+}
+template <int HYD, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_rich_params(View<double> v, DevParams<double> p, ColumnArgs<double> a, RichSweepArgs aa, HydParamPtrs hp) {
+    adjoint_rich_program<HYD, LPC, true, false>(v, p, a, aa, hp, NoRecord{});
+}
+template <int HYD, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_rich_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, RichSweepArgs aa, RecordArgs r) {
+    adjoint_rich_program<HYD, LPC, false, true>(v, p, a, aa, NoHydParams{}, r);
+}
+template <int HYD, int LPC>
+__global__ void __launch_bounds__(TRM_STEP_BLOCK) k_column_adjoint_rich_params_record(View<double> v, DevParams<double> p, ColumnArgs<double> a, RichSweepArgs aa, HydParamPtrs hp, RecordArgs r) {
+    adjoint_rich_program<HYD, LPC, true, true>(v, p, a, aa, hp, r);
 }
 
 // trm_adjoint_backward's last launch with the hydraulic-parameter gradients open: one thread per column adds each parameter's cells from

@@ -42,6 +42,12 @@ int CheckpointLaunch::record(trm_ctx* c, double dt, int nsteps, int slot, int fi
 int CheckpointLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, Ride ride, bool record, int first) {
     return backward_launch<true>(c, dt, nsteps, slot, fold, ride, record, first);
 }
+// the heat + Richards sweep: every (params, record) has an instance
+int AdjointRichLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, bool params, bool record) {
+    auto launch = [&](auto par, auto rec) { return adjoint_backward_rich<decltype(par)::value, decltype(rec)::value>(c, dt, nsteps, slot, fold); };
+    if (params) return record ? launch(std::true_type{}, std::true_type{}) : launch(std::true_type{}, std::false_type{});
+    return record ? launch(std::false_type{}, std::true_type{}) : launch(std::false_type{}, std::false_type{});
+}
 }  // namespace trmh
 
 namespace {
@@ -446,6 +452,14 @@ bool observed(const trm_ctx* c, int position) {
     for (const auto& o : c->observations)
         if (o.position == position) return true;
     return false;
+}
+// trm_adjoint_backward walks the per-step tape in blocks of up to `spl` taped steps that share one dt, newest block first: the first step
+// of the block that ends below `end`.  A block also ends at an observed position: its cotangent enters lam between two launches (a
+// Richards context has none: observe_args)
+int tape_block_begin(const trm_ctx* c, int end, int spl) {
+    int begin = end;
+    while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1] && !(begin < end && observed(c, begin))) --begin;
+    return begin;
 }
 // The observations of taped position p, in registration order (trm_adjoint_backward: in front of the launch whose newest step is p - 1,
 // behind the last launch for p = 0).  U_p: tape slot p, the checkpoint of the segment that starts at p, the context's U for p = n.
@@ -947,25 +961,24 @@ int trm_adjoint_backward(trm_ctx* c) {
     const int nser = derivative_series_count(c);
     if (int rc = params_with_series_ok(c, c->d_adj_param_out != nullptr, who)) return rc;
     if (c->adj_stale) return fail(c, TRM_ESTALE, std::string(who) + kStaleTape);
+    // An attached record (trm_adjoint_observe_record; on a Richards context the soil-moisture record of TRM_OPT_DERIVATIVE_RICHARDS_RECORD)
+    // is read inside the launches: no position of it is a launch boundary.  A record longer than the tape is refused here, in front of
+    // everything the sweep does
+    const bool rec = c->rec.npos > 0;
+    if (int rc = record_fits_tape(c, taped_steps(c), who)) return rc;
+    if (rec)
+        if (int rc = record_tables(c, taped_steps(c), who)) return rc;
     if (richards(c)) {
-        // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch folds
-        // the cotangents of T, liq and psi in (an empty tape: that launch alone).  With the hydraulic-parameter gradients open the
-        // launches are the accumulating instances, and k_hyd_param_reduce ends the sweep
-        // An attached soil-moisture record (TRM_OPT_DERIVATIVE_RICHARDS_RECORD) is read inside the launches, by the record twins of the two
-        // sweeps; one longer than the tape is refused here, in front of everything the sweep does.  Without one the launches are the ones above
-        const bool hyd = c->d_adj_hyd_out != nullptr, rec = c->rec.npos > 0;
-        if (int rc = record_fits_tape(c, taped_steps(c), who)) return rc;
-        if (rec)
-            if (int rc = record_tables(c, taped_steps(c), who)) return rc;
+        // one launch per block of the tape (tape_block_begin), newest block first; the first launch folds the cotangents of T, liq and psi
+        // in (an empty tape: that launch alone).  With the hydraulic-parameter gradients open the launches carry their sums, and
+        // k_hyd_param_reduce ends the sweep
+        const bool hyd = c->d_adj_hyd_out != nullptr;
         const int spl = derivative_steps_per_launch(c);
         int end = (int)c->tape_dt.size(), fold = 1;
         do {
-            int begin = end;
-            while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1]) --begin;
+            const int begin = tape_block_begin(c, end, spl);
             const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
-            const auto launch = rec ? (hyd ? AdjointRichLaunch::backward_params_record : AdjointRichLaunch::backward_record)
-                                    : (hyd ? AdjointRichLaunch::backward_params : AdjointRichLaunch::backward);
-            if (int rc = launch(c, dt_block, end - begin, begin, fold)) {
+            if (int rc = AdjointRichLaunch::backward(c, dt_block, end - begin, begin, fold, hyd, rec)) {
                 c->adj_stale = true;       // (lam is part way down the tape)
                 return rc;
             }
@@ -985,12 +998,6 @@ int trm_adjoint_backward(trm_ctx* c) {
         c->adj_stale = false;
         return finish(c, hyd ? AdjointRichLaunch::param_reduce(c) : TRM_OK);
     }
-    // An attached record (trm_adjoint_observe_record) is read inside the launches: no position of it is a launch boundary.  A record
-    // longer than the tape is refused here, in front of everything the sweep does
-    const bool rec = c->rec.npos > 0;
-    if (int rc = record_fits_tape(c, taped_steps(c), who)) return rc;
-    if (rec)
-        if (int rc = record_tables(c, taped_steps(c), who)) return rc;
     if (nser) {
         // series ride with the accumulating instances: the per-column accumulators if nobody has opened them, and the node accumulators,
         // zero in front of the sweep's first launch; every launch gets the rows the record kept for its steps
@@ -1025,14 +1032,12 @@ int trm_adjoint_backward(trm_ctx* c) {
             if (s > 0) --s;
         } while (s > 0);
     } else {
-        // one launch per block of up to TRM_OPT_STEPS_PER_LAUNCH taped steps that share one dt, newest block first; the first launch
-        // folds the cotangents of T and liq in (an empty tape: that launch alone)
+        // one launch per block of the tape (tape_block_begin), newest block first; the first launch folds the cotangents of T and liq in
+        // (an empty tape: that launch alone)
         const int spl = derivative_steps_per_launch(c);
         int end = (int)c->tape_dt.size();
         do {
-            int begin = end;
-            // (a block also ends at an observed position: its cotangent enters lam between two launches)
-            while (begin > 0 && end - begin < spl && c->tape_dt[(size_t)begin - 1] == c->tape_dt[(size_t)end - 1] && !(begin < end && observed(c, begin))) --begin;
+            const int begin = tape_block_begin(c, end, spl);
             const double dt_block = end > 0 ? c->tape_dt[(size_t)end - 1] : 0.0;
             rc = inject_observations(c, end, true, !fold);
             if (!rc) rc = nser ? kept_rows(begin, end - begin) : TRM_OK;

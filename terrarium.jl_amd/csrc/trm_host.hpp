@@ -704,6 +704,8 @@ template <Ride R> int tangent_closure(trm_ctx* c);
 template <bool STRIDED, bool SERIES> int adjoint_record(trm_ctx* c, double dt, int nsteps, int slot, int first, int every);
 // (`first`: the taped position of the launch's first step, read with RECORD alone)
 template <bool CKPT, Ride R, bool RECORD> int adjoint_backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, int first);
+// (the heat + Richards sweep: AdjointRichLaunch below)
+template <bool PARAMS, bool RECORD> int adjoint_backward_rich(trm_ctx* c, double dt, int nsteps, int slot, int fold);
 // k_column_tangent{,_record} / k_closure_tangent (fp64 NoFlow only); the closure knows the parameter seeds alone.  These choose the
 // instantiation of the ride, with a record or without (ride_launch, trm_derivative_api.hip)
 struct TangentLaunch {
@@ -716,19 +718,15 @@ struct TangentRichLaunch {
     static int step(trm_ctx* c, double dt, int nsteps);
     static int closure(trm_ctx* c);
 };
-// k_column_record_rich / k_column_adjoint_rich (fp64 heat + Richards, final-state cotangents on the per-step tape alone:
-// TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT), both in trm_launch_column_adjoint_rich.hip; `slot` is the tape slot of the launch's first step.
-// backward_params / param_reduce: the sweep that carries the hydraulic-parameter gradients and the reduction that ends it
-// (k_column_adjoint_rich_params, k_hyd_param_reduce; trm_launch_column_adjoint_rich_param.hip).  backward_record /
-// backward_params_record: the two sweeps reading the attached soil-moisture record (k_column_adjoint_rich_record,
-// k_column_adjoint_rich_params_record; trm_launch_column_adjoint_rich_record.hip, trm_launch_column_adjoint_rich_param_record.hip); the
-// taped position of their first step is `slot`
+// The heat + Richards adjoint (fp64, final-state cotangents on the per-step tape alone: TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT); `slot` is
+// the tape slot of the launch's first step, and its taped position.  record: k_column_record_rich (trm_launch_column_adjoint_rich.hip).
+// backward: the sweep, one device program behind four kernels -- `params`: with the hydraulic-parameter gradients, `record`: reading the
+// attached soil-moisture record -- which chooses among the four instantiations of adjoint_backward_rich, one in each of
+// trm_launch_column_adjoint_rich{,_param,_record,_param_record}.hip (trm_derivative_api.hip).  param_reduce: k_hyd_param_reduce, which
+// ends a sweep with `params` (trm_launch_column_adjoint_rich_param.hip)
 struct AdjointRichLaunch {
     static int record(trm_ctx* c, double dt, int nsteps, int slot);
-    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold);
-    static int backward_params(trm_ctx* c, double dt, int nsteps, int slot, int fold);
-    static int backward_record(trm_ctx* c, double dt, int nsteps, int slot, int fold);
-    static int backward_params_record(trm_ctx* c, double dt, int nsteps, int slot, int fold);
+    static int backward(trm_ctx* c, double dt, int nsteps, int slot, int fold, bool params, bool record);
     static int param_reduce(trm_ctx* c);
 };
 // the row of a TRM_HYDRAULIC_PARAM_* id in the result [TRM_HYDRAULIC_PARAM_COUNT][Nh], -1 for any other number (the thermal ids, which

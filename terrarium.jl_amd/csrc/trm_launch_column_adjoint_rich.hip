@@ -5,5 +5,5 @@
 
 namespace trmh {
 int AdjointRichLaunch::record(trm_ctx* c, double dt, int nsteps, int slot) { return adjoint_record_rich<>(c, dt, nsteps, slot); }
-int AdjointRichLaunch::backward(trm_ctx* c, double dt, int nsteps, int slot, int fold) { return adjoint_backward_rich<>(c, dt, nsteps, slot, fold); }
+template int adjoint_backward_rich<false, false>(trm_ctx*, double, int, int, int);
 }  // namespace trmh

@@ -5,6 +5,6 @@
 #include "trm_launch_derivative.inl"
 
 namespace trmh {
-int AdjointRichLaunch::backward_params(trm_ctx* c, double dt, int nsteps, int slot, int fold) { return adjoint_backward_rich_params<>(c, dt, nsteps, slot, fold); }
+template int adjoint_backward_rich<true, false>(trm_ctx*, double, int, int, int);
 int AdjointRichLaunch::param_reduce(trm_ctx* c) { return adjoint_rich_param_reduce<>(c); }
 }  // namespace trmh

@@ -3,7 +3,8 @@
 // (trm_column_adjoint_ckpt.hpp), each with what rides along (Ride, trm_kernels.hpp), and their record twins: k_column_tangent_record
 // (trm_column_tangent_record.hpp; DESIGN 4.7 "Tangent records"), k_column_adjoint_record and k_column_adjoint_ckpt_record (DESIGN 4.8
 // "Attached records").  A sweep and its record twin are the two wrappers of one device program (adjoint_program,
-// adjoint_ckpt_program <.., RECORD>); the two tangent kernels are two bodies.  Included by the
+// adjoint_ckpt_program <.., RECORD>); the two tangent kernels are two bodies.  Behind them the heat + Richards families:
+// k_column_tangent_rich, k_column_record_rich and the four wrappers of adjoint_rich_program <.., PARAMS, RECORD>.  Included by the
 // trm_launch_column_tangent*.hip and trm_launch_column_adjoint*.hip files, each of which
 // instantiates the launcher of one family and ride, with a record or without.
 #include "trm_host.hpp"
@@ -11,7 +12,6 @@
 #include "trm_column_tangent_record.hpp"
 #include "trm_column_tangent_rich.hpp"
 #include "trm_column_adjoint_rich.hpp"
-#include "trm_column_adjoint_rich_record.hpp"
 
 namespace trmh {
 
@@ -263,8 +263,8 @@ template <class = void> int tangent_closure_rich(trm_ctx* c) {
 }
 
 // ---- the heat + Richards adjoint (k_column_record_rich / k_column_adjoint_rich, trm_column_adjoint_rich.hpp;
-// TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT): final-state cotangents on the per-step tape, no ride.  Templates so that only the translation unit
-// that instantiates them (trm_launch_column_adjoint_rich.hip) holds the kernels.  A slot holds two fields, U_k and sat_k.
+// TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT): final-state cotangents on the per-step tape, no ride.  Templates so that only the translation units
+// that instantiate them (trm_launch_column_adjoint_rich*.hip) hold the kernels.  A slot holds two fields, U_k and sat_k.
 // The preconditions: a Richards context, the branch-free boundary kinds, the five cotangent fields, the launch's slots inside the tape
 inline int adjoint_rich_ok(trm_ctx* c, int nsteps, int slot, const std::string& who) {
     if (c->params.flow != TRM_FLOW_RICHARDS) return fail(c, TRM_EINVAL, who + ": a Richards context only");
@@ -293,24 +293,9 @@ template <class = void> int adjoint_record_rich(trm_ctx* c, double dt, int nstep
         return (int)TRM_OK;
     });
 }
-template <class = void> int adjoint_backward_rich(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    const std::string who = "k_column_adjoint_rich";
-    if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
-    const LaunchArgs<double>& la = launch_args<double>(c);
-    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
-    const RichSweepArgs aa = rich_sweep_args(c, slot, fold);
-    return by_instance(c, [&](auto h, auto lpc) {
-        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        hipLaunchKernelGGL((k_column_adjoint_rich<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa);
-        TRM_HIP(c, hipGetLastError());
-        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, 0);
-        return (int)TRM_OK;
-    });
-}
 
-// ---- ... with the hydraulic-parameter gradients (k_column_adjoint_rich_params / k_hyd_param_reduce; TRM_OPT_DERIVATIVE_RICHARDS_PARAMS,
-// trm_adjoint_param_open on such a context): the same sweep, the seven per-cell accumulators beside it.  Instantiated by
-// trm_launch_column_adjoint_rich_param.hip alone.  The preconditions: the sweep's, and the accumulators and their result
+// ---- the hydraulic-parameter gradients (TRM_OPT_DERIVATIVE_RICHARDS_PARAMS, trm_adjoint_param_open on such a context): the seven
+// per-cell accumulators beside the sweep, and k_hyd_param_reduce, which ends it (trm_launch_column_adjoint_rich_param.hip)
 inline HydParamPtrs hyd_param_ptrs(const trm_ctx* c) {
     HydParamPtrs g;
     for (int q = 0; q < HP_COUNT; ++q) g.g[q] = c->d_adj_hyd[q];
@@ -321,22 +306,6 @@ inline int hyd_params_ok(trm_ctx* c, const std::string& who) {
     if (!c->d_adj_hyd_out) return fail(c, TRM_EINVAL, who + ": no accumulators");
     return arrays_ok(c, c->d_adj_hyd, who, "accumulators");
 }
-template <class = void> int adjoint_backward_rich_params(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    const std::string who = "k_column_adjoint_rich (parameter gradients)";
-    if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
-    if (int rc = hyd_params_ok(c, who)) return rc;
-    const LaunchArgs<double>& la = launch_args<double>(c);
-    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
-    const RichSweepArgs aa = rich_sweep_args(c, slot, fold);
-    const HydParamPtrs hp = hyd_param_ptrs(c);
-    return by_instance(c, [&](auto h, auto lpc) {
-        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        hipLaunchKernelGGL((k_column_adjoint_rich_params<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa, hp);
-        TRM_HIP(c, hipGetLastError());
-        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, (int)TRM_PROGRAM_PARAMETERS);
-        return (int)TRM_OK;
-    });
-}
 template <class = void> int adjoint_rich_param_reduce(trm_ctx* c) {
     if (c->params.flow != TRM_FLOW_RICHARDS) return fail(c, TRM_EINVAL, "k_hyd_param_reduce: a Richards context only");
     if (int rc = hyd_params_ok(c, "k_hyd_param_reduce")) return rc;
@@ -346,42 +315,32 @@ template <class = void> int adjoint_rich_param_reduce(trm_ctx* c) {
     return TRM_OK;
 }
 
-// ---- ... and with an attached soil-moisture record (k_column_adjoint_rich_record / k_column_adjoint_rich_params_record,
-// trm_column_adjoint_rich_record.hpp; TRM_OPT_DERIVATIVE_RICHARDS_RECORD): the two sweeps above with the record as their last kernel
-// argument.  On the per-step tape the taped position of the launch's first step is its slot.  Instantiated by
-// trm_launch_column_adjoint_rich_record.hip and trm_launch_column_adjoint_rich_param_record.hip alone.  The preconditions: the sweep's,
-// and record_launch_ok.  TRM_INFO_LAST_PROGRAM is that of the same launch without a record
-template <class = void> int adjoint_backward_rich_record(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    const std::string who = "k_column_adjoint_rich_record";
+// ---- the backward sweep: the four wrappers of adjoint_rich_program (trm_column_adjoint_rich.hpp).  PARAMS: with the hydraulic-parameter
+// gradients (k_column_adjoint_rich_params); RECORD: reading the attached soil-moisture record (k_column_adjoint_rich_record,
+// k_column_adjoint_rich_params_record; TRM_OPT_DERIVATIVE_RICHARDS_RECORD) -- on the per-step tape the taped position of the launch's
+// first step is its slot.  One explicit instantiation in each of trm_launch_column_adjoint_rich{,_param,_record,_param_record}.hip.
+// The preconditions: the sweep's, the accumulators and their result, record_launch_ok.  TRM_INFO_LAST_PROGRAM knows of no record
+template <bool PARAMS, bool RECORD> int adjoint_backward_rich(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
+    const std::string who = std::string(RECORD ? "k_column_adjoint_rich_record" : "k_column_adjoint_rich") + (PARAMS ? " (parameter gradients)" : "");
     if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
-    if (int rc = record_launch_ok(c, nsteps, slot, who)) return rc;
+    if constexpr (PARAMS)
+        if (int rc = hyd_params_ok(c, who)) return rc;
+    if constexpr (RECORD)
+        if (int rc = record_launch_ok(c, nsteps, slot, who)) return rc;
     const LaunchArgs<double>& la = launch_args<double>(c);
     const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
     const RichSweepArgs aa = rich_sweep_args(c, slot, fold);
-    const RecordArgs r = record_args(c, slot);
+    const HydParamPtrs hp = PARAMS ? hyd_param_ptrs(c) : HydParamPtrs{};
+    const RecordArgs r = RECORD ? record_args(c, slot) : RecordArgs{};
     return by_instance(c, [&](auto h, auto lpc) {
         constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        hipLaunchKernelGGL((k_column_adjoint_rich_record<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa, r);
+        const dim3 grid = column_grid(c, LPC), block(TRM_STEP_BLOCK);
+        if constexpr (PARAMS && RECORD) hipLaunchKernelGGL((k_column_adjoint_rich_params_record<H, LPC>), grid, block, 0, c->stream, la.state, la.p, a, aa, hp, r);
+        else if constexpr (PARAMS) hipLaunchKernelGGL((k_column_adjoint_rich_params<H, LPC>), grid, block, 0, c->stream, la.state, la.p, a, aa, hp);
+        else if constexpr (RECORD) hipLaunchKernelGGL((k_column_adjoint_rich_record<H, LPC>), grid, block, 0, c->stream, la.state, la.p, a, aa, r);
+        else hipLaunchKernelGGL((k_column_adjoint_rich<H, LPC>), grid, block, 0, c->stream, la.state, la.p, a, aa);
         TRM_HIP(c, hipGetLastError());
-        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, 0);
-        return (int)TRM_OK;
-    });
-}
-template <class = void> int adjoint_backward_rich_params_record(trm_ctx* c, double dt, int nsteps, int slot, int fold) {
-    const std::string who = "k_column_adjoint_rich_record (parameter gradients)";
-    if (int rc = adjoint_rich_ok(c, nsteps, slot, who)) return rc;
-    if (int rc = hyd_params_ok(c, who)) return rc;
-    if (int rc = record_launch_ok(c, nsteps, slot, who)) return rc;
-    const LaunchArgs<double>& la = launch_args<double>(c);
-    const ColumnArgs<double> a = column_args<double>(c, dt, 1, nsteps, PROG_MULTI);
-    const RichSweepArgs aa = rich_sweep_args(c, slot, fold);
-    const HydParamPtrs hp = hyd_param_ptrs(c);
-    const RecordArgs r = record_args(c, slot);
-    return by_instance(c, [&](auto h, auto lpc) {
-        constexpr int H = decltype(h)::value, LPC = decltype(lpc)::value;
-        hipLaunchKernelGGL((k_column_adjoint_rich_params_record<H, LPC>), column_grid(c, LPC), dim3(TRM_STEP_BLOCK), 0, c->stream, la.state, la.p, a, aa, hp, r);
-        TRM_HIP(c, hipGetLastError());
-        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, (int)TRM_PROGRAM_PARAMETERS);
+        c->last_program = derivative_program_id(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS, H, LPC, 0, PARAMS ? (int)TRM_PROGRAM_PARAMETERS : 0);
         return (int)TRM_OK;
     });
 }

@@ -1,5 +1,5 @@
 // Exercises the host-side preconditions of the heat + Richards sweep that carries the hydraulic-parameter gradients
-// (adjoint_backward_rich_params / adjoint_rich_param_reduce, trm_launch_derivative.inl; TRM_OPT_DERIVATIVE_RICHARDS_PARAMS) on contexts
+// (adjoint_backward_rich<true, false> / adjoint_rich_param_reduce, trm_launch_derivative.inl; TRM_OPT_DERIVATIVE_RICHARDS_PARAMS) on contexts
 // built by hand: no GPU call.  What the sweep without them needs, then the seven per-cell accumulators and the per-column result -- one
 // missing at a time -- the addresses the argument filler hands to the kernel, and the id rule of trm_adjoint_param_download /
 // _device_ptr: exactly the seven TRM_HYDRAULIC_PARAM_* ids name a row.  Built with the host sanitizers and run by
@@ -15,6 +15,7 @@ template <class NF> const LaunchArgs<NF>& launch_args(trm_ctx*) { static LaunchA
 using namespace trmh;
 
 int main() {
+    const auto sweep = adjoint_backward_rich<true, false>;      // PARAMS, no record
     static_assert(std::is_trivially_copyable<HydParamPtrs>::value && sizeof(HydParamPtrs) == 7 * sizeof(double*), "a kernel argument: seven accumulators");
     static_assert(TRM_OPT_DERIVATIVE_RICHARDS_PARAMS == 18 && TRM_HYDRAULIC_PARAM_COUNT == 7 && HP_COUNT == 7, "the public values");
     static_assert(TRM_HYDRAULIC_PARAM_K_SAT == TRM_THERMAL_PARAM_COUNT && TRM_HYDRAULIC_PARAM_IMPEDANCE == 16, "one id space with the thermal ids");
@@ -61,29 +62,29 @@ int main() {
         q = nullptr;
         assert(hyd_params_ok(&c, who) == TRM_EINVAL && last == "k: no accumulators");
         assert(adjoint_rich_param_reduce<>(&c) == TRM_EINVAL && last == "k_hyd_param_reduce: no accumulators");
-        assert(adjoint_backward_rich_params<>(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): no accumulators");
+        assert(sweep(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): no accumulators");
         q = kept;
     }
     c.d_adj_hyd_out = nullptr;
     assert(hyd_params_ok(&c, who) == TRM_EINVAL && last == "k: no accumulators");
     assert(adjoint_rich_param_reduce<>(&c) == TRM_EINVAL && last == "k_hyd_param_reduce: no accumulators");
-    assert(adjoint_backward_rich_params<>(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): no accumulators");
+    assert(sweep(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): no accumulators");
     c.d_adj_hyd_out = out;
     // the sweep's own conditions come first: the tape, the fields, the kind of context, the boundary kinds
-    assert(adjoint_backward_rich_params<>(&c, 60.0, CAP + 1, 0, 0) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): the launch leaves the tape");
-    assert(adjoint_backward_rich_params<>(&c, 60.0, 3, 4, 0) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): the launch leaves the tape");
+    assert(sweep(&c, 60.0, CAP + 1, 0, 0) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): the launch leaves the tape");
+    assert(sweep(&c, 60.0, 3, 4, 0) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): the launch leaves the tape");
     c.ckpt_interval = 4;
-    assert(adjoint_backward_rich_params<>(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): no per-step tape");
+    assert(sweep(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): no per-step tape");
     c.ckpt_interval = 0;
     c.d_adj[TRM_ADJOINT_PRESSURE_HEAD] = nullptr;
-    assert(adjoint_backward_rich_params<>(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): no cotangent fields");
+    assert(sweep(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): no cotangent fields");
     c.d_adj[TRM_ADJOINT_PRESSURE_HEAD] = x[TRM_ADJOINT_PRESSURE_HEAD];
     c.params.flow = TRM_FLOW_NOFLOW;
-    assert(adjoint_backward_rich_params<>(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): a Richards context only");
+    assert(sweep(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): a Richards context only");
     assert(adjoint_rich_param_reduce<>(&c) == TRM_EINVAL && last == "k_hyd_param_reduce: a Richards context only");
     c.params.flow = TRM_FLOW_RICHARDS;
     c.bc_kind[TRM_BCV_PRESSURE_HEAD][TRM_BOTTOM] = TRM_BC_VALUE;
-    assert(adjoint_backward_rich_params<>(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): the generic boundary kinds");
+    assert(sweep(&c, 60.0, 1, 0, 1) == TRM_EINVAL && last == "k_column_adjoint_rich (parameter gradients): the generic boundary kinds");
     c.bc_kind[TRM_BCV_PRESSURE_HEAD][TRM_BOTTOM] = TRM_BC_NOFLUX;
     assert(adjoint_rich_ok(&c, CAP, 0, who) == TRM_OK && hyd_params_ok(&c, who) == TRM_OK);
     std::puts("derivative preconditions (heat + Richards hydraulic-parameter gradients) ok");

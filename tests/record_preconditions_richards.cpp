@@ -1,5 +1,5 @@
 // Exercises the host-side preconditions of the heat + Richards sweeps that read an attached soil-moisture record
-// (adjoint_backward_rich_record / adjoint_backward_rich_params_record, trm_launch_derivative.inl; TRM_OPT_DERIVATIVE_RICHARDS_RECORD) on
+// (adjoint_backward_rich<false, true> and <true, true>, trm_launch_derivative.inl; TRM_OPT_DERIVATIVE_RICHARDS_RECORD) on
 // contexts built by hand: no GPU call.  What the sweeps without a record need, then the record's: no record, missing tables, a position
 // behind the tape, a launch that leaves the position table; the addresses the argument filler hands to the kernel; and the option gate
 // of richards_tape_only (trm_host.hpp): the seven record calls pass under both options alone, every other call stays refused.  Built with
@@ -15,6 +15,7 @@ template <class NF> const LaunchArgs<NF>& launch_args(trm_ctx*) { static LaunchA
 using namespace trmh;
 
 int main() {
+    const auto sweep = adjoint_backward_rich<false, true>, sweep_hyd = adjoint_backward_rich<true, true>;      // RECORD, and PARAMS with it
     static_assert(TRM_OPT_DERIVATIVE_RICHARDS_RECORD == 19 && TRM_OPT_DERIVATIVE_RICHARDS_PARAMS == 18 && TRM_OPT_DERIVATIVE_RICHARDS_ADJOINT == 17, "the public values");
     static_assert(TRM_PROGRAM_COLUMN_ADJOINT_RICHARDS == 17 && TRM_ABI_VERSION == 20, "the family and the ABI version as they were");
     static_assert(std::is_trivially_copyable<RecordArgs>::value, "a kernel argument");
@@ -59,8 +60,8 @@ int main() {
     const std::string plain = "k_column_adjoint_rich_record", hyd = "k_column_adjoint_rich_record (parameter gradients)";
     const std::string none = ": no record is attached, or its tables are not built";
     auto both_refuse = [&](int nsteps, int slot, int fold, const std::string& why) {
-        assert(adjoint_backward_rich_record<>(&c, 60.0, nsteps, slot, fold) == TRM_EINVAL && last == plain + why);
-        assert(adjoint_backward_rich_params_record<>(&c, 60.0, nsteps, slot, fold) == TRM_EINVAL && last == hyd + why);
+        assert(sweep(&c, 60.0, nsteps, slot, fold) == TRM_EINVAL && last == plain + why);
+        assert(sweep_hyd(&c, 60.0, nsteps, slot, fold) == TRM_EINVAL && last == hyd + why);
     };
     // no record
     assert(adjoint_rich_ok(&c, 4, 2, plain) == TRM_OK && hyd_params_ok(&c, hyd) == TRM_OK);
@@ -112,7 +113,7 @@ int main() {
     both_refuse(1, 0, 0, ": a Richards context only");
     c.params.flow = TRM_FLOW_RICHARDS;
     c.d_adj_hyd_out = nullptr;
-    assert(adjoint_backward_rich_params_record<>(&c, 60.0, 1, 0, 0) == TRM_EINVAL && last == hyd + ": no accumulators");
+    assert(sweep_hyd(&c, 60.0, 1, 0, 0) == TRM_EINVAL && last == hyd + ": no accumulators");
     c.d_adj_hyd_out = out;
     c.d_rec_out = nullptr;
     both_refuse(1, 0, 0, none);
