@@ -446,7 +446,9 @@ int trm_gather_ring_device(trm_ctx* ctx, int field, const void* dev_full);
 /* Device address of a field, for zero-copy consumers on the same device.  The device layout is z-fastest:
  * element (column i, level k) of a 3-D field is at dev[i * pitch_elems + k] (pitch 32 for Nz <= 32, 64 for
  * Nz <= 64); 2-D fields are dev[i] (pitch 1).  The top face of hydraulic_conductivity is not part of this
- * buffer (use trm_download). */
+ * buffer (use trm_download).  The 3-D vegetation fields TRM_FIELD_PLANT_AVAILABLE_WATER and TRM_FIELD_ROOT_FRACTION are allocated by
+ * trm_set_vegetation: before it the call fails with TRM_EINVAL ("the field exists only after trm_set_vegetation") instead of handing
+ * back a null address, as does trm_stage_field_device_ptr. */
 int trm_field_device_ptr(trm_ctx* ctx, int field, void** dev, int64_t* pitch_elems);
 
 /* Field boundary conditions (src/models/soil/soil_model_bcs.jl, src/boundary_conditions.jl:25-28):
@@ -1045,8 +1047,15 @@ int trm_clock(const trm_ctx* ctx, double* time, int64_t* iteration);
 int trm_set_clock(trm_ctx* ctx, double time, int64_t iteration);
 
 /* Local (this device's columns) reduction of a field.  SUM/MIN/MAX/HASNAN give one value per row in
- * out[rows]; VOLUME_INTEGRAL_Z gives one value (sum over columns of sum_k f*dz).  trm_reduce_global (below)
- * combines the devices' results. */
+ * out[rows]; VOLUME_INTEGRAL_Z gives one value (sum over columns of sum_k f*dz) and takes a cell-centred 3-D field (Nz rows)
+ * only.  trm_reduce_global (below) combines the devices' results.
+ * MIN / MAX are Julia's Base.minimum / maximum: a NaN anywhere in a row gives NaN (HASNAN is 1 for that row, SUM and
+ * VOLUME_INTEGRAL_Z are NaN by arithmetic), and where zeros of both signs tie, MIN is -0.0 and MAX is +0.0, whatever the order of
+ * the fold (minimum([0.0, -0.0]) === -0.0, maximum([-0.0, 0.0]) === 0.0).  Infinities are ordinary values: HASNAN of a row of
+ * infinities is 0, the SUM of +Inf and -Inf is NaN.
+ * The 3-D vegetation fields TRM_FIELD_PLANT_AVAILABLE_WATER and TRM_FIELD_ROOT_FRACTION are allocated by trm_set_vegetation: before it
+ * trm_reduce (and with it trm_reduce_global / trm_reduce_global_all) fails with TRM_EINVAL ("the field exists only after
+ * trm_set_vegetation") before anything is launched, as trm_upload / trm_download do. */
 int trm_reduce(trm_ctx* ctx, int field, int op, double* out);
 int trm_status(trm_ctx* ctx, uint32_t* flags);
 /* Sets the status word: a restart puts back the flags its checkpoint carried (the word is sticky: steps only OR into it), so a run
@@ -1064,7 +1073,9 @@ int trm_set_status(trm_ctx* ctx, uint32_t flags);
  *   every rank:  trm_comm_init(ctx, rank, world, id);    -- collective: returns once every rank has called it
  *                trm_reduce_global / trm_status_global   -- collective, same arguments on every rank
  * trm_reduce_global gives what trm_reduce would give on the unsharded grid: SUM / VOLUME_INTEGRAL_Z sums over ranks
- * (in RCCL's deterministic ring order), MIN / MAX / HASNAN exactly, a NaN on any rank propagating into MIN / MAX. */
+ * (in RCCL's deterministic ring order), MIN / MAX / HASNAN exactly, a NaN on any rank propagating into MIN / MAX.  The zero-sign
+ * rule of trm_reduce holds across the shards where the library folds them itself (trm_reduce_global_all without communicators); the
+ * sign of a zero that RCCL's min / max pick between ranks is RCCL's. */
 int trm_comm_unique_id(void* id128);
 int trm_comm_init(trm_ctx* ctx, int rank, int world_size, const void* id128);
 int trm_comm_destroy(trm_ctx* ctx);

@@ -2,6 +2,7 @@
 // global reductions and status of one context, and their grouped forms over n contexts driven by one host thread (trm_*_all, but the two
 // that step: trm_step_api.hip).  check_ctx_list is defined here, with the other callers of a context list.  Host code alone.
 #include "trm_host.hpp"
+#include "trm_reduce_fold.hpp"
 
 #include <dlfcn.h>
 
@@ -182,11 +183,12 @@ void unpack_reduce(int op, int rows, const std::vector<double>& buf, double* out
     }
     for (int r = 0; r < rows; ++r) out[r] = buf[r];
 }
-// the all-reduce of the packed form on the HOST, ranks folded in order (one process: no wire needed)
+// the all-reduce of the packed form on the HOST, ranks folded in order (one process: no wire needed); the folds of trm_reduce, so that
+// the sign of a zero minimum / maximum does not depend on which shard held it
 void fold_packed(int op, int n, std::vector<double>& acc, const std::vector<double>& x) {
     for (int j = 0; j < n; ++j) {
-        if (op == TRM_REDUCE_MIN) acc[j] = std::min(acc[j], x[j]);
-        else if (op == TRM_REDUCE_MAX || op == TRM_REDUCE_HASNAN) acc[j] = std::max(acc[j], x[j]);
+        if (op == TRM_REDUCE_MIN) acc[j] = nan_min(acc[j], x[j]);
+        else if (op == TRM_REDUCE_MAX || op == TRM_REDUCE_HASNAN) acc[j] = nan_max(acc[j], x[j]);
         else acc[j] += x[j];
     }
 }

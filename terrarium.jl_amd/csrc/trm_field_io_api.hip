@@ -3,6 +3,7 @@
 // kernels (transposition, row staging, ring scatter / gather, reductions) and their launch code.  trm_set_bc sits here, not with the series
 // it may replace: it uploads per-column values like trm_set_forcing.  Defines upload_3d / download_3d and upload_field (trm_host.hpp).
 #include "trm_host.hpp"
+#include "trm_reduce_fold.hpp"
 
 using namespace trm;
 using namespace trmh;
@@ -10,9 +11,8 @@ using namespace trmh;
 namespace {
 
 // ---- reductions ------------------------------------------------------------------------------------
-// minimum / maximum as Julia's Base.minimum / maximum: a NaN anywhere gives NaN
-__host__ __device__ inline double nan_min(double a, double b) { return (a != a || b != b) ? (a + b) : (a < b ? a : b); }
-__host__ __device__ inline double nan_max(double a, double b) { return (a != a || b != b) ? (a + b) : (a > b ? a : b); }
+// minimum / maximum as Julia's Base.minimum / maximum (nan_min / nan_max, trm_reduce_fold.hpp): a NaN anywhere gives NaN, the
+// minimum of zeros of both signs is -0, their maximum +0
 // element (row r, column i) of a field sits at base[r] + i * stride[r]
 template <class NF, int OP> __global__ void k_reduce_rows(const NF* f3, const NF* ftop, long Nh, int Nzp, int Nz, int is3d,
                                                           const NF* weight, double* partial) {
@@ -69,7 +69,8 @@ template <class NF> int reduce_impl(trm_ctx* c, int field, int op, double* out) 
         case TRM_REDUCE_MAX: TRM_REDUCE_LAUNCH(TRM_REDUCE_MAX); break;
         case TRM_REDUCE_HASNAN: TRM_REDUCE_LAUNCH(TRM_REDUCE_HASNAN); break;
         case TRM_REDUCE_VOLUME_INTEGRAL_Z:
-            if (rows != c->Nz) return fail(c, TRM_EINVAL, "VOLUME_INTEGRAL_Z needs a cell-centred 3-D field");
+            // (rows alone does not tell: a grid of one layer would give every 2-D field Nz rows)
+            if (!(is_3d(field) && rows == c->Nz)) return fail(c, TRM_EINVAL, "VOLUME_INTEGRAL_Z needs a cell-centred 3-D field");
             TRM_REDUCE_LAUNCH(TRM_REDUCE_VOLUME_INTEGRAL_Z);
             break;
         default: return fail(c, TRM_EINVAL, "unknown reduction op");
@@ -342,6 +343,7 @@ int trm_download(trm_ctx* c, int field, void* host) {
 
 int trm_field_device_ptr(trm_ctx* c, int field, void** dev, int64_t* pitch_elems) {
     if (!c || !dev || !valid_field(field)) return fail(c, TRM_EINVAL, "trm_field_device_ptr: bad argument");
+    if (!c->state.f[field]) return fail(c, TRM_EINVAL, "trm_field_device_ptr: the field exists only after trm_set_vegetation");
     if (is_tendency(field) && !c->tend_valid) return fail(c, TRM_ESTALE, kStaleTendencies);
     if (c->closure_deferred) {      // (the caller reads the arrays behind the library's back from now on; closure_escaped below ends deferral)
         TRM_HIP(c, hipSetDevice(c->device));
@@ -503,8 +505,11 @@ int trm_gather_ring_device(trm_ctx* c, int field, const void* dev_full) {
 }
 
 int trm_reduce(trm_ctx* c, int field, int op, double* out) {
-    TRM_ENTER_HEUN(c);
+    if (!c) return TRM_EINVAL;
     if (!out || !valid_field(field)) return fail(c, TRM_EINVAL, "trm_reduce: bad argument");
+    // (before the device is touched: k_reduce_rows would read through the null base of a field that was never allocated)
+    if (!c->state.f[field]) return fail(c, TRM_EINVAL, "trm_reduce: the field exists only after trm_set_vegetation");
+    TRM_ENTER_HEUN(c);
     if (is_tendency(field) && !c->tend_valid) return fail(c, TRM_ESTALE, kStaleTendencies);
     return by_precision(c->precision, [&](auto nf) { return reduce_impl<typename decltype(nf)::type>(c, field, op, out); });
 }
